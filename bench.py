@@ -8,11 +8,19 @@ synthetic instances that is already resident in HBM.  Workload = BASELINE config
 
     python bench.py [--gpus N] [--steps K] [--warmup W]          (N > 1 without WORLD_SIZE: spawns the N ranks itself)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
+    python bench.py ... --dump-outputs DIR                        (the last timed step's outputs as DIR/<name>.npy)
+    python bench.py ... --full                                    (+ everything beside the headline, see below)
 
 Multi-GPU: weak scaling, instances shard embarrassingly (one process per GPU, each
 with its own 4 096 instances and a replica of the costmap); the only exchange is one
 RCCL all-gather of the (vx, vy, omega) commands per step.
 Prints ONE JSON line on rank 0.
+
+A plain run sets up, settles and warms up the device, times the K steps and prints the headline (`value`,
+`ms_per_step`, the roofline of the timed launches).  `--full` adds the figures that take runs of their own: the
+settle-free reading (`settle.value_without`), two streams, the host-buffer (PCIe-inclusive) paths, the other BASELINE
+configs and parameter sets, the closed-loop warm ticks and the CPU baselines (`--no-cpu-baseline`, `--no-pcie`,
+`--no-others` leave single legs out of it).
 """
 import argparse
 import json
@@ -428,6 +436,51 @@ def warm_tick(dev, local_rank, ticks=60):
     return res
 
 
+#: --dump-outputs: at most this many bytes of .npy files in all
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def last_step_outputs(batch, n, gathered=None):
+    """What the caller of the timed path receives from one step, as float64 arrays with the instance on axis 0: the
+    command records (field by field), the packed (vx, vy, w), the updated state records (field by field), the shifted
+    warm start and, with more than one rank, the all-gathered commands (instance, rank, 3)."""
+    from neo_mpc_planner2_amd import abi
+    out = {}
+    cmds = batch.commands_host()
+    for name in abi.COMMAND_DTYPE.names:
+        out["command_" + name] = cmds[name].astype(np.float64)
+    out["velocities"] = batch.vel.cpu().numpy().astype(np.float64)
+    st = batch.states_host()
+    for name in abi.STATE_DTYPE.names:
+        out["state_" + name] = st[name].astype(np.float64)
+    out["warm_start"] = batch.warm.cpu().numpy().astype(np.float64).reshape(batch.count, 3 * n)
+    if gathered is not None:
+        out["gathered_velocities"] = gathered.cpu().numpy().astype(np.float64).transpose(1, 0, 2).copy()
+    return out
+
+
+def write_outputs(directory, arrays, limit=DUMP_LIMIT_BYTES):
+    """DIR/<name>.npy for every array (float32 / float64 kept, anything else as float64).  Over `limit` bytes in all, the
+    same fixed sample of instances (rows on axis 0, drawn with numpy's default_rng(0), ascending) is written for every
+    array, and the row numbers beside them as `sample_rows.npy`.  Returns the names written."""
+    arrays = {k: (v if v.dtype in (np.float32, np.float64) else v.astype(np.float64)) for k, v in arrays.items()}
+    count = {len(v) for v in arrays.values()}
+    assert len(count) == 1, "every output has the instance on axis 0"
+    count = count.pop()
+    header = 128                                          # (an .npy header: 128 bytes for arrays of these shapes)
+    total = sum(v.nbytes + header for v in arrays.values())
+    if total > limit:
+        per_row = sum(v.nbytes for v in arrays.values()) / count + 8.0     # (+ its entry in sample_rows.npy)
+        keep = int((limit - header * (len(arrays) + 1)) // per_row)
+        rows = np.sort(np.random.default_rng(0).choice(count, size=keep, replace=False))
+        arrays = {k: np.ascontiguousarray(v[rows]) for k, v in arrays.items()}
+        arrays["sample_rows"] = rows.astype(np.float64)
+    os.makedirs(directory, exist_ok=True)
+    for k, v in arrays.items():
+        np.save(os.path.join(directory, k + ".npy"), v)
+    return sorted(arrays)
+
+
 def spawn_ranks(n):
     """`python bench.py --gpus N` with no launcher around it: re-exec under torch.distributed.run, one rank per
     GPU of this node (RCCL over xGMI).  Fails loudly when the node has fewer devices."""
@@ -455,11 +508,17 @@ def main():
                     help="BASELINE config: C2 (default, the metric's), C3, C5; C4 = its per-GPU shard "
                          "(262 144 instances of the C2 problem per GPU; with --gpus 8 the full 2 097 152)")
     ap.add_argument("--batch", type=int, default=None, help="instances per GPU (default: the config's)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-pcie", action="store_true", help="skip the host-buffer (PCIe-inclusive) leg")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also measure what takes runs of its own (settle-free reading, two streams, "
+                         "host-buffer paths, other configs, warm ticks, CPU baselines); off by default")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write the outputs of the last timed step as DIR/<name>.npy (float64; over 64 MB in all, a fixed "
+                         "seeded sample of the instances)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baselines")
+    ap.add_argument("--no-pcie", action="store_true", help="with --full: skip the host-buffer (PCIe-inclusive) leg")
     ap.add_argument("--no-others", action="store_true",
-                    help="skip the other BASELINE configs (C3, C5, C4 shard, general-kernel parameter sets) and the "
-                         "closed-loop warm ticks that ride in the default line")
+                    help="with --full: skip the settle-free reading, two streams, the other BASELINE configs (C3, C5, C4 "
+                         "shard, general-kernel parameter sets) and the closed-loop warm ticks")
     ap.add_argument("--cpu-worker", default=None, help=argparse.SUPPRESS)   # internal: one process of the all-cores CPU leg
     ap.add_argument("--max-iterations", type=int, default=None, help="study knob: cap the solver iterations")
     ap.add_argument("--control-steps", type=int, default=None, help="study knob: override the config's control_steps")
@@ -477,6 +536,8 @@ def main():
     args = ap.parse_args()
     if args.cpu_worker:
         return cpu_worker(args.cpu_worker, args.workload)
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
 
     import torch
     import torch.distributed as dist
@@ -612,7 +673,7 @@ def main():
                 b.states.copy_(base.states)
                 b.warm.copy_(base.warm)
             torch.cuda.synchronize()
-        if not use_dist and not args.no_others:
+        if args.full and not use_dist and not args.no_others:
             # what the same command read WITHOUT the settle -- W warm-up steps, K timed steps, as rounds 1-3 reported it --,
             # kept beside the headline so that rounds stay comparable (`settle.value_without`); every set is put back to
             # its cold state afterwards
@@ -687,6 +748,11 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
     elapsed = float(t.item())
 
+    if args.dump_outputs and rank == 0:
+        # (before anything below solves into the sets again)
+        last = args.steps - 1
+        write_outputs(args.dump_outputs, last_step_outputs(sets[last], n, gathered[last % ring] if use_dist else None))
+
     cmds = sets[0].commands_host()
     if rank == 0:
         total_instances = cfg["batch"] * world
@@ -697,7 +763,7 @@ def main():
             "metric": "MPC solves/sec (control_steps=%d, %dx%d costmap)" % (n, cfg["map_size"], cfg["map_size"]),
             "value": value, "unit": "solves/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
             "ms_per_step": 1e3 * elapsed / args.steps, "higher_is_better": True, "scaling": "weak",
-            "vs_baseline": None, "dtype": "f64", "data": "synthetic",
+            "vs_baseline": None, "dtype": "f64", "data": "synthetic", "full": args.full,
             "config": {"workload": "%s: batch %d instances/GPU, control_steps=%d, horizon=0.8 s, %dx%d u8 costmap, "
                                    "README params, cold start" % (args.workload, cfg["batch"], n, cfg["map_size"],
                                                                   cfg["map_size"]),
@@ -725,7 +791,7 @@ def main():
                                          "value": cfg["batch"] * args.steps / e} for r, (e, k) in enumerate(per_rank)],
                            "what": "one all-gather of (vx, vy, w) per step on a side stream, overlapped with the next "
                                    "step's solve; gather_ms = its own duration (events on the side stream)"}
-        if world == 1 and args.streams == 1 and not args.no_others:
+        if args.full and world == 1 and args.streams == 1 and not args.no_others:
             # Two independent batches in flight (NOT the headline, which is one stream, one batch after the other): the same
             # K launches again, alternating over two streams -- a launch of 4096 instances is one residency round whose last
             # third runs on half-empty SIMDs, and the next batch's waves fill them (two fleets served by one GPU).
@@ -746,14 +812,14 @@ def main():
                                               "study figure, not `value`" % args.steps}
             except Exception as e:
                 out["two_streams"] = {"error": str(e)}
-        if world == 1 and not args.no_pcie:
+        if args.full and world == 1 and not args.no_pcie:
             out["pcie_inclusive"] = pcie_inclusive(solver, probs, st, warm, n)
             # SURVEY 8d's own metric (H2D of the requests and D2H of the results inside the clock), first class beside
             # `value` (the resident-data variant): page-locked arrays worked on in place, and pageable ones
             pin = out["pcie_inclusive"].get("pinned") or {}
             out["value_pcie_inclusive"] = pin.get("value")
             out["value_pcie_inclusive_pageable"] = out["pcie_inclusive"]["value"]
-        if world == 1 and not args.no_others and args.workload == "C2" and not args.batch:
+        if args.full and world == 1 and not args.no_others and args.workload == "C2" and not args.batch:
             # the other BASELINE configs and the deployed (closed-loop, warm-started) mode, a few launches each, so
             # that the driver's line carries them; the inputs are generated here, outside every timed region
             others = []
@@ -771,7 +837,7 @@ def main():
                 out["warm_tick"] = warm_tick(dev, local_rank)
             except Exception as e:
                 out["warm_tick"] = {"error": str(e)}
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             rate, cnt, secs = cpu_baseline(params, cmap, probs)
             out["cpu_baseline"] = {"value": rate, "unit": "solves/s", "cores": 1, "kind": "port",
                                    "cpu_model": cpu_model(), "host_threads_available": os.cpu_count(),

@@ -198,6 +198,48 @@ def test_bench_cpu_worker_and_cpu_count_without_a_gpu():
     assert 1 <= n <= (os.cpu_count() or 1)
 
 
+def test_bench_dump_outputs_layout_and_cap(tmp_path):
+    """bench.py --dump-outputs without a GPU: a step's outputs (command and state records field by field, packed velocities,
+    warm start) read back as float64 arrays with the instance on axis 0, values unchanged; over the byte cap, the same seeded
+    sample of instances in every file, the same sample on every run, and the files within the cap."""
+    import sys
+    import torch
+    sys.path.insert(0, ROOT)
+    import bench
+    from neo_mpc_planner2_amd import synthetic
+    from neo_mpc_planner2_amd.solver import DeviceBatch
+    n, count = 3, 600
+    probs = synthetic.make_problems(count, 500, seed=1000)
+    st, warm = synthetic.make_states(probs, n)
+    b = DeviceBatch(probs, st, warm, "cpu", want_solution=False)
+    cmd = np.zeros(count, dtype=abi.COMMAND_DTYPE)
+    cmd["vel"] = np.random.default_rng(1).normal(size=(count, 3))
+    cmd["cost"] = np.arange(count) * 0.5
+    cmd["iterations"] = np.arange(count) % 17
+    b.commands.copy_(torch.from_numpy(cmd.view(np.uint8).reshape(count, -1)))
+    b.vel.copy_(torch.from_numpy(cmd["vel"]))
+    arrays = bench.last_step_outputs(b, n)
+    assert {"command_vel", "command_cost", "command_status", "command_iterations", "velocities", "state_last_control",
+            "state_old_goal", "warm_start"} <= set(arrays)
+    names = bench.write_outputs(str(tmp_path / "all"), arrays)
+    for k in names:
+        a = np.load(str(tmp_path / "all" / (k + ".npy")))
+        assert a.dtype == np.float64 and a.shape[0] == count, k
+    assert np.array_equal(np.load(str(tmp_path / "all" / "command_vel.npy")), cmd["vel"])
+    assert np.array_equal(np.load(str(tmp_path / "all" / "command_iterations.npy")), cmd["iterations"].astype(np.float64))
+    assert np.array_equal(np.load(str(tmp_path / "all" / "warm_start.npy")), warm.reshape(count, 3 * n))
+    assert "sample_rows" not in names
+    limit = 40000
+    for run in ("s1", "s2"):
+        bench.write_outputs(str(tmp_path / run), arrays, limit=limit)
+        assert sum(os.path.getsize(str(tmp_path / run / f)) for f in os.listdir(str(tmp_path / run))) <= limit
+    rows = np.load(str(tmp_path / "s1" / "sample_rows.npy")).astype(int)
+    assert 0 < len(rows) < count and (np.diff(rows) > 0).all()
+    assert np.array_equal(rows, np.load(str(tmp_path / "s2" / "sample_rows.npy")).astype(int))
+    assert np.array_equal(np.load(str(tmp_path / "s1" / "command_cost.npy")), cmd["cost"][rows])
+    assert np.array_equal(np.load(str(tmp_path / "s1" / "state_old_goal.npy")), st["old_goal"][rows])
+
+
 def test_baseline_kernels_are_scratch_free():
     """The kernels of the BASELINE configs -- k_solve_routed<4, tame, static tile> (config 2 / 4: control_steps 3, AUTO) and
     k_solve<4, 0, stage-wise, tame> (configs 3 and 5) -- spill no vector register: 0 bytes of scratch per lane at their four

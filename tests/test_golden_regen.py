@@ -14,7 +14,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GOLDEN = os.path.join(ROOT, "tests", "golden")
 REFERENCE = "/root/reference/neo_mpc_planner2/mpc_optimization_server.py"
 
-pytestmark = pytest.mark.skipif(not os.path.exists(REFERENCE), reason="the reference is not on this machine")
+needs_reference = pytest.mark.skipif(not os.path.exists(REFERENCE), reason="the reference is not on this machine")
 
 #: generator name -> the files it writes
 QUICK = {"g1": ["g1_objective.npz"], "g2": ["g2_yaw.npz"], "g5": ["g5_shift.npz"], "g6": ["g6_fd_gradient.npz"],
@@ -50,12 +50,14 @@ def test_every_fixture_file_has_a_generator():
     assert listed == {f for f in os.listdir(GOLDEN) if f.endswith(".npz")}
 
 
+@needs_reference
 @pytest.mark.parametrize("name", sorted(QUICK))
 def test_quick_sets_regenerate_bit_for_bit(name, tmp_path):
     _regenerate_and_compare(name, QUICK[name], tmp_path)
 
 
 @pytest.mark.slow
+@needs_reference
 @pytest.mark.skipif(os.environ.get("NEO_MPC_REGEN_ALL") != "1", reason="about an hour of SLSQP: NEO_MPC_REGEN_ALL=1")
 @pytest.mark.parametrize("name", sorted(SLOW))
 def test_slow_sets_regenerate_bit_for_bit(name, tmp_path):

@@ -975,7 +975,7 @@ def test_warm_drift_gate(solver_mod):
 
 
 def test_bench_emits_the_contract_line():
-    """`python bench.py --gpus 1 --steps K --warmup W` prints ONE JSON line, last on stdout, with the
+    """`python bench.py --gpus 1 --steps K --warmup W --full` prints ONE JSON line, last on stdout, with the
     driver's keys, BASELINE.json's metric, the roofline object of the dominant kernel and (without
     --no-cpu-baseline) the CPU baseline object."""
     import json
@@ -984,7 +984,7 @@ def test_bench_emits_the_contract_line():
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "5", "--warmup", "2",
-                          "--no-cpu-baseline"], capture_output=True, text=True, timeout=300, cwd=root)
+                          "--full", "--no-cpu-baseline"], capture_output=True, text=True, timeout=300, cwd=root)
     assert out.returncode == 0, out.stderr[-800:]
     rec = json.loads(out.stdout.strip().splitlines()[-1])
     for key in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling",
@@ -1032,6 +1032,45 @@ def test_bench_emits_the_contract_line():
     assert abs(wt["mean_iterations"] - wt["launch_order"]["mean_iterations"]) < 1e-12       # (the same searches)
     # HBM traffic from the PMC passes is reported only for the build it was measured on
     assert r["traffic"] is not None or any(w in r["traffic_note"] for w in ("stale", "no PMC", "batch"))
+
+
+def test_bench_plain_line_and_dumped_outputs(tmp_path):
+    """A plain `bench.py --gpus 1 --steps K --warmup W --dump-outputs DIR`: the headline alone (K timed steps, value =
+    instances x K over K x ms_per_step, none of --full's legs), and DIR holds what the last timed step computed -- equal to
+    a solve of the same seeded instances through BatchSolver.solve."""
+    import json
+    import os
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    sys.path.insert(0, root)
+    import bench
+    from neo_mpc_planner2_amd.solver import BatchSolver
+    out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "7", "--warmup", "2",
+                          "--dump-outputs", str(tmp_path)], capture_output=True, text=True, timeout=300, cwd=root)
+    assert out.returncode == 0, out.stderr[-800:]
+    rec = json.loads(out.stdout.strip().splitlines()[-1])
+    assert rec["steps"] == 7 and rec["warmup"] == 2 and rec["full"] is False and rec["unit"] == "solves/s"
+    assert rec["metric"].startswith("MPC solves/sec") and rec["higher_is_better"] is True and rec["dtype"] == "f64"
+    assert abs(rec["value"] - 4096 / (rec["ms_per_step"] * 1e-3)) / rec["value"] < 1e-9 and rec["value"] > 1e6
+    for key in ("pcie_inclusive", "other_workloads", "warm_tick", "two_streams", "cpu_baseline", "cpu_mirror"):
+        assert key not in rec, key
+    assert rec["settle"]["value_without"] is None
+    got = {f[:-4]: np.load(str(tmp_path / f)) for f in os.listdir(str(tmp_path))}
+    assert all(a.dtype in (np.float32, np.float64) for a in got.values())
+    assert sum(a.nbytes for a in got.values()) <= bench.DUMP_LIMIT_BYTES
+    cmap = synthetic.make_costmap(500, seed=0)
+    probs = synthetic.make_problems(4096, 500, seed=1000)
+    st, warm = synthetic.make_states(probs, 3)
+    with BatchSolver(bench.readme_params(3), device=0) as s:
+        s.set_costmap(*cmap)
+        cmds, _ = s.solve(probs, st, warm)
+    assert np.array_equal(got["command_status"], cmds["status"]) and np.array_equal(got["command_iterations"], cmds["iterations"])
+    assert np.allclose(got["command_vel"], cmds["vel"], rtol=0, atol=1e-12)
+    assert np.allclose(got["velocities"], cmds["vel"], rtol=0, atol=1e-12)
+    assert np.allclose(got["command_cost"], cmds["cost"], rtol=1e-12, atol=1e-12)
+    assert np.allclose(got["warm_start"], warm.reshape(4096, 9), rtol=0, atol=1e-12)
+    assert np.allclose(got["state_last_control"], st["last_control"], rtol=0, atol=1e-12)
 
 
 def test_bench_refuses_more_gpus_than_the_node_has():

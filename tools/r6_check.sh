@@ -1,5 +1,5 @@
 #!/bin/bash
-# one gpurun call while developing (round 6): the GPU tests (optionally a -k expression), the default bench line, the same
+# one GPU job while developing (round 6): the GPU tests (optionally a -k expression), the --full bench line, the plain
 # line with the dense direction for every instance (method 2 = round 5's AUTO: the A/B partner of the routed kernel), a
 # warm-tick loop.   usage: bash tools/r6_check.sh <tag> ["pytest -k expression"]
 TAG=${1:-r06a}; K=${2:-}
@@ -7,7 +7,7 @@ O=gpurun_out/check_$TAG
 mkdir -p $O
 if [ -n "$K" ]; then timeout 2400 python -m pytest tests -m gpu -q -k "$K" 2>&1 | tail -40 > $O/gpu_tests.log
 else timeout 2400 python -m pytest tests -m gpu -q 2>&1 | tail -40 > $O/gpu_tests.log; fi
-timeout 900 python bench.py > $O/bench_c2.log 2>&1; tail -1 $O/bench_c2.log > $O/bench_c2.json
+timeout 900 python bench.py --full > $O/bench_c2.log 2>&1; tail -1 $O/bench_c2.log > $O/bench_c2.json
 for rep in 1 2; do
   timeout 300 python bench.py --no-cpu-baseline --no-pcie --no-others 2>/dev/null | tail -1 > $O/ab_routed_$rep.json
   timeout 300 python bench.py --no-cpu-baseline --no-pcie --no-others --method 2 2>/dev/null | tail -1 > $O/ab_dense_$rep.json

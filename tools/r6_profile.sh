@@ -1,5 +1,5 @@
 #!/bin/bash
-# one gpurun call: GPU tests, rocprofv3 evidence for C2 / C3 / C5 (kernel stats + PMC in separate passes) and K3, the default
+# one GPU job: GPU tests, rocprofv3 evidence for C2 / C3 / C5 (kernel stats + PMC in separate passes) and K3, the --full
 # bench line (other_workloads, warm_tick, pcie variants ride in it), parity report, closed loop, tick latency
 # usage: bash tools/r6_profile.sh <tag>      then: bash tools/r6_install.sh <tag> <prefix>
 TAG=${1:-r06a}
@@ -20,7 +20,7 @@ for d in ("gpurun_out/prof_$TAG", "gpurun_out/prof_${TAG}_C3", "gpurun_out/prof_
     except Exception as e: print("no traffic entry in", d, e)
 json.dump(out, open("profiles/hbm_traffic.json", "w"), indent=1)
 PY
-timeout 900 python bench.py > $O/bench_c2.log 2>&1; tail -1 $O/bench_c2.log > $O/bench_c2.json
+timeout 900 python bench.py --full > $O/bench_c2.log 2>&1; tail -1 $O/bench_c2.log > $O/bench_c2.json
 # (the A/B partner of the routed headline kernel: the dense direction for every instance, round 5's AUTO)
 timeout 300 python bench.py --no-cpu-baseline --no-pcie --no-others --method 2 2>/dev/null | tail -1 > $O/bench_c2_dense_only.json
 NEO_MPC_LIB=neo_mpc_planner2_amd/libneo_mpc_timing.so timeout 300 python tools/phase_timing_routed.py > $O/phase_timing_routed.txt 2>&1
