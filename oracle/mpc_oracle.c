@@ -22,7 +22,6 @@
  */
 #include <math.h>
 #include <stdint.h>
-#include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
 
@@ -304,33 +303,47 @@ static double orc_step_term(const orc_ctx* c, double x, double y) {
   return c->term[raw];
 }
 
+/* The rollout of u (py:230-232, in the frame of the robot's pose): per stage the heading th, its cos / sin, the step
+ * (dx, dy) and the position (x, y) it ends at. */
+typedef struct orc_path {
+  double th[ORC_MAXN], cs[ORC_MAXN], sn[ORC_MAXN], dx[ORC_MAXN], dy[ORC_MAXN], x[ORC_MAXN], y[ORC_MAXN];
+} orc_path;
+
+static void orc_rollout(const orc_ctx* c, const double* u, orc_path* r) {
+  double x = 0.0, y = 0.0, th = 0.0;
+  for (int i = 0; i < c->n; ++i) {
+    th += u[3 * i + 2] * c->dt;
+    r->th[i] = th;
+    r->cs[i] = cos(th); r->sn[i] = sin(th);
+    r->dx[i] = (u[3 * i] * r->cs[i] - u[3 * i + 1] * r->sn[i]) * c->dt;
+    r->dy[i] = (u[3 * i] * r->sn[i] + u[3 * i + 1] * r->cs[i]) * c->dt;
+    x += r->dx[i]; y += r->dy[i];
+    r->x[i] = x; r->y[i] = y;
+  }
+}
+
 /* the solver's objective (same value as orc_objective up to rounding) */
 static double orc_eval(const orc_ctx* c, const double* u) {
-  double f = 0.0, x = 0.0, y = 0.0, th = 0.0;
+  orc_path r;
+  orc_rollout(c, u, &r);
+  double f = 0.0;
   for (int i = 0; i < c->n; ++i) {
-    double vx = u[3 * i], vy = u[3 * i + 1], w = u[3 * i + 2];
-    th += w * c->dt;
-    double cs = cos(th), sn = sin(th);
-    x += (vx * cs - vy * sn) * c->dt;
-    y += (vx * sn + vy * cs) * c->dt;
-    double dx = c->cx - x, dy = c->cy - y, et = c->tyaw - th;
-    double e0 = c->v[0] - vx, e1 = c->v[1] - vy, e2 = c->v[2] - w;
+    double dx = c->cx - r.x[i], dy = c->cy - r.y[i], et = c->tyaw - r.th[i];
+    double e0 = c->v[0] - u[3 * i], e1 = c->v[1] - u[3 * i + 1], e2 = c->v[2] - u[3 * i + 2];
     f += c->wt_n * (dx * dx + dy * dy) + c->wo_n * (et * et);
     f += c->wc_n * sqrt(e0 * e0 + e1 * e1 + e2 * e2);
-    f += orc_step_term(c, x, y);
+    f += orc_step_term(c, r.x[i], r.y[i]);
   }
-  double et = c->fyaw - th;
+  double et = c->fyaw - r.th[c->n - 1];
   return f + c->wterm_o * (et * et) + c->konst;
 }
 
 /* does every stage of the rollout sit in a free cell (raw cost 0, inside the map)? */
 static int orc_free_path(const orc_ctx* c, const double* u) {
-  double x = 0.0, y = 0.0, th = 0.0;
+  orc_path r;
+  orc_rollout(c, u, &r);
   for (int i = 0; i < c->n; ++i) {
-    th += u[3 * i + 2] * c->dt;
-    const double cs = cos(th), sn = sin(th);
-    x += (u[3 * i] * cs - u[3 * i + 1] * sn) * c->dt;
-    y += (u[3 * i] * sn + u[3 * i + 1] * cs) * c->dt;
+    const double x = r.x[i], y = r.y[i];
     const double X = c->X0 + (c->c0 * x - c->s0 * y), Y = c->Y0 + (c->s0 * x + c->c0 * y);
     int64_t mx, my;
     orc_world_to_map(c->map, X, Y, &mx, &my);
@@ -343,26 +356,21 @@ static int orc_free_path(const orc_ctx* c, const double* u) {
 /* gradient of the smooth (tracking + terminal) part, adjoint sweep */
 static void orc_grad_smooth(const orc_ctx* c, const double* u, double* g) {
   const int n = c->n;
-  double cs[ORC_MAXN], sn[ORC_MAXN], dxs[ORC_MAXN], dys[ORC_MAXN], rx[ORC_MAXN], ry[ORC_MAXN], rt[ORC_MAXN] = {0.0};
-  double x = 0.0, y = 0.0, th = 0.0;
+  orc_path r;
+  orc_rollout(c, u, &r);
+  double rx[ORC_MAXN], ry[ORC_MAXN], rt[ORC_MAXN] = {0.0};
   for (int i = 0; i < n; ++i) {
-    double vx = u[3 * i], vy = u[3 * i + 1], w = u[3 * i + 2];
-    th += w * c->dt;
-    cs[i] = cos(th); sn[i] = sin(th);
-    dxs[i] = (vx * cs[i] - vy * sn[i]) * c->dt;
-    dys[i] = (vx * sn[i] + vy * cs[i]) * c->dt;
-    x += dxs[i]; y += dys[i];
-    rx[i] = -2.0 * c->wt_n * (c->cx - x);
-    ry[i] = -2.0 * c->wt_n * (c->cy - y);
-    rt[i] = -2.0 * c->wo_n * (c->tyaw - th);
+    rx[i] = -2.0 * c->wt_n * (c->cx - r.x[i]);
+    ry[i] = -2.0 * c->wt_n * (c->cy - r.y[i]);
+    rt[i] = -2.0 * c->wo_n * (c->tyaw - r.th[i]);
   }
-  rt[n - 1] += -2.0 * c->wterm_o * (c->fyaw - th);
+  rt[n - 1] += -2.0 * c->wterm_o * (c->fyaw - r.th[n - 1]);
   double SX = 0.0, SY = 0.0, ST = 0.0;
   for (int k = n - 1; k >= 0; --k) {
     SX += rx[k]; SY += ry[k];
-    ST += rt[k] - dys[k] * SX + dxs[k] * SY;
-    g[3 * k] = c->dt * (cs[k] * SX + sn[k] * SY);
-    g[3 * k + 1] = c->dt * (-sn[k] * SX + cs[k] * SY);
+    ST += rt[k] - r.dy[k] * SX + r.dx[k] * SY;
+    g[3 * k] = c->dt * (r.cs[k] * SX + r.sn[k] * SY);
+    g[3 * k + 1] = c->dt * (-r.sn[k] * SX + r.cs[k] * SY);
     g[3 * k + 2] = c->dt * ST;
   }
 }
@@ -389,8 +397,6 @@ typedef struct orc_active {
 /* Tangent-cone reduction of a block's gradient g at u_i: omega frozen at a bound the descent direction -g pushes into;
  * (vx, vy) free, sliding along one active constraint (longest slide that keeps the others satisfied) or pinned.
  * Out: the reduced gradient gr[3] and the face (wfroz, mode 0/1/2, outward normal, disc flag, multiplier). */
-static int orc_near_reduced = 1;
-void orc_set_near_reduced(int m) { orc_near_reduced = m; }
 static void orc_tangent(const orc_ctx* c, const double* ui, const double* gi, double* gr, uint8_t* wfroz, uint8_t* mode,
                         double* nxo, double* nyo, uint8_t* disc, double* lambda) {
   gr[0] = gi[0]; gr[1] = gi[1]; gr[2] = gi[2];
@@ -458,12 +464,10 @@ static void orc_reduce(const orc_ctx* c, const double* u, double* gs, double* gt
     double ne = sqrt(e[0] * e[0] + e[1] * e[1] + e[2] * e[2]);
     a->near[i] = ne < c->kink_radius;
     if (a->near[i]) {
-      if (orc_near_reduced) {
-        double gsr[3], nxo, nyo, lam;
-        uint8_t wf, md, dc;
-        orc_tangent(c, ui, gsi, gsr, &wf, &md, &nxo, &nyo, &dc, &lam);
-        gsi[0] = gsr[0]; gsi[1] = gsr[1]; gsi[2] = gsr[2];
-      }
+      double gsr[3], nxo, nyo, lam;
+      uint8_t wf, md, dc;
+      orc_tangent(c, ui, gsi, gsr, &wf, &md, &nxo, &nyo, &dc, &lam);
+      gsi[0] = gsr[0]; gsi[1] = gsr[1]; gsi[2] = gsr[2];
       /* a block sitting exactly ON the kink with a smooth gradient inside the norm's subdifferential
        * (|g_s| <= w_control/N) stays there under every proximal step: it is at rest */
       a->rest[i] = ne == 0.0 && gsi[0] * gsi[0] + gsi[1] * gsi[1] + gsi[2] * gsi[2] <= c->wc_n * c->wc_n;
@@ -503,11 +507,11 @@ static void orc_apply_active(const orc_ctx* c, const orc_active* a, double* d) {
  * of the analytic gradient (one column per perturbed coordinate -- one lane each on the GPU),
  * plus the control norm's Hessian on blocks away from the kink and the curvature lambda/r of a
  * binding disc; restricted to the tangent cone's face with the projector P (H_r = P H P + I - P)
- * and solved by Gaussian elimination without pivoting, non-positive pivots replaced. */
+ * and solved by Gaussian elimination without pivoting, non-positive pivots replaced.  f64 (the test hook's): the same
+ * elimination in float64. */
 #define ORC_NEWTON_MAXV 24
-static int orc_newton_f64 = 0;
 static void orc_newton_direction(const orc_ctx* c, const double* u, const double* gs, const double* gr,
-                                 const orc_active* a, double* d) {
+                                 const orc_active* a, int f64, double* d) {
   const int n = c->n, nv = 3 * n;
   const double h = 1e-6;
   double H[ORC_NEWTON_MAXV][ORC_NEWTON_MAXV], rhs[ORC_NEWTON_MAXV], up[ORC_NEWTON_MAXV], gk[ORC_NEWTON_MAXV];
@@ -562,7 +566,7 @@ static void orc_newton_direction(const orc_ctx* c, const double* u, const double
     H[3 * i + 2][3 * i + 2] += 1.0 - PW[i];
   }
   for (int j = 0; j < nv; ++j) { rhs[j] = -gr[j]; dmax = fmax(dmax, fabs(H[j][j])); }
-  if (orc_newton_f64) { /* test hook: the same elimination in float64 */
+  if (f64) {
     const double delta = fmax(1e-6 * dmax, 1e-30);
     for (int p = 0; p < nv; ++p) {
       double piv = H[p][p];
@@ -613,14 +617,13 @@ static void orc_newton_direction(const orc_ctx* c, const double* u, const double
  * W_i the stage cost's Hessian, lambda_i = (SX_i, SY_i) the costate of the adjoint sweep, J_i the
  * sensitivity of z_i.  One backward sweep over the stages with 3x3 value-function Hessians and one
  * forward sweep give d in O(control_steps) -- no (3N)^2 matrix, no finite differences. */
-static int orc_piv_replaced;
 static void orc_sym3_solve_prepare(double Q[3][3], double L[3][3], double delta) {
   /* LDL^T-free Cholesky-like elimination without pivoting, non-positive pivots replaced:
    * L holds the eliminated upper triangle rows (as orc_newton_direction does for the dense system) */
   for (int r = 0; r < 3; ++r) for (int q = 0; q < 3; ++q) L[r][q] = Q[r][q];
   for (int p = 0; p < 3; ++p) {
     double piv = L[p][p];
-    if (!(piv > delta)) { piv = fmax(fabs(piv), delta); ++orc_piv_replaced; }
+    if (!(piv > delta)) piv = fmax(fabs(piv), delta);
     L[p][p] = piv;
     for (int j = p + 1; j < 3; ++j) {
       const double fac = L[j][p] / piv;
@@ -688,27 +691,27 @@ static void orc_wall_model(const orc_ctx* c, double x, double y, double* W, doub
     }
   }
 }
-static int orc_kink_predict = 1; /* (the debug hook switches it off to compare with the dense direction) */
-static void orc_riccati_direction(const orc_ctx* c, const double* u, const double* gs, const double* gt, orc_active* a,
-                                  double* d) {
+/* Nominal rollout of u and the costates (SX_i, SY_i) of its positions (the adjoint sweep of orc_grad_smooth). */
+static void orc_costates(const orc_ctx* c, const double* u, orc_path* r, double* SX, double* SY) {
+  orc_rollout(c, u, r);
+  double rx[ORC_MAXN], ry[ORC_MAXN];
+  for (int i = 0; i < c->n; ++i) {
+    rx[i] = -2.0 * c->wt_n * (c->cx - r->x[i]);
+    ry[i] = -2.0 * c->wt_n * (c->cy - r->y[i]);
+  }
+  double ax = 0.0, ay = 0.0;
+  for (int i = c->n - 1; i >= 0; --i) { ax += rx[i]; ay += ry[i]; SX[i] = ax; SY[i] = ay; }
+}
+
+/* (what the solver runs is the displacement form below; this one is the reference the equivalence test holds it to,
+ * without the kink prediction) */
+static void orc_riccati_direction(const orc_ctx* c, const double* u, const double* gt, orc_active* a, double* d) {
   const int n = c->n;
   const double dt = c->dt;
-  double cs[ORC_MAXN], sn[ORC_MAXN], px[ORC_MAXN], py[ORC_MAXN], SX[ORC_MAXN], SY[ORC_MAXN], xs_[ORC_MAXN], ys_[ORC_MAXN];
-  { /* nominal rollout and position costates */
-    double x = 0.0, y = 0.0, th = 0.0, rx[ORC_MAXN], ry[ORC_MAXN];
-    for (int i = 0; i < n; ++i) {
-      th += u[3 * i + 2] * dt;
-      cs[i] = cos(th); sn[i] = sin(th);
-      px[i] = (u[3 * i] * cs[i] - u[3 * i + 1] * sn[i]) * dt;
-      py[i] = (u[3 * i] * sn[i] + u[3 * i + 1] * cs[i]) * dt;
-      x += px[i]; y += py[i];
-      xs_[i] = x; ys_[i] = y;
-      rx[i] = -2.0 * c->wt_n * (c->cx - x);
-      ry[i] = -2.0 * c->wt_n * (c->cy - y);
-    }
-    double ax = 0.0, ay = 0.0;
-    for (int i = n - 1; i >= 0; --i) { ax += rx[i]; ay += ry[i]; SX[i] = ax; SY[i] = ay; }
-  }
+  orc_path ro;
+  double SX[ORC_MAXN], SY[ORC_MAXN];
+  orc_costates(c, u, &ro, SX, SY);
+  const double *cs = ro.cs, *sn = ro.sn, *px = ro.dx, *py = ro.dy, *xs = ro.x, *ys = ro.y;
   static _Thread_local double Kf[ORC_MAXN][3][3], kf[ORC_MAXN][3];
   double V[3][3] = {{0}}, v[3] = {0.0, 0.0, 0.0};
   for (int i = n - 1; i >= 0; --i) {
@@ -719,7 +722,7 @@ static void orc_riccati_direction(const orc_ctx* c, const double* u, const doubl
     S[2][2] += 2.0 * c->wo_n + (i == n - 1 ? 2.0 * c->wterm_o : 0.0);
     { /* wall model (orc_wall_model): curvature on the stage position, linear push-back from a lethal wall */
       double W[3], l[2];
-      orc_wall_model(c, xs_[i], ys_[i], W, l);
+      orc_wall_model(c, xs[i], ys[i], W, l);
       S[0][0] += W[0]; S[0][1] += W[1]; S[1][0] += W[1]; S[1][1] += W[2];
       v[0] += l[0]; v[1] += l[1];
     }
@@ -751,34 +754,6 @@ static void orc_riccati_direction(const orc_ctx* c, const double* u, const doubl
     /* block curvature R_i and the face projector P_i (as in orc_newton_direction) */
     double P[3][3] = {{0}};
     a->tokink[i] = 0;
-    if (!a->near[i] && orc_kink_predict) {
-      /* does the stage model put this block ON the kink u_i = v_cur?  0 in Qu_s + Quu_s k + w d|u_i + k - v|
-       * at k = v - u_i  <=>  |Qu_s + Quu_s (v - u_i)| <= w  (smooth parts only) */
-      const double* ui = u + 3 * i;
-      double kk[3] = {c->v[0] - ui[0], c->v[1] - ui[1], c->v[2] - ui[2]}, r[3];
-      for (int q = 0; q < 3; ++q) {
-        r[q] = gs[3 * i + q];
-        for (int k = 0; k < 3; ++k) r[q] += B[k][q] * v[k] + Quu[q][k] * kk[k];
-      }
-      double vv[3] = {c->v[0], c->v[1], c->v[2]}, vp[3] = {c->v[0], c->v[1], c->v[2]};
-      orc_project(c, vp);
-      const int feasible = vp[0] == vv[0] && vp[1] == vv[1] && vp[2] == vv[2];
-      if (feasible && r[0] * r[0] + r[1] * r[1] + r[2] * r[2] <= c->wc_n * c->wc_n) a->tokink[i] = 1;
-    }
-    if (a->tokink[i]) {
-      const double* ui = u + 3 * i;
-      for (int r = 0; r < 3; ++r) {
-        kf[i][r] = c->v[r] - ui[r];
-        for (int q = 0; q < 3; ++q) Kf[i][r][q] = 0.0;
-      }
-      /* fixed step, no feedback: v = Qz + Quz^T k, V = Qzz */
-      for (int r = 0; r < 3; ++r) {
-        v[r] = Qz[r];
-        for (int k = 0; k < 3; ++k) v[r] += Quz[k][r] * kf[i][k];
-        for (int q = 0; q < 3; ++q) V[r][q] = Qzz[r][q];
-      }
-      continue;
-    }
     if (!a->near[i]) {
       const double* ui = u + 3 * i;
       double e[3] = {ui[0] - c->v[0], ui[1] - c->v[1], ui[2] - c->v[2]};
@@ -852,45 +827,23 @@ static void orc_riccati_direction(const orc_ctx* c, const double* u, const doubl
  * stage, w = B0 du with B0 = dt diag(Rot(theta_i), 1).  The linearised step is then dz_i = A_i (dz_{i-1} + w_i),
  * the Gauss-Newton part of Quu, Quz and Qzz is one matrix M = A^T S A, the second-order terms of the step are
  * T = [[0 0 SY] [0 0 -SX] [SY -SX kappa]], and every stage is solved in the coordinates of its face (0-3 free
- * directions) instead of through projector products.  float64 here, float32 on the device. */
-static int orc_disp = 1;
-static _Thread_local double orc_mu = 0.0;   /* damping of the displacement-form direction (set per call) */
-void orc_set_disp(int on) { orc_disp = on; }
-static int orc_piv_replaced = 0;
-static double orc_piv(double p, double delta) { if (!(p > delta)) ++orc_piv_replaced; return p > delta ? p : fmax(fabs(p), delta); }
-int orc_get_piv_replaced(void) { int r = orc_piv_replaced; orc_piv_replaced = 0; return r; }
+ * directions) instead of through projector products.  float64 here, float32 on the device.
+ * tau weighs the second-order terms (the lambda . d2F terms of the rollout step).  The solver takes them (tau = 1) only
+ * behind an iteration won by a decent Newton step, and the Gauss-Newton part of the Hessian (tau = 0) otherwise: every
+ * stage system is then positive definite by construction and the recursion is safe in float32 (the device's precision);
+ * with the second-order terms far from the minimiser stage systems turn indefinite, pivots get replaced and the forward
+ * sweep can blow up (control_steps 64: |d| ~ 1e53) -- for 1-3 % fewer iterations (12.07 against 12.21 at control_steps
+ * 32, 7.01 / 7.06 at 8).  mu: the damping below.  kink_predict: a block the stage model puts on the control norm's kink
+ * takes the step onto it (the solver passes 1, the equivalence test 0). */
+static double orc_piv(double p, double delta) { return p > delta ? p : fmax(fabs(p), delta); }
 static void orc_riccati_direction_disp_tau(const orc_ctx* c, const double* u, const double* gs, const double* gt,
-                                       orc_active* a, double* d, double tau);
-/* What the solver uses: the GAUSS-NEWTON part of the Hessian (tau = 0: the lambda . d2F terms of the rollout
- * step are left out).  Every stage system is then positive definite by construction and the recursion is
- * safe in float32 (the device's precision); with the second-order terms (tau = 1, kept for the equivalence
- * test against the dense Newton direction) stage systems turn indefinite far from the minimiser, pivots
- * get replaced and the forward sweep can blow up (control_steps 64: |d| ~ 1e53) -- for 1-3 % fewer
- * iterations (12.07 against 12.21 at control_steps 32, 7.01 / 7.06 at 8). */
-static void orc_riccati_direction_disp(const orc_ctx* c, const double* u, const double* gs, const double* gt,
-                                       orc_active* a, double* d) {
-  orc_riccati_direction_disp_tau(c, u, gs, gt, a, d, 0.0);
-}
-static void orc_riccati_direction_disp_tau(const orc_ctx* c, const double* u, const double* gs, const double* gt,
-                                       orc_active* a, double* d, double tau) {
+                                           orc_active* a, double tau, double mu, int kink_predict, double* d) {
   const int n = c->n;
   const double dt = c->dt;
-  double cs[ORC_MAXN], sn[ORC_MAXN], px[ORC_MAXN], py[ORC_MAXN], SX[ORC_MAXN], SY[ORC_MAXN], xs_[ORC_MAXN], ys_[ORC_MAXN];
-  {
-    double x = 0.0, y = 0.0, th = 0.0, rx[ORC_MAXN], ry[ORC_MAXN];
-    for (int i = 0; i < n; ++i) {
-      th += u[3 * i + 2] * dt;
-      cs[i] = cos(th); sn[i] = sin(th);
-      px[i] = (u[3 * i] * cs[i] - u[3 * i + 1] * sn[i]) * dt;
-      py[i] = (u[3 * i] * sn[i] + u[3 * i + 1] * cs[i]) * dt;
-      x += px[i]; y += py[i];
-      xs_[i] = x; ys_[i] = y;
-      rx[i] = -2.0 * c->wt_n * (c->cx - x);
-      ry[i] = -2.0 * c->wt_n * (c->cy - y);
-    }
-    double ax = 0.0, ay = 0.0;
-    for (int i = n - 1; i >= 0; --i) { ax += rx[i]; ay += ry[i]; SX[i] = ax; SY[i] = ay; }
-  }
+  orc_path ro;
+  double SX[ORC_MAXN], SY[ORC_MAXN];
+  orc_costates(c, u, &ro, SX, SY);
+  const double *cs = ro.cs, *sn = ro.sn, *px = ro.dx, *py = ro.dy, *xs = ro.x, *ys = ro.y;
   double vv[3] = {c->v[0], c->v[1], c->v[2]}, vp[3] = {c->v[0], c->v[1], c->v[2]};
   orc_project(c, vp);
   const int v_feasible = vp[0] == vv[0] && vp[1] == vv[1] && vp[2] == vv[2];
@@ -900,7 +853,7 @@ static void orc_riccati_direction_disp_tau(const orc_ctx* c, const double* u, co
   for (int i = n - 1; i >= 0; --i) {
     /* wall model (orc_wall_model) */
     double Ww[3], lw[2];
-    orc_wall_model(c, xs_[i], ys_[i], Ww, lw);
+    orc_wall_model(c, xs[i], ys[i], Ww, lw);
     const double wxx = Ww[0], wxy = Ww[1], wyy = Ww[2];
     v0 += lw[0]; v1 += lw[1];
     const double S00 = V00 + w2 + wxx, S01 = V01 + wxy, S11 = V11 + w2 + wyy;
@@ -920,7 +873,7 @@ static void orc_riccati_direction_disp_tau(const orc_ctx* c, const double* u, co
     const double f0 = cs[i] * e0 - sn[i] * e1, f1 = sn[i] * e0 + cs[i] * e1, f2 = e2;
     double k[3] = {0, 0, 0}, K[3][3] = {{0}};
     a->tokink[i] = 0;
-    if (!a->near[i] && v_feasible && orc_kink_predict) {
+    if (!a->near[i] && v_feasible && kink_predict) {
       const double w0 = -f0 * dt, w1 = -f1 * dt, w2k = -f2 * dt;
       const double r0 = gs0 + z0 + S00 * w0 + S01 * w1 + Z02 * w2k, r1 = gs1 + z1 + S01 * w0 + S11 * w1 + Z12 * w2k,
                    r2 = gs2 + z2 + Z02 * w0 + Z12 * w1 + Z22 * w2k;
@@ -937,7 +890,7 @@ static void orc_riccati_direction_disp_tau(const orc_ctx* c, const double* u, co
         c00 = sN * (1 - h0 * h0) + k2 * tx * tx; c01 = -sN * h0 * h1 + k2 * tx * ty; c02 = -sN * h0 * h2;
         c11 = sN * (1 - h1 * h1) + k2 * ty * ty; c12 = -sN * h1 * h2; c22 = sN * (1 - h2 * h2);
         /* Levenberg-Marquardt damping, in units of one stage's tracking weights (orc_pg_solve adapts it) */
-        c00 += orc_mu * w2; c11 += orc_mu * w2; c22 += orc_mu * 2.0 * c->wo_n;
+        c00 += mu * w2; c11 += mu * w2; c22 += mu * 2.0 * c->wo_n;
       }
       const double Q00 = S00 + c00, Q01 = S01 + c01, Q02 = Z02 + c02, Q11 = S11 + c11, Q12 = Z12 + c12, Q22 = Z22 + c22;
       const double q0 = gt0 + z0, q1 = gt1 + z1, q2 = gt2 + z2;
@@ -1012,11 +965,6 @@ static void orc_riccati_direction_disp_tau(const orc_ctx* c, const double* u, co
   }
 }
 
-/* debug/test hook: both Newton directions at a feasible point u (the dense one in float64) */
-void orc_debug_newton_directions(const neo_mpc_params* p, const uint8_t* cells, int32_t sx, int32_t sy, double res,
-                                 double ox, double oy, const neo_mpc_problem* q, const double* u, double* d_dense,
-                                 double* d_stage, double* d_disp);
-
 static double orc_dot(const double* a, const double* b, int n) {
   double s = 0.0;
   for (int k = 0; k < n; ++k) s += a[k] * b[k];
@@ -1040,43 +988,19 @@ static double orc_lane_scale(int lane, int longshots) {
   return (lane & 1) ? s * 1.4142135623730951 : s;
 }
 
-/* (round 4) A block sliding along a box bound stops where the bound meets the speed disc: the Euclidean projection of a
- * point beyond that corner slides DOWN the disc, away from the bound, so a Newton step along the bound was cut to the
- * fraction that reaches the corner and every other block's step with it (held-out set "a", control_steps 12: searches
- * jammed at the corner for 20 iterations).  A/B hook: orc_set_corner_stop(0). */
-static int orc_final_confirm = 1;
-void orc_set_final_confirm(int m) { orc_final_confirm = m; }
-static int orc_closing_need = NEO_RULE_CLOSING_RUN;
-void orc_set_closing_need(int m) { orc_closing_need = m; }
-static int orc_repin = 1;
-void orc_set_repin(int m) { orc_repin = m; }
-static long orc_repin_count = 0;
-long orc_get_repin_count(void) { return orc_repin_count; }
-static int orc_corner_stop = 1;
-void orc_set_corner_stop(int m) { orc_corner_stop = m; }
-static int orc_land_mode = 0;
-void orc_set_land_mode(int m) { orc_land_mode = m; }
-static int orc_near_mode = 1;
-void orc_set_near_mode(int m) { orc_near_mode = m; }
+/* The candidate of one lane.  Lanes 0-31 take the proximal-gradient step; lanes 32-63 step along d, and a block next
+ * to the kink takes the proximal step on the even ones of them and stays where it is on the odd ones. */
 static void orc_candidate(const orc_ctx* c, const orc_active* act, int lane, double alpha, const double* u,
                           const double* gs, const double* d, double* cand) {
   const double sc = orc_lane_scale(lane, act->longshots);
   for (int i = 0; i < c->n; ++i) {
     double b[3];
-    if ((orc_near_mode == 1 || orc_near_mode == 3) && lane >= 32 && (lane & 1) && act->near[i]) {
-      for (int k = 0; k < 3; ++k) b[k] = u[3 * i + k];
-    } else if (orc_near_mode == 2 && lane >= 32 && act->near[i]) {
+    if (lane >= 32 && (lane & 1) && act->near[i]) {
       for (int k = 0; k < 3; ++k) b[k] = u[3 * i + k];
     } else if (lane < 32 || act->near[i]) {
       /* per-block step: the curvature of block i's own tracking terms is proportional to the number
        * of stages it still moves, N - i (diagonal of the Gauss-Newton Hessian: 2 w_trans/N dt^2 (N - i)) */
       double a = alpha * sc * (act->riccati ? (double)c->n / (double)(c->n - i) : 1.0);
-      if (orc_near_mode == 3 && lane >= 32) {
-        /* the block's own curvature bound: 2 dt^2 ((N - i)/N (max(w_trans, w_orient) + w_trans (r H)^2) + w_terminal w_orient) */
-        const double wt = c->wt_n * c->n, wo = c->wo_n * c->n, reach = c->r * c->dt * c->n;
-        const double L = 2.0 * c->dt * c->dt * ((double)(c->n - i) / c->n * (fmax(wt, wo) + wt * reach * reach) + c->wterm_o);
-        a = 1.0 / L;
-      }
       double e[3], ne2 = 0.0;
       for (int k = 0; k < 3; ++k) { e[k] = (u[3 * i + k] - a * gs[3 * i + k]) - c->v[k]; ne2 += e[k] * e[k]; }
       double ne = sqrt(ne2);
@@ -1086,18 +1010,13 @@ static void orc_candidate(const orc_ctx* c, const orc_active* act, int lane, dou
       const double t = act->tokink[i] ? fmin(sc, 1.0) : sc;
       for (int k = 0; k < 3; ++k) b[k] = u[3 * i + k] + t * d[3 * i + k];
       if (act->tokink[i] && t == 1.0) for (int k = 0; k < 3; ++k) b[k] = c->v[k];
-      if (orc_land_mode && !act->riccati && !act->tokink[i]) {
-        /* a Newton step that carries the block THROUGH the kink (radially inward by more than its distance) ends on it */
-        double e[3] = {u[3 * i] - c->v[0], u[3 * i + 1] - c->v[1], u[3 * i + 2] - c->v[2]};
-        const double rho2 = e[0] * e[0] + e[1] * e[1] + e[2] * e[2];
-        const double inward = -(t * (d[3 * i] * e[0] + d[3 * i + 1] * e[1] + d[3 * i + 2] * e[2]));
-        if (rho2 > 0.0 && inward >= rho2) for (int k = 0; k < 3; ++k) b[k] = c->v[k];
-      }
       const double rl = c->r * (1.0 - 1e-12);
-      if (orc_corner_stop && act->mode[i] == 1 && !act->disc[i] && !act->tokink[i] &&
+      if (act->mode[i] == 1 && !act->disc[i] && !act->tokink[i] &&
           u[3 * i] * u[3 * i] + u[3 * i + 1] * u[3 * i + 1] < rl * rl) {   /* (not AT the corner already: from there the projection slides it along the disc) */
-        /* a block sliding along a box bound stops where the bound meets the speed disc (the Euclidean projection of a
-         * point beyond the corner slides down the disc instead, away from the bound) */
+        /* (round 4) a block sliding along a box bound stops where the bound meets the speed disc: the Euclidean projection
+         * of a point beyond that corner slides DOWN the disc, away from the bound, so a Newton step along the bound was cut
+         * to the fraction that reaches the corner and every other block's step with it (held-out set "a", control_steps 12:
+         * searches jammed at the corner for 20 iterations) */
         const int free_axis = act->nx[i] != 0.0 ? 1 : 0, fixed_axis = 1 - free_axis;
         const double fixed = u[3 * i + fixed_axis];
         const double lim2 = c->r * c->r - fixed * fixed, lim = lim2 > 0.0 ? sqrt(lim2) * (1.0 - 1e-15) : 0.0;
@@ -1127,13 +1046,11 @@ void orc_set_hops(int on) { orc_hops_on = on; }
 static int orc_hops(const orc_ctx* c, const double* u, double min_drop, double hop[][2], uint8_t* has) {
   const orc_map* m = c->map;
   const double range = fmin(ORC_HOP_DIST, ORC_HOP_MAX_DV * c->dt / m->resolution);
-  double x = 0.0, y = 0.0, th = 0.0;
+  orc_path r;
+  orc_rollout(c, u, &r);
   int any = 0;
   for (int i = 0; i < c->n; ++i) {
-    th += u[3 * i + 2] * c->dt;
-    const double cs = cos(th), sn = sin(th);
-    x += (u[3 * i] * cs - u[3 * i + 1] * sn) * c->dt;
-    y += (u[3 * i] * sn + u[3 * i + 1] * cs) * c->dt;
+    const double x = r.x[i], y = r.y[i], cs = r.cs[i], sn = r.sn[i];
     const double X = c->X0 + (c->c0 * x - c->s0 * y), Y = c->Y0 + (c->s0 * x + c->c0 * y);
     int64_t mx, my;
     orc_world_to_map(m, X, Y, &mx, &my);
@@ -1172,25 +1089,16 @@ static int orc_hops(const orc_ctx* c, const double* u, double min_drop, double h
  * updated).  A/B hook: orc_set_scan(0) switches it off. */
 static int orc_scan_on = 1;
 void orc_set_scan(int on) { orc_scan_on = on; }
-static long orc_scan_calls = 0, orc_scan_cands = 0, orc_scan_wins = 0;   /* (development statistics; not exact under OpenMP) */
-long orc_get_scan_stat(int k) { return k == 0 ? orc_scan_calls : k == 1 ? orc_scan_cands : orc_scan_wins; }
 static int orc_cell_scan(const orc_ctx* c, int reach, double* u, double* f, double min_drop, int* nfev) {
   const orc_map* m = c->map;
   const int n = c->n, nv = 3 * n, R = NEO_RULE_SCAN_CELLS, W = 2 * R + 1, ncell = W * W - 1;
-  double px[ORC_MAXN], py[ORC_MAXN], pcs[ORC_MAXN], psn[ORC_MAXN];
-  double x = 0.0, y = 0.0, th = 0.0;
-  for (int i = 0; i < n; ++i) {
-    th += u[3 * i + 2] * c->dt;
-    pcs[i] = cos(th); psn[i] = sin(th);
-    x += (u[3 * i] * pcs[i] - u[3 * i + 1] * psn[i]) * c->dt;
-    y += (u[3 * i] * psn[i] + u[3 * i + 1] * pcs[i]) * c->dt;
-    px[i] = x; py[i] = y;
-  }
+  orc_path r;
+  orc_rollout(c, u, &r);
+  const double *px = r.x, *py = r.y, *pcs = r.cs, *psn = r.sn;
   int64_t mx0, my0;
   orc_world_to_map(m, c->X0, c->Y0, &mx0, &my0);
   double fbest = *f, best_u[ORC_MAXV], cand[ORC_MAXV];
   int won = 0;
-  ++orc_scan_calls;
   *nfev += 2;
   const int lps = n < ORC_LANES ? ORC_LANES / n : 1;
   const double idt = 1.0 / c->dt;
@@ -1232,11 +1140,10 @@ static int orc_cell_scan(const orc_ctx* c, int reach, double* u, double* f, doub
         cand[3 * j] = b2[0]; cand[3 * j + 1] = b2[1];
       }
       const double fc = orc_eval(c, cand);
-      ++orc_scan_cands;
       if (fc < fbest) { fbest = fc; won = 1; memcpy(best_u, cand, sizeof(double) * nv); }
     }
   }
-  if (won) { memcpy(u, best_u, sizeof(double) * nv); *f = fbest; ++orc_scan_wins; }
+  if (won) { memcpy(u, best_u, sizeof(double) * nv); *f = fbest; }
   return won;
 }
 
@@ -1250,25 +1157,15 @@ void orc_capture_direction(int it, double* d_out) { orc_capture_it = it; orc_cap
 static int orc_trial = 1;
 void orc_set_trial(int on) { orc_trial = on; }
 #define ORC_ALT_LANE 5   /* = kAltLane (solver_context.h) */
-static int orc_unshift = 1;
-void orc_set_unshift(int on) { orc_unshift = on; }
 /* sum of the costmap terms of the rollout of u: 0.0 exactly when every stage sits in a cell whose term is zero (what the
  * kernels read off the winner's rollout: rollout.h term_sum) */
 static double orc_term_sum(const orc_ctx* c, const double* u) {
-  double x = 0.0, y = 0.0, th = 0.0, ts = 0.0;
-  for (int i = 0; i < c->n; ++i) {
-    th += u[3 * i + 2] * c->dt;
-    const double cs = cos(th), sn = sin(th);
-    x += (u[3 * i] * cs - u[3 * i + 1] * sn) * c->dt;
-    y += (u[3 * i] * sn + u[3 * i + 1] * cs) * c->dt;
-    ts += orc_step_term(c, x, y);
-  }
+  orc_path r;
+  orc_rollout(c, u, &r);
+  double ts = 0.0;
+  for (int i = 0; i < c->n; ++i) ts += orc_step_term(c, r.x[i], r.y[i]);
   return ts;
 }
-static int orc_rest_rule = 1;
-void orc_set_rest_rule(int on) { orc_rest_rule = on; }
-static int orc_trace = 0;
-void orc_set_trace(int on) { orc_trace = on; }
 /* Blocked-run stop rule (dense Newton direction).  ORC_BLOCKED_RUN consecutive iterations NOT won by a decent Newton
  * step -- a proximal lane, or a Newton step cut below ORC_BLOCKED_STEP -- that together gain less than
  * ORC_BLOCKED_TOL_MAP * opt_tolerance (ORC_BLOCKED_TOL_FREE * opt_tolerance when no stage of the rollout has a costmap
@@ -1304,19 +1201,14 @@ static int orc_wall_in_reach(const orc_ctx* c, int reach) {
 static int orc_route = 1;   /* A/B hook: 0 = round 5's AUTO (the dense direction for every instance at control_steps 3) */
 void orc_set_route(int on) { orc_route = on; }
 
-/* Returns status; x_out = minimiser estimate, *f_out its objective. */
-/* (round 4) A/B hooks.  orc_tau_mode 1 (default): the stage-wise direction carries the second-order terms of the rollout
- * step (lambda . d2F: the exact Hessian, quadratic convergence); 0: Gauss-Newton (rounds 2-3: linear convergence wherever
- * the tracking residuals are large -- held-out parameter sets "a" and "c": first controls 1.4e-3 ... 3.2e-3 from SLSQP's
- * converged ones when the window rule cut in).  orc_rule_mode 1 (default): the gain thresholds are relative to the part
- * of the objective that depends on u (the constant terminal distance term, py:266, can be 20x that), and with the
- * stage-wise direction the three-iteration window and the closing-in rule only judge runs of BLOCKED iterations
- * (iterations won by a decent Newton step end through the Newton step test); 0: rounds 2-3. */
-static double orc_final_frac = NEO_RULE_FINAL_FRAC_GN;
-void orc_set_final_frac(double f) { orc_final_frac = f; }
-static int orc_tau_mode = 1, orc_rule_mode = 1;
-void orc_set_tau_mode(int m) { orc_tau_mode = m; }
-void orc_set_rule_mode(int m) { orc_rule_mode = m; }
+/* Returns status; x_out = minimiser estimate, *f_out its objective.
+ * (round 4) Behind an iteration won by a decent Newton step the stage-wise direction carries the second-order terms of
+ * the rollout step (lambda . d2F: the exact Hessian, quadratic convergence); Gauss-Newton alone (rounds 2-3) converges
+ * linearly wherever the tracking residuals are large -- held-out parameter sets "a" and "c": first controls 1.4e-3 ...
+ * 3.2e-3 from SLSQP's converged ones when the window rule cut in.  The gain thresholds are relative to the part of the
+ * objective that depends on u (the constant terminal distance term, py:266, can be 20x that), and with the stage-wise
+ * direction the three-iteration window and the closing-in rule only judge runs of BLOCKED iterations (iterations won by
+ * a decent Newton step end through the Newton step test). */
 int orc_pg_solve(const neo_mpc_params* p, const orc_map* m, const neo_mpc_problem* q,
                  double footprint_cost, const double* x0, const double* prev_u0, double* x_out, double* f_out,
                  int32_t* nit_out, int32_t* nfev_out) {
@@ -1367,7 +1259,7 @@ int orc_pg_solve(const neo_mpc_params* p, const orc_map* m, const neo_mpc_proble
   for (int k = 0; k < nv; ++k) cold = cold && (u[k] == 0.0);
   int alt_lane = 0;
   double alt_u[ORC_MAXV];
-  if (orc_unshift && !cold && n > 1) {
+  if (!cold && n > 1) {
     /* The warm start is the previous solution shifted by a WHOLE control step (py:198-202: block i <- block i + 1, the
      * FILTERED first control last, py:366-367) although only one control interval -- an eighth of a step at 30 Hz and the
      * README's horizon -- has passed: the previous solution itself, i.e. the shift undone with the first block as the solver
@@ -1428,22 +1320,18 @@ resume_search:
        * Newton step almost never wins there (9 % of the cases): lanes 32-63 walk the reduced
        * steepest-descent direction in that first iteration instead */
       if (it == 0 && cold) for (int k = 0; k < nv; ++k) d[k] = -gr[k];
-      else if (riccati && orc_disp) {
-        orc_mu = mu;
+      else if (riccati) {
         /* second-order terms only behind an iteration won by a decent Newton step (the model held there): far from the
          * minimiser -- a search blocked by a wall, the first steps of a cold start -- the exact Hessian is indefinite
          * and the Gauss-Newton direction is the safer one */
-        const double tau = orc_tau_mode == 1 ? (nblocked == 0 ? 1.0 : 0.0) : orc_tau_mode == 2 ? 1.0 : 0.0;
-        exact_step = tau != 0.0;
-        orc_riccati_direction_disp_tau(&c, u, gs, gt, &act, d, tau);
-        orc_mu = 0.0;
+        exact_step = nblocked == 0;
+        orc_riccati_direction_disp_tau(&c, u, gs, gt, &act, exact_step ? 1.0 : 0.0, mu, 1, d);
       }
-      else if (riccati) orc_riccati_direction(&c, u, gs, gt, &act, d);
-      else orc_newton_direction(&c, u, gs, gr, &act, d);
+      else orc_newton_direction(&c, u, gs, gr, &act, 0, d);
       orc_apply_active(&c, &act, d);
-      if (orc_repin && (riccati || orc_repin == 1) && !(it == 0 && cold) &&
+      if (!(it == 0 && cold) &&
           !(c.lo[0] <= -c.r && c.hi[0] >= c.r && c.lo[1] <= -c.r && c.hi[1] >= c.r) &&   /* (the box cuts the disc: there are corners) */
-          (orc_repin == 3 || (riccati ? orc_free_path(&c, u) : (it > 0 && orc_term_sum(&c, u) == 0.0)))) {
+          (riccati ? orc_free_path(&c, u) : (it > 0 && orc_term_sum(&c, u) == 0.0))) {
         /* (round 4) one-sided slides: a block in a corner of the feasible set (two constraints active) that slides along
          * one of them can only slide AWAY from the other -- a Newton step that sends it the other way is stopped by the
          * projection while every other block takes the step that counted on it.  Such blocks are pinned and the direction
@@ -1471,16 +1359,11 @@ resume_search:
             const double rin = c.r - NEO_RULE_CORNER_ROOM;
             blocked |= d0 * u0 + d1 * u1 > 0.0 && u0 * u0 + u1 * u1 >= rin * rin;
           }
-          if (blocked) {
-            if (orc_trace) fprintf(stderr, "      repin block %d: d %.3e %.3e\n", i, d0, d1);
-            act.mode[i] = 2; gr[3 * i] = 0.0; gr[3 * i + 1] = 0.0; redo = 1;
-          }
+          if (blocked) { act.mode[i] = 2; gr[3 * i] = 0.0; gr[3 * i + 1] = 0.0; redo = 1; }
         }
         if (redo) {
-          ++orc_repin_count;
-          if (riccati && orc_disp) { orc_mu = mu; orc_riccati_direction_disp_tau(&c, u, gs, gt, &act, d, exact_step ? 1.0 : 0.0); orc_mu = 0.0; }
-          else if (riccati) orc_riccati_direction(&c, u, gs, gt, &act, d);
-          else orc_newton_direction(&c, u, gs, gr, &act, d);
+          if (riccati) orc_riccati_direction_disp_tau(&c, u, gs, gt, &act, exact_step ? 1.0 : 0.0, mu, 1, d);
+          else orc_newton_direction(&c, u, gs, gr, &act, 0, d);
           orc_apply_active(&c, &act, d);
         }
       }
@@ -1491,14 +1374,14 @@ resume_search:
         for (int k = 0; k < nv; ++k) dm = fmax(dm, fabs(d[k]));
         /* (blocks next to the kink are moved by the prox step, which d does not describe -- unless they are at
          * rest on it) */
-        for (int i = 0; i < n; ++i) anynear |= act.near[i] && !(orc_rest_rule && act.rest[i]);
+        for (int i = 0; i < n; ++i) anynear |= act.near[i] && !act.rest[i];
         /* (with a cheaper cell a hop away the search runs once more: its hop lanes decide) */
         if (dm < xtol && !anynear && nhops == 0) { status = NEO_MPC_STATUS_CONVERGED; goto exit_check; }
         /* a full Newton step below opt_tolerance (SLSQP's own step test) is the last one: it is
          * searched and taken like any other, but nothing re-checks the point it lands on (the
          * error left is of the order of the step squared) */
         /* (a Gauss-Newton step converges linearly: it has to be shorter to be the last) */
-        if (dm < (riccati && !exact_step ? orc_final_frac : 1.0) * final_tol && !anynear) final = 1;
+        if (dm < (riccati && !exact_step ? NEO_RULE_FINAL_FRAC_GN : 1.0) * final_tol && !anynear) final = 1;
       }
     }
     if (!newton && it > 0) {
@@ -1541,8 +1424,8 @@ resume_search:
     }
     if (orc_capture_it == it && orc_capture_d) memcpy(orc_capture_d, d, sizeof(double) * nv);
     /* 64 candidates, lowest objective wins (ties: lowest lane) */
-    double fb = INFINITY, fb_qn = INFINITY;
-    int best = -1, best_qn = -1;
+    double fb = INFINITY;
+    int best = -1;
     /* Riccati direction, rollout in free space (no costmap term at any stage: the objective is smooth up to the
      * control norm's kink): the full Newton step (lane 32's candidate) is tried on its own first -- one
      * objective evaluation, lane = stage on the device -- and taken without the 64-candidate search when it
@@ -1573,32 +1456,8 @@ resume_search:
       if (it == 0 && lane == ORC_ALT_LANE && alt_lane) memcpy(cand, alt_u, sizeof(double) * nv);
       double fc = orc_eval(&c, cand);
       if (fc < fb) { fb = fc; best = lane; memcpy(best_c, cand, sizeof(double) * nv); }
-      if (lane >= 32 && fc < fb_qn) { fb_qn = fc; best_qn = lane; }
-      if (orc_trace > 1 && it == orc_trace) {
-        fprintf(stderr, "  lane %2d sc %.3e fc-f %.3e cand", lane, orc_lane_scale(lane, act.longshots), fc - f);
-        for (int k = 0; k < nv; ++k) fprintf(stderr, " %.7f", cand[k] - u[k]);
-        fprintf(stderr, "\n");
-      }
-    }
-    if (orc_trace > 1 && it == orc_trace) {
-      fprintf(stderr, "  u "); for (int k = 0; k < nv; ++k) fprintf(stderr, " %.7f", u[k]);
-      fprintf(stderr, "\n  gs"); for (int k = 0; k < nv; ++k) fprintf(stderr, " %.3e", gs[k]);
-      fprintf(stderr, "\n  gr"); for (int k = 0; k < nv; ++k) fprintf(stderr, " %.3e", gr[k]);
-      fprintf(stderr, "\n  d "); for (int k = 0; k < nv; ++k) fprintf(stderr, " %.3e", d[k]);
-      fprintf(stderr, "\n");
     }
     ++nfev;
-    if (orc_trace) {
-      double gn = 0.0;
-      for (int k = 0; k < nv; ++k) gn = fmax(gn, fabs(gr[k]));
-      int nact = 0, nnear = 0;
-      for (int i = 0; i < n; ++i) { nact += act.mode[i] != 0 || act.wfroz[i]; nnear += act.near[i]; }
-      fprintf(stderr, "it %3d f %.15g fb-f %.3e best %2d alpha %.3e |gr|inf %.3e npairs %d | qn best %2d df %.3e active %d near %d |",
-              it, f, fb - f, best, alpha, gn, npairs, best_qn, fb_qn - f, nact, nnear);
-      for (int i = 0; i < n; ++i) fprintf(stderr, " %d%s%s", act.mode[i], act.wfroz[i] ? "w" : "", act.near[i] ? "k" : "");
-      fprintf(stderr, "\n");
-      if (orc_trace > 2) { for (int i = 0; i < n; ++i) fprintf(stderr, "      u[%d] % .6f % .6f % .6f  d % .3e % .3e % .3e  gt % .3e % .3e % .3e\n", i, u[3*i], u[3*i+1], u[3*i+2], d[3*i], d[3*i+1], d[3*i+2], gt[3*i], gt[3*i+1], gt[3*i+2]); }
-    }
     if (!(fb < f)) { status = NEO_MPC_STATUS_CONVERGED; ++it; goto exit_check; }
     double step = 0.0;
     for (int k = 0; k < nv; ++k) {
@@ -1624,7 +1483,7 @@ resume_search:
      * slow tail next to the control-norm kink) end the search once ORC_STALL_ITERATIONS of them
      * are in a row */
     /* (gain thresholds are relative to the u-dependent part of the objective: f without the constant terms) */
-    const double fsc = orc_rule_mode >= 1 ? fmax(1.0, fabs(fb - c.konst)) : fmax(1.0, fabs(fb));
+    const double fsc = fmax(1.0, fabs(fb - c.konst));
     stall = (decrease <= ftol * fsc || step <= stall_step) ? stall + 1 : 0;
     /* (from ORC_LATE_ITERATION on the window is the control_steps-3 one again: a long-horizon search that has run
      * twice its usual length is creeping, gaining 1e-8 of f per iteration up to the iteration cap -- a handful per
@@ -1633,7 +1492,7 @@ resume_search:
     /* stage-wise direction: the window and closing-in rules only judge runs of BLOCKED iterations (none of the three won
      * by a Newton step of at least half its length); iterations won by the Newton step end through the step test */
     nblocked = (best < 32 || orc_lane_scale(best, act.longshots) < NEO_RULE_WINDOW_STEP || hop_won) ? nblocked + 1 : 0;
-    const int creeping = wnow > 0.0 && decrease + gain1 + gain2 <= wnow * fsc && (orc_rule_mode < 1 || !riccati || routed || nblocked >= 3);
+    const int creeping = wnow > 0.0 && decrease + gain1 + gain2 <= wnow * fsc && (!riccati || routed || nblocked >= 3);
     /* ... and so does a step below stall_step whose gain halved twice in a row: the search is closing in on a
      * costmap cell edge (or the kink) geometrically, what is left to gain is less than the last gain (part of the
      * window rule: off with it).  -3 % iterations at control_steps 3 and 32, no command moves by 1e-3.
@@ -1645,16 +1504,15 @@ resume_search:
      * NEW iterate's rollout; stage-wise: under the rollout the iteration started from) */
     const int free_now = riccati ? free_before : (newton ? orc_term_sum(&c, u) == 0.0 : 0);
     const int closing_in = wtol > 0.0 && step <= stall_step && decrease <= 0.5 * gain1 && gain1 <= 0.5 * gain2 &&
-                           (!free_now || (gain2 < INFINITY && decrease * decrease <= ftol * fsc * (gain1 - decrease))) && (orc_rule_mode < 1 || ((riccati && !routed) ? nblocked >= 3 : nblocked >= orc_closing_need));
+                           (!free_now || (gain2 < INFINITY && decrease * decrease <= ftol * fsc * (gain1 - decrease))) &&
+                           ((riccati && !routed) ? nblocked >= 3 : nblocked >= NEO_RULE_CLOSING_RUN);
     int blocked_stop = 0;
     if (newton && (!riccati || routed) && orc_blocked_rule && wtol > 0.0 && blocked_run >= ORC_BLOCKED_RUN)
       blocked_stop = decrease + gain1 + gain2 <= (orc_term_sum(&c, u) == 0.0 ? rules.btol_free : rules.btol_map);
     gain2 = gain1; gain1 = decrease;
     /* (round 4) the last-step rule rests on the Newton model having held: an iteration announced as the last but WON by a
      * proximal step or a short Newton step (the model was off: a bound about to become active, the kink) is not the last */
-    if (orc_final_confirm && final && !(best >= 32 && orc_lane_scale(best, act.longshots) >= NEO_RULE_WINDOW_STEP)) final = 0;
-    if (orc_trace) fprintf(stderr, "      rules: step %.3e (xtol %.1e stall_step %.1e) decrease %.3e stall %d creeping %d closing_in %d final %d blocked_stop %d (run %d) nblocked %d\n",
-                           step, xtol, stall_step, decrease, stall, creeping, closing_in, final, blocked_stop, blocked_run, nblocked);
+    if (final && !(best >= 32 && orc_lane_scale(best, act.longshots) >= NEO_RULE_WINDOW_STEP)) final = 0;
     if (step < xtol || stall >= ORC_STALL_ITERATIONS || creeping || closing_in || final || blocked_stop) { status = NEO_MPC_STATUS_CONVERGED; ++it; goto exit_check; }
     continue;
   exit_check:
@@ -1829,6 +1687,8 @@ void orc_gradient_batch(const neo_mpc_params* p, const uint8_t* cells, int32_t s
   }
 }
 
+/* debug/test hook: the Newton directions at a feasible point u -- dense (in float64), stage-wise in the projector form
+ * and in the displacement form (both with the second-order terms and without the kink prediction) */
 void orc_debug_newton_directions(const neo_mpc_params* p, const uint8_t* cells, int32_t sx, int32_t sy, double res,
                                  double ox, double oy, const neo_mpc_problem* q, const double* u, double* d_dense,
                                  double* d_stage, double* d_disp) {
@@ -1841,21 +1701,15 @@ void orc_debug_newton_directions(const neo_mpc_params* p, const uint8_t* cells, 
   orc_reduce(&c, u, gs, gt, gr, &act);
   const int nv = 3 * c.n;
   if (d_dense && nv <= ORC_NEWTON_MAXV) {
-    orc_newton_f64 = 1;
-    orc_newton_direction(&c, u, gs, gr, &act, d_dense);
-    orc_newton_f64 = 0;
+    orc_newton_direction(&c, u, gs, gr, &act, 1, d_dense);
     orc_apply_active(&c, &act, d_dense);
   }
   if (d_stage) {
-    orc_kink_predict = 0;
-    orc_riccati_direction(&c, u, gs, gt, &act, d_stage);
-    orc_kink_predict = 1;
+    orc_riccati_direction(&c, u, gt, &act, d_stage);
     orc_apply_active(&c, &act, d_stage);
   }
   if (d_disp) {   /* the device's formulation: displacement coordinates, face-reduced stage solves */
-    orc_kink_predict = 0;
-    orc_riccati_direction_disp_tau(&c, u, gs, gt, &act, d_disp, 1.0);
-    orc_kink_predict = 1;
+    orc_riccati_direction_disp_tau(&c, u, gs, gt, &act, 1.0, 0.0, 0, d_disp);
     orc_apply_active(&c, &act, d_disp);
   }
 }
