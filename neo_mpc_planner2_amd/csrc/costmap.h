@@ -1,5 +1,5 @@
 // costmap.h -- costmap lookups: world -> cell, bordered device map, LDS reach tile, footprint raster
-// Part of libneo_mpc.so's device code (included by neo_mpc_kernels.hip only).
+// Part of libneo_mpc.so's device code (included through k1_solve.h by neo_mpc_kernels.hip and neo_mpc_riccati.hip).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <math.h>

@@ -1,5 +1,5 @@
 // fast_math.h -- float64 elementary functions sized for the solver loop (gfx950)
-// Part of libneo_mpc.so's device code (included by neo_mpc_kernels.hip only).
+// Part of libneo_mpc.so's device code (included through k1_solve.h by neo_mpc_kernels.hip and neo_mpc_riccati.hip).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <math.h>

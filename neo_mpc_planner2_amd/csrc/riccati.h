@@ -1,5 +1,5 @@
 // riccati.h -- projected Newton direction by a stage-wise (Riccati) recursion over the rollout chain
-// Part of libneo_mpc.so's device code (included by neo_mpc_kernels.hip only).
+// Part of libneo_mpc.so's device code (included through k1_solve.h by neo_mpc_kernels.hip and neo_mpc_riccati.hip).
 //
 // The system is the one the dense Newton kernels solve -- H_r d = -g_r, H the exact Hessian of the
 // smooth part of the objective (py:250-252, 266-268) plus the control norm's curvature (py:253-254)
@@ -36,15 +36,19 @@
 //                    only yields a search direction; the float64 objective decides); each stage is solved
 //                    in the coordinates of its face (0-3 free directions) instead of through 3x3 projector
 //                    products.
-//   riccati_finish   lane = stage: back to control coordinates, du = B0^-1 w.
+//   riccati_finish   lane = stage: back to control coordinates, du = B0^-1 w.  (And riccati_free_space_trial, at the end.)
 #pragma once
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdint.h>
 
 #include "neo_mpc_device.h"
+#include "wave_ops.h"
 #include "fast_math.h"
 #include "solver_context.h"
+#include "solver_rules.h"
+#include "costmap.h"
+#include "feasible_set.h"
 
 namespace neo_mpc {
 namespace {
@@ -384,6 +388,54 @@ __device__ __forceinline__ void riccati_finish(const SolveArgs& a, const Ctx& c,
     }
   }
   WAVE_SYNC();
+}
+
+// lane = stage: the free-space trial of the full Newton step.  Rollout in free space (no costmap term at any stage: the objective is smooth up to the control
+// norm's kink): the full Newton step -- lane 32's candidate -- is tried on its own first, one objective
+// evaluation with lane = stage, and taken without the 64-candidate search when it achieves kTrialRatio of
+// the decrease the quadratic model promises (-1/2 g_r . step).  Measured at control_steps 32 (8192 cold
+// starts, CPU mirror): 71 % of such trials succeed, 3.9 searches saved per solve for 0.3 iterations more;
+// the results are the same.  (With a costmap term under the rollout the search's spread of candidates is
+// what steps over cost edges and out of lethal cells.)
+// Returns whether the step was taken: u_new then holds the new iterate, `fb` its objective and (kWantTerm) `cterm` the
+// costmap terms under its rollout.
+template <bool kTame, bool kCovered, int kFew, bool kWantTerm>
+__device__ __forceinline__ bool riccati_free_space_trial(const SolveArgs& a, const Ctx& c, double* L, int n, int lane,
+                                                         double alpha_now, double f, double& fb, double& cterm) {
+  constexpr double kTrialRatio = NEO_RULE_TRIAL_RATIO;
+  const DevParams& p = a.p;
+  const double *u = L + a.lds.u, *gr = L + a.lds.gr;
+  double* u_new = L + a.lds.u_new;
+  bool took_trial = false;
+  const bool on = lane < n;
+  double b0 = 0.0, b1 = 0.0, b2 = 0.0, g0 = 0.0, g1 = 0.0, g2 = 0.0;
+  if (on) {
+    candidate_block<kTame, true>(a, c, L, 32, 1.0, alpha_now, lane, b0, b1, b2);   // (lane 32: step length 1)
+    g0 = gr[3 * lane]; g1 = gr[3 * lane + 1]; g2 = gr[3 * lane + 2];   // (u_new takes the reduced gradient's place)
+    u_new[3 * lane] = b0; u_new[3 * lane + 1] = b1; u_new[3 * lane + 2] = b2;
+  }
+  auto scan = [](double v) { if constexpr (kFew > 0) return wave_scan_few<kFew>(v); else return wave_scan(v); };
+  auto sum = [](double v) { if constexpr (kFew > 0) return wave_sum_few<kFew>(v); else return wave_sum(v); };
+  const double th = scan(b2 * p.dt);
+  double sn, cs;
+  sincos_heading<kTame>(th, &sn, &cs);
+  const double x = scan((b0 * cs - b1 * sn) * p.dt), y = scan((b0 * sn + b1 * cs) * p.dt);
+  double fi = 0.0, pr = 0.0, tm = 0.0;   // (tm: the stage's costmap term alone)
+  if (on) {
+    const double dx = c.cx - x, dy = c.cy - y, et = c.tyaw - th;
+    const double e0 = c.v0 - b0, e1 = c.v1 - b1, e2 = c.v2 - b2;
+    tm = step_term<kCovered>(a, c, L, x, y);
+    fi = p.wt_n * (dx * dx + dy * dy) + p.wo_n * (et * et) + p.wc_n * sqrt_fast(e0 * e0 + e1 * e1 + e2 * e2) + tm;
+    if (lane == n - 1) { const double ef = c.fyaw - th; fi += p.wterm_o * (ef * ef); }
+    pr = -0.5 * (g0 * (b0 - u[3 * lane]) + g1 * (b1 - u[3 * lane + 1]) + g2 * (b2 - u[3 * lane + 2]));
+  }
+  const double ft = sum(fi), pred = sum(pr);
+  if (ft < f && f - ft >= kTrialRatio * pred) {
+    took_trial = true; fb = ft;
+    if (kWantTerm) cterm = sum(tm);   // (the blocked-run rule asks whether the new iterate's rollout is free)
+  }
+  WAVE_SYNC();
+  return took_trial;
 }
 
 }  // namespace

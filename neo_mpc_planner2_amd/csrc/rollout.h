@@ -1,5 +1,5 @@
 // rollout.h -- rollout + objective of one control sequence (py:224-268), set-up shared by the kernels, K2 (py:365-403)
-// Part of libneo_mpc.so's device code (included by neo_mpc_kernels.hip only).
+// Part of libneo_mpc.so's device code (included through k1_solve.h by neo_mpc_kernels.hip and neo_mpc_riccati.hip).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <math.h>

@@ -1,7 +1,7 @@
 /* solver_rules.h -- every constant and derived tolerance of the search, ONCE.
  *
  * Plain C: included by the host side of the library (neo_mpc_capi.cpp: derive()), by the device code
- * (neo_mpc_kernels.hip, costmap.h) and by the CPU mirror of the search that the test infrastructure keeps (mpc_oracle.c, part 2 --
+ * (k1_solve.h, costmap.h) and by the CPU mirror of the search that the test infrastructure keeps (mpc_oracle.c, part 2 --
  * the mirror follows the build's algorithm by construction and takes its rule book from here; the restatement of the
  * REFERENCE in the same file shares nothing with the product).  A threshold changed here changes on the GPU and in
  * the mirror at once. */

@@ -14,7 +14,7 @@
  * at that boundary), SLSQP is exercised through oracle/mpc_oracle.py + SciPy.
  *
  * Part 2 is a scalar CPU mirror of the build's batched solver (the algorithm of
- * neo_mpc_planner2_amd/csrc/neo_mpc_kernels.hip: L-BFGS / proximal-gradient
+ * neo_mpc_planner2_amd/csrc/k1_solve.h: L-BFGS / proximal-gradient
  * projected arc search with 64 candidates per iteration), written independently of
  * the HIP source so that GPU results can be checked against it on the same inputs.
  *

@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """Static instruction count of one kernel per top-level source line (inlined code is attributed to
 the call site inside the kernel).  usage: asm_profile.py <kernel-mangled-substring> [lo hi]
-Compiles neo_mpc_kernels.hip with -gline-tables-only -S (device only) and parses the .loc chain."""
+Compiles the kernel's translation unit with -gline-tables-only -S (device only) and parses the .loc chain; the lines are
+those of k1_solve.h, where K1 lives."""
 import collections, os, re, subprocess, sys
 root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 key = sys.argv[1]
@@ -23,13 +24,10 @@ cnt = collections.defaultdict(collections.Counter)
 for l in text[start:end]:
     m = re.match(r"\s*\.loc\s+(\d+)\s+(\d+)\s+\d+", l)
     if m:
-        chain = re.findall(r"neo_mpc_kernels\.hip:(\d+):\d+", l)
+        chain = re.findall(r"k1_solve\.h:(\d+):\d+", l)
         if chain:
             cur = int(chain[-2]) if len(chain) >= 2 else int(chain[-1])   # the frame under the kernel's call site: the line in solve_search (K1 is split into solve_setup / solve_search / solve_finish)
-            inner = int(chain[0]) if "neo_mpc_kernels.hip:%s:" % chain[0] in l.split("@[")[0] else -int(m.group(2))
-        elif int(m.group(1)) <= 1:
-            cur = int(m.group(2))       # not inlined: the kernel's own line
-            inner = cur
+            inner = int(chain[0]) if "k1_solve.h:%s:" % chain[0] in l.split("@[")[0] else -int(m.group(2))
         continue
     t = l.strip()
     if not t or t[0] in ".;_" or t.endswith(":"):
@@ -47,6 +45,6 @@ for k in sorted(cnt):
     tot.update(cnt[k])
 print("total", dict(tot))
 if by_inner:
-    print("-- by innermost source line (negative: a line of a system header) inside [%d, %d]" % (lo, hi))
+    print("-- by innermost source line (negative: a line of another header) inside [%d, %d]" % (lo, hi))
     for k in sorted(by_inner):
         print(k, sum(by_inner[k].values()), dict(by_inner[k]))

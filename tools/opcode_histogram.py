@@ -23,7 +23,7 @@ subprocess.run(["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++
                (["-fno-slp-vectorize", "-mllvm", "-disable-machine-licm"] if riccati else []) +
                ["-gline-tables-only", "-x", "hip", "--cuda-device-only", "-S", src, "-o", out],
                check=True, stderr=subprocess.DEVNULL)
-ksrc = open(os.path.join(csrc, "neo_mpc_kernels.hip")).read().split("\n")
+ksrc = open(os.path.join(csrc, "k1_solve.h")).read().split("\n")   # (K1's own file: the lines below are its lines)
 loop_lo = next(i + 1 for i, l in enumerate(ksrc) if "for (; it < p.max_it && !scan_only; ++it) {" in l)
 branch = sys.argv[sys.argv.index("--branch") + 1] if "--branch" in sys.argv else None
 # (the two call sites of solve_search in k_solve_routed: direction 2 = stage-wise, 1 = dense)
@@ -84,11 +84,9 @@ dpp_loop = 0
 for l in text[start:end]:
     m = re.match(r"\s*\.loc\s+(\d+)\s+(\d+)\s+\d+", l)
     if m:
-        chain = [int(x) for x in re.findall(r"neo_mpc_kernels\.hip:(\d+):\d+", l)]
-        own = int(m.group(2)) if int(m.group(1)) <= 1 else None    # (the .loc's own line when it is in neo_mpc_kernels.hip)
-        frames = ([own] if own is not None and not chain else []) + chain   # innermost ... outermost (the kernel's call site)
-        if own is not None and chain:
-            frames = [own] + chain
+        # the frames of the inlining chain that lie in k1_solve.h: innermost ... outermost (the kernel's call site)
+        # (a .loc at column 0 names its own line without a column)
+        frames = [int(x) for x in re.findall(r"k1_solve\.h:(\d+)(?::\d+)?", l)]
         skip = branch is not None and site[branch] not in frames
         # the line in solve_search: the frame under the kernel-level call site (a plain kernel: its own line)
         cur = frames[-2] if len(frames) >= 2 else (frames[-1] if frames else cur)
