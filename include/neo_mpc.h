@@ -33,6 +33,8 @@ extern "C" {
  * NEO_MPC_FLAG_SKIPPED; neo_mpc_carrot.status 3.  No record changed its size or the offset of a field that existed.
  * Round 5 added entry points only (neo_mpc_effective_method, neo_mpc_balance_dispatch_device) and gave the last 28 bytes
  * of neo_mpc_state, reserved until then, a meaning (has_prev_u0, prev_u0): still ABI 2.
+ * The footprint gate (neo_mpc_footprint_batch, neo_mpc_footprint_gate, neo_mpc_footprint_gate_device) added a record and two
+ * entry points; no existing record, entry point or result changed: still ABI 2, behaviour 6.
  *
  * Behaviour history (iterates and iteration counts differ between versions, results stay inside the parity protocol of
  * DESIGN.md section 1; neo_mpc_behaviour_version() returns the number of the build that answers):
@@ -277,6 +279,44 @@ typedef struct neo_mpc_plan_batch {
                                     requests the solver will consume (cpp:242) */
 } neo_mpc_plan_batch;
 
+/* ---- the step in front of the carrot: the footprint gate (cpp:218-219) ------------------------- */
+
+/* `collision_checker_->footprintCostAtPose(x, y, yaw, footprint)` (cpp:218-219) for `count` robots on the costmap(s) the
+ * handle holds -- nav2's FootprintCollisionChecker<Costmap2D*> (Humble) with nav2_util::LineIterator and
+ * Costmap2D::worldToMap, evaluated on the raw cell values:
+ *   oriented polygon  P_j = (x + p_j.x cos(yaw) - p_j.y sin(yaw), y + p_j.x sin(yaw) + p_j.y cos(yaw)), float64;
+ *   cell of a vertex  off the map when X < origin_x, Y < origin_y or a coordinate is not finite; else
+ *                     mx = trunc((X - origin_x) / resolution), my likewise, off the map unless mx < size_x and my < size_y
+ *                     (the map's true size -- not the lethal border the device copy carries);
+ *   cells of an edge  LineIterator from (x0, y0) to (x1, y1), end points included: with dx = |x1 - x0|, dy = |y1 - y0|,
+ *                     sx, sy = +1 / -1 (+1 when equal) and dx >= dy, cell k = 0 .. dx is
+ *                     (x0 + sx k, y0 + sy ((dx / 2 + k dy) / dx)) in integer arithmetic (dx = 0: the one cell); dx < dy: the
+ *                     same with the axes swapped;
+ *   cost of an edge   254 when any of its cells is 254, else the largest raw value among them (which may be 255);
+ *   cost of the outline (order-dependent, like nav2's fold)  254 when P_0 is off the map; then with c = 0, for
+ *                     j = 0 .. n - 2: 254 when P_(j+1) is off the map; c = max(c, edge(j, j + 1)); 254 when c == 254;
+ *                     at the end max(c, edge(n - 1, 0)).  255 comes out when an unknown cell was met before a lethal one
+ *                     decided the fold: the plugin throws on 255 (cpp:234-236) and not on 254.
+ * This is NOT the py:343 outline cost that neo_mpc_batch.footprints feeds (a different line walk on normalised costs).
+ * Pointers are host pointers for neo_mpc_footprint_gate and device pointers for neo_mpc_footprint_gate_device.  64 bytes. */
+typedef struct neo_mpc_footprint_batch {
+  size_t count;
+  const double* footprint;       /* [footprint_points][2] base frame, shared by every robot -- or, with
+                                    per_robot_footprints, [count][footprint_points][2] */
+  uint32_t footprint_points;     /* 3 .. NEO_MPC_MAX_FOOTPRINT_POINTS */
+  uint32_t per_robot_footprints; /* 0: one polygon for all; 1: one per robot; anything else is refused */
+  const double* poses;           /* optional [count][3]: x, y, yaw in the costmap's global frame.  NULL: problems[i].cur_xy and
+                                    the yaw of problems[i].cur_q (py:176-178) */
+  const int32_t* map_indices;    /* optional [count]: which map of a pool.  NULL: problems[i].map_index, or 0 without
+                                    `problems`.  Ignored with a single costmap, like neo_mpc_problem.map_index */
+  neo_mpc_problem* problems;     /* optional [count] (required when `poses` is NULL): footprint_cost is written as
+                                    cost >= 254 ? 1.0 : 0.0; no other byte of the records is touched (`skip` stays
+                                    neo_mpc_select_carrots' to set) */
+  double* footprint_costs;       /* [count] out: nav2's 0 .. 255 scale -- what neo_mpc_plan_batch.footprint_costs takes */
+  double* footprints_out;        /* optional [count][footprint_points][2] out: the oriented polygons, global frame -- what
+                                    neo_mpc_batch.footprints takes */
+} neo_mpc_footprint_batch;
+
 typedef struct neo_mpc_handle neo_mpc_handle;
 
 /* library / ABI */
@@ -425,6 +465,19 @@ int neo_mpc_select_carrots(neo_mpc_handle* handle, const neo_mpc_lookahead_param
                            const neo_mpc_plan_batch* batch);
 int neo_mpc_select_carrots_device(neo_mpc_handle* handle, const neo_mpc_lookahead_params* params,
                                   const neo_mpc_plan_batch* batch, void* stream);
+
+/* The footprint gate for `count` robots (neo_mpc_footprint_batch above).  Host pointers, synchronous: the results are in the
+ * caller's arrays when it returns.  NEO_MPC_ERR_NO_COSTMAP before a costmap is set; NEO_MPC_ERR_INVALID_ARGUMENT for
+ * footprint_points outside 3 .. 16, a null `footprint` / `footprint_costs`, `poses` and `problems` both null, a pose, quaternion
+ * or polygon coordinate that is not finite, and -- with a costmap pool -- a map index (map_indices[i], else
+ * problems[i].map_index) outside [0, pool size).  count == 0 is NEO_MPC_OK and launches nothing. */
+int neo_mpc_footprint_gate(neo_mpc_handle* handle, const neo_mpc_footprint_batch* batch);
+/* Same with every pointer in device memory; enqueued on `stream` (hipStream_t, may be NULL), returns without waiting.  The
+ * values are not looked at on the host: a coordinate that is not finite puts its vertex off the map (cost 254), and a map
+ * index outside the pool is clamped into it -- below 0 reads map 0, beyond the last map the last one -- exactly as the solve
+ * kernel treats neo_mpc_problem.map_index.  Both variants wait for a costmap ingest in flight on their stream and count as a
+ * user of the device map for the next ingest, like a solve (see neo_mpc_set_costmap). */
+int neo_mpc_footprint_gate_device(neo_mpc_handle* handle, const neo_mpc_footprint_batch* batch, void* stream);
 
 /* ---- multi-GPU fleets: the one exchange step ------------------------------------------------
  * Instances of one tick shard embarrassingly over the GPUs of a node (one handle per GPU, costmap and parameters

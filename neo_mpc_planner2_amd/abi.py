@@ -131,6 +131,13 @@ class NeoMpcPlanBatch(_C.Structure):
                 ("carrots", _C.c_void_p), ("problems", _C.c_void_p)]
 
 
+class NeoMpcFootprintBatch(_C.Structure):
+    """`neo_mpc_footprint_batch` (include/neo_mpc.h): one footprint gate call (NeoMpcPlanner.cpp:218-219)."""
+    _fields_ = [("count", _C.c_size_t), ("footprint", _C.c_void_p), ("footprint_points", _C.c_uint32),
+                ("per_robot_footprints", _C.c_uint32), ("poses", _C.c_void_p), ("map_indices", _C.c_void_p),
+                ("problems", _C.c_void_p), ("footprint_costs", _C.c_void_p), ("footprints_out", _C.c_void_p)]
+
+
 def params_struct(params=None, **over):
     """dict of ROS parameter names (+ solver options) -> NeoMpcParams.  Missing names take
     the reference node's declared defaults (py:49-75)."""

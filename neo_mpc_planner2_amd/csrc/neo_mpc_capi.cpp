@@ -89,6 +89,7 @@ struct neo_mpc_handle {
   DeviceBuffer map_buf, raw_buf, term_buf, origins_buf;
   DeviceBuffer problems, states, warm, commands, solution, path, footprints, success, u, cost;
   DeviceBuffer plan_poses, plan_offsets, robot_poses, fp_costs, slow_down, carrots, vel;
+  DeviceBuffer gate_polygon, gate_poses, gate_indices, gate_polygons_out;   // neo_mpc_footprint_gate (its costs: fp_costs)
   // latency path of neo_mpc_solve_batch (small host batches, the plugin's count = 1): one pinned
   // staging block and one device arena, so a tick is one H2D, K1, one D2H and one synchronisation
   void* pin = nullptr;
@@ -504,7 +505,8 @@ void neo_mpc_destroy(neo_mpc_handle* h) {
   DeviceBuffer* all[] = {&h->map_buf, &h->raw_buf, &h->term_buf, &h->problems, &h->states, &h->warm, &h->commands,
                          &h->solution, &h->path, &h->footprints, &h->success, &h->u, &h->cost, &h->plan_poses,
                          &h->plan_offsets, &h->robot_poses, &h->fp_costs, &h->slow_down, &h->carrots, &h->vel,
-                         &h->arena, &h->origins_buf, &h->order_buf, &h->load_buf};
+                         &h->arena, &h->origins_buf, &h->order_buf, &h->load_buf, &h->gate_polygon, &h->gate_poses,
+                         &h->gate_indices, &h->gate_polygons_out};
   for (DeviceBuffer* b : all) b->release();
   if (h->pin) (void)hipHostFree(h->pin);
   if (h->map_ready) (void)hipEventDestroy(h->map_ready);
@@ -1101,6 +1103,106 @@ int neo_mpc_select_carrots(neo_mpc_handle* h, const neo_mpc_lookahead_params* lp
   HIP_TRY(hipMemcpy(b->slow_down, h->slow_down.ptr, n * 4, hipMemcpyDeviceToHost));
   if (b->problems)
     HIP_TRY(hipMemcpy(b->problems, h->problems.ptr, n * sizeof(neo_mpc_problem), hipMemcpyDeviceToHost));
+  return NEO_MPC_OK;
+}
+
+// K6.  What both gate entry points check: the record's shape, never a value behind a pointer.
+static int check_footprint_batch(const neo_mpc_handle* h, const neo_mpc_footprint_batch* b) {
+  if (!h || !b) return fail(NEO_MPC_ERR_INVALID_ARGUMENT, "null argument");
+  if (!h->has_map) return fail(NEO_MPC_ERR_NO_COSTMAP, "neo_mpc_set_costmap has not been called");
+  if (b->footprint_points < 3 || b->footprint_points > NEO_MPC_MAX_FOOTPRINT_POINTS)
+    return fail(NEO_MPC_ERR_INVALID_ARGUMENT, "footprint_points %u outside [3, %d]", b->footprint_points,
+                NEO_MPC_MAX_FOOTPRINT_POINTS);
+  if (b->per_robot_footprints > 1)
+    return fail(NEO_MPC_ERR_INVALID_ARGUMENT, "per_robot_footprints must be 0 or 1 (got %u)", b->per_robot_footprints);
+  if (b->count > 0x7fffffffull) return fail(NEO_MPC_ERR_INVALID_ARGUMENT, "count too large");
+  if (b->count > 0 && (!b->footprint || !b->footprint_costs))
+    return fail(NEO_MPC_ERR_INVALID_ARGUMENT, "footprint/footprint_costs must not be null");
+  if (b->count > 0 && !b->poses && !b->problems)
+    return fail(NEO_MPC_ERR_INVALID_ARGUMENT, "poses and problems are both null: no pose to place the footprint at");
+  return NEO_MPC_OK;
+}
+
+static void fill_gate_args(const neo_mpc_handle* h, const neo_mpc_footprint_batch& d, FootprintGateArgs& a) {
+  std::memset(&a, 0, sizeof(a));
+  a.footprint = d.footprint; a.poses = d.poses; a.map_indices = d.map_indices; a.problems = d.problems;
+  a.footprint_costs = d.footprint_costs; a.footprints_out = d.footprints_out;
+  a.count = (uint32_t)d.count; a.footprint_points = d.footprint_points; a.per_robot = d.per_robot_footprints;
+  a.map = h->map;
+}
+
+int neo_mpc_footprint_gate_device(neo_mpc_handle* h, const neo_mpc_footprint_batch* b, void* stream) {
+  int rc = check_footprint_batch(h, b);
+  if (rc) return rc;
+  if (b->count == 0) return NEO_MPC_OK;
+  HIP_TRY(hipSetDevice(h->device));
+  FootprintGateArgs a;
+  fill_gate_args(h, *b, a);
+  if ((rc = map_acquire(h, stream))) return rc;
+  launch_footprint_gate(a, stream);
+  HIP_TRY(hipGetLastError());
+  return map_release(h, stream);
+}
+
+int neo_mpc_footprint_gate(neo_mpc_handle* h, const neo_mpc_footprint_batch* b) {
+  int rc = check_footprint_batch(h, b);
+  if (rc) return rc;
+  if (b->count == 0) return NEO_MPC_OK;
+  const size_t n = b->count, np = b->footprint_points, poly_doubles = (b->per_robot_footprints ? n : 1) * np * 2;
+  // the values the device variant takes as they come are looked at here
+  for (size_t k = 0; k < poly_doubles; ++k)
+    if (!std::isfinite(b->footprint[k]))
+      return fail(NEO_MPC_ERR_INVALID_ARGUMENT, "footprint vertex %zu of polygon %zu is not finite", (k / 2) % np, k / (2 * np));
+  for (size_t i = 0; i < n; ++i) {
+    bool finite = true;
+    if (b->poses) for (int k = 0; k < 3; ++k) finite = finite && std::isfinite(b->poses[3 * i + k]);
+    else {
+      for (int k = 0; k < 2; ++k) finite = finite && std::isfinite(b->problems[i].cur_xy[k]);
+      for (int k = 0; k < 4; ++k) finite = finite && std::isfinite(b->problems[i].cur_q[k]);
+    }
+    if (!finite) return fail(NEO_MPC_ERR_INVALID_ARGUMENT, "the pose of robot %zu is not finite", i);
+    if (h->map.pool_count > 0 && (b->map_indices || b->problems)) {
+      const int32_t idx = b->map_indices ? b->map_indices[i] : b->problems[i].map_index;
+      if (idx < 0 || idx >= h->map.pool_count)
+        return fail(NEO_MPC_ERR_INVALID_ARGUMENT, "map index %d of robot %zu outside the pool of %d maps", idx, i, h->map.pool_count);
+    }
+  }
+  HIP_TRY(hipSetDevice(h->device));
+  if ((rc = h->gate_polygon.reserve(poly_doubles * 8))) return rc;
+  if ((rc = h->fp_costs.reserve(n * 8))) return rc;
+  neo_mpc_footprint_batch d = *b;
+  HIP_TRY(hipMemcpy(h->gate_polygon.ptr, b->footprint, poly_doubles * 8, hipMemcpyHostToDevice));
+  d.footprint = (const double*)h->gate_polygon.ptr;
+  d.footprint_costs = (double*)h->fp_costs.ptr;
+  if (b->poses) {
+    if ((rc = h->gate_poses.reserve(n * 24))) return rc;
+    HIP_TRY(hipMemcpy(h->gate_poses.ptr, b->poses, n * 24, hipMemcpyHostToDevice));
+    d.poses = (const double*)h->gate_poses.ptr;
+  }
+  if (b->map_indices) {
+    if ((rc = h->gate_indices.reserve(n * 4))) return rc;
+    HIP_TRY(hipMemcpy(h->gate_indices.ptr, b->map_indices, n * 4, hipMemcpyHostToDevice));
+    d.map_indices = (const int32_t*)h->gate_indices.ptr;
+  }
+  if (b->problems) {
+    if ((rc = h->problems.reserve(n * sizeof(neo_mpc_problem)))) return rc;
+    HIP_TRY(hipMemcpy(h->problems.ptr, b->problems, n * sizeof(neo_mpc_problem), hipMemcpyHostToDevice));
+    d.problems = (neo_mpc_problem*)h->problems.ptr;
+  }
+  if (b->footprints_out) {
+    if ((rc = h->gate_polygons_out.reserve(n * np * 16))) return rc;
+    d.footprints_out = (double*)h->gate_polygons_out.ptr;
+  }
+  FootprintGateArgs a;
+  fill_gate_args(h, d, a);
+  if ((rc = map_acquire(h, nullptr))) return rc;
+  launch_footprint_gate(a, nullptr);
+  HIP_TRY(hipGetLastError());
+  if ((rc = map_release(h, nullptr))) return rc;
+  // (blocking copies on the null stream, behind the kernel; the records come back whole -- the kernel wrote footprint_cost alone)
+  HIP_TRY(hipMemcpy(b->footprint_costs, h->fp_costs.ptr, n * 8, hipMemcpyDeviceToHost));
+  if (b->footprints_out) HIP_TRY(hipMemcpy(b->footprints_out, h->gate_polygons_out.ptr, n * np * 16, hipMemcpyDeviceToHost));
+  if (b->problems) HIP_TRY(hipMemcpy(b->problems, h->problems.ptr, n * sizeof(neo_mpc_problem), hipMemcpyDeviceToHost));
   return NEO_MPC_OK;
 }
 

@@ -194,6 +194,20 @@ struct CarrotArgs {
   neo_mpc_plan_batch b;  // device pointers
 };
 
+// K6: the footprint gate (neo_mpc_footprint_batch, device pointers) on the handle's map(s)
+struct FootprintGateArgs {
+  const double* footprint;     // [points][2], or [count][points][2] with per_robot
+  const double* poses;         // optional [count][3]
+  const int32_t* map_indices;  // optional [count]
+  neo_mpc_problem* problems;   // optional [count]
+  double* footprint_costs;     // [count]
+  double* footprints_out;      // optional [count][points][2]
+  uint32_t count;
+  uint32_t footprint_points;
+  uint32_t per_robot;
+  DevMap map;
+};
+
 // A/B switches of the measurement tools: read from the environment ONCE, by neo_mpc_create (include/neo_mpc.h), kept in
 // the handle -- nothing on the solve path looks at the environment.
 struct LaunchTuning {
@@ -207,6 +221,7 @@ void launch_carrots(const CarrotArgs& a, void* stream);
 void launch_postprocess(const SolveArgs& a, void* stream);
 void launch_objective(const ObjectiveArgs& a, void* stream);
 void launch_ingest(const IngestArgs& a, const LaunchTuning& t, void* stream);
+void launch_footprint_gate(const FootprintGateArgs& a, void* stream);
 // K5: dispatch order of the next launch from the iteration counts of the previous one (neo_mpc_balance_dispatch_device)
 void launch_dispatch_order(const neo_mpc_command* commands, float* load, uint32_t* order, uint32_t count, bool fresh, void* stream);
 constexpr uint32_t kDispatchSimds = 1024;   // a 4096-instance launch is one residency round: workgroups w, w + 1024, w + 2048, w + 3072 share a SIMD

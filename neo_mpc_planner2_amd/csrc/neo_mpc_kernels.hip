@@ -15,7 +15,9 @@
 //                     (src/NeoMpcPlanner.cpp:83-104, 157-189, 221-232), HBM-streaming.
 //   k_objective       py:204-269 for given controls (parity checks of the objective).
 //   K5 k_dispatch_order  which instance each workgroup of a K1 launch solves (balanced dispatch).
+//   K6 k_footprint_gate  footprint_gate.h: the footprint gate in front of the carrot (cpp:218-219), one wave per robot.
 #include "k1_solve.h"
+#include "footprint_gate.h"
 
 namespace neo_mpc {
 namespace {
@@ -375,6 +377,11 @@ __global__ __launch_bounds__(1024) void k_dispatch_order(const neo_mpc_command* 
 void launch_dispatch_order(const neo_mpc_command* commands, float* load, uint32_t* order, uint32_t count, bool fresh, void* stream) {
   if (count == 0) return;
   hipLaunchKernelGGL(k_dispatch_order, dim3(1), dim3(1024), 0, (hipStream_t)stream, commands, load, order, count, fresh ? 1 : 0);
+}
+void launch_footprint_gate(const FootprintGateArgs& a, void* stream) {
+  if (a.count == 0) return;
+  hipLaunchKernelGGL(k_footprint_gate, dim3((a.count + kGateWaves - 1) / kGateWaves), dim3(kLanes * kGateWaves), 0,
+                     (hipStream_t)stream, a);
 }
 void launch_ingest(const IngestArgs& a, const LaunchTuning& tuning, void* stream) {
   const long total = (long)a.rows * (a.pitch >> 4);

@@ -13,14 +13,18 @@ import numpy as np
 from . import abi
 
 
-def closed_loop(solver, batch, ticks, hz=30.0, before_tick=None, after_tick=None, balance_every=0):
+def closed_loop(solver, batch, ticks, hz=30.0, before_tick=None, after_tick=None, balance_every=0, footprint=None):
     """Run `ticks` control ticks of `batch` (a solver.DeviceBatch) through `solver` (a BatchSolver with its costmap
     set).  Returns per-tick lists: kernel_ms (HIP events around the K1 launch), mean_iterations, max_iterations,
     stopped_fraction.  `before_tick(t, pos)` runs before tick t's launch (e.g. re-centre a costmap pool),
     `after_tick(t, commands)` after its commands are on the host.  `balance_every` = R > 0: every R-th tick the
     dispatch order of the following ticks is rebuilt from that tick's iteration counts (neo_mpc_balance_dispatch_device:
     one small kernel behind K1 on the same stream; `balance_ms` in the result is its own duration) -- results do not
-    depend on it, only which robots share a SIMD."""
+    depend on it, only which robots share a SIMD.  `footprint` = a base-frame polygon ((x, y), ...), e.g.
+    synthetic.RECT_FOOTPRINT: every tick runs the footprint gate (K6, neo_mpc_footprint_gate_device) at the loop's own
+    poses in front of K1 and hands K1 the oriented polygons (`footprints`), so the collision latch of py:343-347 acts on
+    the robots' real outlines; the result gains `footprint_lethal_fraction`, the share of robots whose gate cost is >= 254.
+    None: no gate, no polygons -- the loop every caller had before."""
     import torch
     b = batch
     P = b.problems.view(torch.float64).reshape(b.count, -1)          # the 32 doubles of each request
@@ -44,10 +48,21 @@ def closed_loop(solver, batch, ticks, hz=30.0, before_tick=None, after_tick=None
     torch.cuda.synchronize()
     out = {"kernel_ms": [], "mean_iterations": [], "max_iterations": [], "stopped_fraction": []}
     bal_evs = []
+    polygons = None
+    if footprint is not None:
+        base = torch.tensor(np.asarray(footprint, dtype=np.float64).reshape(-1, 2), device=pos.device)
+        gate_costs = torch.zeros(b.count, dtype=torch.float64, device=pos.device)
+        polygons = torch.zeros((b.count, base.shape[0], 2), dtype=torch.float64, device=pos.device)
+        out["footprint_lethal_fraction"] = []
     for t in range(ticks):
         if before_tick is not None:
             before_tick(t, pos)
-        solver.solve_device(b.problems, b.states, b.warm, b.commands, velocities=b.vel, events=evs[t])
+        if footprint is not None:
+            # (the requests ride along for their map_index -- a pool -- and get the normalised cost written)
+            solver.footprint_gate_device(base, gate_costs, poses=torch.cat([pos, yaw[:, None]], 1).contiguous(),
+                                         problems=b.problems, footprints_out=polygons)
+        solver.solve_device(b.problems, b.states, b.warm, b.commands, velocities=b.vel, events=evs[t],
+                            footprints=polygons)
         if balance_every and t % balance_every == 0:
             e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
             e0.record(stream)
@@ -77,6 +92,8 @@ def closed_loop(solver, batch, ticks, hz=30.0, before_tick=None, after_tick=None
         out["mean_iterations"].append(float(cm["iterations"].mean()))
         out["max_iterations"].append(int(cm["iterations"].max()))
         out["stopped_fraction"].append(float(((cm["flags"] & abi.FLAG_STOPPED) != 0).mean()))
+        if footprint is not None:
+            out["footprint_lethal_fraction"].append(float((gate_costs >= 254.0).double().mean().item()))
         if after_tick is not None:
             after_tick(t, cm)
     out["kernel_ms"] = [a.elapsed_time(e) for a, e in evs]

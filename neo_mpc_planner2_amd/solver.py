@@ -271,6 +271,66 @@ class BatchSolver:
             stream = torch.cuda.current_stream(robot_poses.device).cuda_stream
         _lib.check(self._lib.neo_mpc_select_carrots_device(self._handle, C.byref(lp), C.byref(b), C.c_void_p(stream)))
 
+    # -- footprint gate (the step before the carrot) --------------------------------------
+    def footprint_gate(self, footprint, poses=None, problems=None, map_indices=None, want_polygons=False):
+        """`footprintCostAtPose` (NeoMpcPlanner.cpp:218-219; nav2's FootprintCollisionChecker on raw cell values) for a
+        batch of host arrays.  `footprint`: the base-frame polygon, [points, 2] shared by every robot or
+        [count, points, 2] one per robot.  `poses` [count, 3] (x, y, yaw); without them `problems` supplies cur_xy and
+        the yaw of cur_q.  `map_indices` (int32) picks the map of a pool; without it problems["map_index"], else map 0.
+        When `problems` is given its footprint_cost is set in place (1.0 where the cost is >= 254, else 0.0).
+        Returns the costs on nav2's 0..255 scale (float64 [count]) -- what `select_carrots(footprint_costs=...)`
+        takes -- and with `want_polygons` also the oriented polygons [count, points, 2] (`solve(footprints=...)`)."""
+        footprint = np.ascontiguousarray(footprint, dtype=np.float64)
+        assert footprint.ndim in (2, 3) and footprint.shape[-1] == 2
+        b = abi.NeoMpcFootprintBatch()
+        if poses is not None:
+            poses = np.ascontiguousarray(poses, dtype=np.float64).reshape(-1, 3)
+            count = poses.shape[0]
+            b.poses = poses.ctypes.data
+        else:
+            assert problems is not None, "poses or problems"
+            count = problems.shape[0]
+        if problems is not None:
+            assert problems.dtype == abi.PROBLEM_DTYPE and problems.shape == (count,) and problems.flags.c_contiguous
+            b.problems = problems.ctypes.data
+        if map_indices is not None:
+            map_indices = np.ascontiguousarray(map_indices, dtype=np.int32)
+            assert map_indices.shape == (count,)
+            b.map_indices = map_indices.ctypes.data
+        assert footprint.ndim == 2 or footprint.shape[0] == count
+        points = footprint.shape[-2]
+        costs = np.zeros(count, dtype=np.float64)
+        polygons = np.zeros((count, points, 2), dtype=np.float64) if want_polygons else None
+        b.count = count
+        b.footprint = footprint.ctypes.data
+        b.footprint_points = points
+        b.per_robot_footprints = 1 if footprint.ndim == 3 else 0
+        b.footprint_costs = costs.ctypes.data
+        b.footprints_out = polygons.ctypes.data if want_polygons else None
+        _lib.check(self._lib.neo_mpc_footprint_gate(self._handle, C.byref(b)))
+        return (costs, polygons) if want_polygons else costs
+
+    def footprint_gate_device(self, footprint, footprint_costs, poses=None, problems=None, map_indices=None,
+                              footprints_out=None, stream=None):
+        """Device-resident variant: contiguous torch CUDA tensors (float64; `map_indices` int32; `problems` the request
+        records as bytes); enqueues K6 on `stream` (default: torch's current) and returns without waiting.
+        `footprint_costs` [count] and the optional `footprints_out` [count, points, 2] are written; `footprint` is
+        [points, 2] or [count, points, 2]."""
+        import torch
+        b = abi.NeoMpcFootprintBatch()
+        b.count = footprint_costs.shape[0]
+        b.footprint = footprint.data_ptr()
+        b.footprint_points = footprint.shape[-2]
+        b.per_robot_footprints = 1 if footprint.dim() == 3 else 0
+        b.poses = poses.data_ptr() if poses is not None else None
+        b.map_indices = map_indices.data_ptr() if map_indices is not None else None
+        b.problems = problems.data_ptr() if problems is not None else None
+        b.footprint_costs = footprint_costs.data_ptr()
+        b.footprints_out = footprints_out.data_ptr() if footprints_out is not None else None
+        if stream is None:
+            stream = torch.cuda.current_stream(footprint_costs.device).cuda_stream
+        _lib.check(self._lib.neo_mpc_footprint_gate_device(self._handle, C.byref(b), C.c_void_p(stream)))
+
     # -- device-resident batches (torch tensors as plain device memory) ----------------
     def balance_dispatch(self, commands, stream=None):
         """Dispatch order of the following device solves of the same count from the iteration counts in `commands` (a CUDA
