@@ -35,6 +35,8 @@ extern "C" {
  * of neo_mpc_state, reserved until then, a meaning (has_prev_u0, prev_u0): still ABI 2.
  * The footprint gate (neo_mpc_footprint_batch, neo_mpc_footprint_gate, neo_mpc_footprint_gate_device) added a record and two
  * entry points; no existing record, entry point or result changed: still ABI 2, behaviour 6.
+ * The rolling windows (neo_mpc_window_batch, neo_mpc_set_world_map[_device], neo_mpc_roll_costmap_pool[_device],
+ * neo_mpc_get_costmap_pool) added a record and five entry points in the same way: still ABI 2, behaviour 6.
  *
  * Behaviour history (iterates and iteration counts differ between versions, results stay inside the parity protocol of
  * DESIGN.md section 1; neo_mpc_behaviour_version() returns the number of the build that answers):
@@ -317,6 +319,53 @@ typedef struct neo_mpc_footprint_batch {
                                     neo_mpc_batch.footprints takes */
 } neo_mpc_footprint_batch;
 
+/* ---- the step in front of the gate: a fleet's rolling windows, cut from one world map (K7) ------------ */
+
+/* nav2 gives each robot a rolling local costmap, and those windows are not independent data: each is the static layer's map
+ * re-sampled around its robot (LayeredCostmap::updateMap -> Costmap2D::updateOrigin -> the rolling-window branch of
+ * StaticLayer::updateCosts).  A fleet server holds ONE world map; the library keeps a device copy of it
+ * (neo_mpc_set_world_map) and cuts `count` windows of one geometry from it where the maps live
+ * (neo_mpc_roll_costmap_pool): roll -> gate -> carrots -> solve.  nav2 cannot be built next to this library, so the text
+ * below is the contract (tests/rolling_window_reference.py is its executable form).
+ *
+ * All arithmetic is float64; each + - * / below is ONE correctly rounded operation, evaluated in the order written
+ * (nothing is fused into a multiply-add, no division becomes a multiplication by a reciprocal).
+ *
+ * Moving window k to pose (x, y) -- its origin (ox, oy) is state, in and out (`origins`):
+ *   Sx = (size_x - 1 + 0.5) * res                 getSizeInMetersX
+ *   nx = x - Sx / 2                               updateMap's new origin
+ *   q  = (nx - ox) / res
+ *   c  = trunc(q), toward zero                    updateOrigin's static_cast<int>; c = 0 where q is not finite or
+ *                                                 |q| >= 2^31 (nav2's conversion is undefined there; the device variant
+ *                                                 never looks at a value on the host)
+ *   ox <- ox + c * res                            the origin stays on its own lattice: a sub-cell move does not roll
+ *   likewise for y with size_y.
+ * Filling cell (i, j) of window k from the world map (WSX x WSY cells, resolution wres, origin (wox, woy), same frame as the
+ * windows; wres need not equal res):
+ *   wx = ox + (i + 0.5) * res, wy = oy + (j + 0.5) * res      mapToWorld
+ *   the cell is OUTSIDE when wx < wox or wy < woy              worldToMap's refusal -- not a truncation into cell 0
+ *   else qx = (wx - wox) / wres, qy = (wy - woy) / wres, and the cell is outside unless qx < WSX and qy < WSY (compared in
+ *   float64, before any conversion); inside, its value is world[trunc(qy)][trunc(qx)]
+ *   an outside cell gets `outside_value` (nav2's default_value: 255 with track_unknown_space, else 0).
+ * Out of scope: a tf transform between the world map's frame and the windows' (they are one frame); `use_maximum`; further
+ * layers (the world map IS the master grid the caller wants sampled, inflation included); stamping other robots into the
+ * windows.
+ * Pointers are host pointers for neo_mpc_roll_costmap_pool and device pointers for neo_mpc_roll_costmap_pool_device.
+ * 56 bytes. */
+typedef struct neo_mpc_window_batch {
+  size_t count;                    /* windows = maps of the pool: 1 .. NEO_MPC_MAX_POOL_MAPS (0: nothing happens) */
+  uint32_t size_x, size_y;         /* cells of one window */
+  double resolution;               /* of the windows */
+  const double* poses;             /* optional [count][3]: x, y, yaw -- neo_mpc_footprint_batch.poses' layout, so one array
+                                      serves the roll and the gate; the yaw is not read */
+  const neo_mpc_problem* problems; /* optional [count], used when `poses` is NULL: window k is centred on problems[k].cur_xy.
+                                      Both NULL: the windows stay where `origins` puts them and are filled again (the world
+                                      map changed) */
+  double* origins;                 /* [count][2] in/out */
+  uint32_t outside_value;          /* 0 .. 255 */
+  uint32_t reserved;               /* MUST be zero */
+} neo_mpc_window_batch;
+
 typedef struct neo_mpc_handle neo_mpc_handle;
 
 /* library / ABI */
@@ -478,6 +527,42 @@ int neo_mpc_footprint_gate(neo_mpc_handle* handle, const neo_mpc_footprint_batch
  * kernel treats neo_mpc_problem.map_index.  Both variants wait for a costmap ingest in flight on their stream and count as a
  * user of the device map for the next ingest, like a solve (see neo_mpc_set_costmap). */
 int neo_mpc_footprint_gate_device(neo_mpc_handle* handle, const neo_mpc_footprint_batch* batch, void* stream);
+
+/* The world map the rolling windows are cut from (neo_mpc_window_batch above): raw nav2 costs, row-major
+ * cells[my*size_x + mx], geometry checked like neo_mpc_set_costmap's.  The handle keeps its OWN device copy: `cells` is
+ * consumed before the call returns and no caller pointer is retained.  It does not touch the handle's costmap(s). */
+int neo_mpc_set_world_map(neo_mpc_handle* handle, const uint8_t* cells, uint32_t size_x, uint32_t size_y,
+                          double resolution, double origin_x, double origin_y);
+/* Same, `d_cells` in device memory: a device-to-device copy enqueued on `stream` (hipStream_t, may be NULL) -- `d_cells`
+ * is the caller's again once that copy has run.  Both variants wait for the last roll before they overwrite the copy; the
+ * copy has an event of its own and a roll on another stream waits for it. */
+int neo_mpc_set_world_map_device(neo_mpc_handle* handle, const uint8_t* d_cells, uint32_t size_x, uint32_t size_y,
+                                 double resolution, double origin_x, double origin_y, void* stream);
+
+/* Moves the windows to their robots and fills them from the world map (K7; the contract: neo_mpc_window_batch).  Afterwards
+ * the handle's costmap IS this pool -- `count` maps of size_x x size_y cells, stored as neo_mpc_set_costmap_pool stores
+ * them; it replaces whatever the handle held -- and every instance reads the window its neo_mpc_problem.map_index names.
+ * Host pointers, synchronous: `origins` has been written back when it returns.  NEO_MPC_ERR_NO_COSTMAP before
+ * neo_mpc_set_world_map; NEO_MPC_ERR_INVALID_ARGUMENT for a null `origins`, count > NEO_MPC_MAX_POOL_MAPS, a zero size, a
+ * resolution that is not positive and finite, outside_value > 255, a non-zero `reserved`, and a pose or origin that is not
+ * finite; a refused call leaves the handle's costmap as it was.  count == 0 is NEO_MPC_OK and launches nothing. */
+int neo_mpc_roll_costmap_pool(neo_mpc_handle* handle, const neo_mpc_window_batch* windows);
+/* Same with every pointer in device memory; enqueued on `stream`, returns without waiting; no value behind a pointer is
+ * looked at on the host.  `origins` is retained: it is read by every later solve and gate, exactly like `d_origins` of
+ * neo_mpc_set_costmap_pool_device, and must stay valid.  A roll with the geometry, count and `origins` pointer of the
+ * previous one allocates nothing and does not synchronise, so roll -> gate -> carrots -> solve can be captured in a HIP
+ * graph on one stream and replayed with new poses.  Ordering, both variants: a roll waits on its stream for the previous
+ * ingest or roll, for every launch still reading the device map and for the world map's copy, and the solves and gates
+ * behind it wait for it -- like neo_mpc_set_costmap. */
+int neo_mpc_roll_costmap_pool_device(neo_mpc_handle* handle, const neo_mpc_window_batch* windows, void* stream);
+
+/* Reads the handle's costmap(s) back: the raw cells of maps [first, first + count) of the pool -- or of the single map, a
+ * pool of one -- without border and pitch, cells_out[count][size_y][size_x], and their origins, origins_out[count][2]
+ * (either may be NULL).  Host pointers, synchronous; waits for the ingest or roll in flight.  For callers whose windows
+ * exist in device memory only (logging, display).  NEO_MPC_ERR_NO_COSTMAP without a costmap, NEO_MPC_ERR_INVALID_ARGUMENT
+ * for a range outside the pool. */
+int neo_mpc_get_costmap_pool(neo_mpc_handle* handle, uint32_t first, uint32_t count, uint8_t* cells_out,
+                             double* origins_out);
 
 /* ---- multi-GPU fleets: the one exchange step ------------------------------------------------
  * Instances of one tick shard embarrassingly over the GPUs of a node (one handle per GPU, costmap and parameters

@@ -24,6 +24,8 @@ EXPORTS = (
     "neo_mpc_kernel_info", "neo_mpc_pin_host_memory", "neo_mpc_unpin_host_memory", "neo_mpc_set_host_path",
     "neo_mpc_select_carrots", "neo_mpc_select_carrots_device",
     "neo_mpc_footprint_gate", "neo_mpc_footprint_gate_device",
+    "neo_mpc_set_world_map", "neo_mpc_set_world_map_device", "neo_mpc_roll_costmap_pool",
+    "neo_mpc_roll_costmap_pool_device", "neo_mpc_get_costmap_pool",
     "neo_mpc_rccl_available", "neo_mpc_comm_init_all", "neo_mpc_comm_destroy", "neo_mpc_group_start",
     "neo_mpc_group_end", "neo_mpc_allgather_velocities", "neo_mpc_broadcast_costmap",
 )
@@ -104,6 +106,13 @@ def load():
         lib.neo_mpc_balance_dispatch_device.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
         lib.neo_mpc_footprint_gate.argtypes = [C.c_void_p, P(abi.NeoMpcFootprintBatch)]
         lib.neo_mpc_footprint_gate_device.argtypes = [C.c_void_p, P(abi.NeoMpcFootprintBatch), C.c_void_p]
+        lib.neo_mpc_set_world_map.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_double, C.c_double,
+                                              C.c_double]
+        lib.neo_mpc_set_world_map_device.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_double,
+                                                     C.c_double, C.c_double, C.c_void_p]
+        lib.neo_mpc_roll_costmap_pool.argtypes = [C.c_void_p, P(abi.NeoMpcWindowBatch)]
+        lib.neo_mpc_roll_costmap_pool_device.argtypes = [C.c_void_p, P(abi.NeoMpcWindowBatch), C.c_void_p]
+        lib.neo_mpc_get_costmap_pool.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p]
     _lib = lib
     return lib
 

@@ -138,6 +138,13 @@ class NeoMpcFootprintBatch(_C.Structure):
                 ("problems", _C.c_void_p), ("footprint_costs", _C.c_void_p), ("footprints_out", _C.c_void_p)]
 
 
+class NeoMpcWindowBatch(_C.Structure):
+    """`neo_mpc_window_batch` (include/neo_mpc.h): one roll of a fleet's costmap windows over the world map."""
+    _fields_ = [("count", _C.c_size_t), ("size_x", _C.c_uint32), ("size_y", _C.c_uint32), ("resolution", _C.c_double),
+                ("poses", _C.c_void_p), ("problems", _C.c_void_p), ("origins", _C.c_void_p),
+                ("outside_value", _C.c_uint32), ("reserved", _C.c_uint32)]
+
+
 def params_struct(params=None, **over):
     """dict of ROS parameter names (+ solver options) -> NeoMpcParams.  Missing names take
     the reference node's declared defaults (py:49-75)."""

@@ -90,6 +90,15 @@ struct neo_mpc_handle {
   DeviceBuffer problems, states, warm, commands, solution, path, footprints, success, u, cost;
   DeviceBuffer plan_poses, plan_offsets, robot_poses, fp_costs, slow_down, carrots, vel;
   DeviceBuffer gate_polygon, gate_poses, gate_indices, gate_polygons_out;   // neo_mpc_footprint_gate (its costs: fp_costs)
+  // neo_mpc_set_world_map / neo_mpc_roll_costmap_pool (K7): the handle's own copy of the world map, the fill's index tables
+  // and the host variant's poses (its origins: origins_buf)
+  DeviceBuffer world_buf, roll_tables, roll_poses;
+  bool has_world = false;
+  int32_t world_size_x = 0, world_size_y = 0;
+  double world_resolution = 0.0, world_origin_x = 0.0, world_origin_y = 0.0;
+  hipEvent_t world_ready = nullptr;         // recorded behind the copy into world_buf; a roll on another stream waits for it
+  hipStream_t world_ready_stream = nullptr;
+  bool rolled = false;                      // the device map was written by a roll (map_ready: that roll's end)
   // latency path of neo_mpc_solve_batch (small host batches, the plugin's count = 1): one pinned
   // staging block and one device arena, so a tick is one H2D, K1, one D2H and one synchronisation
   void* pin = nullptr;
@@ -322,6 +331,7 @@ int ingest(neo_mpc_handle* h, const uint8_t* d_cells, uint32_t maps, uint32_t sx
   h->map.pool_stride = (int64_t)stride;
   h->map.pool_origins = d_origins;
   h->has_map = true;
+  h->rolled = false;
   derive(h);
   return NEO_MPC_OK;
 }
@@ -506,10 +516,11 @@ void neo_mpc_destroy(neo_mpc_handle* h) {
                          &h->solution, &h->path, &h->footprints, &h->success, &h->u, &h->cost, &h->plan_poses,
                          &h->plan_offsets, &h->robot_poses, &h->fp_costs, &h->slow_down, &h->carrots, &h->vel,
                          &h->arena, &h->origins_buf, &h->order_buf, &h->load_buf, &h->gate_polygon, &h->gate_poses,
-                         &h->gate_indices, &h->gate_polygons_out};
+                         &h->gate_indices, &h->gate_polygons_out, &h->world_buf, &h->roll_tables, &h->roll_poses};
   for (DeviceBuffer* b : all) b->release();
   if (h->pin) (void)hipHostFree(h->pin);
   if (h->map_ready) (void)hipEventDestroy(h->map_ready);
+  if (h->world_ready) (void)hipEventDestroy(h->world_ready);
   for (auto& u : h->map_users) (void)hipEventDestroy(u.done);
   for (hipStream_t cs : h->chunk_streams) if (cs) (void)hipStreamDestroy(cs);
   for (auto& f : h->in_flight) {
@@ -1203,6 +1214,193 @@ int neo_mpc_footprint_gate(neo_mpc_handle* h, const neo_mpc_footprint_batch* b) 
   HIP_TRY(hipMemcpy(b->footprint_costs, h->fp_costs.ptr, n * 8, hipMemcpyDeviceToHost));
   if (b->footprints_out) HIP_TRY(hipMemcpy(b->footprints_out, h->gate_polygons_out.ptr, n * np * 16, hipMemcpyDeviceToHost));
   if (b->problems) HIP_TRY(hipMemcpy(b->problems, h->problems.ptr, n * sizeof(neo_mpc_problem), hipMemcpyDeviceToHost));
+  return NEO_MPC_OK;
+}
+
+// K7.  The world map: the handle's own device copy, from host cells (stream == nullptr, blocking) or device cells (on `stream`).
+static int set_world_map(neo_mpc_handle* h, const uint8_t* cells, bool on_device, uint32_t sx, uint32_t sy, double res, double ox,
+                         double oy, void* stream) {
+  if (!h || !cells) return fail(NEO_MPC_ERR_INVALID_ARGUMENT, "null argument");
+  if (sx == 0 || sy == 0 || sx > (1u << 20) || sy > (1u << 20) || !(res > 0.0) || !std::isfinite(res) || !std::isfinite(ox) ||
+      !std::isfinite(oy))
+    return fail(NEO_MPC_ERR_INVALID_ARGUMENT, "bad world map geometry %ux%u res %g origin (%g, %g)", sx, sy, res, ox, oy);
+  HIP_TRY(hipSetDevice(h->device));
+  hipStream_t st = (hipStream_t)stream;
+  const size_t bytes = (size_t)sx * sy;
+  // behind the last roll, which reads the copy that is about to be overwritten (and behind the previous copy)
+  if (on_device) {
+    if (h->rolled && h->map_ready_stream != st) HIP_TRY(hipStreamWaitEvent(st, h->map_ready, 0));
+    if (h->world_ready && h->world_ready_stream != st) HIP_TRY(hipStreamWaitEvent(st, h->world_ready, 0));
+  } else {
+    if (h->rolled) HIP_TRY(hipEventSynchronize(h->map_ready));
+    if (h->world_ready) HIP_TRY(hipEventSynchronize(h->world_ready));
+  }
+  int rc = h->world_buf.reserve(bytes);
+  if (rc) { h->has_world = false; return rc; }   // (a failed re-allocation has let the old copy go)
+  if (on_device) HIP_TRY(hipMemcpyAsync(h->world_buf.ptr, cells, bytes, hipMemcpyDeviceToDevice, st));
+  else HIP_TRY(hipMemcpy(h->world_buf.ptr, cells, bytes, hipMemcpyHostToDevice));
+  if (!h->world_ready) HIP_TRY(hipEventCreateWithFlags(&h->world_ready, hipEventDisableTiming));
+  HIP_TRY(hipEventRecord(h->world_ready, st));
+  h->world_ready_stream = st;
+  h->world_size_x = (int32_t)sx; h->world_size_y = (int32_t)sy;
+  h->world_resolution = res; h->world_origin_x = ox; h->world_origin_y = oy;
+  h->has_world = true;
+  return NEO_MPC_OK;
+}
+
+int neo_mpc_set_world_map(neo_mpc_handle* h, const uint8_t* cells, uint32_t sx, uint32_t sy, double res, double ox, double oy) {
+  return set_world_map(h, cells, false, sx, sy, res, ox, oy, nullptr);
+}
+
+int neo_mpc_set_world_map_device(neo_mpc_handle* h, const uint8_t* d_cells, uint32_t sx, uint32_t sy, double res, double ox,
+                                 double oy, void* stream) {
+  return set_world_map(h, d_cells, true, sx, sy, res, ox, oy, stream);
+}
+
+// What both roll entry points check: the record's shape, never a value behind a pointer.
+static int check_window_batch(const neo_mpc_handle* h, const neo_mpc_window_batch* w) {
+  if (!h || !w) return fail(NEO_MPC_ERR_INVALID_ARGUMENT, "null argument");
+  if (!h->has_world) return fail(NEO_MPC_ERR_NO_COSTMAP, "neo_mpc_set_world_map has not been called");
+  if (w->reserved != 0) return fail(NEO_MPC_ERR_INVALID_ARGUMENT, "neo_mpc_window_batch.reserved must be zero (got %u)", w->reserved);
+  if (w->outside_value > 255) return fail(NEO_MPC_ERR_INVALID_ARGUMENT, "outside_value %u is no cell value (0 .. 255)", w->outside_value);
+  if (w->count > NEO_MPC_MAX_POOL_MAPS)
+    return fail(NEO_MPC_ERR_INVALID_ARGUMENT, "%zu windows: a costmap pool holds at most %u maps", w->count, NEO_MPC_MAX_POOL_MAPS);
+  if (w->size_x == 0 || w->size_y == 0 || w->size_x > (1u << 20) || w->size_y > (1u << 20))
+    return fail(NEO_MPC_ERR_INVALID_ARGUMENT, "bad window size %ux%u", w->size_x, w->size_y);
+  if (!(w->resolution > 0.0) || !std::isfinite(w->resolution))
+    return fail(NEO_MPC_ERR_INVALID_ARGUMENT, "window resolution %g must be positive and finite", w->resolution);
+  if (w->count > 0 && !w->origins) return fail(NEO_MPC_ERR_INVALID_ARGUMENT, "origins must not be null");
+  const size_t pitch = (w->size_x + 2 * kPoolBorder + 127) & ~(size_t)127, rows = (size_t)w->size_y + 2 * kPoolBorder;
+  if (pitch * rows / 16 >= (1ull << 31))   // K7 indexes the 16-byte chunks of one map with 32 bits, like K3
+    return fail(NEO_MPC_ERR_UNSUPPORTED, "window %ux%u is too large (over 32 GiB padded)", w->size_x, w->size_y);
+  return NEO_MPC_OK;
+}
+
+// `d`: the record with device pointers.  Orders itself like ingest() and leaves the handle's costmap as this pool.
+static int roll(neo_mpc_handle* h, const neo_mpc_window_batch& d, void* stream) {
+  const int sx = (int)d.size_x, sy = (int)d.size_y, count = (int)d.count, border = kPoolBorder;
+  const int pitch = (int)((d.size_x + 2 * border + 127) & ~127u);
+  const int rows = sy + 2 * border;
+  const size_t stride = (size_t)pitch * rows;
+  const int tab_x = (sx + 15) & ~15, tab_stride = tab_x + ((sy + 3) & ~3);
+  // the roll of every tick -- same geometry, count and origins as the previous one -- finds its buffers and the derived
+  // constants in place: nothing is allocated (a re-allocation synchronises), so the call can be captured in a graph
+  const bool same = h->has_map && h->rolled && h->map.pool_count == count && h->map.size_x == sx && h->map.size_y == sy &&
+                    h->map.resolution == d.resolution && h->map.pool_origins == d.origins;
+  int rc;
+  if (!same) {
+    if ((rc = h->map_buf.reserve(stride * count))) return rc;
+    if ((rc = h->roll_tables.reserve((size_t)count * tab_stride * sizeof(int32_t)))) return rc;
+  }
+  hipStream_t st = (hipStream_t)stream;
+  if (!h->map_ready) HIP_TRY(hipEventCreateWithFlags(&h->map_ready, hipEventDisableTiming));
+  // behind the previous ingest or roll, every launch still reading the old map (it reads `origins` too: the device variant
+  // rewrites them in-stream behind these waits) and the world map's copy
+  else if (h->map_ready_stream != st) HIP_TRY(hipStreamWaitEvent(st, h->map_ready, 0));
+  for (auto& u : h->map_users)
+    if (u.pending) {
+      if (u.stream != st) HIP_TRY(hipStreamWaitEvent(st, u.done, 0));
+      u.pending = false;
+    }
+  if (h->world_ready_stream != st) HIP_TRY(hipStreamWaitEvent(st, h->world_ready, 0));
+  RollArgs a;
+  std::memset(&a, 0, sizeof(a));
+  a.poses = d.poses; a.problems = d.poses ? nullptr : d.problems; a.origins = d.origins;
+  a.tables = (int32_t*)h->roll_tables.ptr;
+  a.world = (const uint8_t*)h->world_buf.ptr; a.dst = (uint8_t*)h->map_buf.ptr;
+  a.res = d.resolution; a.wres = h->world_resolution; a.wox = h->world_origin_x; a.woy = h->world_origin_y;
+  a.dst_stride = (int64_t)stride;
+  a.wsx = h->world_size_x; a.wsy = h->world_size_y;
+  a.size_x = sx; a.size_y = sy; a.pitch = pitch; a.rows = rows; a.border = border;
+  a.tab_x = tab_x; a.tab_stride = tab_stride;
+  a.count = (uint32_t)count; a.outside = d.outside_value;
+  launch_roll(a, stream);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipEventRecord(h->map_ready, st));
+  h->map_ready_stream = st;
+  if (!same) {
+    h->map.cells = (const uint8_t*)h->map_buf.ptr + (size_t)border * pitch + border;
+    h->map.size_x = sx; h->map.size_y = sy; h->map.pitch = pitch;
+    h->map.resolution = d.resolution; h->map.inv_resolution = 1.0 / d.resolution;
+    h->map.origin_x = 0.0; h->map.origin_y = 0.0;
+    h->map.pool_count = count;
+    h->map.border = border;
+    h->map.pool_stride = (int64_t)stride;
+    h->map.pool_origins = d.origins;
+    h->has_map = true;
+    h->rolled = true;
+    derive(h);
+  }
+  return NEO_MPC_OK;
+}
+
+int neo_mpc_roll_costmap_pool_device(neo_mpc_handle* h, const neo_mpc_window_batch* w, void* stream) {
+  int rc = check_window_batch(h, w);
+  if (rc) return rc;
+  if (w->count == 0) return NEO_MPC_OK;
+  HIP_TRY(hipSetDevice(h->device));
+  return roll(h, *w, stream);
+}
+
+int neo_mpc_roll_costmap_pool(neo_mpc_handle* h, const neo_mpc_window_batch* w) {
+  int rc = check_window_batch(h, w);
+  if (rc) return rc;
+  if (w->count == 0) return NEO_MPC_OK;
+  const size_t n = w->count;
+  // the values the device variant takes as they come are looked at here
+  for (size_t i = 0; i < n; ++i)
+    if (!std::isfinite(w->origins[2 * i]) || !std::isfinite(w->origins[2 * i + 1]))
+      return fail(NEO_MPC_ERR_INVALID_ARGUMENT, "the origin of window %zu is not finite", i);
+  std::vector<double> poses;
+  if (w->poses || w->problems) {
+    poses.resize(3 * n);
+    for (size_t i = 0; i < n; ++i) {
+      const double x = w->poses ? w->poses[3 * i] : w->problems[i].cur_xy[0];
+      const double y = w->poses ? w->poses[3 * i + 1] : w->problems[i].cur_xy[1];
+      if (!std::isfinite(x) || !std::isfinite(y)) return fail(NEO_MPC_ERR_INVALID_ARGUMENT, "the pose of window %zu is not finite", i);
+      poses[3 * i] = x; poses[3 * i + 1] = y; poses[3 * i + 2] = 0.0;
+    }
+  }
+  HIP_TRY(hipSetDevice(h->device));
+  // origins_buf is rewritten with blocking copies on the null stream: every launch that may still read it -- a pool of
+  // neo_mpc_set_costmap_pool's or of an earlier roll -- is waited for first (see wait_map_users)
+  if ((rc = wait_map_users(h))) return rc;
+  if (h->map_ready) HIP_TRY(hipEventSynchronize(h->map_ready));
+  if ((rc = h->origins_buf.reserve(n * 16))) return rc;
+  HIP_TRY(hipMemcpy(h->origins_buf.ptr, w->origins, n * 16, hipMemcpyHostToDevice));
+  neo_mpc_window_batch d = *w;
+  d.origins = (double*)h->origins_buf.ptr;
+  d.poses = nullptr; d.problems = nullptr;
+  if (!poses.empty()) {
+    if ((rc = h->roll_poses.reserve(n * 24))) return rc;
+    HIP_TRY(hipMemcpy(h->roll_poses.ptr, poses.data(), n * 24, hipMemcpyHostToDevice));
+    d.poses = (const double*)h->roll_poses.ptr;
+  }
+  if ((rc = roll(h, d, nullptr))) return rc;
+  // (a blocking copy on the null stream, behind the two kernels)
+  HIP_TRY(hipMemcpy(w->origins, h->origins_buf.ptr, n * 16, hipMemcpyDeviceToHost));
+  return NEO_MPC_OK;
+}
+
+int neo_mpc_get_costmap_pool(neo_mpc_handle* h, uint32_t first, uint32_t count, uint8_t* cells_out, double* origins_out) {
+  if (!h) return fail(NEO_MPC_ERR_INVALID_ARGUMENT, "null handle");
+  if (!h->has_map) return fail(NEO_MPC_ERR_NO_COSTMAP, "neo_mpc_set_costmap has not been called");
+  const uint32_t maps = h->map.pool_count > 0 ? (uint32_t)h->map.pool_count : 1u;
+  if (first > maps || count > maps - first)
+    return fail(NEO_MPC_ERR_INVALID_ARGUMENT, "maps [%u, %u + %u) outside the pool of %u", first, first, count, maps);
+  if (count == 0) return NEO_MPC_OK;
+  HIP_TRY(hipSetDevice(h->device));
+  HIP_TRY(hipEventSynchronize(h->map_ready));   // the ingest or roll in flight
+  const size_t sx = (size_t)h->map.size_x, sy = (size_t)h->map.size_y;
+  if (cells_out)
+    for (uint32_t k = 0; k < count; ++k)   // a strided copy per map: border and pitch stay behind
+      HIP_TRY(hipMemcpy2D(cells_out + (size_t)k * sx * sy, sx, h->map.cells + (size_t)(first + k) * h->map.pool_stride,
+                          (size_t)h->map.pitch, sx, sy, hipMemcpyDeviceToHost));
+  if (origins_out) {
+    if (h->map.pool_count > 0)
+      HIP_TRY(hipMemcpy(origins_out, h->map.pool_origins + 2 * (size_t)first, (size_t)count * 16, hipMemcpyDeviceToHost));
+    else { origins_out[0] = h->map.origin_x; origins_out[1] = h->map.origin_y; }
+  }
   return NEO_MPC_OK;
 }
 

@@ -208,6 +208,24 @@ struct FootprintGateArgs {
   DevMap map;
 };
 
+// K7: the rolling windows (neo_mpc_window_batch, device pointers) cut from the handle's world map into its map pool
+struct RollArgs {
+  const double* poses;              // optional [count][3]
+  const neo_mpc_problem* problems;  // optional [count], read when poses is null
+  double* origins;                  // [count][2] in/out
+  int32_t* tables;                  // [count][tab_stride] handle-owned: the fill's column and row indices (rolling_window.h)
+  const uint8_t* world;             // the world map, row-major wsx * wsy
+  uint8_t* dst;                     // padded map base (row 0 of the border) of the first window
+  double res, wres, wox, woy;
+  int64_t dst_stride;               // bytes between padded maps
+  int32_t wsx, wsy;
+  int32_t size_x, size_y, pitch, rows;  // rows = size_y + 2*border
+  int32_t border;
+  int32_t tab_x, tab_stride;        // column entries per window (size_x rounded up to 16), entries per window
+  uint32_t count;
+  uint32_t outside;                 // outside_value
+};
+
 // A/B switches of the measurement tools: read from the environment ONCE, by neo_mpc_create (include/neo_mpc.h), kept in
 // the handle -- nothing on the solve path looks at the environment.
 struct LaunchTuning {
@@ -222,6 +240,7 @@ void launch_postprocess(const SolveArgs& a, void* stream);
 void launch_objective(const ObjectiveArgs& a, void* stream);
 void launch_ingest(const IngestArgs& a, const LaunchTuning& t, void* stream);
 void launch_footprint_gate(const FootprintGateArgs& a, void* stream);
+void launch_roll(const RollArgs& a, void* stream);   // K7: k_roll_index, then k_roll_fill
 // K5: dispatch order of the next launch from the iteration counts of the previous one (neo_mpc_balance_dispatch_device)
 void launch_dispatch_order(const neo_mpc_command* commands, float* load, uint32_t* order, uint32_t count, bool fresh, void* stream);
 constexpr uint32_t kDispatchSimds = 1024;   // a 4096-instance launch is one residency round: workgroups w, w + 1024, w + 2048, w + 3072 share a SIMD

@@ -16,8 +16,10 @@
 //   k_objective       py:204-269 for given controls (parity checks of the objective).
 //   K5 k_dispatch_order  which instance each workgroup of a K1 launch solves (balanced dispatch).
 //   K6 k_footprint_gate  footprint_gate.h: the footprint gate in front of the carrot (cpp:218-219), one wave per robot.
+//   K7 k_roll_index, k_roll_fill  rolling_window.h: a fleet's rolling costmap windows cut from one world map, HBM-streaming.
 #include "k1_solve.h"
 #include "footprint_gate.h"
+#include "rolling_window.h"
 
 namespace neo_mpc {
 namespace {
@@ -382,6 +384,17 @@ void launch_footprint_gate(const FootprintGateArgs& a, void* stream) {
   if (a.count == 0) return;
   hipLaunchKernelGGL(k_footprint_gate, dim3((a.count + kGateWaves - 1) / kGateWaves), dim3(kLanes * kGateWaves), 0,
                      (hipStream_t)stream, a);
+}
+// K7: origins and index tables first (one wave per window), then the fill -- two launches, so that a window's new origin is
+// final before any workgroup fills that window
+void launch_roll(const RollArgs& a, void* stream) {
+  if (a.count == 0) return;
+  hipLaunchKernelGGL(k_roll_index, dim3((a.count + kRollWaves - 1) / kRollWaves), dim3(kLanes * kRollWaves), 0,
+                     (hipStream_t)stream, a);
+  const long total = (long)a.rows * (a.pitch >> 4);
+  int blocks = (int)((total + 256L * kRollUnroll - 1) / (256L * kRollUnroll));
+  if (blocks > 2048) blocks = 2048;
+  hipLaunchKernelGGL(k_roll_fill, dim3(blocks, a.count), dim3(256), 0, (hipStream_t)stream, a);
 }
 void launch_ingest(const IngestArgs& a, const LaunchTuning& tuning, void* stream) {
   const long total = (long)a.rows * (a.pitch >> 4);

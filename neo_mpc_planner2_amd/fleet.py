@@ -13,7 +13,8 @@ import numpy as np
 from . import abi
 
 
-def closed_loop(solver, batch, ticks, hz=30.0, before_tick=None, after_tick=None, balance_every=0, footprint=None):
+def closed_loop(solver, batch, ticks, hz=30.0, before_tick=None, after_tick=None, balance_every=0, footprint=None,
+                rolling=None):
     """Run `ticks` control ticks of `batch` (a solver.DeviceBatch) through `solver` (a BatchSolver with its costmap
     set).  Returns per-tick lists: kernel_ms (HIP events around the K1 launch), mean_iterations, max_iterations,
     stopped_fraction.  `before_tick(t, pos)` runs before tick t's launch (e.g. re-centre a costmap pool),
@@ -24,7 +25,10 @@ def closed_loop(solver, batch, ticks, hz=30.0, before_tick=None, after_tick=None
     synthetic.RECT_FOOTPRINT: every tick runs the footprint gate (K6, neo_mpc_footprint_gate_device) at the loop's own
     poses in front of K1 and hands K1 the oriented polygons (`footprints`), so the collision latch of py:343-347 acts on
     the robots' real outlines; the result gains `footprint_lethal_fraction`, the share of robots whose gate cost is >= 254.
-    None: no gate, no polygons -- the loop every caller had before."""
+    None: no gate, no polygons -- the loop every caller had before.  `rolling` = (size_x, size_y, resolution, origins), `origins`
+    a CUDA float64 [count, 2] tensor: every tick rolls the fleet's costmap windows over the solver's world map
+    (BatchSolver.set_world_map) at the loop's own poses (K7, neo_mpc_roll_costmap_pool_device) in front of the gate and K1
+    -- robot i reads window `map_index` = i of its request.  None: no roll, the loop is unchanged."""
     import torch
     b = batch
     P = b.problems.view(torch.float64).reshape(b.count, -1)          # the 32 doubles of each request
@@ -57,10 +61,13 @@ def closed_loop(solver, batch, ticks, hz=30.0, before_tick=None, after_tick=None
     for t in range(ticks):
         if before_tick is not None:
             before_tick(t, pos)
+        if rolling is not None or footprint is not None:
+            poses = torch.cat([pos, yaw[:, None]], 1).contiguous()   # one array serves the roll and the gate
+        if rolling is not None:
+            solver.roll_costmap_pool(rolling[0], rolling[1], rolling[2], rolling[3], poses=poses)
         if footprint is not None:
             # (the requests ride along for their map_index -- a pool -- and get the normalised cost written)
-            solver.footprint_gate_device(base, gate_costs, poses=torch.cat([pos, yaw[:, None]], 1).contiguous(),
-                                         problems=b.problems, footprints_out=polygons)
+            solver.footprint_gate_device(base, gate_costs, poses=poses, problems=b.problems, footprints_out=polygons)
         solver.solve_device(b.problems, b.states, b.warm, b.commands, velocities=b.vel, events=evs[t],
                             footprints=polygons)
         if balance_every and t % balance_every == 0:

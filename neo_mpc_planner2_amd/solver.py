@@ -32,6 +32,7 @@ class BatchSolver:
         self._keep = None
         self._last_call = None
         self._in_flight = {}    # ticket -> (batch struct, arrays): kept alive until solve_wait
+        self._map_shape = None  # (maps, size_y, size_x) of the costmap(s) the handle holds (get_costmap_pool)
 
     # -- lifecycle ------------------------------------------------------------------
     def close(self):
@@ -81,6 +82,7 @@ class BatchSolver:
             _lib.check(self._lib.neo_mpc_set_costmap_device(
                 self._handle, C.c_void_p(cells.data_ptr()), sx, sy, float(resolution), float(origin_x),
                 float(origin_y), C.c_void_p(stream)))
+        self._map_shape = (1, int(sy), int(sx))
 
     def set_costmap_pool(self, cells, resolution, origins):
         """Fleet variant: cells uint8 [count, size_y, size_x] (NumPy or CUDA torch tensor), origins
@@ -105,6 +107,82 @@ class BatchSolver:
             _lib.check(self._lib.neo_mpc_set_costmap_pool_device(
                 self._handle, C.c_void_p(cells.data_ptr()), m, sx, sy, float(resolution),
                 C.c_void_p(origins.data_ptr()), C.c_void_p(stream)))
+        self._map_shape = (int(m), int(sy), int(sx))
+
+    # -- rolling windows (the step before the gate) ----------------------------------------
+    def set_world_map(self, cells, resolution, origin_x, origin_y):
+        """The one world map a fleet's rolling windows are cut from (`roll_costmap_pool`): uint8 [size_y, size_x] raw
+        nav2 costs, NumPy or a CUDA torch tensor.  The handle keeps its own device copy; the costmap(s) it holds are
+        not touched."""
+        if isinstance(cells, np.ndarray):
+            cells = np.ascontiguousarray(cells, dtype=np.uint8)
+            sy, sx = cells.shape
+            _lib.check(self._lib.neo_mpc_set_world_map(self._handle, C.c_void_p(cells.ctypes.data), sx, sy,
+                                                      float(resolution), float(origin_x), float(origin_y)))
+        else:
+            import torch
+            assert cells.is_cuda and cells.dtype == torch.uint8 and cells.is_contiguous()
+            sy, sx = cells.shape
+            stream = torch.cuda.current_stream(cells.device).cuda_stream
+            _lib.check(self._lib.neo_mpc_set_world_map_device(
+                self._handle, C.c_void_p(cells.data_ptr()), sx, sy, float(resolution), float(origin_x),
+                float(origin_y), C.c_void_p(stream)))
+
+    def roll_costmap_pool(self, size_x, size_y, resolution, origins, poses=None, problems=None, outside_value=255):
+        """Moves `count` windows of size_x x size_y cells to their robots and fills them from the world map (K7;
+        nav2's rolling local costmaps, the contract: neo_mpc_window_batch in include/neo_mpc.h).  Afterwards the
+        handle's costmap is this pool.  `origins` float64 [count, 2] is state: read, moved by whole cells and written
+        in place.  `poses` [count, 3] (x, y, yaw -- the gate's array) centre the windows; without them
+        `problems["cur_xy"]`; without both the windows stay where they are and are filled again.  NumPy arrays go
+        through the synchronous host call; CUDA tensors (float64; `problems` the request records as bytes) through
+        the device call on torch's current stream, which retains `origins` -- every later solve and gate reads it."""
+        b = abi.NeoMpcWindowBatch()
+        b.size_x, b.size_y, b.resolution = int(size_x), int(size_y), float(resolution)
+        b.outside_value = int(outside_value)
+        if isinstance(origins, np.ndarray):
+            assert origins.dtype == np.float64 and origins.ndim == 2 and origins.shape[1] == 2 and origins.flags.c_contiguous
+            count = origins.shape[0]
+            if poses is not None:
+                poses = np.ascontiguousarray(poses, dtype=np.float64).reshape(-1, 3)
+                assert poses.shape[0] == count
+                b.poses = poses.ctypes.data
+            if problems is not None:
+                assert problems.dtype == abi.PROBLEM_DTYPE and problems.shape == (count,) and problems.flags.c_contiguous
+                b.problems = problems.ctypes.data
+            b.count = count
+            b.origins = origins.ctypes.data
+            _lib.check(self._lib.neo_mpc_roll_costmap_pool(self._handle, C.byref(b)))
+        else:
+            import torch
+            assert origins.is_cuda and origins.dtype == torch.float64 and origins.is_contiguous() and origins.shape[1] == 2
+            count = origins.shape[0]
+            if poses is not None:
+                assert poses.is_cuda and poses.dtype == torch.float64 and poses.is_contiguous() and tuple(poses.shape) == (count, 3)
+                b.poses = poses.data_ptr()
+            if problems is not None:
+                assert problems.is_cuda and problems.is_contiguous() and problems.shape[0] == count
+                b.problems = problems.data_ptr()
+            b.count = count
+            b.origins = origins.data_ptr()
+            self._pool_origins = origins   # keep it alive
+            stream = torch.cuda.current_stream(origins.device).cuda_stream
+            _lib.check(self._lib.neo_mpc_roll_costmap_pool_device(self._handle, C.byref(b), C.c_void_p(stream)))
+        if count:
+            self._map_shape = (int(count), int(size_y), int(size_x))
+
+    def get_costmap_pool(self, first=0, count=None):
+        """The raw cells of maps [first, first + count) of the pool (or of the single map: a pool of one) the handle
+        holds, uint8 [count, size_y, size_x] without border and pitch, and their origins, float64 [count, 2].
+        Synchronous; waits for the ingest or roll in flight."""
+        assert self._map_shape is not None, "no costmap has been set through this BatchSolver"
+        maps, sy, sx = self._map_shape
+        if count is None:
+            count = maps - first
+        cells = np.zeros((count, sy, sx), dtype=np.uint8)
+        origins = np.zeros((count, 2), dtype=np.float64)
+        _lib.check(self._lib.neo_mpc_get_costmap_pool(self._handle, int(first), int(count), C.c_void_p(cells.ctypes.data),
+                                                     C.c_void_p(origins.ctypes.data)))
+        return cells, origins
 
     HOST_PATHS = {"auto": 0, "staged": 1, "zerocopy": 2, "zerocopy_out": 3}
 
