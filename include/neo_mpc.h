@@ -37,6 +37,8 @@ extern "C" {
  * entry points; no existing record, entry point or result changed: still ABI 2, behaviour 6.
  * The rolling windows (neo_mpc_window_batch, neo_mpc_set_world_map[_device], neo_mpc_roll_costmap_pool[_device],
  * neo_mpc_get_costmap_pool) added a record and five entry points in the same way: still ABI 2, behaviour 6.
+ * The fleet stamp (neo_mpc_stamp_batch, neo_mpc_stamp_fleet[_device], neo_mpc_inflation_costs) added a record and three
+ * entry points in the same way: still ABI 2, behaviour 6.
  *
  * Behaviour history (iterates and iteration counts differ between versions, results stay inside the parity protocol of
  * DESIGN.md section 1; neo_mpc_behaviour_version() returns the number of the build that answers):
@@ -348,8 +350,8 @@ typedef struct neo_mpc_footprint_batch {
  *   float64, before any conversion); inside, its value is world[trunc(qy)][trunc(qx)]
  *   an outside cell gets `outside_value` (nav2's default_value: 255 with track_unknown_space, else 0).
  * Out of scope: a tf transform between the world map's frame and the windows' (they are one frame); `use_maximum`; further
- * layers (the world map IS the master grid the caller wants sampled, inflation included); stamping other robots into the
- * windows.
+ * layers (the world map IS the master grid the caller wants sampled, inflation included).  The other robots of the fleet
+ * are stamped into the windows by the step behind the roll: neo_mpc_stamp_batch below (K8).
  * Pointers are host pointers for neo_mpc_roll_costmap_pool and device pointers for neo_mpc_roll_costmap_pool_device.
  * 56 bytes. */
 typedef struct neo_mpc_window_batch {
@@ -365,6 +367,67 @@ typedef struct neo_mpc_window_batch {
   uint32_t outside_value;          /* 0 .. 255 */
   uint32_t reserved;               /* MUST be zero */
 } neo_mpc_window_batch;
+
+/* ---- the step behind the roll: the fleet's robots stamped into each other's windows (K8) -------------- */
+
+#define NEO_MPC_MAX_INFLATION_CELLS 64 /* largest R = ceil(inflation_radius / resolution): 1.6 m at 2.5 cm */
+
+/* Inside nav2 a robot sees the others through the obstacle layer and the inflation layer of its own local costmap.  A server
+ * that cuts every window from one world map has no such layer, but it holds every pose: neo_mpc_stamp_fleet writes the
+ * other robots' outlines into each window as lethal cells with nav2's inflation ring around them, between the roll and the
+ * gate: roll -> stamp -> gate -> carrots -> solve.  Windows and robots are one to one, as in the roll: window k of the
+ * handle's costmap pool -- the one a roll or neo_mpc_set_costmap_pool left there; its origins, size and resolution `res`
+ * are the handle's -- belongs to robot k, and `count` must equal the pool's map count.
+ *
+ * nav2 cannot be built next to this library, so the text below is the contract (tests/fleet_stamp_reference.py is its
+ * executable form).  Of its two halves the COST rule is nav2's InflationLayer::computeCost and its combination rule by
+ * transcription; the STAMP rule is this library's own -- it is not nav2's Costmap2D::setConvexPolygonCost, which refuses a
+ * polygon with a vertex off the map.  Neither is pinned against nav2 itself: nav2's layers are not available to the tests.
+ * Every float64 + - * / below is ONE correctly rounded operation in the order written (nothing fused); nothing else in the
+ * contract is floating point.
+ *
+ * Polygon of robot j: P_j[0 .. n-1] in the windows' global frame, n = footprint_points, convex with an area, either
+ * winding.  Either `polygons` [count][n][2], used as they are (the array neo_mpc_footprint_gate writes as footprints_out
+ * and neo_mpc_batch.footprints takes), or a base-frame `footprint` (shared, or one per robot) placed at `poses` / `problems`
+ * by the device routine of the footprint gate: for the same inputs the gate's footprints_out is bit for bit what is stamped.
+ *
+ * Stamped cells of robot j on window k's lattice, which continues beyond the window's edges (a robot just outside still
+ * inflates into the window): cell (i, l), any integers, has the centre cx = ox_k + (i + 0.5) res, cy = oy_k + (l + 0.5) res
+ * and is stamped when that centre is inside or on the polygon: with c_e = (b.x - a.x) (cy - a.y) - (b.y - a.y) (cx - a.x)
+ * for the edge e from a = P[e] to b = P[(e + 1) % n], when every c_e >= 0 or every c_e <= 0.  A polygon with a vertex that
+ * is not finite stamps nothing.  A polygon whose bounding box lies more than R cells from the window is out of its reach
+ * (decided in float64, before any conversion to an integer).
+ *
+ * Distance: for the window's cell (i, l), n_j = min (i - i')^2 + (l - l')^2 over the stamped cells (i', l') of robot j, an
+ * integer, and N = min of n_j over j != k: robot k is never stamped into its own window.
+ *
+ * Cost, tabulated by squared cell distance: R = ceil(inflation_radius / res); T[0] = 254; for 1 <= n <= R^2 with
+ * d = sqrt(n): T[n] = 253 when d res <= inscribed_radius, else (uint8)(252 exp(-cost_scaling_factor (d res -
+ * inscribed_radius))).  N > R^2 leaves the cell as it is (nav2's cell_inflation_radius_ cut-off).  T is built on the host
+ * with libm (neo_mpc_inflation_costs); the kernel never evaluates exp.
+ *
+ * Combination (nav2's inflation with inflate_unknown false), c = T[N], old = the cell's value: old == 255 becomes c when
+ * c >= 253 and stays 255 otherwise; any other old becomes max(old, c).  The rule is monotone in c and T does not increase,
+ * so the result does not depend on the order of the robots.
+ *
+ * Not touched: the lethal border and the pitch padding of the device maps (they stay 254); `origins`.  Stamps are not
+ * undone: the next roll cuts the windows afresh, and on an ingested pool they stay until the pool is set again.
+ * Pointers are host pointers for neo_mpc_stamp_fleet and device pointers for neo_mpc_stamp_fleet_device.  80 bytes. */
+typedef struct neo_mpc_stamp_batch {
+  size_t count;                    /* robots = windows: the pool's map count (0: nothing happens) */
+  const double* polygons;          /* optional [count][footprint_points][2], global frame; when given, footprint, poses and
+                                      problems are not read */
+  const double* footprint;         /* used when `polygons` is NULL: [footprint_points][2] base frame, shared by every robot
+                                      -- or, with per_robot_footprints, [count][footprint_points][2] */
+  uint32_t footprint_points;       /* 3 .. NEO_MPC_MAX_FOOTPRINT_POINTS */
+  uint32_t per_robot_footprints;   /* 0: one footprint for all; 1: one per robot; anything else is refused */
+  const double* poses;             /* with `footprint`: optional [count][3] x, y, yaw (the roll's and the gate's array) */
+  const neo_mpc_problem* problems; /* with `footprint`, used when `poses` is NULL: cur_xy and the yaw of cur_q */
+  double inscribed_radius;         /* m; >= 0, finite */
+  double inflation_radius;         /* m; >= 0, finite; R = ceil(inflation_radius / res) <= NEO_MPC_MAX_INFLATION_CELLS */
+  double cost_scaling_factor;      /* 1/m; >= 0, finite */
+  uint64_t reserved;               /* MUST be zero */
+} neo_mpc_stamp_batch;
 
 typedef struct neo_mpc_handle neo_mpc_handle;
 
@@ -563,6 +626,31 @@ int neo_mpc_roll_costmap_pool_device(neo_mpc_handle* handle, const neo_mpc_windo
  * for a range outside the pool. */
 int neo_mpc_get_costmap_pool(neo_mpc_handle* handle, uint32_t first, uint32_t count, uint8_t* cells_out,
                              double* origins_out);
+
+/* The cost table T of neo_mpc_stamp_batch for windows of resolution `resolution`: pure host arithmetic (libm), no handle, no
+ * device.  *cells_out = R (may be NULL); with `table_out` not NULL, T[0 .. R^2] is written and `capacity` must be at
+ * least R^2 + 1 bytes.  NEO_MPC_ERR_INVALID_ARGUMENT for a resolution that is not positive and finite, a radius or scaling
+ * factor that is negative or not finite, or a capacity that is too small; NEO_MPC_ERR_UNSUPPORTED when
+ * R > NEO_MPC_MAX_INFLATION_CELLS. */
+int neo_mpc_inflation_costs(double resolution, double inscribed_radius, double inflation_radius, double cost_scaling_factor,
+                            uint8_t* table_out, size_t capacity, uint32_t* cells_out);
+
+/* Stamps the fleet's robots into each other's windows (K8; the contract: neo_mpc_stamp_batch).  Host pointers, synchronous.
+ * Refusals, all of which leave the pool as it was: NEO_MPC_ERR_INVALID_ARGUMENT for a null argument, a non-zero `reserved`,
+ * footprint_points outside 3 .. NEO_MPC_MAX_FOOTPRINT_POINTS, per_robot_footprints other than 0 or 1, a radius or scaling
+ * factor that is negative or not finite, neither `polygons` nor a `footprint` with `poses` or `problems`, a pose or vertex
+ * that is not finite, and a `count` that is not the pool's map count; NEO_MPC_ERR_NO_COSTMAP when the handle holds no
+ * costmap; NEO_MPC_ERR_UNSUPPORTED when it holds a single costmap instead of a pool, and when
+ * R > NEO_MPC_MAX_INFLATION_CELLS.  count == 0 is NEO_MPC_OK and does nothing. */
+int neo_mpc_stamp_fleet(neo_mpc_handle* handle, const neo_mpc_stamp_batch* batch);
+/* Same with every pointer in device memory; enqueued on `stream`, returns without waiting; no value behind a pointer is
+ * looked at on the host.  The cost table is kept in the handle: when (resolution, inscribed_radius, inflation_radius,
+ * cost_scaling_factor) differ from the previous call's it is rebuilt and uploaded synchronously; otherwise a call with the
+ * count and footprint_points of an earlier one allocates nothing and copies nothing, so roll -> stamp -> gate -> carrots ->
+ * solve can be captured in a HIP graph on one stream.  Ordering, both variants: a stamp rewrites the device maps in place,
+ * so like a roll it waits on its stream for the previous ingest, roll or stamp and for every launch still reading the maps,
+ * and the gates and solves behind it wait for it. */
+int neo_mpc_stamp_fleet_device(neo_mpc_handle* handle, const neo_mpc_stamp_batch* batch, void* stream);
 
 /* ---- multi-GPU fleets: the one exchange step ------------------------------------------------
  * Instances of one tick shard embarrassingly over the GPUs of a node (one handle per GPU, costmap and parameters

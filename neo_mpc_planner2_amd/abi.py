@@ -145,6 +145,17 @@ class NeoMpcWindowBatch(_C.Structure):
                 ("outside_value", _C.c_uint32), ("reserved", _C.c_uint32)]
 
 
+class NeoMpcStampBatch(_C.Structure):
+    """`neo_mpc_stamp_batch` (include/neo_mpc.h): the fleet's robots stamped into each other's windows."""
+    _fields_ = [("count", _C.c_size_t), ("polygons", _C.c_void_p), ("footprint", _C.c_void_p),
+                ("footprint_points", _C.c_uint32), ("per_robot_footprints", _C.c_uint32), ("poses", _C.c_void_p),
+                ("problems", _C.c_void_p), ("inscribed_radius", _C.c_double), ("inflation_radius", _C.c_double),
+                ("cost_scaling_factor", _C.c_double), ("reserved", _C.c_uint64)]
+
+
+MAX_INFLATION_CELLS = 64
+
+
 def params_struct(params=None, **over):
     """dict of ROS parameter names (+ solver options) -> NeoMpcParams.  Missing names take
     the reference node's declared defaults (py:49-75)."""

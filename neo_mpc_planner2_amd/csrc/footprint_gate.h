@@ -31,6 +31,24 @@ __device__ __forceinline__ int wave_or(int v) {
   return __builtin_amdgcn_readlane(v, 63);
 }
 
+// Where robot `b` stands -- its row of `poses`, else cur_xy and the yaw of cur_q of its request -- and one base-frame vertex
+// placed there.  K6 and K8 (fleet_stamp.h) both go through these two, so the polygons K6 writes as footprints_out are bit
+// for bit the ones K8 stamps for the same inputs.
+__device__ __forceinline__ void footprint_pose(const double* poses, const neo_mpc_problem* problems, size_t b, double& x,
+                                               double& y, double& th) {
+  if (poses) {
+    x = poses[3 * b]; y = poses[3 * b + 1]; th = poses[3 * b + 2];
+  } else {
+    const double* P = reinterpret_cast<const double*>(problems + b);
+    x = P[P_CUR_X]; y = P[P_CUR_Y]; th = yaw_of(P + P_CUR_Q);
+  }
+}
+__device__ __forceinline__ void orient_vertex(double x, double y, double sn, double cs, double px, double py, double& X,
+                                              double& Y) {
+  const double ox = x + px * cs - py * sn, oy = y + px * sn + py * cs;
+  X = ox; Y = oy;
+}
+
 // K6: nav2's FootprintCollisionChecker::footprintCostAtPose on raw cell values (the contract: include/neo_mpc.h,
 // neo_mpc_footprint_batch), one wavefront per robot.  Vertices go one per lane (<= 16: one DPP row): oriented in float64,
 // turned into cells by worldToMap's rule against the map's TRUE size.  LineIterator's walk has a closed form -- cell k of an
@@ -45,12 +63,7 @@ __global__ __launch_bounds__(kLanes * kGateWaves) void k_footprint_gate(const Fo
   if (b >= a.count) return;
   const int n = (int)a.footprint_points;   // 3 .. 16 (neo_mpc_capi.cpp refuses anything else)
   double x, y, th;
-  if (a.poses) {
-    x = a.poses[3 * b]; y = a.poses[3 * b + 1]; th = a.poses[3 * b + 2];
-  } else {
-    const double* P = reinterpret_cast<const double*>(a.problems + b);
-    x = P[P_CUR_X]; y = P[P_CUR_Y]; th = yaw_of(P + P_CUR_Q);
-  }
+  footprint_pose(a.poses, a.problems, b, x, y, th);
   DevMap m = a.map;
   if (m.pool_count > 0) {   // (select_map's rule: an index outside the pool is clamped into it)
     int idx = a.map_indices ? a.map_indices[b] : a.problems ? a.problems[b].map_index : 0;
@@ -65,7 +78,8 @@ __global__ __launch_bounds__(kLanes * kGateWaves) void k_footprint_gate(const Fo
   const double px = poly[0], py = poly[1];
   double sn, cs;
   sincos(th, &sn, &cs);
-  const double X = x + px * cs - py * sn, Y = y + px * sn + py * cs;
+  double X, Y;
+  orient_vertex(x, y, sn, cs, px, py, X, Y);
   if (a.footprints_out && has) {
     double* out = a.footprints_out + (b * (size_t)n + lane) * 2;
     out[0] = X; out[1] = Y;

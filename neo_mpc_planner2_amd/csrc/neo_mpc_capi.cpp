@@ -99,6 +99,12 @@ struct neo_mpc_handle {
   hipEvent_t world_ready = nullptr;         // recorded behind the copy into world_buf; a roll on another stream waits for it
   hipStream_t world_ready_stream = nullptr;
   bool rolled = false;                      // the device map was written by a roll (map_ready: that roll's end)
+  // neo_mpc_stamp_fleet (K8): the cost table and the key it was built for, the oriented polygons and their bounding
+  // boxes, and the host variant's polygons / footprint and poses
+  DeviceBuffer stamp_table, stamp_polys, stamp_boxes, stamp_in, stamp_poses;
+  bool has_stamp_table = false;
+  double stamp_key[4] = {0.0, 0.0, 0.0, 0.0};   // resolution, inscribed_radius, inflation_radius, cost_scaling_factor
+  int32_t stamp_reach = 0;
   // latency path of neo_mpc_solve_batch (small host batches, the plugin's count = 1): one pinned
   // staging block and one device arena, so a tick is one H2D, K1, one D2H and one synchronisation
   void* pin = nullptr;
@@ -516,7 +522,8 @@ void neo_mpc_destroy(neo_mpc_handle* h) {
                          &h->solution, &h->path, &h->footprints, &h->success, &h->u, &h->cost, &h->plan_poses,
                          &h->plan_offsets, &h->robot_poses, &h->fp_costs, &h->slow_down, &h->carrots, &h->vel,
                          &h->arena, &h->origins_buf, &h->order_buf, &h->load_buf, &h->gate_polygon, &h->gate_poses,
-                         &h->gate_indices, &h->gate_polygons_out, &h->world_buf, &h->roll_tables, &h->roll_poses};
+                         &h->gate_indices, &h->gate_polygons_out, &h->world_buf, &h->roll_tables, &h->roll_poses,
+                         &h->stamp_table, &h->stamp_polys, &h->stamp_boxes, &h->stamp_in, &h->stamp_poses};
   for (DeviceBuffer* b : all) b->release();
   if (h->pin) (void)hipHostFree(h->pin);
   if (h->map_ready) (void)hipEventDestroy(h->map_ready);
@@ -1401,6 +1408,173 @@ int neo_mpc_get_costmap_pool(neo_mpc_handle* h, uint32_t first, uint32_t count, 
       HIP_TRY(hipMemcpy(origins_out, h->map.pool_origins + 2 * (size_t)first, (size_t)count * 16, hipMemcpyDeviceToHost));
     else { origins_out[0] = h->map.origin_x; origins_out[1] = h->map.origin_y; }
   }
+  return NEO_MPC_OK;
+}
+
+// K8.  The cost table of the contract (neo_mpc_stamp_batch): nav2's InflationLayer::computeCost by squared cell distance.
+static bool stamp_radii_ok(double ins, double infl, double csf) {
+  return std::isfinite(ins) && std::isfinite(infl) && std::isfinite(csf) && ins >= 0.0 && infl >= 0.0 && csf >= 0.0;
+}
+// R = ceil(inflation_radius / res), or -1 beyond NEO_MPC_MAX_INFLATION_CELLS (compared in float64, before the conversion)
+static int stamp_reach_cells(double res, double infl) {
+  const double r = std::ceil(infl / res);
+  return r <= (double)NEO_MPC_MAX_INFLATION_CELLS ? (int)r : -1;
+}
+static void stamp_costs(double res, double ins, double csf, int reach, uint8_t* table) {
+  table[0] = 254;
+  for (int n = 1; n <= reach * reach; ++n) {
+    const double dist = std::sqrt((double)n) * res;
+    if (dist <= ins) table[n] = 253;
+    else {
+      const double factor = std::exp(-csf * (dist - ins));
+      table[n] = (uint8_t)(252.0 * factor);
+    }
+  }
+}
+
+int neo_mpc_inflation_costs(double res, double ins, double infl, double csf, uint8_t* table_out, size_t capacity,
+                            uint32_t* cells_out) {
+  if (!(res > 0.0) || !std::isfinite(res))
+    return fail(NEO_MPC_ERR_INVALID_ARGUMENT, "resolution %g must be positive and finite", res);
+  if (!stamp_radii_ok(ins, infl, csf))
+    return fail(NEO_MPC_ERR_INVALID_ARGUMENT, "inscribed_radius %g, inflation_radius %g and cost_scaling_factor %g must be finite and not negative", ins, infl, csf);
+  const int reach = stamp_reach_cells(res, infl);
+  if (reach < 0)
+    return fail(NEO_MPC_ERR_UNSUPPORTED, "inflation_radius %g at resolution %g is more than %d cells", infl, res, NEO_MPC_MAX_INFLATION_CELLS);
+  if (cells_out) *cells_out = (uint32_t)reach;
+  if (table_out) {
+    if (capacity < (size_t)reach * reach + 1)
+      return fail(NEO_MPC_ERR_INVALID_ARGUMENT, "the table needs %zu bytes, capacity is %zu", (size_t)reach * reach + 1, capacity);
+    stamp_costs(res, ins, csf, reach, table_out);
+  }
+  return NEO_MPC_OK;
+}
+
+// What both stamp entry points check: the record's shape and the handle's pool, never a value behind a pointer.
+static int check_stamp_batch(const neo_mpc_handle* h, const neo_mpc_stamp_batch* b) {
+  if (!h || !b) return fail(NEO_MPC_ERR_INVALID_ARGUMENT, "null argument");
+  if (b->reserved != 0) return fail(NEO_MPC_ERR_INVALID_ARGUMENT, "neo_mpc_stamp_batch.reserved must be zero");
+  if (b->footprint_points < 3 || b->footprint_points > NEO_MPC_MAX_FOOTPRINT_POINTS)
+    return fail(NEO_MPC_ERR_INVALID_ARGUMENT, "footprint_points %u outside [3, %d]", b->footprint_points, NEO_MPC_MAX_FOOTPRINT_POINTS);
+  if (b->per_robot_footprints > 1)
+    return fail(NEO_MPC_ERR_INVALID_ARGUMENT, "per_robot_footprints must be 0 or 1 (got %u)", b->per_robot_footprints);
+  if (!stamp_radii_ok(b->inscribed_radius, b->inflation_radius, b->cost_scaling_factor))
+    return fail(NEO_MPC_ERR_INVALID_ARGUMENT, "inscribed_radius %g, inflation_radius %g and cost_scaling_factor %g must be finite and not negative",
+                b->inscribed_radius, b->inflation_radius, b->cost_scaling_factor);
+  if (b->count > 0 && !b->polygons && (!b->footprint || (!b->poses && !b->problems)))
+    return fail(NEO_MPC_ERR_INVALID_ARGUMENT, "neither polygons nor a footprint with poses or problems");
+  if (!h->has_map) return fail(NEO_MPC_ERR_NO_COSTMAP, "the handle holds no costmap");
+  if (h->map.pool_count <= 0) return fail(NEO_MPC_ERR_UNSUPPORTED, "the handle holds a single costmap, not a pool");
+  if (b->count > 0 && b->count != (size_t)h->map.pool_count)
+    return fail(NEO_MPC_ERR_INVALID_ARGUMENT, "%zu robots for a pool of %d windows: they are one to one", b->count, h->map.pool_count);
+  if (stamp_reach_cells(h->map.resolution, b->inflation_radius) < 0)
+    return fail(NEO_MPC_ERR_UNSUPPORTED, "inflation_radius %g at resolution %g is more than %d cells", b->inflation_radius,
+                h->map.resolution, NEO_MPC_MAX_INFLATION_CELLS);
+  return NEO_MPC_OK;
+}
+
+// `d`: the record with device pointers.  Orders itself like roll(): it rewrites the device maps in place.
+static int stamp(neo_mpc_handle* h, const neo_mpc_stamp_batch& d, void* stream) {
+  const size_t n = d.count, np = d.footprint_points;
+  const double key[4] = {h->map.resolution, d.inscribed_radius, d.inflation_radius, d.cost_scaling_factor};
+  // the stamp of every tick -- same parameters as the previous one -- finds its table in place: nothing is built, allocated
+  // or copied, so the call can be captured in a graph
+  const bool same = h->has_stamp_table && std::memcmp(key, h->stamp_key, sizeof(key)) == 0;
+  int rc;
+  if (!same) {
+    const int reach = stamp_reach_cells(key[0], key[2]);
+    std::vector<uint8_t> table((size_t)reach * reach + 1);
+    stamp_costs(key[0], key[1], key[3], reach, table.data());
+    // (a stamp in flight reads the old table: every stamp records map_ready)
+    if (h->map_ready) HIP_TRY(hipEventSynchronize(h->map_ready));
+    h->has_stamp_table = false;
+    if ((rc = h->stamp_table.reserve(table.size()))) return rc;
+    HIP_TRY(hipMemcpy(h->stamp_table.ptr, table.data(), table.size(), hipMemcpyHostToDevice));
+    std::memcpy(h->stamp_key, key, sizeof(key));
+    h->stamp_reach = reach;
+    h->has_stamp_table = true;
+  }
+  // (no-ops from the second call with this count and footprint_points on)
+  if ((rc = h->stamp_boxes.reserve(n * 32))) return rc;
+  if (!d.polygons && (rc = h->stamp_polys.reserve(n * np * 16))) return rc;
+  hipStream_t st = (hipStream_t)stream;
+  // behind the ingest, roll or stamp that wrote the maps and every launch still reading them
+  if (h->map_ready && h->map_ready_stream != st) HIP_TRY(hipStreamWaitEvent(st, h->map_ready, 0));
+  if (!h->map_ready) HIP_TRY(hipEventCreateWithFlags(&h->map_ready, hipEventDisableTiming));
+  for (auto& u : h->map_users)
+    if (u.pending) {
+      if (u.stream != st) HIP_TRY(hipStreamWaitEvent(st, u.done, 0));
+      u.pending = false;
+    }
+  StampArgs a;
+  std::memset(&a, 0, sizeof(a));
+  a.polygons = d.polygons;
+  if (!d.polygons) { a.footprint = d.footprint; a.poses = d.poses; a.problems = d.poses ? nullptr : d.problems; }
+  a.polys = (double*)h->stamp_polys.ptr; a.boxes = (double*)h->stamp_boxes.ptr;
+  a.table = (const uint8_t*)h->stamp_table.ptr;
+  a.cells = const_cast<uint8_t*>(h->map.cells);   // (cell (0, 0) of the first map of map_buf, the handle's own)
+  a.origins = h->map.pool_origins;
+  a.res = h->map.resolution;
+  a.stride = h->map.pool_stride;
+  a.size_x = h->map.size_x; a.size_y = h->map.size_y; a.pitch = h->map.pitch;
+  a.reach = h->stamp_reach;
+  a.count = (uint32_t)n; a.points = d.footprint_points; a.per_robot = d.per_robot_footprints;
+  launch_stamp(a, stream);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipEventRecord(h->map_ready, st));   // a gate or solve behind it sees the stamped pool
+  h->map_ready_stream = st;
+  return NEO_MPC_OK;
+}
+
+int neo_mpc_stamp_fleet_device(neo_mpc_handle* h, const neo_mpc_stamp_batch* b, void* stream) {
+  int rc = check_stamp_batch(h, b);
+  if (rc) return rc;
+  if (b->count == 0) return NEO_MPC_OK;
+  HIP_TRY(hipSetDevice(h->device));
+  return stamp(h, *b, stream);
+}
+
+int neo_mpc_stamp_fleet(neo_mpc_handle* h, const neo_mpc_stamp_batch* b) {
+  int rc = check_stamp_batch(h, b);
+  if (rc) return rc;
+  if (b->count == 0) return NEO_MPC_OK;
+  const size_t n = b->count, np = b->footprint_points;
+  // the values the device variant takes as they come are looked at here
+  const double* verts = b->polygons ? b->polygons : b->footprint;
+  const size_t vert_doubles = (b->polygons || b->per_robot_footprints ? n : 1) * np * 2;
+  for (size_t k = 0; k < vert_doubles; ++k)
+    if (!std::isfinite(verts[k]))
+      return fail(NEO_MPC_ERR_INVALID_ARGUMENT, "vertex %zu of polygon %zu is not finite", (k / 2) % np, k / (2 * np));
+  if (!b->polygons)
+    for (size_t i = 0; i < n; ++i) {
+      bool finite = true;
+      if (b->poses) for (int k = 0; k < 3; ++k) finite = finite && std::isfinite(b->poses[3 * i + k]);
+      else {
+        for (int k = 0; k < 2; ++k) finite = finite && std::isfinite(b->problems[i].cur_xy[k]);
+        for (int k = 0; k < 4; ++k) finite = finite && std::isfinite(b->problems[i].cur_q[k]);
+      }
+      if (!finite) return fail(NEO_MPC_ERR_INVALID_ARGUMENT, "the pose of robot %zu is not finite", i);
+    }
+  HIP_TRY(hipSetDevice(h->device));
+  neo_mpc_stamp_batch d = *b;
+  if ((rc = h->stamp_in.reserve(vert_doubles * 8))) return rc;
+  HIP_TRY(hipMemcpy(h->stamp_in.ptr, verts, vert_doubles * 8, hipMemcpyHostToDevice));
+  d.polygons = nullptr; d.footprint = nullptr; d.poses = nullptr; d.problems = nullptr;
+  if (b->polygons) d.polygons = (const double*)h->stamp_in.ptr;
+  else {
+    d.footprint = (const double*)h->stamp_in.ptr;
+    if (b->poses) {
+      if ((rc = h->stamp_poses.reserve(n * 24))) return rc;
+      HIP_TRY(hipMemcpy(h->stamp_poses.ptr, b->poses, n * 24, hipMemcpyHostToDevice));
+      d.poses = (const double*)h->stamp_poses.ptr;
+    } else {
+      if ((rc = h->problems.reserve(n * sizeof(neo_mpc_problem)))) return rc;
+      HIP_TRY(hipMemcpy(h->problems.ptr, b->problems, n * sizeof(neo_mpc_problem), hipMemcpyHostToDevice));
+      d.problems = (const neo_mpc_problem*)h->problems.ptr;
+    }
+  }
+  if ((rc = stamp(h, d, nullptr))) return rc;
+  HIP_TRY(hipStreamSynchronize(nullptr));
   return NEO_MPC_OK;
 }
 

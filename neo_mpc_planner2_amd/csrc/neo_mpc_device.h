@@ -226,6 +226,26 @@ struct RollArgs {
   uint32_t outside;                 // outside_value
 };
 
+// K8: the fleet's robots stamped into each other's windows (neo_mpc_stamp_batch, device pointers) -- the handle's map pool
+struct StampArgs {
+  const double* polygons;           // [count][points][2] global frame, or null: footprint + poses / problems
+  const double* footprint;          // [points][2], or [count][points][2] with per_robot
+  const double* poses;              // optional [count][3]
+  const neo_mpc_problem* problems;  // optional [count], read when poses is null
+  double* polys;                    // [count][points][2] handle-owned: the oriented polygons (written without `polygons`)
+  double* boxes;                    // [count][4] handle-owned: the polygons' bounding boxes, min x, min y, max x, max y
+  const uint8_t* table;             // [reach^2 + 1]: cost by squared cell distance (neo_mpc_inflation_costs)
+  uint8_t* cells;                   // cell (0, 0) of the first window
+  const double* origins;            // [count][2]
+  double res;
+  int64_t stride;                   // bytes between windows
+  int32_t size_x, size_y, pitch;
+  int32_t reach;                    // R, cells: 0 .. NEO_MPC_MAX_INFLATION_CELLS
+  uint32_t count;
+  uint32_t points;
+  uint32_t per_robot;
+};
+
 // A/B switches of the measurement tools: read from the environment ONCE, by neo_mpc_create (include/neo_mpc.h), kept in
 // the handle -- nothing on the solve path looks at the environment.
 struct LaunchTuning {
@@ -241,6 +261,7 @@ void launch_objective(const ObjectiveArgs& a, void* stream);
 void launch_ingest(const IngestArgs& a, const LaunchTuning& t, void* stream);
 void launch_footprint_gate(const FootprintGateArgs& a, void* stream);
 void launch_roll(const RollArgs& a, void* stream);   // K7: k_roll_index, then k_roll_fill
+void launch_stamp(const StampArgs& a, void* stream); // K8: k_stamp_boxes, then k_stamp_fleet
 // K5: dispatch order of the next launch from the iteration counts of the previous one (neo_mpc_balance_dispatch_device)
 void launch_dispatch_order(const neo_mpc_command* commands, float* load, uint32_t* order, uint32_t count, bool fresh, void* stream);
 constexpr uint32_t kDispatchSimds = 1024;   // a 4096-instance launch is one residency round: workgroups w, w + 1024, w + 2048, w + 3072 share a SIMD

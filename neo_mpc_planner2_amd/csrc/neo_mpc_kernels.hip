@@ -17,9 +17,11 @@
 //   K5 k_dispatch_order  which instance each workgroup of a K1 launch solves (balanced dispatch).
 //   K6 k_footprint_gate  footprint_gate.h: the footprint gate in front of the carrot (cpp:218-219), one wave per robot.
 //   K7 k_roll_index, k_roll_fill  rolling_window.h: a fleet's rolling costmap windows cut from one world map, HBM-streaming.
+//   K8 k_stamp_boxes, k_stamp_fleet  fleet_stamp.h: the fleet's robots stamped into each other's windows, inflation ring included.
 #include "k1_solve.h"
 #include "footprint_gate.h"
 #include "rolling_window.h"
+#include "fleet_stamp.h"
 
 namespace neo_mpc {
 namespace {
@@ -395,6 +397,13 @@ void launch_roll(const RollArgs& a, void* stream) {
   int blocks = (int)((total + 256L * kRollUnroll - 1) / (256L * kRollUnroll));
   if (blocks > 2048) blocks = 2048;
   hipLaunchKernelGGL(k_roll_fill, dim3(blocks, a.count), dim3(256), 0, (hipStream_t)stream, a);
+}
+// K8: polygons and bounding boxes first (one thread per robot), then one wave per window -- two launches, so that every box is
+// final before any window searches the fleet
+void launch_stamp(const StampArgs& a, void* stream) {
+  if (a.count == 0) return;
+  hipLaunchKernelGGL(k_stamp_boxes, dim3((a.count + 255) / 256), dim3(256), 0, (hipStream_t)stream, a);
+  hipLaunchKernelGGL(k_stamp_fleet, dim3(a.count), dim3(kLanes), 0, (hipStream_t)stream, a);
 }
 void launch_ingest(const IngestArgs& a, const LaunchTuning& tuning, void* stream) {
   const long total = (long)a.rows * (a.pitch >> 4);

@@ -14,7 +14,7 @@ from . import abi
 
 
 def closed_loop(solver, batch, ticks, hz=30.0, before_tick=None, after_tick=None, balance_every=0, footprint=None,
-                rolling=None):
+                rolling=None, stamp=None):
     """Run `ticks` control ticks of `batch` (a solver.DeviceBatch) through `solver` (a BatchSolver with its costmap
     set).  Returns per-tick lists: kernel_ms (HIP events around the K1 launch), mean_iterations, max_iterations,
     stopped_fraction.  `before_tick(t, pos)` runs before tick t's launch (e.g. re-centre a costmap pool),
@@ -28,7 +28,11 @@ def closed_loop(solver, batch, ticks, hz=30.0, before_tick=None, after_tick=None
     None: no gate, no polygons -- the loop every caller had before.  `rolling` = (size_x, size_y, resolution, origins), `origins`
     a CUDA float64 [count, 2] tensor: every tick rolls the fleet's costmap windows over the solver's world map
     (BatchSolver.set_world_map) at the loop's own poses (K7, neo_mpc_roll_costmap_pool_device) in front of the gate and K1
-    -- robot i reads window `map_index` = i of its request.  None: no roll, the loop is unchanged."""
+    -- robot i reads window `map_index` = i of its request.  None: no roll, the loop is unchanged.  `stamp` =
+    (inscribed_radius, inflation_radius, cost_scaling_factor), with `rolling` and `footprint`: between the roll and the gate
+    every tick stamps the other robots' outlines, inflation ring included, into each window at the loop's own poses (K8,
+    neo_mpc_stamp_fleet_device), so the gate and K1's collision latch see the fleet.  None: no stamp, the loop is unchanged."""
+    assert stamp is None or (rolling is not None and footprint is not None), "stamp needs rolling and footprint"
     import torch
     b = batch
     P = b.problems.view(torch.float64).reshape(b.count, -1)          # the 32 doubles of each request
@@ -65,6 +69,8 @@ def closed_loop(solver, batch, ticks, hz=30.0, before_tick=None, after_tick=None
             poses = torch.cat([pos, yaw[:, None]], 1).contiguous()   # one array serves the roll and the gate
         if rolling is not None:
             solver.roll_costmap_pool(rolling[0], rolling[1], rolling[2], rolling[3], poses=poses)
+        if stamp is not None:
+            solver.stamp_fleet(stamp[0], stamp[1], stamp[2], footprint=base, poses=poses)
         if footprint is not None:
             # (the requests ride along for their map_index -- a pool -- and get the normalised cost written)
             solver.footprint_gate_device(base, gate_costs, poses=poses, problems=b.problems, footprints_out=polygons)

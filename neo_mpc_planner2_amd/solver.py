@@ -184,6 +184,85 @@ class BatchSolver:
                                                      C.c_void_p(origins.ctypes.data)))
         return cells, origins
 
+    # -- fleet stamp (the step behind the roll) -------------------------------------------
+    @staticmethod
+    def inflation_costs(resolution, inscribed_radius, inflation_radius, cost_scaling_factor):
+        """The cost table of the fleet stamp (`neo_mpc_inflation_costs`: nav2's `InflationLayer::computeCost` by squared
+        cell distance) for windows of `resolution`: (T uint8 [R * R + 1], R).  Pure host arithmetic, no device."""
+        lib = _lib.load()
+        cells = C.c_uint32()
+        args = (float(resolution), float(inscribed_radius), float(inflation_radius), float(cost_scaling_factor))
+        _lib.check(lib.neo_mpc_inflation_costs(*args, None, 0, C.byref(cells)))
+        table = np.zeros(cells.value * cells.value + 1, dtype=np.uint8)
+        _lib.check(lib.neo_mpc_inflation_costs(*args, C.c_void_p(table.ctypes.data), table.size, None))
+        return table, int(cells.value)
+
+    def stamp_fleet(self, inscribed_radius, inflation_radius, cost_scaling_factor, polygons=None, footprint=None,
+                    poses=None, problems=None):
+        """Stamps the fleet's robots into each other's windows (K8; the contract: neo_mpc_stamp_batch in
+        include/neo_mpc.h): window k of the pool the handle holds belongs to robot k and gets every OTHER robot's outline
+        as lethal cells with nav2's inflation ring around them.  Either `polygons` [count, points, 2] in the global frame
+        (what the footprint gate writes as `footprints_out`), or a base-frame `footprint` ([points, 2] shared, or
+        [count, points, 2]) with `poses` [count, 3] or `problems`.  NumPy arrays go through the synchronous host call;
+        CUDA tensors (float64; `problems` the request records as bytes) through the device call on torch's current
+        stream."""
+        b = abi.NeoMpcStampBatch()
+        b.inscribed_radius, b.inflation_radius = float(inscribed_radius), float(inflation_radius)
+        b.cost_scaling_factor = float(cost_scaling_factor)
+        shape = polygons if polygons is not None else footprint
+        assert shape is not None, "polygons or footprint"
+        on_host = isinstance(shape, np.ndarray) or not hasattr(shape, "data_ptr")
+        if on_host:
+            keep = []
+
+            def ptr(a, dtype=np.float64):
+                a = np.ascontiguousarray(a, dtype=dtype)
+                keep.append(a)
+                return a, a.ctypes.data
+
+            if polygons is not None:
+                polygons, b.polygons = ptr(polygons)
+                assert polygons.ndim == 3 and polygons.shape[2] == 2
+                b.count, b.footprint_points = polygons.shape[0], polygons.shape[1]
+            else:
+                footprint, b.footprint = ptr(footprint)
+                assert footprint.ndim in (2, 3) and footprint.shape[-1] == 2
+                b.footprint_points = footprint.shape[-2]
+                b.per_robot_footprints = 1 if footprint.ndim == 3 else 0
+                if poses is not None:
+                    poses, b.poses = ptr(poses)
+                    poses = poses.reshape(-1, 3)
+                    b.count = poses.shape[0]
+                elif problems is not None:
+                    assert problems.dtype == abi.PROBLEM_DTYPE and problems.flags.c_contiguous
+                    b.problems = problems.ctypes.data
+                    b.count = problems.shape[0]
+                assert footprint.ndim == 2 or footprint.shape[0] == b.count
+            _lib.check(self._lib.neo_mpc_stamp_fleet(self._handle, C.byref(b)))
+        else:
+            import torch
+            for a in (polygons, footprint, poses, problems):
+                assert a is None or (a.is_cuda and a.is_contiguous())
+            if polygons is not None:
+                assert polygons.dtype == torch.float64 and polygons.dim() == 3 and polygons.shape[2] == 2
+                b.polygons = polygons.data_ptr()
+                b.count, b.footprint_points = polygons.shape[0], polygons.shape[1]
+            else:
+                assert footprint.dtype == torch.float64 and footprint.dim() in (2, 3) and footprint.shape[-1] == 2
+                b.footprint = footprint.data_ptr()
+                b.footprint_points = footprint.shape[-2]
+                b.per_robot_footprints = 1 if footprint.dim() == 3 else 0
+                if poses is not None:
+                    assert poses.dtype == torch.float64 and poses.dim() == 2 and poses.shape[1] == 3
+                    b.poses = poses.data_ptr()
+                    b.count = poses.shape[0]
+                elif problems is not None:
+                    b.problems = problems.data_ptr()
+                    b.count = problems.shape[0]
+                assert footprint.dim() == 2 or footprint.shape[0] == b.count
+            stream = torch.cuda.current_stream(shape.device).cuda_stream
+            _lib.check(self._lib.neo_mpc_stamp_fleet_device(self._handle, C.byref(b), C.c_void_p(stream)))
+
     HOST_PATHS = {"auto": 0, "staged": 1, "zerocopy": 2, "zerocopy_out": 3}
 
     def set_host_path(self, mode):
