@@ -4,6 +4,13 @@
 // (src/NeoMpcPlanner.cpp:240-252) calls instead of the ROS2 service hop, and what
 // `MpcOptimizationServer.__init__` (mpc_optimization_server.py:45-152) sets up.
 // There is deliberately no CPU fallback: without a gfx950 device create() fails.
+//
+// In this order: the error setter; DeviceBuffer (device memory that frees itself, and the one-line uploads); MapFence
+// (the ordering of every launch that writes or reads the device map, and the host's wait for an idle map); the handle;
+// parameters and the term table; the shared checks; the device map (geometry, adoption, K3 ingest); the staging of host
+// batches by range; then the entry points -- costmaps, the solve paths of K1, K2 and the hooks, K4 carrots, K6 footprint
+// gate, K7 rolling windows, K8 fleet stamp.  A new entry point checks with the shared checks, stages with upload(), and
+// launches through fence.read() or between fence.begin_write() and end_write().
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -22,22 +29,12 @@ using namespace neo_mpc;
 
 namespace {
 
+// ---------------------------------------------------------------------------------------------- errors
 thread_local std::string g_error;
 thread_local int g_error_code = 0;
 
-int fail(int code, const char* fmt, ...) {
-  char buf[512];
-  va_list ap;
-  va_start(ap, fmt);
-  vsnprintf(buf, sizeof(buf), fmt, ap);
-  va_end(ap);
-  g_error = buf;
-  g_error_code = code;
-  return code;
-}
-
 }  // namespace
-// (shared with neo_mpc_rccl.cpp)
+// The one error setter (neo_mpc_rccl.cpp reports through it too)
 int neo_mpc_set_error(int code, const char* fmt, ...) {
   char buf[512];
   va_list ap;
@@ -50,21 +47,30 @@ int neo_mpc_set_error(int code, const char* fmt, ...) {
 }
 namespace {
 
-#define HIP_TRY(expr)                                                                   \
-  do {                                                                                  \
-    hipError_t e_ = (expr);                                                             \
-    if (e_ != hipSuccess)                                                               \
-      return fail(NEO_MPC_ERR_DEVICE, "%s failed: %s", #expr, hipGetErrorString(e_));   \
+constexpr auto& fail = neo_mpc_set_error;
+
+int hip_check(hipError_t e, const char* what) {
+  return e == hipSuccess ? NEO_MPC_OK : fail(NEO_MPC_ERR_DEVICE, "%s failed: %s", what, hipGetErrorString(e));
+}
+#define HIP_TRY(expr)                                 \
+  do {                                                \
+    if (int rc_ = hip_check((expr), #expr)) return rc_; \
   } while (0)
 
+// ---------------------------------------------------------------------------------------------- device memory
+// A device allocation that grows and is freed with its owner (the handle: hipSetDevice comes before its delete).
 struct DeviceBuffer {
   void* ptr = nullptr;
   size_t bytes = 0;
+  DeviceBuffer() = default;
+  DeviceBuffer(const DeviceBuffer&) = delete;
+  DeviceBuffer& operator=(const DeviceBuffer&) = delete;
+  ~DeviceBuffer() { release(); }
+  // (a failed re-allocation leaves the buffer empty: the old block has been let go.  A successful one never does, not even
+  // for need == 0: upload() can then say "failed" with a null pointer, and a zero-sized costmap goes on to ingest()'s refusal)
   int reserve(size_t need) {
-    if (need <= bytes) return NEO_MPC_OK;
-    if (ptr) (void)hipFree(ptr);
-    ptr = nullptr;
-    bytes = 0;
+    if (ptr && need <= bytes) return NEO_MPC_OK;
+    release();
     size_t cap = need + need / 4 + 256;
     HIP_TRY(hipMalloc(&ptr, cap));
     bytes = cap;
@@ -75,62 +81,166 @@ struct DeviceBuffer {
     ptr = nullptr;
     bytes = 0;
   }
+  template <class T> T* as() const { return static_cast<T*>(ptr); }
+  // Room for `total` bytes, then bytes [at, at + n) of it from `src` on `stream` (asynchronous) -> where they went, or
+  // nullptr with the error set.
+  template <class T> T* upload_range(const T* src, size_t total, size_t at, size_t n, hipStream_t stream) {
+    if (reserve(total)) return nullptr;
+    char* dst = as<char>() + at;
+    if (hip_check(hipMemcpyAsync(dst, src, n, hipMemcpyHostToDevice, stream), "hipMemcpyAsync")) return nullptr;
+    return reinterpret_cast<T*>(dst);
+  }
+  template <class T> T* upload(const T* src, size_t n, hipStream_t stream) { return upload_range(src, n, 0, n, stream); }
+  // ... and back: bytes [at, at + n) to `dst` on `stream` (asynchronous)
+  int download_range(void* dst, size_t at, size_t n, hipStream_t stream) const {
+    return hip_check(hipMemcpyAsync(dst, as<char>() + at, n, hipMemcpyDeviceToHost, stream), "hipMemcpyAsync");
+  }
+  // The whole of `src` with a blocking copy: it is free when this returns
+  template <class T> T* upload(const T* src, size_t n) {
+    if (reserve(n) || hip_check(hipMemcpy(ptr, src, n, hipMemcpyHostToDevice), "hipMemcpy")) return nullptr;
+    return as<T>();
+  }
+};
+
+// ---------------------------------------------------------------------------------------------- the map fence
+// Stream ordering around the device map (map_buf).  A WRITE -- ingest, roll, stamp: the kernels that rewrite the maps in
+// place -- runs behind the previous write and behind every launch still reading the maps, whatever stream it went to, and
+// records `ready` on its stream.  A READ -- every solve / postprocess / objective / gate launch -- waits for `ready` on its
+// own stream and records the in-use event OF ITS STREAM (one per distinct stream the caller has used), which the next
+// write waits for.  (Waits on the stream an event was recorded on are skipped: in order anyway.)
+struct MapFence {
+  static constexpr size_t kMaxUsers = 64;   // distinct streams with a launch in flight between two writes
+  hipEvent_t ready = nullptr;
+  hipStream_t ready_stream = nullptr;
+  struct User { hipStream_t stream; hipEvent_t done; bool pending; };
+  std::vector<User> users;
+
+  int begin_write(hipStream_t st) {
+    if (!ready) HIP_TRY(hipEventCreateWithFlags(&ready, hipEventDisableTiming));
+    else if (ready_stream != st) HIP_TRY(hipStreamWaitEvent(st, ready, 0));   // (two writes must not overlap in map_buf)
+    for (auto& u : users)
+      if (u.pending && u.stream != st) HIP_TRY(hipStreamWaitEvent(st, u.done, 0));
+    return NEO_MPC_OK;
+  }
+  // (the readers begin_write queued its waits for are covered by `ready` from here on, and only from here on: a write whose
+  // launch failed leaves them pending)
+  int end_write(hipStream_t st) {
+    HIP_TRY(hipEventRecord(ready, st));
+    ready_stream = st;
+    for (auto& u : users) u.pending = false;
+    return NEO_MPC_OK;
+  }
+  // `launch` enqueues one kernel that reads the maps on `stream`
+  template <class Launch> int read(void* stream, Launch&& launch) {
+    hipStream_t st = (hipStream_t)stream;
+    int rc = wait_writer(st);
+    if (rc) return rc;
+    launch();
+    HIP_TRY(hipGetLastError());
+    return release(st);
+  }
+  // behind the last write, on a stream ...
+  int wait_writer(hipStream_t st) {
+    if (ready && ready_stream != st) HIP_TRY(hipStreamWaitEvent(st, ready, 0));
+    return NEO_MPC_OK;
+  }
+  // ... or on the host
+  int wait_writer_host() {
+    if (ready) HIP_TRY(hipEventSynchronize(ready));
+    return NEO_MPC_OK;
+  }
+  // The host's wait for a map nobody is using: before the term table or the pool's origins are rewritten (blocking copies
+  // on the null stream, which do not order against the non-blocking streams batches are in flight on) every launch that
+  // may still read them has to have ENDED.  Those are the pending readers -- and the readers a write has already cleared:
+  // begin_write only queued a wait for them on its stream, so they may still be running, but end_write recorded `ready` on
+  // that stream behind those waits, and it ends after every one of them.  (The device map itself is ordered by the stream waits
+  // above; these two small tables change on reconfiguration / pool re-centring only, so a host-side wait is cheap.)
+  int wait_idle() {
+    for (auto& u : users)
+      if (u.pending) HIP_TRY(hipEventSynchronize(u.done));
+    return wait_writer_host();
+  }
+  void destroy() {
+    if (ready) (void)hipEventDestroy(ready);
+    for (auto& u : users) (void)hipEventDestroy(u.done);
+  }
+
+ private:
+  // one event per distinct stream, re-recorded by that stream's latest launch
+  int release(hipStream_t st) {
+    User* slot = nullptr;
+    for (auto& u : users) if (u.stream == st) { slot = &u; break; }
+    if (!slot) {
+      if (users.size() >= kMaxUsers) {
+        // more streams than slots: the oldest slot's launch is waited for here and the slot re-used
+        slot = &users.front();
+        if (slot->pending) HIP_TRY(hipEventSynchronize(slot->done));
+        slot->stream = st;
+      } else {
+        hipEvent_t ev;
+        HIP_TRY(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
+        users.push_back({st, ev, false});
+        slot = &users.back();
+      }
+    }
+    HIP_TRY(hipEventRecord(slot->done, st));
+    slot->pending = true;
+    return NEO_MPC_OK;
+  }
 };
 
 }  // namespace
 
-struct neo_mpc_handle {
+// (hidden: its destructor, no longer trivial, is no export)
+struct __attribute__((visibility("hidden"))) neo_mpc_handle {
   int device = 0;
   neo_mpc_params params{};
   DevParams dp{};
+  LdsLayout lds{};
+  // the environment's A/B switches, read once by neo_mpc_create (include/neo_mpc.h)
+  LaunchTuning tuning;
+  bool no_chunks = false;     // NEO_MPC_NO_CHUNKS: large staged host batches go through in one piece
+  int auto_host_path = NEO_MPC_HOST_PATH_ZEROCOPY;   // what NEO_MPC_HOST_PATH_AUTO means (NEO_MPC_HOST_PATH)
+  // the device map: one costmap or a pool (map_buf; raw_buf and origins_buf: the host variants' cells and origins), the
+  // term table of the costmap weight, and their ordering
   DevMap map{};
   bool has_map = false;
-  LdsLayout lds{};
+  bool rolled = false;                      // the device map was written by a roll (fence.ready: that roll's end)
   DeviceBuffer map_buf, raw_buf, term_buf, origins_buf;
-  DeviceBuffer problems, states, warm, commands, solution, path, footprints, success, u, cost;
-  DeviceBuffer plan_poses, plan_offsets, robot_poses, fp_costs, slow_down, carrots, vel;
-  DeviceBuffer gate_polygon, gate_poses, gate_indices, gate_polygons_out;   // neo_mpc_footprint_gate (its costs: fp_costs)
-  // neo_mpc_set_world_map / neo_mpc_roll_costmap_pool (K7): the handle's own copy of the world map, the fill's index tables
-  // and the host variant's poses (its origins: origins_buf)
-  DeviceBuffer world_buf, roll_tables, roll_poses;
+  MapFence fence;
+  // staging of host batches: the records of a batch, and what the host variants of K4 / K6 / K7 / K8 share -- a fleet's
+  // [count][3] poses and its footprint or polygon vertices.  (Every host variant has finished with its staging when it
+  // returns -- a blocking copy or a synchronisation behind its kernel -- so one buffer serves them all.)
+  DeviceBuffer problems, states, warm, commands, solution, path, vel, footprints, success, u, cost;
+  DeviceBuffer poses, verts;
+  int host_path = NEO_MPC_HOST_PATH_AUTO;   // neo_mpc_set_host_path
+  // latency path of neo_mpc_solve_batch (small host batches, the plugin's count = 1): one pinned
+  // staging block and one device arena, so a tick is one H2D, K1, one D2H and one synchronisation
+  void* pin = nullptr;
+  DeviceBuffer arena;
+  hipStream_t chunk_streams[2] = {nullptr, nullptr};   // staged host batches of >= kChunkedMinCount instances: copy / solve pipeline
+  // neo_mpc_solve_batch_begin / _wait: page-locked batches in flight, each on a stream of its own
+  struct InFlight { hipStream_t stream = nullptr; hipEvent_t done = nullptr; bool busy = false; };
+  InFlight in_flight[NEO_MPC_MAX_BATCHES_IN_FLIGHT];
+  DeviceBuffer order_buf;     // dispatch order of device batches (neo_mpc_balance_dispatch_device)
+  DeviceBuffer load_buf;      // ... and the exponential average of the iteration counts it is sorted by
+  size_t order_count = 0;     // ... armed for batches of this many instances; 0: launch order
+  // K4 neo_mpc_select_carrots (its robot poses: poses) and K6 neo_mpc_footprint_gate (its polygon: verts; fp_costs: both)
+  DeviceBuffer plan_poses, plan_offsets, fp_costs, slow_down, carrots;
+  DeviceBuffer gate_indices, gate_polygons_out;
+  // K7 neo_mpc_set_world_map / neo_mpc_roll_costmap_pool: the handle's own copy of the world map and the fill's index tables
+  DeviceBuffer world_buf, roll_tables;
   bool has_world = false;
   int32_t world_size_x = 0, world_size_y = 0;
   double world_resolution = 0.0, world_origin_x = 0.0, world_origin_y = 0.0;
   hipEvent_t world_ready = nullptr;         // recorded behind the copy into world_buf; a roll on another stream waits for it
   hipStream_t world_ready_stream = nullptr;
-  bool rolled = false;                      // the device map was written by a roll (map_ready: that roll's end)
-  // neo_mpc_stamp_fleet (K8): the cost table and the key it was built for, the oriented polygons and their bounding
-  // boxes, and the host variant's polygons / footprint and poses
-  DeviceBuffer stamp_table, stamp_polys, stamp_boxes, stamp_in, stamp_poses;
+  // K8 neo_mpc_stamp_fleet: the cost table and the key it was built for, the oriented polygons and their bounding boxes
+  DeviceBuffer stamp_table, stamp_polys, stamp_boxes;
   bool has_stamp_table = false;
   double stamp_key[4] = {0.0, 0.0, 0.0, 0.0};   // resolution, inscribed_radius, inflation_radius, cost_scaling_factor
   int32_t stamp_reach = 0;
-  // latency path of neo_mpc_solve_batch (small host batches, the plugin's count = 1): one pinned
-  // staging block and one device arena, so a tick is one H2D, K1, one D2H and one synchronisation
-  void* pin = nullptr;
-  DeviceBuffer arena;
-  DeviceBuffer order_buf;     // dispatch order of device batches (neo_mpc_balance_dispatch_device)
-  DeviceBuffer load_buf;      // ... and the exponential average of the iteration counts it is sorted by
-  size_t order_count = 0;     // ... armed for batches of this many instances; 0: launch order
-  // Stream ordering around the device map: every ingest records map_ready on the stream it ran on and
-  // every solve / postprocess / objective launch waits for it on its own stream; every such launch
-  // records the in-use event OF ITS STREAM (one per distinct stream the caller has used), and the next
-  // ingest waits for all of them -- and for the previous ingest -- before it rewrites map_buf in place.
-  hipEvent_t map_ready = nullptr;
-  hipStream_t map_ready_stream = nullptr;   // (waits on the stream an event was recorded on are skipped: in order anyway)
-  struct MapUser { hipStream_t stream; hipEvent_t done; bool pending; };
-  std::vector<MapUser> map_users;
-  int host_path = NEO_MPC_HOST_PATH_AUTO;   // neo_mpc_set_host_path
-  // the environment's A/B switches, read once by neo_mpc_create (include/neo_mpc.h)
-  LaunchTuning tuning;
-  bool no_chunks = false;     // NEO_MPC_NO_CHUNKS: large staged host batches go through in one piece
-  int auto_host_path = NEO_MPC_HOST_PATH_ZEROCOPY;   // what NEO_MPC_HOST_PATH_AUTO means (NEO_MPC_HOST_PATH)
-  // neo_mpc_solve_batch_begin / _wait: page-locked batches in flight, each on a stream of its own
-  struct InFlight { hipStream_t stream = nullptr; hipEvent_t done = nullptr; bool busy = false; };
-  InFlight in_flight[NEO_MPC_MAX_BATCHES_IN_FLIGHT];
-  hipStream_t chunk_streams[2] = {nullptr, nullptr};   // staged host batches of >= kChunkedMinCount instances: copy / solve pipeline
 };
-constexpr size_t kMaxMapUsers = 64;   // distinct streams with a launch in flight between two ingests
 constexpr size_t kLatencyPathMaxCount = 64;
 constexpr size_t kChunkedMinCount = 65536;   // staged host batches from here on go through in kChunks pieces on two streams
                                              // (measured: pageable 32 768 instances 24.0 M solves/s in pieces against 28.6 M in one,
@@ -260,17 +370,6 @@ void derive(neo_mpc_handle* h) {
   l.total_bytes = (l.total_bytes + 15) & ~15;
 }
 
-// The term table and the pool's origins are read by every K1 wave as it starts: before either is rewritten (blocking
-// copies on the null stream, which do not order against the non-blocking streams batches are in flight on) every launch
-// that may still read them is waited for -- the events map_release recorded, one per stream.  (The device map itself is
-// ordered by stream waits in ingest(); these two small tables change on reconfiguration / pool re-centring only, so a
-// host-side wait is cheap.)
-int wait_map_users(neo_mpc_handle* h) {
-  for (auto& u : h->map_users)
-    if (u.pending) HIP_TRY(hipEventSynchronize(u.done));
-  return NEO_MPC_OK;
-}
-
 int upload_term_table(neo_mpc_handle* h) {
   double table[256];
   const neo_mpc_params& p = h->params;
@@ -280,11 +379,9 @@ int upload_term_table(neo_mpc_handle* h) {
     const double cc = c * c;                           // py:247
     table[raw] = (c == 1.0) ? cc * 1000 / n : p.w_costmap * cc / n;  // py:257-260
   }
-  int rc = wait_map_users(h);   // (a batch in flight reads the old table to its end)
+  int rc = h->fence.wait_idle();   // (a batch in flight reads the old table to its end)
   if (rc) return rc;
-  if ((rc = h->term_buf.reserve(sizeof(table)))) return rc;
-  HIP_TRY(hipMemcpy(h->term_buf.ptr, table, sizeof(table), hipMemcpyHostToDevice));
-  return NEO_MPC_OK;
+  return h->term_buf.upload(table, sizeof(table)) ? NEO_MPC_OK : NEO_MPC_ERR_DEVICE;
 }
 
 int apply_params(neo_mpc_handle* h, const neo_mpc_params* params, bool live_handle) {
@@ -295,50 +392,104 @@ int apply_params(neo_mpc_handle* h, const neo_mpc_params* params, bool live_hand
   return upload_term_table(h);
 }
 
+// ---------------------------------------------------------------------------------------------- shared checks
+int check_count(size_t count, size_t most = 0x7fffffffull) {
+  return count > most ? fail(NEO_MPC_ERR_INVALID_ARGUMENT, "count too large") : NEO_MPC_OK;
+}
+
+int check_pool_count(uint32_t count) {
+  if (count == 0) return fail(NEO_MPC_ERR_INVALID_ARGUMENT, "bad costmap count %u", count);
+  if (count > NEO_MPC_MAX_POOL_MAPS)   // K3 takes the map index from the grid's y coordinate
+    return fail(NEO_MPC_ERR_UNSUPPORTED, "costmap pool of %u maps: at most %u per call", count, NEO_MPC_MAX_POOL_MAPS);
+  return NEO_MPC_OK;
+}
+
+int check_footprint_shape(uint32_t points, uint32_t per_robot) {
+  if (points < 3 || points > NEO_MPC_MAX_FOOTPRINT_POINTS)
+    return fail(NEO_MPC_ERR_INVALID_ARGUMENT, "footprint_points %u outside [3, %d]", points, NEO_MPC_MAX_FOOTPRINT_POINTS);
+  if (per_robot > 1) return fail(NEO_MPC_ERR_INVALID_ARGUMENT, "per_robot_footprints must be 0 or 1 (got %u)", per_robot);
+  return NEO_MPC_OK;
+}
+
+// The value checks of the host variants (the device variants take values as they come).  `polygons` polygons of `np` vertices:
+int check_vertices_finite(const double* v, size_t polygons, size_t np, const char* vertex, const char* polygon) {
+  for (size_t k = 0; k < polygons * np * 2; ++k)
+    if (!std::isfinite(v[k]))
+      return fail(NEO_MPC_ERR_INVALID_ARGUMENT, "%s %zu of %s %zu is not finite", vertex, (k / 2) % np, polygon, k / (2 * np));
+  return NEO_MPC_OK;
+}
+
+// ... and the poses a footprint is placed at: poses[i], else the pose of problems[i].  `more(i)`: what else a caller looks at
+// robot by robot, behind robot i's pose
+inline int nothing_more(size_t) { return NEO_MPC_OK; }
+template <class More = int (*)(size_t)>
+int check_poses_finite(const double* poses, const neo_mpc_problem* problems, size_t n, More&& more = nothing_more) {
+  for (size_t i = 0; i < n; ++i) {
+    bool finite = true;
+    if (poses) for (int k = 0; k < 3; ++k) finite = finite && std::isfinite(poses[3 * i + k]);
+    else {
+      for (int k = 0; k < 2; ++k) finite = finite && std::isfinite(problems[i].cur_xy[k]);
+      for (int k = 0; k < 4; ++k) finite = finite && std::isfinite(problems[i].cur_q[k]);
+    }
+    if (!finite) return fail(NEO_MPC_ERR_INVALID_ARGUMENT, "the pose of robot %zu is not finite", i);
+    if (int rc = more(i)) return rc;
+  }
+  return NEO_MPC_OK;
+}
+
+// ---------------------------------------------------------------------------------------------- the device map
+// A map of sx x sy cells as it lies in map_buf: `border` cells around it, rows pitched to 128 bytes.
+struct PaddedMap {
+  uint32_t sx, sy;
+  int border, pitch, rows;
+  size_t stride;   // bytes from one map of a pool to the next
+  PaddedMap(uint32_t sx_, uint32_t sy_, int border_)
+      : sx(sx_), sy(sy_), border(border_), pitch((int)((sx_ + 2 * border_ + 127) & ~127u)), rows((int)sy_ + 2 * border_),
+        stride((size_t)pitch * rows) {}
+  // K3 and K7 index the 16-byte chunks of one map with 32 bits
+  int check(const char* what) const {
+    if (stride / 16 < (1ull << 31)) return NEO_MPC_OK;
+    return fail(NEO_MPC_ERR_UNSUPPORTED, "%s %ux%u is too large (over 32 GiB padded)", what, sx, sy);
+  }
+};
+
+// map_buf holds `maps` such maps from here on (d_origins == nullptr: the single map with origin (ox, oy))
+void adopt_map(neo_mpc_handle* h, const PaddedMap& g, uint32_t maps, double res, double ox, double oy, const double* d_origins,
+               bool rolled) {
+  h->map.cells = h->map_buf.as<const uint8_t>() + (size_t)g.border * g.pitch + g.border;
+  h->map.size_x = (int)g.sx; h->map.size_y = (int)g.sy; h->map.pitch = g.pitch;
+  h->map.resolution = res; h->map.inv_resolution = 1.0 / res;
+  h->map.origin_x = ox; h->map.origin_y = oy;
+  h->map.pool_count = d_origins ? (int)maps : 0;
+  h->map.border = g.border;
+  h->map.pool_stride = (int64_t)g.stride;
+  h->map.pool_origins = d_origins;
+  h->has_map = true;
+  h->rolled = rolled;
+  derive(h);
+}
+
 // `maps` raw costmaps back to back in device memory -> bordered, pitched device maps (K3).
 // d_origins == nullptr: a single map with origin (ox, oy); else a pool whose origins stay where they are.
 int ingest(neo_mpc_handle* h, const uint8_t* d_cells, uint32_t maps, uint32_t sx, uint32_t sy, double res, double ox,
            double oy, const double* d_origins, void* stream) {
   if (!d_cells || maps == 0 || sx == 0 || sy == 0 || sx > (1u << 20) || sy > (1u << 20) || !(res > 0.0))
     return fail(NEO_MPC_ERR_INVALID_ARGUMENT, "bad costmap geometry %ux%u x%u res %g", sx, sy, maps, res);
-  const int border = d_origins ? kPoolBorder : kMapBorder;
-  const int pitch = (int)((sx + 2 * border + 127) & ~127u);
-  const int rows = (int)sy + 2 * border;
-  const size_t stride = (size_t)pitch * rows;
-  if (stride / 16 >= (1ull << 31))   // K3 indexes the 16-byte chunks of one map with 32 bits
-    return fail(NEO_MPC_ERR_UNSUPPORTED, "costmap %ux%u is too large (over 32 GiB padded)", sx, sy);
-  int rc = h->map_buf.reserve(stride * maps);
+  const PaddedMap g(sx, sy, d_origins ? kPoolBorder : kMapBorder);
+  int rc = g.check("costmap");
   if (rc) return rc;
+  if ((rc = h->map_buf.reserve(g.stride * maps))) return rc;
   hipStream_t st = (hipStream_t)stream;
-  if (!h->map_ready) HIP_TRY(hipEventCreateWithFlags(&h->map_ready, hipEventDisableTiming));
-  // behind the previous ingest (two ingests on different streams must not overlap in map_buf) ...
-  else if (h->map_ready_stream != st) HIP_TRY(hipStreamWaitEvent(st, h->map_ready, 0));
-  // ... and behind every launch still reading the old map, whatever stream it went to
-  for (auto& u : h->map_users)
-    if (u.pending) {
-      if (u.stream != st) HIP_TRY(hipStreamWaitEvent(st, u.done, 0));
-      u.pending = false;
-    }
+  if ((rc = h->fence.begin_write(st))) return rc;
   IngestArgs a;
   a.src = d_cells;
-  a.dst = (uint8_t*)h->map_buf.ptr;
-  a.size_x = (int)sx; a.size_y = (int)sy; a.pitch = pitch; a.rows = rows;
-  a.maps = (int)maps; a.border = border; a.dst_stride = (int64_t)stride;
+  a.dst = h->map_buf.as<uint8_t>();
+  a.size_x = (int)sx; a.size_y = (int)sy; a.pitch = g.pitch; a.rows = g.rows;
+  a.maps = (int)maps; a.border = g.border; a.dst_stride = (int64_t)g.stride;
   launch_ingest(a, h->tuning, stream);
   HIP_TRY(hipGetLastError());
-  HIP_TRY(hipEventRecord(h->map_ready, st));
-  h->map_ready_stream = st;
-  h->map.cells = (const uint8_t*)h->map_buf.ptr + (size_t)border * pitch + border;
-  h->map.size_x = (int)sx; h->map.size_y = (int)sy; h->map.pitch = pitch;
-  h->map.resolution = res; h->map.inv_resolution = 1.0 / res;
-  h->map.origin_x = ox; h->map.origin_y = oy;
-  h->map.pool_count = d_origins ? (int)maps : 0;
-  h->map.border = border;
-  h->map.pool_stride = (int64_t)stride;
-  h->map.pool_origins = d_origins;
-  h->has_map = true;
-  h->rolled = false;
-  derive(h);
+  if ((rc = h->fence.end_write(st))) return rc;
+  adopt_map(h, g, maps, res, ox, oy, d_origins, false);
   return NEO_MPC_OK;
 }
 
@@ -348,7 +499,7 @@ int fill_args(neo_mpc_handle* h, const neo_mpc_batch* b, SolveArgs& a) {
   if (!h->has_map) return fail(NEO_MPC_ERR_NO_COSTMAP, "neo_mpc_set_costmap has not been called");
   if (b->count > 0 && (!b->problems || !b->states || !b->warm_start || !b->commands))
     return fail(NEO_MPC_ERR_INVALID_ARGUMENT, "problems/states/warm_start/commands must not be null");
-  if (b->count > 0x7fffffffull) return fail(NEO_MPC_ERR_INVALID_ARGUMENT, "count too large");
+  if (int rc = check_count(b->count)) return rc;
   if (b->footprints && b->footprint_points > NEO_MPC_MAX_FOOTPRINT_POINTS)
     return fail(NEO_MPC_ERR_INVALID_ARGUMENT, "footprint_points > %d", NEO_MPC_MAX_FOOTPRINT_POINTS);
   std::memset(&a, 0, sizeof(a));
@@ -358,95 +509,100 @@ int fill_args(neo_mpc_handle* h, const neo_mpc_batch* b, SolveArgs& a) {
   a.footprints = b->footprint_points ? b->footprints : nullptr;
   a.footprint_points = b->footprints ? b->footprint_points : 0;
   a.count = (uint32_t)b->count;
-  a.term_table = (const double*)h->term_buf.ptr;
+  a.term_table = h->term_buf.as<const double>();
   a.p = h->dp; a.map = h->map; a.lds = h->lds;
   return NEO_MPC_OK;
 }
 
-// order a launch that reads the device map on `stream`: behind the last ingest ...
-int map_acquire(neo_mpc_handle* h, void* stream) {
-  if (h->map_ready && h->map_ready_stream != (hipStream_t)stream)
-    HIP_TRY(hipStreamWaitEvent((hipStream_t)stream, h->map_ready, 0));
-  return NEO_MPC_OK;
-}
-// ... and in front of the next one: one event per distinct stream, re-recorded by that stream's latest launch
-int map_release(neo_mpc_handle* h, void* stream) {
-  hipStream_t st = (hipStream_t)stream;
-  neo_mpc_handle::MapUser* slot = nullptr;
-  for (auto& u : h->map_users) if (u.stream == st) { slot = &u; break; }
-  if (!slot) {
-    if (h->map_users.size() >= kMaxMapUsers) {
-      // more streams than slots: the oldest slot's launch is waited for here and the slot re-used
-      slot = &h->map_users.front();
-      if (slot->pending) HIP_TRY(hipEventSynchronize(slot->done));
-      slot->stream = st;
-    } else {
-      hipEvent_t ev;
-      HIP_TRY(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
-      h->map_users.push_back({st, ev, false});
-      slot = &h->map_users.back();
-    }
-  }
-  HIP_TRY(hipEventRecord(slot->done, st));
-  slot->pending = true;
-  return NEO_MPC_OK;
+// K1 with `a` on `stream`, in its place between the map's writes
+int solve_on(neo_mpc_handle* h, const SolveArgs& a, void* stream) {
+  return h->fence.read(stream, [&] { launch_solve(a, h->tuning, stream); });
 }
 
-// host batch -> device staging; returns the device-pointer batch in `d`
-int stage_in(neo_mpc_handle* h, const neo_mpc_batch* b, neo_mpc_batch& d, bool solution_is_input) {
+// ---------------------------------------------------------------------------------------------- staging of host batches
+// Host batches go up and come back by range: records [off, off + m) of the batch `b`, to and from their place in the handle's
+// staging buffers (sized for the whole batch), queued on `st`.  A staged batch is the range [0, count) on the null stream,
+// a chunked one kChunks ranges on two streams.  Every copy is asynchronous: the caller leaves no way out while one may
+// still be reading or writing the host arrays.
+//
+// The request / state / warm-start records -> d.problems, d.states, d.warm_start
+int stage_records(neo_mpc_handle* h, const neo_mpc_batch* b, size_t off, size_t m, hipStream_t st, neo_mpc_batch& d) {
   const size_t n = b->count, nv = 3 * (size_t)h->params.control_steps;
-  int rc;
-  if ((rc = h->problems.reserve(n * sizeof(neo_mpc_problem)))) return rc;
-  if ((rc = h->states.reserve(n * sizeof(neo_mpc_state)))) return rc;
-  if ((rc = h->warm.reserve(n * nv * 8))) return rc;
-  if ((rc = h->commands.reserve(n * sizeof(neo_mpc_command)))) return rc;
+  const size_t prob = sizeof(neo_mpc_problem), state = sizeof(neo_mpc_state), row = nv * 8;
+  d.problems = h->problems.upload_range(b->problems + off, n * prob, off * prob, m * prob, st);
+  d.states = d.problems ? h->states.upload_range(b->states + off, n * state, off * state, m * state, st) : nullptr;
+  d.warm_start = d.states ? h->warm.upload_range(b->warm_start + off * nv, n * row, off * row, m * row, st) : nullptr;
+  return d.warm_start ? NEO_MPC_OK : NEO_MPC_ERR_DEVICE;
+}
+
+// ... and with room for every output the batch asks for -> `d`: those m records as a device-pointer batch, without a
+// footprint raster
+int stage_up(neo_mpc_handle* h, const neo_mpc_batch* b, size_t off, size_t m, hipStream_t st, neo_mpc_batch& d,
+             bool solution_is_input) {
+  const size_t n = b->count, nv = 3 * (size_t)h->params.control_steps;
   d = *b;
-  d.problems = (const neo_mpc_problem*)h->problems.ptr;
-  d.states = (neo_mpc_state*)h->states.ptr;
-  d.warm_start = (double*)h->warm.ptr;
-  d.commands = (neo_mpc_command*)h->commands.ptr;
-  HIP_TRY(hipMemcpyAsync(h->problems.ptr, b->problems, n * sizeof(neo_mpc_problem), hipMemcpyHostToDevice, nullptr));
-  HIP_TRY(hipMemcpyAsync(h->states.ptr, b->states, n * sizeof(neo_mpc_state), hipMemcpyHostToDevice, nullptr));
-  HIP_TRY(hipMemcpyAsync(h->warm.ptr, b->warm_start, n * nv * 8, hipMemcpyHostToDevice, nullptr));
+  d.count = m;
+  d.footprints = nullptr; d.footprint_points = 0;
+  int rc = stage_records(h, b, off, m, st, d);
+  if (rc) return rc;
+  if ((rc = h->commands.reserve(n * sizeof(neo_mpc_command)))) return rc;
+  d.commands = h->commands.as<neo_mpc_command>() + off;
   if (b->solution) {
-    if ((rc = h->solution.reserve(n * nv * 8))) return rc;
-    d.solution = (double*)h->solution.ptr;
-    if (solution_is_input) HIP_TRY(hipMemcpyAsync(h->solution.ptr, b->solution, n * nv * 8, hipMemcpyHostToDevice, nullptr));
+    if (solution_is_input) {
+      d.solution = h->solution.upload_range(b->solution + off * nv, n * nv * 8, off * nv * 8, m * nv * 8, st);
+      if (!d.solution) return NEO_MPC_ERR_DEVICE;
+    } else {
+      if ((rc = h->solution.reserve(n * nv * 8))) return rc;
+      d.solution = h->solution.as<double>() + off * nv;
+    }
   }
   if (b->predicted_path) {
     if ((rc = h->path.reserve(n * nv * 8))) return rc;
-    d.predicted_path = (double*)h->path.ptr;
+    d.predicted_path = h->path.as<double>() + off * nv;
   }
   if (b->velocities) {
     if ((rc = h->vel.reserve(n * 24))) return rc;
-    d.velocities = (double*)h->vel.ptr;
-  }
-  if (b->footprints && b->footprint_points) {
-    const size_t bytes = n * b->footprint_points * 2 * 8;
-    for (size_t k = 0; k < n * b->footprint_points * 2; ++k)
-      if (!std::isfinite(b->footprints[k]))
-        return fail(NEO_MPC_ERR_INVALID_ARGUMENT, "footprint vertex %zu of instance %zu is not finite",
-                    (k / 2) % b->footprint_points, k / (2 * b->footprint_points));
-    if ((rc = h->footprints.reserve(bytes))) return rc;
-    HIP_TRY(hipMemcpyAsync(h->footprints.ptr, b->footprints, bytes, hipMemcpyHostToDevice, nullptr));
-    d.footprints = (const double*)h->footprints.ptr;
+    d.velocities = h->vel.as<double>() + off * 3;
   }
   return NEO_MPC_OK;
 }
 
+// The results of that range, queued on `st` behind the kernel and not waited for: with page-locked host arrays (hipHostMalloc /
+// hipHostRegister / torch pin_memory) they are DMA transfers that overlap the host side of what follows; with pageable arrays
+// the runtime stages them and each call returns when its copy is done
+int stage_down(neo_mpc_handle* h, const neo_mpc_batch* b, size_t off, size_t m, hipStream_t st, bool solution_is_output) {
+  const size_t nv = 3 * (size_t)h->params.control_steps;
+  const size_t cmd = sizeof(neo_mpc_command), state = sizeof(neo_mpc_state), row = nv * 8;
+  int rc;
+  if ((rc = h->commands.download_range(b->commands + off, off * cmd, m * cmd, st))) return rc;
+  if ((rc = h->states.download_range(b->states + off, off * state, m * state, st))) return rc;
+  if ((rc = h->warm.download_range(b->warm_start + off * nv, off * row, m * row, st))) return rc;
+  if (b->solution && solution_is_output &&
+      (rc = h->solution.download_range(b->solution + off * nv, off * row, m * row, st)))
+    return rc;
+  if (b->predicted_path && (rc = h->path.download_range(b->predicted_path + off * nv, off * row, m * row, st)))
+    return rc;
+  if (b->velocities && (rc = h->vel.download_range(b->velocities + off * 3, off * 24, m * 24, st))) return rc;
+  return NEO_MPC_OK;
+}
+
+// A whole host batch on the null stream, with its footprint raster
+int stage_in(neo_mpc_handle* h, const neo_mpc_batch* b, neo_mpc_batch& d, bool solution_is_input) {
+  int rc = stage_up(h, b, 0, b->count, nullptr, d, solution_is_input);
+  if (rc) return rc;
+  if (b->footprints && b->footprint_points) {
+    if ((rc = check_vertices_finite(b->footprints, b->count, b->footprint_points, "footprint vertex", "instance"))) return rc;
+    d.footprints = h->footprints.upload(b->footprints, b->count * b->footprint_points * 16, nullptr);
+    if (!d.footprints) return NEO_MPC_ERR_DEVICE;
+    d.footprint_points = b->footprint_points;
+  }
+  return NEO_MPC_OK;
+}
+
+// ... and back, waited for once
 int stage_out(neo_mpc_handle* h, const neo_mpc_batch* b, bool solution_is_output) {
-  const size_t n = b->count, nv = 3 * (size_t)h->params.control_steps;
-  // every copy is queued on the null stream behind the kernel and waited for once: with page-locked host buffers
-  // (hipHostMalloc / hipHostRegister / torch pin_memory) they are DMA transfers that overlap the host side of the
-  // next call; with pageable buffers the runtime stages them and each call returns when its copy is done
-  HIP_TRY(hipMemcpyAsync(b->commands, h->commands.ptr, n * sizeof(neo_mpc_command), hipMemcpyDeviceToHost, nullptr));
-  HIP_TRY(hipMemcpyAsync(b->states, h->states.ptr, n * sizeof(neo_mpc_state), hipMemcpyDeviceToHost, nullptr));
-  HIP_TRY(hipMemcpyAsync(b->warm_start, h->warm.ptr, n * nv * 8, hipMemcpyDeviceToHost, nullptr));
-  if (b->solution && solution_is_output)
-    HIP_TRY(hipMemcpyAsync(b->solution, h->solution.ptr, n * nv * 8, hipMemcpyDeviceToHost, nullptr));
-  if (b->predicted_path)
-    HIP_TRY(hipMemcpyAsync(b->predicted_path, h->path.ptr, n * nv * 8, hipMemcpyDeviceToHost, nullptr));
-  if (b->velocities) HIP_TRY(hipMemcpyAsync(b->velocities, h->vel.ptr, n * 24, hipMemcpyDeviceToHost, nullptr));
+  int rc = stage_down(h, b, 0, b->count, nullptr, solution_is_output);
+  if (rc) return rc;
   HIP_TRY(hipStreamSynchronize(nullptr));
   return NEO_MPC_OK;
 }
@@ -518,24 +674,16 @@ neo_mpc_handle* neo_mpc_create(const neo_mpc_params* params, int device) {
 void neo_mpc_destroy(neo_mpc_handle* h) {
   if (!h) return;
   (void)hipSetDevice(h->device);
-  DeviceBuffer* all[] = {&h->map_buf, &h->raw_buf, &h->term_buf, &h->problems, &h->states, &h->warm, &h->commands,
-                         &h->solution, &h->path, &h->footprints, &h->success, &h->u, &h->cost, &h->plan_poses,
-                         &h->plan_offsets, &h->robot_poses, &h->fp_costs, &h->slow_down, &h->carrots, &h->vel,
-                         &h->arena, &h->origins_buf, &h->order_buf, &h->load_buf, &h->gate_polygon, &h->gate_poses,
-                         &h->gate_indices, &h->gate_polygons_out, &h->world_buf, &h->roll_tables, &h->roll_poses,
-                         &h->stamp_table, &h->stamp_polys, &h->stamp_boxes, &h->stamp_in, &h->stamp_poses};
-  for (DeviceBuffer* b : all) b->release();
-  if (h->pin) (void)hipHostFree(h->pin);
-  if (h->map_ready) (void)hipEventDestroy(h->map_ready);
-  if (h->world_ready) (void)hipEventDestroy(h->world_ready);
-  for (auto& u : h->map_users) (void)hipEventDestroy(u.done);
-  for (hipStream_t cs : h->chunk_streams) if (cs) (void)hipStreamDestroy(cs);
   for (auto& f : h->in_flight) {
     if (f.busy) (void)hipEventSynchronize(f.done);
     if (f.done) (void)hipEventDestroy(f.done);
     if (f.stream) (void)hipStreamDestroy(f.stream);
   }
-  delete h;
+  for (hipStream_t cs : h->chunk_streams) if (cs) (void)hipStreamDestroy(cs);
+  h->fence.destroy();
+  if (h->world_ready) (void)hipEventDestroy(h->world_ready);
+  if (h->pin) (void)hipHostFree(h->pin);
+  delete h;   // (every DeviceBuffer frees its own memory, on the device set above)
 }
 
 int neo_mpc_set_params(neo_mpc_handle* h, const neo_mpc_params* params) {
@@ -560,12 +708,11 @@ int neo_mpc_set_costmap(neo_mpc_handle* h, const uint8_t* cells, uint32_t sx, ui
                         double oy) {
   if (!h || !cells) return fail(NEO_MPC_ERR_INVALID_ARGUMENT, "null argument");
   HIP_TRY(hipSetDevice(h->device));
-  int rc = h->raw_buf.reserve((size_t)sx * sy);
-  if (rc) return rc;
-  HIP_TRY(hipMemcpy(h->raw_buf.ptr, cells, (size_t)sx * sy, hipMemcpyHostToDevice));
+  const uint8_t* d_cells = h->raw_buf.upload(cells, (size_t)sx * sy);
+  if (!d_cells) return NEO_MPC_ERR_DEVICE;
   // no synchronisation: `cells` has been consumed by the (blocking) copy above; K3 runs on the null
-  // stream and every later launch waits for map_ready (recorded by ingest) on its own stream
-  return ingest(h, (const uint8_t*)h->raw_buf.ptr, 1, sx, sy, res, ox, oy, nullptr, nullptr);
+  // stream and every later launch waits for the fence (ingest's end_write) on its own stream
+  return ingest(h, d_cells, 1, sx, sy, res, ox, oy, nullptr, nullptr);
 }
 
 int neo_mpc_set_costmap_device(neo_mpc_handle* h, const uint8_t* d_cells, uint32_t sx, uint32_t sy, double res,
@@ -578,9 +725,7 @@ int neo_mpc_set_costmap_device(neo_mpc_handle* h, const uint8_t* d_cells, uint32
 int neo_mpc_set_costmap_pool_device(neo_mpc_handle* h, const uint8_t* d_cells, uint32_t count, uint32_t sx,
                                     uint32_t sy, double res, const double* d_origins, void* stream) {
   if (!h || !d_cells || !d_origins) return fail(NEO_MPC_ERR_INVALID_ARGUMENT, "null argument");
-  if (count == 0) return fail(NEO_MPC_ERR_INVALID_ARGUMENT, "bad costmap count %u", count);
-  if (count > NEO_MPC_MAX_POOL_MAPS)   // K3 takes the map index from the grid's y coordinate
-    return fail(NEO_MPC_ERR_UNSUPPORTED, "costmap pool of %u maps: at most %u per call", count, NEO_MPC_MAX_POOL_MAPS);
+  if (int rc = check_pool_count(count)) return rc;
   HIP_TRY(hipSetDevice(h->device));
   return ingest(h, d_cells, count, sx, sy, res, 0.0, 0.0, d_origins, stream);
 }
@@ -588,19 +733,14 @@ int neo_mpc_set_costmap_pool_device(neo_mpc_handle* h, const uint8_t* d_cells, u
 int neo_mpc_set_costmap_pool(neo_mpc_handle* h, const uint8_t* cells, uint32_t count, uint32_t sx, uint32_t sy,
                              double res, const double* origins) {
   if (!h || !cells || !origins) return fail(NEO_MPC_ERR_INVALID_ARGUMENT, "null argument");
-  if (count == 0) return fail(NEO_MPC_ERR_INVALID_ARGUMENT, "bad costmap count %u", count);
-  if (count > NEO_MPC_MAX_POOL_MAPS)   // K3 takes the map index from the grid's y coordinate
-    return fail(NEO_MPC_ERR_UNSUPPORTED, "costmap pool of %u maps: at most %u per call", count, NEO_MPC_MAX_POOL_MAPS);
-  HIP_TRY(hipSetDevice(h->device));
-  const size_t bytes = (size_t)sx * sy * count;
-  int rc = h->raw_buf.reserve(bytes);
+  int rc = check_pool_count(count);
   if (rc) return rc;
-  if ((rc = wait_map_users(h))) return rc;   // (batches in flight pair the old origins with the old cells to their end)
-  if ((rc = h->origins_buf.reserve((size_t)count * 16))) return rc;
-  HIP_TRY(hipMemcpy(h->raw_buf.ptr, cells, bytes, hipMemcpyHostToDevice));
-  HIP_TRY(hipMemcpy(h->origins_buf.ptr, origins, (size_t)count * 16, hipMemcpyHostToDevice));
-  return ingest(h, (const uint8_t*)h->raw_buf.ptr, count, sx, sy, res, 0.0, 0.0, (const double*)h->origins_buf.ptr,
-                nullptr);
+  HIP_TRY(hipSetDevice(h->device));
+  if ((rc = h->fence.wait_idle())) return rc;   // (batches in flight pair the old origins with the old cells to their end)
+  const uint8_t* d_cells = h->raw_buf.upload(cells, (size_t)sx * sy * count);
+  const double* d_origins = d_cells ? h->origins_buf.upload(origins, (size_t)count * 16) : nullptr;
+  if (!d_origins) return NEO_MPC_ERR_DEVICE;
+  return ingest(h, d_cells, count, sx, sy, res, 0.0, 0.0, d_origins, nullptr);
 }
 
 int neo_mpc_solve_batch_device_timed(neo_mpc_handle* h, const neo_mpc_batch* batch, void* stream, void* start_event,
@@ -609,18 +749,15 @@ int neo_mpc_solve_batch_device_timed(neo_mpc_handle* h, const neo_mpc_batch* bat
   int rc = fill_args(h, batch, a);
   if (rc) return rc;
   HIP_TRY(hipSetDevice(h->device));  // the stream and the buffers must belong to the handle's device
-  if ((rc = map_acquire(h, stream))) return rc;
-  if (h->order_count != 0 && h->order_count == batch->count) a.order = (const uint32_t*)h->order_buf.ptr;
-  launch_solve(a, h->tuning, stream, start_event, stop_event);
-  HIP_TRY(hipGetLastError());
-  return map_release(h, stream);
+  if (h->order_count != 0 && h->order_count == batch->count) a.order = h->order_buf.as<const uint32_t>();
+  return h->fence.read(stream, [&] { launch_solve(a, h->tuning, stream, start_event, stop_event); });
 }
 
 // Balanced dispatch for a fleet's next tick (K5): see k_dispatch_order.  Results do not depend on it.
 int neo_mpc_balance_dispatch_device(neo_mpc_handle* h, const neo_mpc_command* d_previous_commands, size_t count, void* stream) {
   if (!h) return fail(NEO_MPC_ERR_INVALID_ARGUMENT, "null handle");
   if (!d_previous_commands || count == 0) { h->order_count = 0; return NEO_MPC_OK; }
-  if (count > 0xffffffffull) return fail(NEO_MPC_ERR_INVALID_ARGUMENT, "count too large");
+  if (int rc = check_count(count, 0xffffffffull)) return rc;
   HIP_TRY(hipSetDevice(h->device));
   // (the average is kept while calls of the same count follow one another; disarming or another count starts it afresh)
   const bool fresh = h->order_count != count;
@@ -630,7 +767,7 @@ int neo_mpc_balance_dispatch_device(neo_mpc_handle* h, const neo_mpc_command* d_
   int rc = h->order_buf.reserve(count * sizeof(uint32_t));
   if (rc) return rc;
   if ((rc = h->load_buf.reserve(count * sizeof(float)))) return rc;
-  launch_dispatch_order(d_previous_commands, (float*)h->load_buf.ptr, (uint32_t*)h->order_buf.ptr, (uint32_t)count, fresh, stream);
+  launch_dispatch_order(d_previous_commands, h->load_buf.as<float>(), h->order_buf.as<uint32_t>(), (uint32_t)count, fresh, stream);
   HIP_TRY(hipGetLastError());
   h->order_count = count;
   return NEO_MPC_OK;
@@ -653,7 +790,7 @@ static int solve_batch_latency_path(neo_mpc_handle* h, const neo_mpc_batch* b) {
                o_cmd = o_warm + n * nv * 8, o_vel = o_cmd + n * sizeof(neo_mpc_command), o_sol = o_vel + n * 24,
                o_path = o_sol + (b->solution ? n * nv * 8 : 0), o_end = o_path + (b->predicted_path ? n * nv * 8 : 0);
   char* pin = (char*)h->pin;
-  char* dev = (char*)h->arena.ptr;
+  char* dev = h->arena.as<char>();
   memcpy(pin + o_prob, b->problems, n * sizeof(neo_mpc_problem));
   memcpy(pin + o_state, b->states, n * sizeof(neo_mpc_state));
   memcpy(pin + o_warm, b->warm_start, n * nv * 8);
@@ -668,10 +805,7 @@ static int solve_batch_latency_path(neo_mpc_handle* h, const neo_mpc_batch* b) {
   if (b->predicted_path) d.predicted_path = (double*)(dev + o_path);
   SolveArgs a;
   if ((rc = fill_args(h, &d, a))) return rc;
-  if ((rc = map_acquire(h, nullptr))) return rc;
-  launch_solve(a, h->tuning, nullptr);
-  HIP_TRY(hipGetLastError());
-  if ((rc = map_release(h, nullptr))) return rc;
+  if ((rc = solve_on(h, a, nullptr))) return rc;
   HIP_TRY(hipMemcpyAsync(pin + o_state, dev + o_state, o_end - o_state, hipMemcpyDeviceToHost, nullptr));
   HIP_TRY(hipStreamSynchronize(nullptr));
   memcpy(b->states, pin + o_state, n * sizeof(neo_mpc_state));
@@ -717,28 +851,14 @@ static HostPath host_path_mode(const neo_mpc_handle* h) {
 }
 
 static int solve_batch_zero_copy(neo_mpc_handle* h, const neo_mpc_batch* b, const neo_mpc_batch& dev, HostPath mode) {
-  const size_t n = b->count, nv = 3 * (size_t)h->params.control_steps;
   neo_mpc_batch d = dev;          // every pointer: the device-side address of the caller's page-locked array
   SolveArgs a;
   int rc;
   auto bail = [](int code) { (void)hipStreamSynchronize(nullptr); return code; };
-  if (mode == kZeroCopyOut) {
-    if ((rc = h->problems.reserve(n * sizeof(neo_mpc_problem)))) return rc;
-    if ((rc = h->states.reserve(n * sizeof(neo_mpc_state)))) return rc;
-    if ((rc = h->warm.reserve(n * nv * 8))) return rc;
-    HIP_TRY(hipMemcpyAsync(h->problems.ptr, b->problems, n * sizeof(neo_mpc_problem), hipMemcpyHostToDevice, nullptr));
-    HIP_TRY(hipMemcpyAsync(h->states.ptr, b->states, n * sizeof(neo_mpc_state), hipMemcpyHostToDevice, nullptr));
-    HIP_TRY(hipMemcpyAsync(h->warm.ptr, b->warm_start, n * nv * 8, hipMemcpyHostToDevice, nullptr));
-    d.problems = (const neo_mpc_problem*)h->problems.ptr;
-    d.states = (neo_mpc_state*)h->states.ptr;
-    d.warm_start = (double*)h->warm.ptr;
-  }
+  if (mode == kZeroCopyOut && (rc = stage_records(h, b, 0, b->count, nullptr, d))) return bail(rc);
   if ((rc = fill_args(h, &d, a))) return bail(rc);
   a.states_out = dev.states; a.warm_out = dev.warm_start;
-  if ((rc = map_acquire(h, nullptr))) return bail(rc);
-  launch_solve(a, h->tuning, nullptr);
-  if (hipGetLastError() != hipSuccess) return bail(fail(NEO_MPC_ERR_DEVICE, "kernel launch failed"));
-  if ((rc = map_release(h, nullptr))) return bail(rc);
+  if ((rc = solve_on(h, a, nullptr))) return bail(rc);
   HIP_TRY(hipStreamSynchronize(nullptr));   // kernel end = system-scope release: the results are in the caller's arrays
   return NEO_MPC_OK;
 }
@@ -764,15 +884,7 @@ static bool batch_page_locked(const neo_mpc_handle* h, const neo_mpc_batch* batc
 // overlap (with pageable arrays the runtime's bounce copies block the host, the kernels run behind them; with
 // page-locked arrays everything is asynchronous).  The instances are independent: the pieces' results are the batch's.
 static int solve_batch_staged_chunks(neo_mpc_handle* h, const neo_mpc_batch* b) {
-  const size_t n = b->count, nv = 3 * (size_t)h->params.control_steps;
-  int rc;
-  if ((rc = h->problems.reserve(n * sizeof(neo_mpc_problem)))) return rc;
-  if ((rc = h->states.reserve(n * sizeof(neo_mpc_state)))) return rc;
-  if ((rc = h->warm.reserve(n * nv * 8))) return rc;
-  if ((rc = h->commands.reserve(n * sizeof(neo_mpc_command)))) return rc;
-  if (b->solution && (rc = h->solution.reserve(n * nv * 8))) return rc;
-  if (b->predicted_path && (rc = h->path.reserve(n * nv * 8))) return rc;
-  if (b->velocities && (rc = h->vel.reserve(n * 24))) return rc;
+  const size_t n = b->count;
   for (hipStream_t& cs : h->chunk_streams)
     if (!cs) HIP_TRY(hipStreamCreateWithFlags(&cs, hipStreamNonBlocking));
   auto bail = [&](int code) {
@@ -786,44 +898,18 @@ static int solve_batch_staged_chunks(neo_mpc_handle* h, const neo_mpc_batch* b) 
     piece(c, off, m);
     if (!m) return NEO_MPC_OK;
     hipStream_t st = h->chunk_streams[c & 1];
-    char* d_prob = (char*)h->problems.ptr + off * sizeof(neo_mpc_problem);
-    char* d_state = (char*)h->states.ptr + off * sizeof(neo_mpc_state);
-    double* d_warm = (double*)h->warm.ptr + off * nv;
-    HIP_TRY(hipMemcpyAsync(d_prob, b->problems + off, m * sizeof(neo_mpc_problem), hipMemcpyHostToDevice, st));
-    HIP_TRY(hipMemcpyAsync(d_state, b->states + off, m * sizeof(neo_mpc_state), hipMemcpyHostToDevice, st));
-    HIP_TRY(hipMemcpyAsync(d_warm, b->warm_start + off * nv, m * nv * 8, hipMemcpyHostToDevice, st));
-    neo_mpc_batch d = *b;
-    d.count = m;
-    d.problems = (const neo_mpc_problem*)d_prob;
-    d.states = (neo_mpc_state*)d_state;
-    d.warm_start = d_warm;
-    d.commands = (neo_mpc_command*)h->commands.ptr + off;
-    d.solution = b->solution ? (double*)h->solution.ptr + off * nv : nullptr;
-    d.predicted_path = b->predicted_path ? (double*)h->path.ptr + off * nv : nullptr;
-    d.velocities = b->velocities ? (double*)h->vel.ptr + off * 3 : nullptr;
-    d.footprints = nullptr; d.footprint_points = 0;
+    neo_mpc_batch d;
     SolveArgs a;
-    int r = fill_args(h, &d, a);
-    if (r) return r;
-    if ((r = map_acquire(h, st))) return r;
-    launch_solve(a, h->tuning, st);
-    if (hipGetLastError() != hipSuccess) return fail(NEO_MPC_ERR_DEVICE, "kernel launch failed");
-    return map_release(h, st);
+    int r = stage_up(h, b, off, m, st, d, false);   // (the first piece sizes the staging buffers for the whole batch)
+    if (r || (r = fill_args(h, &d, a))) return r;
+    return solve_on(h, a, st);
   };
   auto down = [&](size_t c) -> int {
     size_t off, m;
     piece(c, off, m);
-    if (!m) return NEO_MPC_OK;
-    hipStream_t st = h->chunk_streams[c & 1];
-    HIP_TRY(hipMemcpyAsync(b->commands + off, (neo_mpc_command*)h->commands.ptr + off, m * sizeof(neo_mpc_command), hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipMemcpyAsync(b->states + off, (neo_mpc_state*)h->states.ptr + off, m * sizeof(neo_mpc_state), hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipMemcpyAsync(b->warm_start + off * nv, (double*)h->warm.ptr + off * nv, m * nv * 8, hipMemcpyDeviceToHost, st));
-    if (b->solution) HIP_TRY(hipMemcpyAsync(b->solution + off * nv, (double*)h->solution.ptr + off * nv, m * nv * 8, hipMemcpyDeviceToHost, st));
-    if (b->predicted_path)
-      HIP_TRY(hipMemcpyAsync(b->predicted_path + off * nv, (double*)h->path.ptr + off * nv, m * nv * 8, hipMemcpyDeviceToHost, st));
-    if (b->velocities) HIP_TRY(hipMemcpyAsync(b->velocities + off * 3, (double*)h->vel.ptr + off * 3, m * 24, hipMemcpyDeviceToHost, st));
-    return NEO_MPC_OK;
+    return m ? stage_down(h, b, off, m, h->chunk_streams[c & 1], true) : NEO_MPC_OK;
   };
+  int rc;
   if ((rc = up_and_launch(0))) return bail(rc);
   for (size_t c = 0; c < kChunks; ++c) {
     if (c + 1 < kChunks && (rc = up_and_launch(c + 1))) return bail(rc);
@@ -865,10 +951,7 @@ int neo_mpc_solve_batch(neo_mpc_handle* h, const neo_mpc_batch* batch) {
   auto bail = [](int code) { (void)hipStreamSynchronize(nullptr); return code; };
   if ((rc = stage_in(h, batch, d, false))) return bail(rc);
   if ((rc = fill_args(h, &d, a))) return bail(rc);
-  if ((rc = map_acquire(h, nullptr))) return bail(rc);
-  launch_solve(a, h->tuning, nullptr);
-  if (hipGetLastError() != hipSuccess) return bail(fail(NEO_MPC_ERR_DEVICE, "kernel launch failed"));
-  if ((rc = map_release(h, nullptr))) return bail(rc);
+  if ((rc = solve_on(h, a, nullptr))) return bail(rc);
   return bail(stage_out(h, batch, true));   // (queued behind the kernel on the null stream, one wait at the end)
 }
 
@@ -901,12 +984,9 @@ int neo_mpc_solve_batch_begin(neo_mpc_handle* h, const neo_mpc_batch* batch, uin
   if (!slot->done) HIP_TRY(hipEventCreateWithFlags(&slot->done, hipEventDisableTiming | hipEventReleaseToSystem));
   if ((rc = fill_args(h, &dv, a))) return rc;
   a.states_out = dv.states; a.warm_out = dv.warm_start;
-  if ((rc = map_acquire(h, slot->stream))) return rc;
-  launch_solve(a, h->tuning, slot->stream);
   // from here on a kernel may be writing the caller's arrays: no way out without a ticket unless it has been waited for
   auto bail = [&](int code) { (void)hipStreamSynchronize(slot->stream); return code; };
-  if (hipGetLastError() != hipSuccess) return bail(fail(NEO_MPC_ERR_DEVICE, "kernel launch failed"));
-  if ((rc = map_release(h, slot->stream))) return bail(rc);
+  if ((rc = solve_on(h, a, slot->stream))) return bail(rc);
   if (hipEventRecord(slot->done, slot->stream) != hipSuccess) return bail(fail(NEO_MPC_ERR_DEVICE, "hipEventRecord failed"));
   slot->busy = true;
   *ticket = index + 1;
@@ -956,16 +1036,8 @@ int neo_mpc_postprocess_batch(neo_mpc_handle* h, const neo_mpc_batch* batch, con
   auto bail = [](int code) { (void)hipStreamSynchronize(nullptr); return code; };
   if ((rc = stage_in(h, batch, d, true))) return bail(rc);
   if ((rc = fill_args(h, &d, a))) return bail(rc);
-  if (success) {
-    if ((rc = h->success.reserve(batch->count * 4))) return bail(rc);
-    if (hipMemcpy(h->success.ptr, success, batch->count * 4, hipMemcpyHostToDevice) != hipSuccess)
-      return bail(fail(NEO_MPC_ERR_DEVICE, "copy of the success flags failed"));
-    a.success = (const int32_t*)h->success.ptr;
-  }
-  if ((rc = map_acquire(h, nullptr))) return bail(rc);
-  launch_postprocess(a, nullptr);
-  if (hipGetLastError() != hipSuccess) return bail(fail(NEO_MPC_ERR_DEVICE, "kernel launch failed"));
-  if ((rc = map_release(h, nullptr))) return bail(rc);
+  if (success && !(a.success = h->success.upload(success, batch->count * 4))) return bail(NEO_MPC_ERR_DEVICE);
+  if ((rc = h->fence.read(nullptr, [&] { launch_postprocess(a, nullptr); }))) return bail(rc);
   return bail(stage_out(h, batch, false));
 }
 
@@ -977,31 +1049,58 @@ int neo_mpc_objective_batch(neo_mpc_handle* h, const neo_mpc_problem* problems, 
   HIP_TRY(hipSetDevice(h->device));
   const size_t nv = 3 * (size_t)h->params.control_steps;
   int rc;
-  if ((rc = h->problems.reserve(count * sizeof(neo_mpc_problem)))) return rc;
-  if ((rc = h->u.reserve(count * nv * 8))) return rc;
-  if ((rc = h->cost.reserve(count * 8))) return rc;
-  HIP_TRY(hipMemcpy(h->problems.ptr, problems, count * sizeof(neo_mpc_problem), hipMemcpyHostToDevice));
-  HIP_TRY(hipMemcpy(h->u.ptr, u, count * nv * 8, hipMemcpyHostToDevice));
   ObjectiveArgs a;
   std::memset(&a, 0, sizeof(a));
-  a.problems = (const neo_mpc_problem*)h->problems.ptr;
-  a.u = (const double*)h->u.ptr;
-  a.cost = (double*)h->cost.ptr;
-  a.term_table = (const double*)h->term_buf.ptr;
+  if ((rc = h->cost.reserve(count * 8))) return rc;
+  if (!(a.problems = h->problems.upload(problems, count * sizeof(neo_mpc_problem)))) return NEO_MPC_ERR_DEVICE;
+  if (!(a.u = h->u.upload(u, count * nv * 8))) return NEO_MPC_ERR_DEVICE;
+  a.cost = h->cost.as<double>();
+  a.term_table = h->term_buf.as<const double>();
   a.count = (uint32_t)count;
   a.p = h->dp; a.map = h->map;
   a.w_trans = h->params.w_trans; a.w_orient = h->params.w_orient; a.w_control = h->params.w_control;
   a.w_terminal = h->params.w_terminal; a.w_costmap = h->params.w_costmap;
-  if ((rc = map_acquire(h, nullptr))) return rc;
-  launch_objective(a, nullptr);
-  HIP_TRY(hipGetLastError());
-  if ((rc = map_release(h, nullptr))) return rc;
+  if ((rc = h->fence.read(nullptr, [&] { launch_objective(a, nullptr); }))) return rc;
   HIP_TRY(hipMemcpy(cost_out, h->cost.ptr, count * 8, hipMemcpyDeviceToHost));
   return NEO_MPC_OK;
 }
 
+// The gradient / direction hooks: K1 itself with `u` as the warm start of instances whose goal is unchanged (no reset), stopped
+// right after its first gradient pass (DevParams.max_it = kDumpGradient), or after the direction of `iteration`: the vector
+// comes out of `solution`
 static int hook_batch(neo_mpc_handle* h, const neo_mpc_problem* problems, const double* u, double* out, size_t count,
-                      int max_it);
+                      int max_it) {
+  if (!h || !problems || !u || !out) return fail(NEO_MPC_ERR_INVALID_ARGUMENT, "null argument");
+  if (!h->has_map) return fail(NEO_MPC_ERR_NO_COSTMAP, "neo_mpc_set_costmap has not been called");
+  if (count == 0) return NEO_MPC_OK;
+  int rc = check_count(count);
+  if (rc) return rc;
+  HIP_TRY(hipSetDevice(h->device));
+  const size_t nv = 3 * (size_t)h->params.control_steps;
+  std::vector<neo_mpc_state> st(count);
+  std::memset(st.data(), 0, count * sizeof(neo_mpc_state));
+  for (size_t i = 0; i < count; ++i) {
+    for (int k = 0; k < 3; ++k) st[i].old_goal[k] = problems[i].goal_xyz[k];
+    for (int k = 0; k < 4; ++k) st[i].old_goal[3 + k] = problems[i].goal_q[k];
+    st[i].has_old_goal = 1;
+  }
+  neo_mpc_batch b, d;   // the hook's inputs as a host batch whose only output is the solution
+  std::memset(&b, 0, sizeof(b));
+  b.count = count;
+  b.problems = problems; b.states = st.data(); b.warm_start = const_cast<double*>(u); b.solution = out;
+  SolveArgs a;
+  // (the staging copies are asynchronous and `st` is this call's own)
+  auto bail = [](int code) { (void)hipStreamSynchronize(nullptr); return code; };
+  if ((rc = stage_up(h, &b, 0, count, nullptr, d, false))) return bail(rc);
+  if ((rc = fill_args(h, &d, a))) return bail(rc);
+  a.p.max_it = max_it;
+  // NaN rows for instances that stop before the dump
+  if ((rc = hip_check(hipMemsetAsync(d.solution, 0xFF, count * nv * 8, nullptr), "hipMemsetAsync"))) return bail(rc);
+  if ((rc = solve_on(h, a, nullptr))) return bail(rc);
+  // (a blocking copy on the null stream, behind the staging copies and the kernel)
+  return bail(hip_check(hipMemcpy(out, d.solution, count * nv * 8, hipMemcpyDeviceToHost), "hipMemcpy"));
+}
+
 int neo_mpc_gradient_batch(neo_mpc_handle* h, const neo_mpc_problem* problems, const double* u, double* grad_out,
                            size_t count) {
   return hook_batch(h, problems, u, grad_out, count, kDumpGradient);
@@ -1011,58 +1110,13 @@ int neo_mpc_direction_batch(neo_mpc_handle* h, const neo_mpc_problem* problems, 
   if (iteration < 0 || iteration > 1000) return fail(NEO_MPC_ERR_INVALID_ARGUMENT, "iteration %d", iteration);
   return hook_batch(h, problems, u, dir_out, count, kDumpGradient + 1 + iteration);
 }
-static int hook_batch(neo_mpc_handle* h, const neo_mpc_problem* problems, const double* u, double* grad_out, size_t count,
-                      int max_it) {
-  if (!h || !problems || !u || !grad_out) return fail(NEO_MPC_ERR_INVALID_ARGUMENT, "null argument");
-  if (!h->has_map) return fail(NEO_MPC_ERR_NO_COSTMAP, "neo_mpc_set_costmap has not been called");
-  if (count == 0) return NEO_MPC_OK;
-  if (count > 0x7fffffffull) return fail(NEO_MPC_ERR_INVALID_ARGUMENT, "count too large");
-  HIP_TRY(hipSetDevice(h->device));
-  const size_t nv = 3 * (size_t)h->params.control_steps;
-  // K1 itself with `u` as the warm start of instances whose goal is unchanged (no reset), stopped right
-  // after its first gradient pass (DevParams.max_it = kDumpGradient): the gradient comes out of `solution`
-  std::vector<neo_mpc_state> st(count);
-  std::memset(st.data(), 0, count * sizeof(neo_mpc_state));
-  for (size_t i = 0; i < count; ++i) {
-    for (int k = 0; k < 3; ++k) st[i].old_goal[k] = problems[i].goal_xyz[k];
-    for (int k = 0; k < 4; ++k) st[i].old_goal[3 + k] = problems[i].goal_q[k];
-    st[i].has_old_goal = 1;
-  }
-  int rc;
-  if ((rc = h->problems.reserve(count * sizeof(neo_mpc_problem)))) return rc;
-  if ((rc = h->states.reserve(count * sizeof(neo_mpc_state)))) return rc;
-  if ((rc = h->warm.reserve(count * nv * 8))) return rc;
-  if ((rc = h->commands.reserve(count * sizeof(neo_mpc_command)))) return rc;
-  if ((rc = h->solution.reserve(count * nv * 8))) return rc;
-  HIP_TRY(hipMemcpy(h->problems.ptr, problems, count * sizeof(neo_mpc_problem), hipMemcpyHostToDevice));
-  HIP_TRY(hipMemcpy(h->states.ptr, st.data(), count * sizeof(neo_mpc_state), hipMemcpyHostToDevice));
-  HIP_TRY(hipMemcpy(h->warm.ptr, u, count * nv * 8, hipMemcpyHostToDevice));
-  neo_mpc_batch d;
-  std::memset(&d, 0, sizeof(d));
-  d.count = count;
-  d.problems = (const neo_mpc_problem*)h->problems.ptr;
-  d.states = (neo_mpc_state*)h->states.ptr;
-  d.warm_start = (double*)h->warm.ptr;
-  d.commands = (neo_mpc_command*)h->commands.ptr;
-  d.solution = (double*)h->solution.ptr;
-  SolveArgs a;
-  if ((rc = fill_args(h, &d, a))) return rc;
-  a.p.max_it = max_it;
-  HIP_TRY(hipMemset(h->solution.ptr, 0xFF, count * nv * 8));   // NaN rows for instances that stop before the dump
-  if ((rc = map_acquire(h, nullptr))) return rc;
-  launch_solve(a, h->tuning, nullptr);
-  HIP_TRY(hipGetLastError());
-  if ((rc = map_release(h, nullptr))) return rc;
-  HIP_TRY(hipMemcpy(grad_out, h->solution.ptr, count * nv * 8, hipMemcpyDeviceToHost));
-  return NEO_MPC_OK;
-}
 
+// K4.
 static int check_plan_batch(const neo_mpc_handle* h, const neo_mpc_lookahead_params* lp, const neo_mpc_plan_batch* b) {
   if (!h || !lp || !b) return fail(NEO_MPC_ERR_INVALID_ARGUMENT, "null argument");
   if (b->count > 0 && (!b->plan_poses || !b->plan_offsets || !b->robot_poses || !b->slow_down || !b->carrots))
     return fail(NEO_MPC_ERR_INVALID_ARGUMENT, "plan_poses/plan_offsets/robot_poses/slow_down/carrots must not be null");
-  if (b->count > 0x7fffffffull) return fail(NEO_MPC_ERR_INVALID_ARGUMENT, "count too large");
-  return NEO_MPC_OK;
+  return check_count(b->count);
 }
 
 int neo_mpc_select_carrots_device(neo_mpc_handle* h, const neo_mpc_lookahead_params* lp,
@@ -1085,35 +1139,18 @@ int neo_mpc_select_carrots(neo_mpc_handle* h, const neo_mpc_lookahead_params* lp
   HIP_TRY(hipSetDevice(h->device));
   const size_t n = b->count;
   const size_t total = b->plan_offsets[n];
-  if ((rc = h->plan_poses.reserve(total * 24 + 8))) return rc;
-  if ((rc = h->plan_offsets.reserve((n + 1) * 4))) return rc;
-  if ((rc = h->robot_poses.reserve(n * 24))) return rc;
-  if ((rc = h->fp_costs.reserve(n * 8))) return rc;
-  if ((rc = h->slow_down.reserve(n * 4))) return rc;
+  if ((rc = h->plan_poses.reserve(total * 24 + 8))) return rc;   // (never empty: a fleet without a plan pose stages nothing)
   if ((rc = h->carrots.reserve(n * sizeof(neo_mpc_carrot)))) return rc;
-  HIP_TRY(hipMemcpy(h->plan_poses.ptr, b->plan_poses, total * 24, hipMemcpyHostToDevice));
-  HIP_TRY(hipMemcpy(h->plan_offsets.ptr, b->plan_offsets, (n + 1) * 4, hipMemcpyHostToDevice));
-  HIP_TRY(hipMemcpy(h->robot_poses.ptr, b->robot_poses, n * 24, hipMemcpyHostToDevice));
-  HIP_TRY(hipMemcpy(h->slow_down.ptr, b->slow_down, n * 4, hipMemcpyHostToDevice));
   CarrotArgs a;
   a.lp = *lp;
   a.b = *b;
-  a.b.plan_poses = (const double*)h->plan_poses.ptr;
-  a.b.plan_offsets = (const uint32_t*)h->plan_offsets.ptr;
-  a.b.robot_poses = (const double*)h->robot_poses.ptr;
-  a.b.slow_down = (int32_t*)h->slow_down.ptr;
-  a.b.carrots = (neo_mpc_carrot*)h->carrots.ptr;
-  a.b.footprint_costs = nullptr;
-  if (b->footprint_costs) {
-    HIP_TRY(hipMemcpy(h->fp_costs.ptr, b->footprint_costs, n * 8, hipMemcpyHostToDevice));
-    a.b.footprint_costs = (const double*)h->fp_costs.ptr;
-  }
-  a.b.problems = nullptr;
-  if (b->problems) {
-    if ((rc = h->problems.reserve(n * sizeof(neo_mpc_problem)))) return rc;
-    HIP_TRY(hipMemcpy(h->problems.ptr, b->problems, n * sizeof(neo_mpc_problem), hipMemcpyHostToDevice));
-    a.b.problems = (neo_mpc_problem*)h->problems.ptr;
-  }
+  a.b.carrots = h->carrots.as<neo_mpc_carrot>();
+  if (!(a.b.plan_poses = h->plan_poses.upload(b->plan_poses, total * 24))) return NEO_MPC_ERR_DEVICE;
+  if (!(a.b.plan_offsets = h->plan_offsets.upload(b->plan_offsets, (n + 1) * 4))) return NEO_MPC_ERR_DEVICE;
+  if (!(a.b.robot_poses = h->poses.upload(b->robot_poses, n * 24))) return NEO_MPC_ERR_DEVICE;
+  if (!(a.b.slow_down = h->slow_down.upload(b->slow_down, n * 4))) return NEO_MPC_ERR_DEVICE;
+  if (b->footprint_costs && !(a.b.footprint_costs = h->fp_costs.upload(b->footprint_costs, n * 8))) return NEO_MPC_ERR_DEVICE;
+  if (b->problems && !(a.b.problems = h->problems.upload(b->problems, n * sizeof(neo_mpc_problem)))) return NEO_MPC_ERR_DEVICE;
   launch_carrots(a, nullptr);
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipDeviceSynchronize());
@@ -1128,12 +1165,8 @@ int neo_mpc_select_carrots(neo_mpc_handle* h, const neo_mpc_lookahead_params* lp
 static int check_footprint_batch(const neo_mpc_handle* h, const neo_mpc_footprint_batch* b) {
   if (!h || !b) return fail(NEO_MPC_ERR_INVALID_ARGUMENT, "null argument");
   if (!h->has_map) return fail(NEO_MPC_ERR_NO_COSTMAP, "neo_mpc_set_costmap has not been called");
-  if (b->footprint_points < 3 || b->footprint_points > NEO_MPC_MAX_FOOTPRINT_POINTS)
-    return fail(NEO_MPC_ERR_INVALID_ARGUMENT, "footprint_points %u outside [3, %d]", b->footprint_points,
-                NEO_MPC_MAX_FOOTPRINT_POINTS);
-  if (b->per_robot_footprints > 1)
-    return fail(NEO_MPC_ERR_INVALID_ARGUMENT, "per_robot_footprints must be 0 or 1 (got %u)", b->per_robot_footprints);
-  if (b->count > 0x7fffffffull) return fail(NEO_MPC_ERR_INVALID_ARGUMENT, "count too large");
+  int rc = check_footprint_shape(b->footprint_points, b->per_robot_footprints);
+  if (rc || (rc = check_count(b->count))) return rc;
   if (b->count > 0 && (!b->footprint || !b->footprint_costs))
     return fail(NEO_MPC_ERR_INVALID_ARGUMENT, "footprint/footprint_costs must not be null");
   if (b->count > 0 && !b->poses && !b->problems)
@@ -1141,12 +1174,15 @@ static int check_footprint_batch(const neo_mpc_handle* h, const neo_mpc_footprin
   return NEO_MPC_OK;
 }
 
-static void fill_gate_args(const neo_mpc_handle* h, const neo_mpc_footprint_batch& d, FootprintGateArgs& a) {
+// `d`: the record with device pointers
+static int gate(neo_mpc_handle* h, const neo_mpc_footprint_batch& d, void* stream) {
+  FootprintGateArgs a;
   std::memset(&a, 0, sizeof(a));
   a.footprint = d.footprint; a.poses = d.poses; a.map_indices = d.map_indices; a.problems = d.problems;
   a.footprint_costs = d.footprint_costs; a.footprints_out = d.footprints_out;
   a.count = (uint32_t)d.count; a.footprint_points = d.footprint_points; a.per_robot = d.per_robot_footprints;
   a.map = h->map;
+  return h->fence.read(stream, [&] { launch_footprint_gate(a, stream); });
 }
 
 int neo_mpc_footprint_gate_device(neo_mpc_handle* h, const neo_mpc_footprint_batch* b, void* stream) {
@@ -1154,69 +1190,36 @@ int neo_mpc_footprint_gate_device(neo_mpc_handle* h, const neo_mpc_footprint_bat
   if (rc) return rc;
   if (b->count == 0) return NEO_MPC_OK;
   HIP_TRY(hipSetDevice(h->device));
-  FootprintGateArgs a;
-  fill_gate_args(h, *b, a);
-  if ((rc = map_acquire(h, stream))) return rc;
-  launch_footprint_gate(a, stream);
-  HIP_TRY(hipGetLastError());
-  return map_release(h, stream);
+  return gate(h, *b, stream);
 }
 
 int neo_mpc_footprint_gate(neo_mpc_handle* h, const neo_mpc_footprint_batch* b) {
   int rc = check_footprint_batch(h, b);
   if (rc) return rc;
   if (b->count == 0) return NEO_MPC_OK;
-  const size_t n = b->count, np = b->footprint_points, poly_doubles = (b->per_robot_footprints ? n : 1) * np * 2;
+  const size_t n = b->count, np = b->footprint_points, polygons = b->per_robot_footprints ? n : 1;
   // the values the device variant takes as they come are looked at here
-  for (size_t k = 0; k < poly_doubles; ++k)
-    if (!std::isfinite(b->footprint[k]))
-      return fail(NEO_MPC_ERR_INVALID_ARGUMENT, "footprint vertex %zu of polygon %zu is not finite", (k / 2) % np, k / (2 * np));
-  for (size_t i = 0; i < n; ++i) {
-    bool finite = true;
-    if (b->poses) for (int k = 0; k < 3; ++k) finite = finite && std::isfinite(b->poses[3 * i + k]);
-    else {
-      for (int k = 0; k < 2; ++k) finite = finite && std::isfinite(b->problems[i].cur_xy[k]);
-      for (int k = 0; k < 4; ++k) finite = finite && std::isfinite(b->problems[i].cur_q[k]);
-    }
-    if (!finite) return fail(NEO_MPC_ERR_INVALID_ARGUMENT, "the pose of robot %zu is not finite", i);
-    if (h->map.pool_count > 0 && (b->map_indices || b->problems)) {
-      const int32_t idx = b->map_indices ? b->map_indices[i] : b->problems[i].map_index;
-      if (idx < 0 || idx >= h->map.pool_count)
-        return fail(NEO_MPC_ERR_INVALID_ARGUMENT, "map index %d of robot %zu outside the pool of %d maps", idx, i, h->map.pool_count);
-    }
-  }
+  if ((rc = check_vertices_finite(b->footprint, polygons, np, "footprint vertex", "polygon"))) return rc;
+  const int pool = (b->map_indices || b->problems) ? h->map.pool_count : 0;
+  auto check_map_index = [&](size_t i) {
+    const int32_t idx = pool <= 0 ? 0 : b->map_indices ? b->map_indices[i] : b->problems[i].map_index;
+    if (idx >= 0 && (pool <= 0 || idx < pool)) return (int)NEO_MPC_OK;
+    return fail(NEO_MPC_ERR_INVALID_ARGUMENT, "map index %d of robot %zu outside the pool of %d maps", idx, i, pool);
+  };
+  if ((rc = check_poses_finite(b->poses, b->problems, n, check_map_index))) return rc;
   HIP_TRY(hipSetDevice(h->device));
-  if ((rc = h->gate_polygon.reserve(poly_doubles * 8))) return rc;
   if ((rc = h->fp_costs.reserve(n * 8))) return rc;
   neo_mpc_footprint_batch d = *b;
-  HIP_TRY(hipMemcpy(h->gate_polygon.ptr, b->footprint, poly_doubles * 8, hipMemcpyHostToDevice));
-  d.footprint = (const double*)h->gate_polygon.ptr;
-  d.footprint_costs = (double*)h->fp_costs.ptr;
-  if (b->poses) {
-    if ((rc = h->gate_poses.reserve(n * 24))) return rc;
-    HIP_TRY(hipMemcpy(h->gate_poses.ptr, b->poses, n * 24, hipMemcpyHostToDevice));
-    d.poses = (const double*)h->gate_poses.ptr;
-  }
-  if (b->map_indices) {
-    if ((rc = h->gate_indices.reserve(n * 4))) return rc;
-    HIP_TRY(hipMemcpy(h->gate_indices.ptr, b->map_indices, n * 4, hipMemcpyHostToDevice));
-    d.map_indices = (const int32_t*)h->gate_indices.ptr;
-  }
-  if (b->problems) {
-    if ((rc = h->problems.reserve(n * sizeof(neo_mpc_problem)))) return rc;
-    HIP_TRY(hipMemcpy(h->problems.ptr, b->problems, n * sizeof(neo_mpc_problem), hipMemcpyHostToDevice));
-    d.problems = (neo_mpc_problem*)h->problems.ptr;
-  }
+  d.footprint_costs = h->fp_costs.as<double>();
+  if (!(d.footprint = h->verts.upload(b->footprint, polygons * np * 16))) return NEO_MPC_ERR_DEVICE;
+  if (b->poses && !(d.poses = h->poses.upload(b->poses, n * 24))) return NEO_MPC_ERR_DEVICE;
+  if (b->map_indices && !(d.map_indices = h->gate_indices.upload(b->map_indices, n * 4))) return NEO_MPC_ERR_DEVICE;
+  if (b->problems && !(d.problems = h->problems.upload(b->problems, n * sizeof(neo_mpc_problem)))) return NEO_MPC_ERR_DEVICE;
   if (b->footprints_out) {
     if ((rc = h->gate_polygons_out.reserve(n * np * 16))) return rc;
-    d.footprints_out = (double*)h->gate_polygons_out.ptr;
+    d.footprints_out = h->gate_polygons_out.as<double>();
   }
-  FootprintGateArgs a;
-  fill_gate_args(h, d, a);
-  if ((rc = map_acquire(h, nullptr))) return rc;
-  launch_footprint_gate(a, nullptr);
-  HIP_TRY(hipGetLastError());
-  if ((rc = map_release(h, nullptr))) return rc;
+  if ((rc = gate(h, d, nullptr))) return rc;
   // (blocking copies on the null stream, behind the kernel; the records come back whole -- the kernel wrote footprint_cost alone)
   HIP_TRY(hipMemcpy(b->footprint_costs, h->fp_costs.ptr, n * 8, hipMemcpyDeviceToHost));
   if (b->footprints_out) HIP_TRY(hipMemcpy(b->footprints_out, h->gate_polygons_out.ptr, n * np * 16, hipMemcpyDeviceToHost));
@@ -1235,14 +1238,15 @@ static int set_world_map(neo_mpc_handle* h, const uint8_t* cells, bool on_device
   hipStream_t st = (hipStream_t)stream;
   const size_t bytes = (size_t)sx * sy;
   // behind the last roll, which reads the copy that is about to be overwritten (and behind the previous copy)
+  int rc;
   if (on_device) {
-    if (h->rolled && h->map_ready_stream != st) HIP_TRY(hipStreamWaitEvent(st, h->map_ready, 0));
+    if (h->rolled && (rc = h->fence.wait_writer(st))) return rc;
     if (h->world_ready && h->world_ready_stream != st) HIP_TRY(hipStreamWaitEvent(st, h->world_ready, 0));
   } else {
-    if (h->rolled) HIP_TRY(hipEventSynchronize(h->map_ready));
+    if (h->rolled && (rc = h->fence.wait_writer_host())) return rc;
     if (h->world_ready) HIP_TRY(hipEventSynchronize(h->world_ready));
   }
-  int rc = h->world_buf.reserve(bytes);
+  rc = h->world_buf.reserve(bytes);
   if (rc) { h->has_world = false; return rc; }   // (a failed re-allocation has let the old copy go)
   if (on_device) HIP_TRY(hipMemcpyAsync(h->world_buf.ptr, cells, bytes, hipMemcpyDeviceToDevice, st));
   else HIP_TRY(hipMemcpy(h->world_buf.ptr, cells, bytes, hipMemcpyHostToDevice));
@@ -1277,18 +1281,13 @@ static int check_window_batch(const neo_mpc_handle* h, const neo_mpc_window_batc
   if (!(w->resolution > 0.0) || !std::isfinite(w->resolution))
     return fail(NEO_MPC_ERR_INVALID_ARGUMENT, "window resolution %g must be positive and finite", w->resolution);
   if (w->count > 0 && !w->origins) return fail(NEO_MPC_ERR_INVALID_ARGUMENT, "origins must not be null");
-  const size_t pitch = (w->size_x + 2 * kPoolBorder + 127) & ~(size_t)127, rows = (size_t)w->size_y + 2 * kPoolBorder;
-  if (pitch * rows / 16 >= (1ull << 31))   // K7 indexes the 16-byte chunks of one map with 32 bits, like K3
-    return fail(NEO_MPC_ERR_UNSUPPORTED, "window %ux%u is too large (over 32 GiB padded)", w->size_x, w->size_y);
-  return NEO_MPC_OK;
+  return PaddedMap(w->size_x, w->size_y, kPoolBorder).check("window");
 }
 
 // `d`: the record with device pointers.  Orders itself like ingest() and leaves the handle's costmap as this pool.
 static int roll(neo_mpc_handle* h, const neo_mpc_window_batch& d, void* stream) {
-  const int sx = (int)d.size_x, sy = (int)d.size_y, count = (int)d.count, border = kPoolBorder;
-  const int pitch = (int)((d.size_x + 2 * border + 127) & ~127u);
-  const int rows = sy + 2 * border;
-  const size_t stride = (size_t)pitch * rows;
+  const int sx = (int)d.size_x, sy = (int)d.size_y, count = (int)d.count;
+  const PaddedMap g(d.size_x, d.size_y, kPoolBorder);
   const int tab_x = (sx + 15) & ~15, tab_stride = tab_x + ((sy + 3) & ~3);
   // the roll of every tick -- same geometry, count and origins as the previous one -- finds its buffers and the derived
   // constants in place: nothing is allocated (a re-allocation synchronises), so the call can be captured in a graph
@@ -1296,48 +1295,29 @@ static int roll(neo_mpc_handle* h, const neo_mpc_window_batch& d, void* stream) 
                     h->map.resolution == d.resolution && h->map.pool_origins == d.origins;
   int rc;
   if (!same) {
-    if ((rc = h->map_buf.reserve(stride * count))) return rc;
+    if ((rc = h->map_buf.reserve(g.stride * count))) return rc;
     if ((rc = h->roll_tables.reserve((size_t)count * tab_stride * sizeof(int32_t)))) return rc;
   }
   hipStream_t st = (hipStream_t)stream;
-  if (!h->map_ready) HIP_TRY(hipEventCreateWithFlags(&h->map_ready, hipEventDisableTiming));
   // behind the previous ingest or roll, every launch still reading the old map (it reads `origins` too: the device variant
   // rewrites them in-stream behind these waits) and the world map's copy
-  else if (h->map_ready_stream != st) HIP_TRY(hipStreamWaitEvent(st, h->map_ready, 0));
-  for (auto& u : h->map_users)
-    if (u.pending) {
-      if (u.stream != st) HIP_TRY(hipStreamWaitEvent(st, u.done, 0));
-      u.pending = false;
-    }
+  if ((rc = h->fence.begin_write(st))) return rc;
   if (h->world_ready_stream != st) HIP_TRY(hipStreamWaitEvent(st, h->world_ready, 0));
   RollArgs a;
   std::memset(&a, 0, sizeof(a));
   a.poses = d.poses; a.problems = d.poses ? nullptr : d.problems; a.origins = d.origins;
-  a.tables = (int32_t*)h->roll_tables.ptr;
-  a.world = (const uint8_t*)h->world_buf.ptr; a.dst = (uint8_t*)h->map_buf.ptr;
+  a.tables = h->roll_tables.as<int32_t>();
+  a.world = h->world_buf.as<const uint8_t>(); a.dst = h->map_buf.as<uint8_t>();
   a.res = d.resolution; a.wres = h->world_resolution; a.wox = h->world_origin_x; a.woy = h->world_origin_y;
-  a.dst_stride = (int64_t)stride;
+  a.dst_stride = (int64_t)g.stride;
   a.wsx = h->world_size_x; a.wsy = h->world_size_y;
-  a.size_x = sx; a.size_y = sy; a.pitch = pitch; a.rows = rows; a.border = border;
+  a.size_x = sx; a.size_y = sy; a.pitch = g.pitch; a.rows = g.rows; a.border = g.border;
   a.tab_x = tab_x; a.tab_stride = tab_stride;
   a.count = (uint32_t)count; a.outside = d.outside_value;
   launch_roll(a, stream);
   HIP_TRY(hipGetLastError());
-  HIP_TRY(hipEventRecord(h->map_ready, st));
-  h->map_ready_stream = st;
-  if (!same) {
-    h->map.cells = (const uint8_t*)h->map_buf.ptr + (size_t)border * pitch + border;
-    h->map.size_x = sx; h->map.size_y = sy; h->map.pitch = pitch;
-    h->map.resolution = d.resolution; h->map.inv_resolution = 1.0 / d.resolution;
-    h->map.origin_x = 0.0; h->map.origin_y = 0.0;
-    h->map.pool_count = count;
-    h->map.border = border;
-    h->map.pool_stride = (int64_t)stride;
-    h->map.pool_origins = d.origins;
-    h->has_map = true;
-    h->rolled = true;
-    derive(h);
-  }
+  if ((rc = h->fence.end_write(st))) return rc;
+  if (!same) adopt_map(h, g, (uint32_t)d.count, d.resolution, 0.0, 0.0, d.origins, true);
   return NEO_MPC_OK;
 }
 
@@ -1369,21 +1349,14 @@ int neo_mpc_roll_costmap_pool(neo_mpc_handle* h, const neo_mpc_window_batch* w) 
     }
   }
   HIP_TRY(hipSetDevice(h->device));
-  // origins_buf is rewritten with blocking copies on the null stream: every launch that may still read it -- a pool of
-  // neo_mpc_set_costmap_pool's or of an earlier roll -- is waited for first (see wait_map_users)
-  if ((rc = wait_map_users(h))) return rc;
-  if (h->map_ready) HIP_TRY(hipEventSynchronize(h->map_ready));
-  if ((rc = h->origins_buf.reserve(n * 16))) return rc;
-  HIP_TRY(hipMemcpy(h->origins_buf.ptr, w->origins, n * 16, hipMemcpyHostToDevice));
+  // origins_buf is rewritten with a blocking copy on the null stream: every launch that may still read it -- a pool of
+  // neo_mpc_set_costmap_pool's or of an earlier roll -- is waited for first
+  if ((rc = h->fence.wait_idle())) return rc;
   neo_mpc_window_batch d = *w;
-  d.origins = (double*)h->origins_buf.ptr;
   d.poses = nullptr; d.problems = nullptr;
-  if (!poses.empty()) {
-    if ((rc = h->roll_poses.reserve(n * 24))) return rc;
-    HIP_TRY(hipMemcpy(h->roll_poses.ptr, poses.data(), n * 24, hipMemcpyHostToDevice));
-    d.poses = (const double*)h->roll_poses.ptr;
-  }
-  if ((rc = roll(h, d, nullptr))) return rc;
+  if (!(d.origins = h->origins_buf.upload(w->origins, n * 16))) return NEO_MPC_ERR_DEVICE;
+  if (!poses.empty() && !(d.poses = h->poses.upload(poses.data(), n * 24))) return NEO_MPC_ERR_DEVICE;
+  if ((rc = roll(h, d, nullptr))) { (void)hipStreamSynchronize(nullptr); return rc; }
   // (a blocking copy on the null stream, behind the two kernels)
   HIP_TRY(hipMemcpy(w->origins, h->origins_buf.ptr, n * 16, hipMemcpyDeviceToHost));
   return NEO_MPC_OK;
@@ -1397,7 +1370,8 @@ int neo_mpc_get_costmap_pool(neo_mpc_handle* h, uint32_t first, uint32_t count, 
     return fail(NEO_MPC_ERR_INVALID_ARGUMENT, "maps [%u, %u + %u) outside the pool of %u", first, first, count, maps);
   if (count == 0) return NEO_MPC_OK;
   HIP_TRY(hipSetDevice(h->device));
-  HIP_TRY(hipEventSynchronize(h->map_ready));   // the ingest or roll in flight
+  int rc = h->fence.wait_writer_host();   // the ingest, roll or stamp in flight
+  if (rc) return rc;
   const size_t sx = (size_t)h->map.size_x, sy = (size_t)h->map.size_y;
   if (cells_out)
     for (uint32_t k = 0; k < count; ++k)   // a strided copy per map: border and pitch stay behind
@@ -1454,10 +1428,7 @@ int neo_mpc_inflation_costs(double res, double ins, double infl, double csf, uin
 static int check_stamp_batch(const neo_mpc_handle* h, const neo_mpc_stamp_batch* b) {
   if (!h || !b) return fail(NEO_MPC_ERR_INVALID_ARGUMENT, "null argument");
   if (b->reserved != 0) return fail(NEO_MPC_ERR_INVALID_ARGUMENT, "neo_mpc_stamp_batch.reserved must be zero");
-  if (b->footprint_points < 3 || b->footprint_points > NEO_MPC_MAX_FOOTPRINT_POINTS)
-    return fail(NEO_MPC_ERR_INVALID_ARGUMENT, "footprint_points %u outside [3, %d]", b->footprint_points, NEO_MPC_MAX_FOOTPRINT_POINTS);
-  if (b->per_robot_footprints > 1)
-    return fail(NEO_MPC_ERR_INVALID_ARGUMENT, "per_robot_footprints must be 0 or 1 (got %u)", b->per_robot_footprints);
+  if (int rc = check_footprint_shape(b->footprint_points, b->per_robot_footprints)) return rc;
   if (!stamp_radii_ok(b->inscribed_radius, b->inflation_radius, b->cost_scaling_factor))
     return fail(NEO_MPC_ERR_INVALID_ARGUMENT, "inscribed_radius %g, inflation_radius %g and cost_scaling_factor %g must be finite and not negative",
                 b->inscribed_radius, b->inflation_radius, b->cost_scaling_factor);
@@ -1485,11 +1456,10 @@ static int stamp(neo_mpc_handle* h, const neo_mpc_stamp_batch& d, void* stream) 
     const int reach = stamp_reach_cells(key[0], key[2]);
     std::vector<uint8_t> table((size_t)reach * reach + 1);
     stamp_costs(key[0], key[1], key[3], reach, table.data());
-    // (a stamp in flight reads the old table: every stamp records map_ready)
-    if (h->map_ready) HIP_TRY(hipEventSynchronize(h->map_ready));
+    // (a stamp in flight reads the old table: every stamp ends a write of the fence)
+    if ((rc = h->fence.wait_writer_host())) return rc;
     h->has_stamp_table = false;
-    if ((rc = h->stamp_table.reserve(table.size()))) return rc;
-    HIP_TRY(hipMemcpy(h->stamp_table.ptr, table.data(), table.size(), hipMemcpyHostToDevice));
+    if (!h->stamp_table.upload(table.data(), table.size())) return NEO_MPC_ERR_DEVICE;
     std::memcpy(h->stamp_key, key, sizeof(key));
     h->stamp_reach = reach;
     h->has_stamp_table = true;
@@ -1499,19 +1469,13 @@ static int stamp(neo_mpc_handle* h, const neo_mpc_stamp_batch& d, void* stream) 
   if (!d.polygons && (rc = h->stamp_polys.reserve(n * np * 16))) return rc;
   hipStream_t st = (hipStream_t)stream;
   // behind the ingest, roll or stamp that wrote the maps and every launch still reading them
-  if (h->map_ready && h->map_ready_stream != st) HIP_TRY(hipStreamWaitEvent(st, h->map_ready, 0));
-  if (!h->map_ready) HIP_TRY(hipEventCreateWithFlags(&h->map_ready, hipEventDisableTiming));
-  for (auto& u : h->map_users)
-    if (u.pending) {
-      if (u.stream != st) HIP_TRY(hipStreamWaitEvent(st, u.done, 0));
-      u.pending = false;
-    }
+  if ((rc = h->fence.begin_write(st))) return rc;
   StampArgs a;
   std::memset(&a, 0, sizeof(a));
   a.polygons = d.polygons;
   if (!d.polygons) { a.footprint = d.footprint; a.poses = d.poses; a.problems = d.poses ? nullptr : d.problems; }
-  a.polys = (double*)h->stamp_polys.ptr; a.boxes = (double*)h->stamp_boxes.ptr;
-  a.table = (const uint8_t*)h->stamp_table.ptr;
+  a.polys = h->stamp_polys.as<double>(); a.boxes = h->stamp_boxes.as<double>();
+  a.table = h->stamp_table.as<const uint8_t>();
   a.cells = const_cast<uint8_t*>(h->map.cells);   // (cell (0, 0) of the first map of map_buf, the handle's own)
   a.origins = h->map.pool_origins;
   a.res = h->map.resolution;
@@ -1521,9 +1485,7 @@ static int stamp(neo_mpc_handle* h, const neo_mpc_stamp_batch& d, void* stream) 
   a.count = (uint32_t)n; a.points = d.footprint_points; a.per_robot = d.per_robot_footprints;
   launch_stamp(a, stream);
   HIP_TRY(hipGetLastError());
-  HIP_TRY(hipEventRecord(h->map_ready, st));   // a gate or solve behind it sees the stamped pool
-  h->map_ready_stream = st;
-  return NEO_MPC_OK;
+  return h->fence.end_write(st);   // a gate or solve behind it sees the stamped pool
 }
 
 int neo_mpc_stamp_fleet_device(neo_mpc_handle* h, const neo_mpc_stamp_batch* b, void* stream) {
@@ -1541,39 +1503,22 @@ int neo_mpc_stamp_fleet(neo_mpc_handle* h, const neo_mpc_stamp_batch* b) {
   const size_t n = b->count, np = b->footprint_points;
   // the values the device variant takes as they come are looked at here
   const double* verts = b->polygons ? b->polygons : b->footprint;
-  const size_t vert_doubles = (b->polygons || b->per_robot_footprints ? n : 1) * np * 2;
-  for (size_t k = 0; k < vert_doubles; ++k)
-    if (!std::isfinite(verts[k]))
-      return fail(NEO_MPC_ERR_INVALID_ARGUMENT, "vertex %zu of polygon %zu is not finite", (k / 2) % np, k / (2 * np));
-  if (!b->polygons)
-    for (size_t i = 0; i < n; ++i) {
-      bool finite = true;
-      if (b->poses) for (int k = 0; k < 3; ++k) finite = finite && std::isfinite(b->poses[3 * i + k]);
-      else {
-        for (int k = 0; k < 2; ++k) finite = finite && std::isfinite(b->problems[i].cur_xy[k]);
-        for (int k = 0; k < 4; ++k) finite = finite && std::isfinite(b->problems[i].cur_q[k]);
-      }
-      if (!finite) return fail(NEO_MPC_ERR_INVALID_ARGUMENT, "the pose of robot %zu is not finite", i);
-    }
+  const size_t polygons = b->polygons || b->per_robot_footprints ? n : 1;
+  if ((rc = check_vertices_finite(verts, polygons, np, "vertex", "polygon"))) return rc;
+  if (!b->polygons && (rc = check_poses_finite(b->poses, b->problems, n))) return rc;
   HIP_TRY(hipSetDevice(h->device));
   neo_mpc_stamp_batch d = *b;
-  if ((rc = h->stamp_in.reserve(vert_doubles * 8))) return rc;
-  HIP_TRY(hipMemcpy(h->stamp_in.ptr, verts, vert_doubles * 8, hipMemcpyHostToDevice));
   d.polygons = nullptr; d.footprint = nullptr; d.poses = nullptr; d.problems = nullptr;
-  if (b->polygons) d.polygons = (const double*)h->stamp_in.ptr;
+  const double* d_verts = h->verts.upload(verts, polygons * np * 16);
+  if (!d_verts) return NEO_MPC_ERR_DEVICE;
+  if (b->polygons) d.polygons = d_verts;
   else {
-    d.footprint = (const double*)h->stamp_in.ptr;
-    if (b->poses) {
-      if ((rc = h->stamp_poses.reserve(n * 24))) return rc;
-      HIP_TRY(hipMemcpy(h->stamp_poses.ptr, b->poses, n * 24, hipMemcpyHostToDevice));
-      d.poses = (const double*)h->stamp_poses.ptr;
-    } else {
-      if ((rc = h->problems.reserve(n * sizeof(neo_mpc_problem)))) return rc;
-      HIP_TRY(hipMemcpy(h->problems.ptr, b->problems, n * sizeof(neo_mpc_problem), hipMemcpyHostToDevice));
-      d.problems = (const neo_mpc_problem*)h->problems.ptr;
-    }
+    d.footprint = d_verts;
+    if (b->poses) d.poses = h->poses.upload(b->poses, n * 24);
+    else d.problems = h->problems.upload(b->problems, n * sizeof(neo_mpc_problem));
+    if (!d.poses && !d.problems) return NEO_MPC_ERR_DEVICE;
   }
-  if ((rc = stamp(h, d, nullptr))) return rc;
+  if ((rc = stamp(h, d, nullptr))) { (void)hipStreamSynchronize(nullptr); return rc; }   // (the staging is free again)
   HIP_TRY(hipStreamSynchronize(nullptr));
   return NEO_MPC_OK;
 }

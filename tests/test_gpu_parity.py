@@ -774,6 +774,35 @@ def test_errors_are_reported_not_thrown(solver_mod):
     s.close()
 
 
+def test_a_costmap_without_cells_is_refused_as_an_argument(solver_mod):
+    """A zero size_x or size_y is NEO_MPC_ERR_INVALID_ARGUMENT with its own text (include/neo_mpc.h), also on a handle that
+    has staged no costmap yet: the host variants stage zero bytes before the geometry is looked at."""
+    import ctypes as C
+    from neo_mpc_planner2_amd import _lib
+    lib = _lib.load()
+    cells = np.zeros((2, 8, 8), dtype=np.uint8)
+    orig = np.zeros((2, 2))
+    for sx, sy in ((0, 8), (8, 0), (0, 0)):
+        s = solver_mod.BatchSolver(util.orc.make_params())     # (a fresh handle each time: nothing staged)
+        with pytest.raises(_lib.NeoMpcError):
+            s.solve(*_tiny_batch())                             # leaves another refusal's text behind
+        assert lib.neo_mpc_set_costmap(s._handle, C.c_void_p(cells.ctypes.data), sx, sy, 0.05, 0.0, 0.0) == -1
+        assert b"bad costmap geometry" in lib.neo_mpc_last_error() and lib.neo_mpc_last_error_code() == -1
+        s.close()
+        s = solver_mod.BatchSolver(util.orc.make_params())
+        with pytest.raises(_lib.NeoMpcError):
+            s.solve(*_tiny_batch())
+        assert lib.neo_mpc_set_costmap_pool(s._handle, C.c_void_p(cells.ctypes.data), 2, sx, sy, 0.05,
+                                            C.c_void_p(orig.ctypes.data)) == -1
+        assert b"bad costmap geometry" in lib.neo_mpc_last_error() and lib.neo_mpc_last_error_code() == -1
+        s.close()
+
+
+def _tiny_batch():
+    probs = synthetic.make_problems(4, 200, seed=1)
+    return (probs,) + tuple(synthetic.make_states(probs, 3))
+
+
 # ------------------------------------------------------------------ host mirror of the service node
 def test_server_mirror_episode_matches_oracle_wrapper():
     """`MpcOptimizationServer.optimizer(request, response)` (the reference's service callback
