@@ -205,7 +205,7 @@ struct __attribute__((visibility("hidden"))) neo_mpc_handle {
   // term table of the costmap weight, and their ordering
   DevMap map{};
   bool has_map = false;
-  bool rolled = false;                      // the device map was written by a roll (fence.ready: that roll's end)
+  bool rolled = false;                      // the device map was written by a roll (its buffers and constants are in place)
   DeviceBuffer map_buf, raw_buf, term_buf, origins_buf;
   MapFence fence;
   // staging of host batches: the records of a batch, and what the host variants of K4 / K6 / K7 / K8 share -- a fleet's
@@ -1237,13 +1237,15 @@ static int set_world_map(neo_mpc_handle* h, const uint8_t* cells, bool on_device
   HIP_TRY(hipSetDevice(h->device));
   hipStream_t st = (hipStream_t)stream;
   const size_t bytes = (size_t)sx * sy;
-  // behind the last roll, which reads the copy that is about to be overwritten (and behind the previous copy)
+  // behind the last roll, which reads the copy that is about to be overwritten (and behind the previous copy).  The last
+  // roll is the fence's last write or lies behind it -- every write runs behind the one before -- so the wait is for that
+  // write whatever it was: `rolled` says nothing here, an ingest enqueued behind a roll that has not started clears it
   int rc;
   if (on_device) {
-    if (h->rolled && (rc = h->fence.wait_writer(st))) return rc;
+    if ((rc = h->fence.wait_writer(st))) return rc;
     if (h->world_ready && h->world_ready_stream != st) HIP_TRY(hipStreamWaitEvent(st, h->world_ready, 0));
   } else {
-    if (h->rolled && (rc = h->fence.wait_writer_host())) return rc;
+    if ((rc = h->fence.wait_writer_host())) return rc;
     if (h->world_ready) HIP_TRY(hipEventSynchronize(h->world_ready));
   }
   rc = h->world_buf.reserve(bytes);
