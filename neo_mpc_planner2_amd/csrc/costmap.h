@@ -56,13 +56,19 @@ __device__ __forceinline__ int cell_raw(const SolveArgs& a, const Ctx& c, const 
   return map_raw(a.map, mx, my);
 }
 
+// the costmap term of a stage at (x, y), rollout frame, in two halves: the raw cost of its cell, then the term-table entry.  A
+// caller with arithmetic of its own between the two (rollout_cost) has the cell byte on its way while it works.
 template <bool kCovered = false>
-__device__ __forceinline__ double step_term(const SolveArgs& a, const Ctx& c, const double* L, double x, double y) {
-  if (c.tile_geom & kTileFree) return L[a.lds.term];   // free neighbourhood (load_tile): the term of a free cell, no lookup
+__device__ __forceinline__ int step_raw(const SolveArgs& a, const Ctx& c, const double* L, double x, double y) {
+  if (c.tile_geom & kTileFree) return 0;   // free neighbourhood (load_tile): the term of a free cell, no lookup
   const double X = c.X0 + (c.c0 * x - c.s0 * y), Y = c.Y0 + (c.s0 * x + c.c0 * y);
   const int mx = cell_of(X, a.map.origin_x, a.map.resolution, a.map.inv_resolution);
   const int my = cell_of(Y, a.map.origin_y, a.map.resolution, a.map.inv_resolution);
-  return L[a.lds.term + cell_raw<kCovered>(a, c, L, mx, my)];
+  return cell_raw<kCovered>(a, c, L, mx, my);
+}
+template <bool kCovered = false>
+__device__ __forceinline__ double step_term(const SolveArgs& a, const Ctx& c, const double* L, double x, double y) {
+  return L[a.lds.term + step_raw<kCovered>(a, c, L, x, y)];
 }
 
 // Wall model of the stage-wise direction (Riccati kernel).  A stage whose position (x, y: rollout frame) sits within

@@ -94,17 +94,33 @@ __device__ __forceinline__ double lane_scale(int lane) {
 //    exactly v_cur at t >= 1.
 //  * hop candidates (lanes 1..count of the hop table, costmap.h): the current point with block `hop_stage` changed by
 //    (hop_x, hop_y); hop_stage < 0: an ordinary candidate.
-template <bool kTame = false, bool kRiccati = false>
+// kPreload (the unrolled three-stage search): everything the block reads from LDS -- u, gs, d and the mode words, wave-uniform
+// addresses all of them -- is fetched together in front of the lane-divergent tree below, one wait for the lot, and the
+// arms share the copies; read where it is used each value costs its own round trip, behind a branch that waited for the
+// one before (the compiler moves no LDS load across a divergent branch).  The same values, the same arithmetic.
+template <bool kTame = false, bool kRiccati = false, bool kPreload = false>
 __device__ __forceinline__ void candidate_block(const SolveArgs& a, const Ctx& c, const double* L, int lane,
                                                 double step, double pstep, int i, double& b0, double& b1,
                                                 double& b2, int hop_stage = -1, float hop_x = 0.0f, float hop_y = 0.0f) {
   const double* u = L + a.lds.u + 3 * i;
+  const double* gs = L + a.lds.gs + 3 * i;
+  const double* d = L + a.lds.d + 3 * i;
+  const int* am = reinterpret_cast<const int*>(L + a.lds.mode) + 4 * i;
+  double pu[3], pg[3], pd[3];
+  int pm[4];
+  if (kPreload) {
+    for (int k = 0; k < 3; ++k) { pu[k] = u[k]; pg[k] = gs[k]; pd[k] = d[k]; }
+    for (int k = 0; k < 4; ++k) pm[k] = am[k];
+    // (held here: otherwise each load sinks back into the arm that uses it)
+    asm volatile("" : "+v"(pu[0]), "+v"(pu[1]), "+v"(pu[2]), "+v"(pg[0]), "+v"(pg[1]), "+v"(pg[2]), "+v"(pd[0]), "+v"(pd[1]),
+                      "+v"(pd[2]), "+v"(pm[0]), "+v"(pm[1]), "+v"(pm[2]), "+v"(pm[3]));
+    u = pu; gs = pg; d = pd; am = pm;
+  }
   if (kRiccati && hop_stage >= 0) {
     b0 = u[0]; b1 = u[1]; b2 = u[2];
     if (i == hop_stage) { b0 += (double)hop_x; b1 += (double)hop_y; project_block<kTame>(a.p, b0, b1, b2); }
     return;
   }
-  const int* am = reinterpret_cast<const int*>(L + a.lds.mode) + 4 * i;
   const bool near = am[2] != 0;
   // (round 4) Newton lanes: every other step length leaves the blocks next to the kink where they are -- their proximal
   // step is made with the gradient at u, the other blocks' Newton step was computed with them held: when both correct
@@ -115,14 +131,12 @@ __device__ __forceinline__ void candidate_block(const SolveArgs& a, const Ctx& c
                             // on its face by the tangent-cone pass), prox of the control norm
     if (lane >= 32) step = pstep;
     if (kRiccati) step *= (double)a.p.n * rcp_fast((double)(a.p.n - i));
-    const double* gs = L + a.lds.gs + 3 * i;
     const double e0 = (u[0] - step * gs[0]) - c.v0, e1 = (u[1] - step * gs[1]) - c.v1,
                  e2 = (u[2] - step * gs[2]) - c.v2;
     const double ne2 = e0 * e0 + e1 * e1 + e2 * e2;
     const double sh = (ne2 > 0.0) ? fmax(0.0, 1.0 - step * a.p.wc_n * rsq_fast1(ne2)) : 0.0;
     b0 = c.v0 + sh * e0; b1 = c.v1 + sh * e1; b2 = c.v2 + sh * e2;
   } else {          // quasi-Newton / Newton direction
-    const double* d = L + a.lds.d + 3 * i;
     if (kRiccati && am[3]) {
       if (step >= 1.0) { b0 = c.v0; b1 = c.v1; b2 = c.v2; }
       else { b0 = u[0] + step * d[0]; b1 = u[1] + step * d[1]; b2 = u[2] + step * d[2]; }

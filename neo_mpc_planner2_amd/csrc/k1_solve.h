@@ -506,7 +506,8 @@ __device__ __forceinline__ bool solve_search(double* L, uint32_t b, SolveCarry& 
           anynear |= (AMODE[4 * (k / 3) + 2] == 1);
         }
       } else if (lane < nvr) { dm = fabsf(newton_sol); anynear = (AMODE[4 * (lane / 3) + 2] == 1); }   // (d[lane], still in a register)
-      dm = wave_max_f(dm);
+      // (three stages: nine values in lanes 0-8, each finite and non-negative or INFINITY -- one DPP row)
+      if constexpr (kFew > 0 && 3 * kFew <= 16) dm = wave_max_f_few<3 * kFew>(dm); else dm = wave_max_f(dm);
       const bool near_any = __ballot(anynear != 0) != 0ull;
       // (with a cheaper cell a hop away the search runs once more: its hop lanes decide)
       if ((double)dm < TOL[T_EARLY] && !near_any && nhops == 0) { status = NEO_MPC_STATUS_CONVERGED; break; }
@@ -550,7 +551,7 @@ __device__ __forceinline__ bool solve_search(double* L, uint32_t b, SolveCarry& 
     double fc = rollout_cost<kSteps, kTame, kCovered>(
         a, c, L,
         [&](int i, double& b0, double& b1, double& b2) {
-          candidate_block<kTame, kRiccati>(a, c, L, lane, step, pstep, i, b0, b1, b2, hop_stage, hop_x, hop_y);
+          candidate_block<kTame, kRiccati, (kFew > 0 && kTame)>(a, c, L, lane, step, pstep, i, b0, b1, b2, hop_stage, hop_x, hop_y);
           // (a scalar branch taken in the first iteration only -- the empty asm keeps the compiler from turning it into
           // six selects per block that every iteration pays)
           if (it == 0) {

@@ -84,6 +84,22 @@ __device__ __forceinline__ double ric_fma(double a, double b, double c) { return
 // non-positive pivots are replaced: the factorisation is then that of a positive definite matrix and the stage
 // step a descent direction (Gauss-Newton stage systems are positive definite; this guards rounding)
 template <typename T> __device__ __forceinline__ T ric_pivot(T p, T delta) { return p > delta ? p : ric_max(ric_abs(p), delta); }
+// float32: the selects as v_max_f32 with |.| as a source modifier -- one instruction where compare + select (+ the wait
+// states between them) took three per select.  Only where the result is the select's for EVERY input, bit for bit
+// (tests/test_sweep_select_identities.py holds the two forms against each other):
+//  * ric_floor(a) = ric_max(a, 1e-30f) = fmaxf(a, 1e-30f): a > c ? a : c with c not NaN -- a NaN gives c either way.
+//  * ric_pivot(p, delta) = fmaxf(|p|, delta) for delta = ric_floor(.), i.e. delta >= 1e-30f and never NaN: p > delta means
+//    |p| = p > delta; p <= delta means the select takes the larger of |p| and delta, ties are the same number (delta > 0:
+//    no -0 against +0); p NaN gives delta either way.
+//  * |a| inside ric_floor(1e-6f * max(...)) may be fabsf although ric_abs keeps -0 and a NaN's sign: a zero of either sign
+//    and a NaN of either sign end as 1e-30f.
+// ric_max(a, b) with a b that can be NaN is NOT fmaxf (the select hands back b, the instruction a): the maxima over the
+// diagonal inside delta keep their selects.
+__device__ __forceinline__ float ric_floor(float a) { return fmaxf(a, 1e-30f); }
+__device__ __forceinline__ double ric_floor(double a) { return ric_max(a, 1e-30); }
+__device__ __forceinline__ float ric_mag(float a) { return fabsf(a); }
+__device__ __forceinline__ double ric_mag(double a) { return ric_abs(a); }
+__device__ __forceinline__ float ric_pivot(float p, float delta) { return fmaxf(fabsf(p), delta); }
 
 // lane = stage.  In: gt / gs / u / tangent-cone description (mode, wfroz, near | nx, ny, k2 = lambda/r of a
 // binding disc) and the stage's cs, sn (record).  Out (record): gradients and the step onto the kink in
@@ -229,7 +245,7 @@ __device__ __forceinline__ void riccati_sweep(const SolveArgs& a, double* L, int
       case RC_FREE3: {
         // L D L^T of Quu = M + R~ without pivoting, pivots made positive
         const T Q00 = S00 + c00, Q01 = S01 + c01, Q02 = Z02 + c02, Q11 = S11 + c11, Q12 = Z12 + c12, Q22 = Z22 + c22;
-        const T delta = ric_max((T)1e-6 * ric_max(ric_abs(Q00), ric_max(ric_abs(Q11), ric_abs(Q22))), (T)1e-30);
+        const T delta = ric_floor((T)1e-6 * ric_max(ric_mag(Q00), ric_max(ric_mag(Q11), ric_mag(Q22))));
         const T d0 = ric_pivot(Q00, delta), i0 = ric_rcp(d0);
         const T l10 = Q01 * i0, l20 = Q02 * i0;
         const T d1 = ric_pivot(Q11 - l10 * Q01, delta), i1 = ric_rcp(d1);
@@ -272,7 +288,7 @@ __device__ __forceinline__ void riccati_sweep(const SolveArgs& a, double* L, int
         const T ga = ax * q0 + ay * q1, gb = bw ? q2 : q1;
         const T Za0 = ax * S00 + ay * S01, Za1 = ax * S01 + ay * S11, Za2 = ax * Z02 + ay * Z12;
         const T Zb0 = bw ? M02 : S01, Zb1 = bw ? M12 : S11, Zb2 = bw ? Z22 : Z12;
-        const T delta = ric_max((T)1e-6 * ric_max(ric_abs(haa), ric_abs(hbb)), (T)1e-30);
+        const T delta = ric_floor((T)1e-6 * ric_max(ric_mag(haa), ric_mag(hbb)));
         const T d0 = ric_pivot(haa, delta), i0 = ric_rcp(d0);
         const T l = hab * i0;
         const T d1 = ric_pivot(hbb - l * hab, delta), i1 = ric_rcp(d1);
@@ -304,7 +320,7 @@ __device__ __forceinline__ void riccati_sweep(const SolveArgs& a, double* L, int
       case RC_SLIDE: {     // the tangent only (omega frozen)
         const T Q00 = S00 + c00, Q01 = S01 + c01, Q11 = S11 + c11;
         const T haa = (rtx * Q00 + rty * Q01) * rtx + (rtx * Q01 + rty * Q11) * rty;
-        const T i0 = -ric_rcp(ric_pivot(haa, ric_max((T)1e-6 * ric_abs(haa), (T)1e-30)));
+        const T i0 = -ric_rcp(ric_pivot(haa, ric_floor((T)1e-6 * ric_mag(haa))));
         const T Za0 = rtx * S00 + rty * S01, Za1 = rtx * S01 + rty * S11, Za2 = rtx * Z02 + rty * Z12;
         const T ka = (rtx * q0 + rty * q1) * i0, Ka0 = Za0 * i0, Ka1 = Za1 * i0, Ka2 = Za2 * i0;
         if (first) { k0 = rtx * ka; k1 = rty * ka; break; }
@@ -316,7 +332,7 @@ __device__ __forceinline__ void riccati_sweep(const SolveArgs& a, double* L, int
       }
       case RC_W: {         // omega only (velocity pinned)
         const T hbb = Z22 + c22;
-        const T i0 = -ric_rcp(ric_pivot(hbb, ric_max((T)1e-6 * ric_abs(hbb), (T)1e-30)));
+        const T i0 = -ric_rcp(ric_pivot(hbb, ric_floor((T)1e-6 * ric_mag(hbb))));
         k2 = q2 * i0;
         if (first) break;
         K20 = M02 * i0; K21 = M12 * i0; K22 = Z22 * i0;
@@ -349,9 +365,18 @@ __device__ __forceinline__ void riccati_sweep(const SolveArgs& a, double* L, int
   WAVE_SYNC();
   // forward sweep: w_i = k_i + K_i dz_{i-1}, dz_i = A_i (dz_{i-1} + w_i)
   T z0 = (T)0.0, z1 = (T)0.0, z2 = (T)0.0;
-  for (int i = 0; i < n; ++i) {
+  // (kFew: every stage's step and gains are fetched in front of the first stage, one wait for all of them -- read stage by
+  // stage each fetch waits behind the d[] stores of the stage before)
+  ric_f4 fs[kFew ? kFew : 1][4];
+  if (kFew) {
+    for (int i = 0; i < kFew; ++i) {
+      const ric_f4* R4 = reinterpret_cast<const ric_f4*>(RS + kRicStage * i);
+      fs[i][0] = R4[0]; fs[i][1] = R4[4]; fs[i][2] = R4[5]; fs[i][3] = R4[6];
+    }
+  }
+  for (int i = 0; i < (kFew ? kFew : n); ++i) {
     const ric_f4* R4 = reinterpret_cast<const ric_f4*>(RS + kRicStage * i);
-    const ric_f4 s0 = R4[0], g0 = R4[4], g1 = R4[5], g2 = R4[6];
+    const ric_f4 s0 = kFew ? fs[i][0] : R4[0], g0 = kFew ? fs[i][1] : R4[4], g1 = kFew ? fs[i][2] : R4[5], g2 = kFew ? fs[i][3] : R4[6];
     const T w0 = (T)g2.y + (T)g0.x * z0 + (T)g0.y * z1 + (T)g0.z * z2;
     const T w1 = (T)g2.z + (T)g0.w * z0 + (T)g1.x * z1 + (T)g1.y * z2;
     const T w2f = (T)g2.w + (T)g1.z * z0 + (T)g1.w * z1 + (T)g2.x * z2;

@@ -38,11 +38,14 @@ __device__ __forceinline__ double rollout_cost(const SolveArgs& a, const Ctx& c,
     record(i, sn, cs);
     x += (vx * cs - vy * sn) * p.dt;                    // py:231
     y += (vx * sn + vy * cs) * p.dt;                    // py:232
+    // (the cell is looked up as soon as x and y exist: its byte, then the table entry, arrive under the two terms below --
+    // f takes the three in the order it always did)
+    const int raw = step_raw<kCovered>(a, c, L, x, y);         // py:246-247
     const double dx = c.cx - x, dy = c.cy - y, et = c.tyaw - th;
     const double e0 = c.v0 - vx, e1 = c.v1 - vy, e2 = c.v2 - w;
     f += p.wt_n * (dx * dx + dy * dy) + p.wo_n * (et * et);   // py:252
+    const double term = L[a.lds.term + raw];                   // py:257-260
     f += p.wc_n * sqrt_fast(e0 * e0 + e1 * e1 + e2 * e2);      // py:253-254
-    const double term = step_term<kCovered>(a, c, L, x, y);    // py:246-247, 257-260
     f += term;
     if (term_sum) ts += term;
   }

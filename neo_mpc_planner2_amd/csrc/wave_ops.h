@@ -89,6 +89,19 @@ __device__ __forceinline__ float wave_max_f(float v) {
   v = fmaxf(v, dpp_move_f<0x143, 0xc>(v));
   return __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), 63));
 }
+// ... of the values in the first kCount lanes only (kCount a compile-time bound within one DPP row; what the other lanes hold
+// is not looked at): the four row steps bring lanes 0 .. kCount-1 into lane kCount-1 and the two row broadcasts fall away.
+// The maximum of non-negative numbers that are not NaN does not depend on the order they are taken in: the same bits as
+// wave_max_f over lanes that hold zeros elsewhere.
+template <int kCount>
+__device__ __forceinline__ float wave_max_f_few(float v) {
+  static_assert(kCount >= 1 && kCount <= 16, "one DPP row");
+  if (kCount > 1) v = fmaxf(v, dpp_move_f<0x111, 0xf>(v));
+  if (kCount > 2) v = fmaxf(v, dpp_move_f<0x112, 0xf>(v));
+  if (kCount > 4) v = fmaxf(v, dpp_move_f<0x114, 0xf>(v));
+  if (kCount > 8) v = fmaxf(v, dpp_move_f<0x118, 0xf>(v));
+  return __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), kCount - 1));
+}
 // lowest value, ties to the lowest lane; every lane returns the same pair
 __device__ __forceinline__ void wave_argmin(double& v, int& idx) {
   const double m = wave_min(v);
