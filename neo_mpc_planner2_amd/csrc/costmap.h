@@ -99,6 +99,11 @@ __device__ __forceinline__ int edge_stickiness(const SolveArgs& a, const Ctx& c,
   wxx = 0.0; wxy = 0.0; wyy = 0.0; lx = 0.0; ly = 0.0;
   hop = false; hop_x = 0.0f; hop_y = 0.0f;
   if (c.tile_geom & kTileFree) return 0;   // free neighbourhood (load_tile): no cost step anywhere near
+  // (the tracking weight as a value the compiler cannot see through: the wall and sticky weights below are products of a
+  // launch constant, and hoisted out of the solver loop they held four vector registers across all of it -- the first to be
+  // spilled, and reloaded from scratch here in every iteration, when the loop needs a few registers more)
+  double wt_n = a.p.wt_n;
+  asm volatile("" : "+s"(wt_n));
   const double X = c.X0 + (c.c0 * x - c.s0 * y), Y = c.Y0 + (c.s0 * x + c.c0 * y);
   const int mx = cell_of(X, a.map.origin_x, a.map.resolution, a.map.inv_resolution);
   const int my = cell_of(Y, a.map.origin_y, a.map.resolution, a.map.inv_resolution);
@@ -121,8 +126,8 @@ __device__ __forceinline__ int edge_stickiness(const SolveArgs& a, const Ctx& c,
     const int raw_n = cell_raw<kCovered>(a, c, L, xlo ? mx - 1 : mx + 1, my);
     const double dist = xlo ? fx : 1.0 - fx, there = L[a.lds.term + raw_n];
     const bool wall = raw_n == 254 && raw_here != 254;
-    if (wall) { if (dist < kWallDist) { rx = kWall * 2.0 * a.p.wt_n; pbx = (xlo ? kWallDist - dist : dist - kWallDist) * a.map.resolution; } }
-    else if (dist < kStickyDist && there > here) rx = kSticky * 2.0 * a.p.wt_n;
+    if (wall) { if (dist < kWallDist) { rx = kWall * 2.0 * wt_n; pbx = (xlo ? kWallDist - dist : dist - kWallDist) * a.map.resolution; } }
+    else if (dist < kStickyDist && there > here) rx = kSticky * 2.0 * wt_n;
     if (dist < hop_range && here - there > drop) {
       drop = here - there; hop = true;
       hwx = (xlo ? -1.0 : 1.0) * (dist + kHopMargin) * a.map.resolution; hwy = 0.0;
@@ -132,8 +137,8 @@ __device__ __forceinline__ int edge_stickiness(const SolveArgs& a, const Ctx& c,
     const int raw_n = cell_raw<kCovered>(a, c, L, mx, ylo ? my - 1 : my + 1);
     const double dist = ylo ? fy : 1.0 - fy, there = L[a.lds.term + raw_n];
     const bool wall = raw_n == 254 && raw_here != 254;
-    if (wall) { if (dist < kWallDist) { ry = kWall * 2.0 * a.p.wt_n; pby = (ylo ? kWallDist - dist : dist - kWallDist) * a.map.resolution; } }
-    else if (dist < kStickyDist && there > here) ry = kSticky * 2.0 * a.p.wt_n;
+    if (wall) { if (dist < kWallDist) { ry = kWall * 2.0 * wt_n; pby = (ylo ? kWallDist - dist : dist - kWallDist) * a.map.resolution; } }
+    else if (dist < kStickyDist && there > here) ry = kSticky * 2.0 * wt_n;
     if (dist < hop_range && here - there > drop) {
       hop = true;
       hwx = 0.0; hwy = (ylo ? -1.0 : 1.0) * (dist + kHopMargin) * a.map.resolution;

@@ -272,6 +272,11 @@ __device__ __forceinline__ bool solve_search(double* L, uint32_t b, SolveCarry& 
   // (kSteps > 0 with the stage-wise direction -- the routed branch: candidates in registers, unrolled rollouts, the winner
   // stored without being recomputed like the dense specialisation; gradient and sweep run lane = stage on three lanes)
   constexpr int kFew = (kRiccati && kSteps > 0) ? kSteps : 0;
+  // three stages: the sweep hands each lane its own stage's step in registers, riccati_finish writes d once and hands the
+  // step test its maximum (riccati.h SweepHandOff); the tame kernels, which never sweep twice with another active set, also
+  // know each stage's case as a scalar before the sweep starts
+  constexpr bool kHandOff = kFew > 0;
+  constexpr bool kScalarCase = kFew > 0 && kTame;
   // Newton: control_steps == kSteps, or (kSteps == 0) any control_steps <= kNewtonMaxSteps -- the
   // system's arrays are sized for the bound and every loop over them is guarded by the run-time size
   constexpr int kNwSteps = !kNewton ? 1 : kSteps ? kSteps : kNewtonMaxSteps;
@@ -387,6 +392,8 @@ __device__ __forceinline__ bool solve_search(double* L, uint32_t b, SolveCarry& 
     int nhops = 0;            // Riccati: hop candidates of this iteration (wave-uniform; the table is in the tolerance block)
     float hc[kVars];     // Newton: column `lane` of the Hessian, then row `lane` (float32, see below)
     float newton_sol = 0.0f;  // Newton: entry `lane` of the direction
+    float dm_reg = 0.0f;                // kHandOff: the step test's maximum over this lane's three entries of d (riccati_finish)
+    int near_reg = 0;                   // ... and the near word of the lane's stage
     if (kNewton) {
       double hcol[kSteps ? kVars : 1];  // control_steps specialisation: gradient of this lane's perturbed copy
       // Every lane runs the rollout + adjoint sweep on its own copy of u: lane k < 3N perturbs
@@ -475,12 +482,19 @@ __device__ __forceinline__ bool solve_search(double* L, uint32_t b, SolveCarry& 
       if (kRiccati) for (int i = lane; i < n; i += kLanes) AMODE[4 * i + 3] = 0;
       WAVE_SYNC();
     } else if (kRiccati) {
-      riccati_prepare(a, c, L, n, lane, v_feasible, (float)TOL[T_MU]);
+      const int my_flags = riccati_prepare(a, c, L, n, lane, v_feasible, (float)TOL[T_MU]);
+      // (the stages' cases as scalars: the sweep's switch does not wait for the record, its conversion and a lane read)
+      int stage_flags[kFew ? kFew : 1] = {};
+      if (kScalarCase) {
+        for (int i = 0; i < kFew; ++i) stage_flags[i] = __builtin_amdgcn_readlane(my_flags, i);
+      }
       WAVE_SYNC();
       if (corner_any) riccati_keep_linear_terms(a, L, n, lane, true);   // (the sweep writes its gains over them)
       auto sweep = [&]() {
-        riccati_sweep<float, (kMinWavesPerSimd < 4), kFew>(a, L, n, lane);
-        riccati_finish(a, c, L, n, lane);
+        SweepHandOff<float> ho = {};
+        riccati_sweep<float, (kMinWavesPerSimd < 4), kFew, kHandOff, kScalarCase>(a, L, n, lane, &ho, stage_flags);
+        riccati_finish<kHandOff>(a, c, L, n, lane, &ho, &dm_reg);
+        near_reg = ho.near;
       };
       sweep();
       if (!kTame && corner_any && repin_corner_blocks<true>(a, L, n, lane)) {   // (one-sided slides: once more, those blocks pinned)
@@ -498,7 +512,15 @@ __device__ __forceinline__ bool solve_search(double* L, uint32_t b, SolveCarry& 
       // the kink are moved by the prox step, which d does not describe -- keep iterating then)
       float dm = 0.0f;
       int anynear = 0;
-      if (kRiccati) {
+      if (kHandOff) {
+        // (riccati_finish has applied the rule below to the three entries of the lane's stage; the lanes without a stage hold
+        // zero.  dm is the maximum of the magnitudes, or INFINITY as soon as one entry is NaN -- a maximum of non-negative
+        // numbers that are not NaN does not depend on the order it is taken in, and INFINITY absorbs everything behind it:
+        // three entries per lane, then three lanes, give the bits that one entry per lane over nine lanes gave;
+        // tests/test_stagewise_phases.py holds the two orders against each other)
+        dm = dm_reg;
+        anynear = near_reg == 1;
+      } else if (kRiccati) {
         // (a non-finite direction must not read as "no step left": fmaxf drops NaN)
         for (int k = lane; k < nv; k += kLanes) {
           const float v = (float)fabs(d[k]);
@@ -507,7 +529,8 @@ __device__ __forceinline__ bool solve_search(double* L, uint32_t b, SolveCarry& 
         }
       } else if (lane < nvr) { dm = fabsf(newton_sol); anynear = (AMODE[4 * (lane / 3) + 2] == 1); }   // (d[lane], still in a register)
       // (three stages: nine values in lanes 0-8, each finite and non-negative or INFINITY -- one DPP row)
-      if constexpr (kFew > 0 && 3 * kFew <= 16) dm = wave_max_f_few<3 * kFew>(dm); else dm = wave_max_f(dm);
+      if constexpr (kHandOff) dm = wave_max_f_few<kFew>(dm);
+      else if constexpr (kFew > 0 && 3 * kFew <= 16) dm = wave_max_f_few<3 * kFew>(dm); else dm = wave_max_f(dm);
       const bool near_any = __ballot(anynear != 0) != 0ull;
       // (with a cheaper cell a hop away the search runs once more: its hop lanes decide)
       if ((double)dm < TOL[T_EARLY] && !near_any && nhops == 0) { status = NEO_MPC_STATUS_CONVERGED; break; }

@@ -105,9 +105,10 @@ __device__ __forceinline__ float ric_pivot(float p, float delta) { return fmaxf(
 // binding disc) and the stage's cs, sn (record).  Out (record): gradients and the step onto the kink in
 // displacement coordinates, tangent, flags, block curvature.
 // mu: Levenberg-Marquardt damping in units of one stage's tracking weights (k_solve adapts it).
-__device__ __forceinline__ void riccati_prepare(const SolveArgs& a, const Ctx& c, double* L, int n, int lane,
-                                                bool v_feasible, float mu) {
-  if (lane >= n) return;
+// Returns the stage's flags word (RS_FLAGS; 0 in the lanes that hold no stage).
+__device__ __forceinline__ int riccati_prepare(const SolveArgs& a, const Ctx& c, double* L, int n, int lane,
+                                               bool v_feasible, float mu) {
+  if (lane >= n) return 0;
   const DevParams& p = a.p;
   float* rs = reinterpret_cast<float*>(L + a.lds.ric) + kRicStage * lane;
   const int* am = reinterpret_cast<const int*>(L + a.lds.mode) + 4 * lane;
@@ -152,6 +153,7 @@ __device__ __forceinline__ void riccati_prepare(const SolveArgs& a, const Ctx& c
     c00 += mt; c11 += mt; c22 += mu * (float)(2.0 * p.wo_n);
   }
   rs[RS_C00] = c00; rs[RS_C01] = c01; rs[RS_C02] = c02; rs[RS_C11] = c11; rs[RS_C12] = c12; rs[RS_C22] = c22;
+  return flags;
 }
 
 // The backward sweep writes each stage's gains over the linear terms of its record (RS_GAIN .. the end).  A sweep that may
@@ -173,8 +175,25 @@ __device__ __forceinline__ void riccati_keep_linear_terms(const SolveArgs& a, do
 // kPrefetch: fetch the next stage's record one stage ahead (28 more live registers: the 4-waves/SIMD build
 // reads each record when it needs it instead)
 // kFew > 0: control_steps == kFew at compile time (the loops unroll and the first stage takes its shortcut)
-template <typename T, bool kPrefetch = true, int kFew = 0>
-__device__ __forceinline__ void riccati_sweep(const SolveArgs& a, double* L, int n, int lane) {
+// What a sweep with kHandOff gives riccati_finish in registers instead of through d and the mode words: lane i its own
+// stage's step w_i (every lane runs the forward sweep and holds every stage's: two selects per value on a lane compare),
+// for each stage whether the stage model puts the block on the kink (wave-uniform, one bit per stage), and the rest of
+// what riccati_finish reads of the lane's stage -- fetched from LDS together with the forward sweep's gains, one wait for
+// all of it, under the forward sweep instead of behind it.
+template <typename T>
+struct SweepHandOff {
+  T w0, w1, w2;
+  unsigned tokink;
+  double u0, u1, u2, nx, ny;
+  float cs, sn;
+  int mode, wfroz, near;
+};
+// kHandOff (kFew only): the steps leave in `ho`; nothing is written to d and no barrier follows the forward sweep.
+// kScalarCase: the stages' flags words come in `stage_flags` (scalars) instead of from the records.
+template <typename T, bool kPrefetch = true, int kFew = 0, bool kHandOff = false, bool kScalarCase = false>
+__device__ __forceinline__ void riccati_sweep(const SolveArgs& a, double* L, int n, int lane, SweepHandOff<T>* ho = nullptr,
+                                              const int* stage_flags = nullptr) {
+  static_assert(!(kHandOff || kScalarCase) || kFew > 0, "register hand-offs: the unrolled sweeps");
   const DevParams& p = a.p;
   float* RS = static_cast<float*>(__builtin_assume_aligned(reinterpret_cast<float*>(L + a.lds.ric), 16));
   int* AMODE = reinterpret_cast<int*>(L + a.lds.mode);
@@ -202,7 +221,8 @@ __device__ __forceinline__ void riccati_sweep(const SolveArgs& a, double* L, int
     // this stage's record (registers), the next one on its way
     const T px = r0.x, py = r0.y, rtx = r0.z, rty = r0.w;
     const T wxx = r1.x, wxy = r1.y, wyy = r1.z;
-    const int flags = __builtin_amdgcn_readfirstlane((int)r1.w);   // (wave-uniform: scalar branches below)
+    // (wave-uniform: scalar branches below.  kScalarCase: known before the record arrives)
+    const int flags = kScalarCase ? stage_flags[kFew ? i : 0] : __builtin_amdgcn_readfirstlane((int)r1.w);
     const T c00 = r2.x, c01 = r2.y, c02 = r2.z, c11 = r2.w, c12 = r3.x, c22 = r3.y;
     const T gt0 = r4.x, gt1 = r4.y, gt2 = r4.z, gs0 = r4.w, gs1 = r5.x, gs2 = r5.y, e0 = r5.z, e1 = r5.w, e2 = r6.x;
     v0 += (T)r6.y; v1 += (T)r6.z;   // wall push-back: linear term of this stage's own cost in its position
@@ -361,6 +381,7 @@ __device__ __forceinline__ void riccati_sweep(const SolveArgs& a, double* L, int
       G4[2] = ric_f4{(float)K22, (float)k0, (float)k1, (float)k2};
       AMODE[4 * i + 3] = tokink ? 1 : 0;
     }
+    if (kHandOff && tokink) ho->tokink |= 1u << i;
   }
   WAVE_SYNC();
   // forward sweep: w_i = k_i + K_i dz_{i-1}, dz_i = A_i (dz_{i-1} + w_i)
@@ -373,6 +394,14 @@ __device__ __forceinline__ void riccati_sweep(const SolveArgs& a, double* L, int
       const ric_f4* R4 = reinterpret_cast<const ric_f4*>(RS + kRicStage * i);
       fs[i][0] = R4[0]; fs[i][1] = R4[4]; fs[i][2] = R4[5]; fs[i][3] = R4[6];
     }
+    if (kHandOff && lane < kFew) {
+      const int* am = AMODE + 4 * lane;
+      const double* u = L + a.lds.u + 3 * lane;
+      ho->mode = am[0]; ho->wfroz = am[1]; ho->near = am[2];
+      ho->u0 = u[0]; ho->u1 = u[1]; ho->u2 = u[2];
+      ho->nx = L[a.lds.nx + lane]; ho->ny = L[a.lds.ny + lane];
+      ho->cs = RS[kRicStage * lane + RS_CS]; ho->sn = RS[kRicStage * lane + RS_SN];
+    }
   }
   for (int i = 0; i < (kFew ? kFew : n); ++i) {
     const ric_f4* R4 = reinterpret_cast<const ric_f4*>(RS + kRicStage * i);
@@ -380,37 +409,70 @@ __device__ __forceinline__ void riccati_sweep(const SolveArgs& a, double* L, int
     const T w0 = (T)g2.y + (T)g0.x * z0 + (T)g0.y * z1 + (T)g0.z * z2;
     const T w1 = (T)g2.z + (T)g0.w * z0 + (T)g1.x * z1 + (T)g1.y * z2;
     const T w2f = (T)g2.w + (T)g1.z * z0 + (T)g1.w * z1 + (T)g2.x * z2;
-    if (lane == 0) { d[3 * i] = (double)w0; d[3 * i + 1] = (double)w1; d[3 * i + 2] = (double)w2f; }
+    if (kHandOff) { if (lane == i) { ho->w0 = w0; ho->w1 = w1; ho->w2 = w2f; } }
+    else if (lane == 0) { d[3 * i] = (double)w0; d[3 * i + 1] = (double)w1; d[3 * i + 2] = (double)w2f; }
     const T e0 = z0 + w0, e1 = z1 + w1, e2 = z2 + w2f;
     z0 = ric_fma(-(T)s0.y, e2, e0); z1 = ric_fma((T)s0.x, e2, e1); z2 = e2;
   }
-  WAVE_SYNC();
+  if (!kHandOff) WAVE_SYNC();
 }
 
 // lane = stage: du = B0^-1 w = (Rot^T w_xy, w_w) / dt; the step of a block sent onto the kink is exact
-__device__ __forceinline__ void riccati_finish(const SolveArgs& a, const Ctx& c, double* L, int n, int lane) {
+// kHandOff: everything comes in `ho` (registers, riccati_sweep); d is written once, final, and the step test's maximum over the
+// lane's three entries is handed back in `dmax` (0 in the lanes that hold no stage; INFINITY as soon as an entry is NaN).
+template <bool kHandOff = false, typename T = float>
+__device__ __forceinline__ void riccati_finish(const SolveArgs& a, const Ctx& c, double* L, int n, int lane,
+                                               const SweepHandOff<T>* ho = nullptr, float* dmax = nullptr) {
+  double dr[3] = {0.0, 0.0, 0.0};
   if (lane < n) {
     const float* rs = reinterpret_cast<const float*>(L + a.lds.ric) + kRicStage * lane;
-    const int* am = reinterpret_cast<const int*>(L + a.lds.mode) + 4 * lane;
     double* d = L + a.lds.d + 3 * lane;
-    if (am[3]) {
-      const double* u = L + a.lds.u + 3 * lane;
-      d[0] = c.v0 - u[0]; d[1] = c.v1 - u[1]; d[2] = c.v2 - u[2];
+    int am[4];
+    double u[3] = {0.0, 0.0, 0.0}, nx = 0.0, ny = 0.0;
+    float fcs = 0.0f, fsn = 0.0f;
+    T hw0 = (T)0.0, hw1 = (T)0.0, hw2 = (T)0.0;
+    if (kHandOff) {
+      am[0] = ho->mode; am[1] = ho->wfroz; am[2] = ho->near; am[3] = (int)((ho->tokink >> lane) & 1u);
+      u[0] = ho->u0; u[1] = ho->u1; u[2] = ho->u2; nx = ho->nx; ny = ho->ny; fcs = ho->cs; fsn = ho->sn;
+      hw0 = ho->w0; hw1 = ho->w1; hw2 = ho->w2;
+      // (as opaque to the compiler as the LDS reads they replace: what it may fold or fuse around them is what it could)
+      asm("" : "+v"(hw0), "+v"(hw1), "+v"(hw2));
     } else {
-      const double cs = rs[RS_CS], sn = rs[RS_SN], idt = rcp_fast(a.p.dt);
-      const double w0 = d[0], w1 = d[1], w2 = d[2];
+      const int* amL = reinterpret_cast<const int*>(L + a.lds.mode) + 4 * lane;
+      am[0] = amL[0]; am[1] = amL[1]; am[2] = amL[2]; am[3] = amL[3];
+    }
+    if (am[3]) {
+      if (!kHandOff) { const double* uL = L + a.lds.u + 3 * lane; u[0] = uL[0]; u[1] = uL[1]; u[2] = uL[2]; }
+      const double k0 = c.v0 - u[0], k1 = c.v1 - u[1], k2 = c.v2 - u[2];
+      d[0] = k0; d[1] = k1; d[2] = k2;
+      if (kHandOff) { dr[0] = k0; dr[1] = k1; dr[2] = k2; }
+    } else {
+      const double cs = kHandOff ? fcs : rs[RS_CS], sn = kHandOff ? fsn : rs[RS_SN], idt = rcp_fast(a.p.dt);
+      const double w0 = kHandOff ? (double)hw0 : d[0], w1 = kHandOff ? (double)hw1 : d[1], w2 = kHandOff ? (double)hw2 : d[2];
       double d0 = (cs * w0 + sn * w1) * idt, d1 = (-sn * w0 + cs * w1) * idt;
       // back on the face EXACTLY: the rotation round trip leaves ~1e-10 of a sliding block's step along the
       // constraint normal; an inward residue would take the block off its bound, the next tangent-cone pass
       // would find it free, and the Newton step would run straight back into the bound
       const int mode = am[2] ? 2 : am[0];
       if (mode == 1) {
-        const double nx = L[a.lds.nx + lane], ny = L[a.lds.ny + lane];
+        if (!kHandOff) { nx = L[a.lds.nx + lane]; ny = L[a.lds.ny + lane]; }
         const double dot = d0 * nx + d1 * ny;
         d0 -= dot * nx; d1 -= dot * ny;
       } else if (mode == 2) { d0 = 0.0; d1 = 0.0; }
-      d[0] = d0; d[1] = d1; d[2] = (am[2] || (am[1] & 1)) ? 0.0 : w2 * idt;
+      const double d2 = (am[2] || (am[1] & 1)) ? 0.0 : w2 * idt;
+      d[0] = d0; d[1] = d1; d[2] = d2;
+      if (kHandOff) { dr[0] = d0; dr[1] = d1; dr[2] = d2; }
     }
+  }
+  if (kHandOff) {
+    // (a non-finite direction must not read as "no step left": fmaxf drops NaN)
+    float dm = 0.0f;
+#pragma unroll
+    for (int j = 0; j < 3; ++j) {
+      const float v = (float)fabs(dr[j]);
+      dm = (v == v) ? fmaxf(dm, v) : INFINITY;
+    }
+    *dmax = dm;
   }
   WAVE_SYNC();
 }
