@@ -45,14 +45,7 @@
 namespace neo_mpc {
 namespace {
 
-// the stop-rule constants: solver_rules.h (shared with the host side and with the CPU mirror)
-constexpr int kStallIterations = NEO_RULE_STALL_ITERATIONS;
-constexpr int kBlockedRun = NEO_RULE_BLOCKED_RUN;
-constexpr double kBlockedStep = NEO_RULE_BLOCKED_STEP;
-constexpr double kFinalFracGaussNewton = NEO_RULE_FINAL_FRAC_GN;
-constexpr double kWindowStep = NEO_RULE_WINDOW_STEP;
-constexpr int kClosingRun = NEO_RULE_CLOSING_RUN;
-constexpr int kLateIteration = NEO_RULE_LATE_ITERATION;
+// (the stop rules and their constants: solver_rules.h, shared with the host side and with the CPU mirror)
 // largest control_steps the run-time-sized Newton kernel takes (a 24 x 24 system: rows in registers)
 constexpr int kNewtonMaxSteps = 8;
 
@@ -291,12 +284,10 @@ __device__ __forceinline__ bool solve_search(double* L, uint32_t b, SolveCarry& 
   double f = sc.f;
   const bool cold = sc.cold;
   // ---- what the search carries from one iteration to the next -- and across the cell scan when it is taken up again
-  int npairs = 0, head = 0, nfev = sc.nfev, it = sc.it, status = sc.status, stall = 0;
-  int blocked_run = 0;   // dense Newton: consecutive iterations not won by a decent Newton step
-  int nblocked = 1;      // consecutive iterations not won by a Newton step of at least half its length (or won by a hop)
+  int npairs = 0, head = 0, nfev = sc.nfev, it = sc.it, status = sc.status;
+  neo_search_run run;    // what the stop rules carry (solver_rules.h; three-stage kernels: the gains wait in LDS, T_GAIN1 / T_GAIN2)
+  neo_search_run_init(&run);
   double u_term = 0.0;   // dense Newton: sum of the costmap terms under the current iterate's rollout (0: every stage in a free cell)
-  double gain1 = INFINITY, gain2 = INFINITY;  // objective decrease of the previous two iterations
-  bool final_step = false;
   double alpha = 1.0;
   bool scanned = false;   // the cell scan has had its turn (cell_scan.h)
   int nscans = 0;         // ... scans of its round so far: a scan that found a cheaper cell is followed by another from the new point
@@ -377,7 +368,7 @@ __device__ __forceinline__ bool solve_search(double* L, uint32_t b, SolveCarry& 
     // at 4 waves/SIMD, parks them in scratch -- recomputing them costs a few integer operations.
     int lane = lane_again();
     // stage-wise direction: this iteration's sweep carries the second-order terms of the rollout step
-    const bool exact_step = kRiccati && nblocked == 0;
+    const bool exact_step = kRiccati && run.nblocked == 0;
     // (same trick for the tolerance block: an opaque LDS offset keeps its loads inside the loop and in
     // the LDS address space -- a volatile pointer would turn them into flat loads with a full wait each)
     int tol_off = a.lds.tol;
@@ -508,8 +499,7 @@ __device__ __forceinline__ bool solve_search(double* L, uint32_t b, SolveCarry& 
     // ---- projected L-BFGS: newest curvature pair, two-loop recursion on the reduced gradient, restriction to the face
     if (!kSecond) lbfgs_direction<kSteps, kPairs>(a, L, it, mem, head, npairs, lane, n);   // (lbfgs.h)
     if (kSecond && it > 0) {
-      // the full Newton step is already below the step tolerance: u is the answer (blocks next to
-      // the kink are moved by the prox step, which d does not describe -- keep iterating then)
+      // the Newton step test (solver_rules.h neo_rules_step_test) on the largest entry of d and on "a block next to the kink"
       float dm = 0.0f;
       int anynear = 0;
       if (kHandOff) {
@@ -532,12 +522,9 @@ __device__ __forceinline__ bool solve_search(double* L, uint32_t b, SolveCarry& 
       if constexpr (kHandOff) dm = wave_max_f_few<kFew>(dm);
       else if constexpr (kFew > 0 && 3 * kFew <= 16) dm = wave_max_f_few<3 * kFew>(dm); else dm = wave_max_f(dm);
       const bool near_any = __ballot(anynear != 0) != 0ull;
-      // (with a cheaper cell a hop away the search runs once more: its hop lanes decide)
-      if ((double)dm < TOL[T_EARLY] && !near_any && nhops == 0) { status = NEO_MPC_STATUS_CONVERGED; break; }
-      // a full Newton step below opt_tolerance (SLSQP's own step test) is the last one: searched
-      // and taken like any other, but nothing re-checks the point it lands on
-      // (a Gauss-Newton step converges linearly: it has to be shorter to be the last)
-      if ((double)dm < ((kRiccati && !exact_step) ? kFinalFracGaussNewton : 1.0) * TOL[T_FINAL] && !near_any) final_step = true;
+      const int verdict = neo_rules_step_test((double)dm, near_any, nhops, TOL[T_EARLY], TOL[T_FINAL], kRiccati && !exact_step);
+      if (verdict == NEO_STEP_CONVERGED) { status = NEO_MPC_STATUS_CONVERGED; break; }
+      if (verdict == NEO_STEP_IS_LAST) run.final_step = true;
     }
     NEO_PHASE(4);
     if (p.max_it > kDumpGradient && it == p.max_it - kDumpGradient - 1) {
@@ -648,70 +635,33 @@ __device__ __forceinline__ bool solve_search(double* L, uint32_t b, SolveCarry& 
       }
       stepmax = wave_max_f(stepmax);
     }
-    const double gain = f - fb;
-    // (gain thresholds are relative to the u-dependent part of the objective: inside the loop f excludes the constant
-    // terms -- the terminal distance term, py:266, can be 20 x the rest)
-    const double fscale = fmax(1.0, fabs(fb));
-    stall = (gain <= TOL[T_FTOL] * fscale || (double)stepmax <= TOL[T_STALL]) ? stall + 1 : 0;
-    // stage-wise direction: the window and closing-in rules only judge runs of BLOCKED iterations (none of the three won
-    // by a Newton step of at least half its length); iterations won by the Newton step end through the step test
+    // ---- does this iteration end the search?  (solver_rules.h neo_rules_iteration_ends: one text for every variant and the mirror)
     // (the un-shifted start that won the first iteration says as little about step lengths as a hop)
     const bool hop_won = (kRiccati && best >= 1 && best <= nhops) || alt_won;
-    nblocked = (best < 32 || lane_value(step, best) < kWindowStep || hop_won) ? nblocked + 1 : 0;
-    const bool window_on = !kRiccati || kRouted || nblocked >= 3;
-    // three iterations that together gained less than wtol: creeping along a costmap cell edge
-    const double wtol0 = TOL[T_WTOL];   // (the closing-in rule below is on whenever the window rule is)
-    const double wtol = it >= kLateIteration ? TOL[T_WTOL_LATE] : wtol0;
-    const double g1 = kFew ? TOL[T_GAIN1] : gain1, g2 = kFew ? TOL[T_GAIN2] : gain2;   // (the previous two iterations' gains)
-    bool creeping = wtol > 0.0 && gain + g1 + g2 <= wtol * fscale && window_on;
-    // ... and so does a step below stall_step whose gain halved twice in a row: the search is closing in on a
-    // costmap cell edge (or the kink) geometrically; what is left to gain is less than the last gain (in free space three
-    // gains it takes: round 5 -- the INFINITY the two older ones start at used to pass for a gain, and a warm search that began next to the
-    // kink ended after its second iteration, 2.4e-3 from the reference's converged first control on one G13 tick -- and the
-    // geometric series the gains start has to be worth less than the stall threshold, gain r / (1 - r) <= ftol f~ with r =
-    // gain / gain1: 3e-6 left to gain is 2.5e-3 in the first control along a direction of curvature 1)
-    // (dense and L-BFGS directions: only behind kClosingRun blocked iterations -- the gains of a Newton search that converges
-    // quadratically halve twice in a row as well, and one blocked iteration after them, a bound about to become active, is
-    // no sign of creeping: random parameter sets, 1 solve in 3000 stopped 5e-3 short)
-    // (in free space -- where the first control is gated, not only the objective: dense direction: no costmap term under the
-    // NEW iterate's rollout; stage-wise: under the rollout the iteration started from)
-    bool free_now = kRiccati ? free_path : false;
-    if (kNewton) free_now = lane_value(cterm, best) == 0.0;
-    creeping = creeping || (wtol0 > 0.0 && (double)stepmax <= TOL[T_STALL] && gain <= 0.5 * g1 && g1 <= 0.5 * g2 &&
-                            (!free_now || (g2 < INFINITY && gain * gain <= TOL[T_FTOL] * fscale * (g1 - gain))) &&
-                            ((kRiccati && !kRouted) ? window_on : nblocked >= kClosingRun));
-    // Blocked-run stop rule (dense Newton).  kBlockedRun iterations in a row not won by a decent Newton step that
-    // together gain less than 0.1 x opt_tolerance (0.03 x with no costmap term under the new iterate's rollout): something
-    // the quadratic model does not see is in the way -- a costmap cell edge, or blocks hovering next to the control norm's
-    // kink -- and the search advances 1e-6 of f per iteration (SLSQP stops on ONE iteration gaining less than
-    // opt_tolerance).  In a closed 30 Hz loop of 4096 robots such searches set the duration of every launch: per-tick
-    // maximum 25 -> 13 iterations in the median, 100 -> 16 at worst; cold solves and the zero-map drift check are untouched.
-    bool blocked_stop = false;
-    if (kBlockedRule) {
-      const double bs = lane_value(step, best);
-      blocked_run = (best < 32 || bs < kBlockedStep) ? blocked_run + 1 : 0;
-      if (blocked_run >= kBlockedRun) {
-        const bool free_rollout = lane_value(cterm, best) == 0.0;
-        const double btol = free_rollout ? TOL[T_BTOL_FREE] : TOL[T_BTOL_MAP];
-        blocked_stop = gain + g1 + g2 <= btol;   // (btol 0: the rule is off -- a gain is never <= 0 here)
-      }
-    }
+    // (no costmap term under the new iterate's rollout; the closing-in rule's free space -- dense direction: the same;
+    // stage-wise: under the rollout the iteration started from)
+    const bool free_rollout = kBlockedRule ? lane_value(cterm, best) == 0.0 : false;
+    const bool free_now = kRiccati ? free_path : (kNewton ? free_rollout : false);
+    if (kFew) { run.gain1 = TOL[T_GAIN1]; run.gain2 = TOL[T_GAIN2]; }
+    // (the gain is wave-uniform but comes out of the vector ALU.  Dense direction: it goes on as a scalar -- the two gains the
+    // rules carry are four vector registers held across the Hessian pass, and the run-time-sized kernel at four waves per SIMD
+    // parked two more registers in scratch with the rules called than with their text in place)
+    const double gain = kNewton ? lane_value(f - fb, 0) : f - fb;
+    const bool ends = neo_rules_iteration_ends(kRiccati, kRouted, kBlockedRule, TOL, &run, it, best >= 32, lane_value(step, best), hop_won,
+                                               gain, fb, (double)stepmax, free_now, free_rollout);
     double* TOLW = L + tol_off;
-    if (kFew) { if (lane == 0) { TOLW[T_GAIN2] = g1; TOLW[T_GAIN1] = gain; } }
-    else { gain2 = gain1; gain1 = gain; }
+    if (kFew) { if (lane == 0) { TOLW[T_GAIN2] = run.gain2; TOLW[T_GAIN1] = run.gain1; } }
     f = fb;
-    // the last-step rule rests on the Newton model having held: an iteration announced as the last but WON by a proximal
-    // step or a short Newton step (a bound about to become active, the kink) is not the last
-    if (nblocked != 0) final_step = false;
     if (kNewton) u_term = lane_value(cterm, best);
     // (a hop that won says nothing about step lengths: damping and proximal step stay as they are)
     if (kRiccati && !(it == 0 && cold) && !hop_won) {   // (an iteration that had a Newton direction)
       // (step lengths of the Newton lanes as lane masks, feasible_set.h: scalar bit tests)
-      constexpr unsigned long long kNearlyFull = newton_lanes_at_least(0.8), kShort = kNewtonLanes & ~newton_lanes_at_least(0.3);
+      constexpr unsigned long long kNearlyFull = newton_lanes_at_least(NEO_RULE_DAMP_RELAX_STEP),
+                                   kShort = kNewtonLanes & ~newton_lanes_at_least(NEO_RULE_DAMP_TIGHTEN_STEP);
       const double mu0 = n > 8 ? (double)(n - 8) * 0.125 : 0.0, mu = TOL[T_MU];
       double* mu_slot = L + tol_off + T_MU;
-      if ((kNearlyFull >> best) & 1ull) { if (lane == 0) *mu_slot = fmax(0.25 * mu, mu0 * 0.0625); }
-      else if (best < 32 || ((kShort >> best) & 1ull)) { if (lane == 0) *mu_slot = fmin(4.0 * mu, 16.0 * mu0); }
+      if ((kNearlyFull >> best) & 1ull) { if (lane == 0) *mu_slot = fmax(NEO_RULE_DAMP_RELAX * mu, mu0 * (1.0 / NEO_RULE_DAMP_RANGE)); }
+      else if (best < 32 || ((kShort >> best) & 1ull)) { if (lane == 0) *mu_slot = fmin(NEO_RULE_DAMP_TIGHTEN * mu, NEO_RULE_DAMP_RANGE * mu0); }
     }
     if (best < 32 && !hop_won) {
       const double al = clampd(lane_value(step, best), 1e-6, 1e6);
@@ -721,7 +671,7 @@ __device__ __forceinline__ bool solve_search(double* L, uint32_t b, SolveCarry& 
     WAVE_SYNC();
     NEO_PHASE(6);
     NEO_PHASE_DUMP();
-    if ((double)stepmax < TOL[T_XTOL] || stall >= kStallIterations || creeping || final_step || blocked_stop) { status = NEO_MPC_STATUS_CONVERGED; ++it; break; }
+    if (ends) { status = NEO_MPC_STATUS_CONVERGED; ++it; break; }
   }
 
   // ---- phase 2, second-order directions: a search that has ENDED looks once at the costmap cells around every stage
@@ -762,8 +712,8 @@ __device__ __forceinline__ bool solve_search(double* L, uint32_t b, SolveCarry& 
   }
   if (scan_only) continue;
   if (!resume) break;
-  status = NEO_MPC_STATUS_MAX_ITER; stall = 0; final_step = false; blocked_run = 0; nblocked = 1;
-  gain1 = INFINITY; gain2 = INFINITY;
+  status = NEO_MPC_STATUS_MAX_ITER;
+  neo_search_run_init(&run);
   }
   NEO_SEGMENT(1);
   NEO_SEGMENT_DUMP();

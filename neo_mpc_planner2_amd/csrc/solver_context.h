@@ -6,6 +6,7 @@
 #include <stdint.h>
 
 #include "neo_mpc_device.h"
+#include "solver_rules.h"
 
 namespace neo_mpc {
 namespace {
@@ -27,12 +28,13 @@ enum : int {
 };
 
 // The tolerance block of LDS (LdsLayout::tol, doubles): stop tolerances and cold per-instance constants, read once per
-// iteration through an opaque offset so that they do not sit in scalar registers; from T_HOP_STAGE on: the hop
-// candidates of the current iteration (costmap.h edge_hop) -- four stage indices + their count as int32, then four
-// (dvx, dvy) pairs as float32.
-enum : int { T_XTOL, T_EARLY, T_FINAL, T_FTOL, T_STALL, T_WTOL, T_KINK, T_KONST, T_TRUE_YAW, T_MU, T_WTOL_LATE,
-             T_HOP_DROP, T_HOP_RANGE, T_HOP_STAGE = 13 /* int32[6]: stage[4], count, - */, T_HOP_VEC = 16 /* float[8] */,
-             T_BTOL_MAP = 20, T_BTOL_FREE = 21,
+// iteration through an opaque offset so that they do not sit in scalar registers.  Its head is the block of stop tolerances
+// the rule book's decisions read (solver_rules.h NEO_TOL_*); from T_HOP_STAGE on: the hop candidates of the current
+// iteration (costmap.h edge_hop) -- four stage indices + their count as int32, then four (dvx, dvy) pairs as float32.
+enum : int { T_XTOL = NEO_TOL_XTOL, T_EARLY = NEO_TOL_EARLY, T_FINAL = NEO_TOL_FINAL, T_FTOL = NEO_TOL_FTOL, T_STALL = NEO_TOL_STALL,
+             T_WTOL = NEO_TOL_WTOL, T_WTOL_LATE = NEO_TOL_WTOL_LATE, T_BTOL_MAP = NEO_TOL_BTOL_MAP, T_BTOL_FREE = NEO_TOL_BTOL_FREE,
+             T_KINK = NEO_TOL_COUNT, T_KONST, T_TRUE_YAW, T_MU,
+             T_HOP_STAGE = 13 /* int32[6]: stage[4], count, - */, T_HOP_VEC = 16 /* float[8] */, T_HOP_DROP = 20, T_HOP_RANGE = 21,
              // what the out-of-line cell scan (cell_scan.h) reads instead of taking arguments: the rest of Ctx ...
              T_C0 = 22, T_S0 = 23, T_TYAW = 24, T_FYAW = 25, T_TILE = 26 /* int32[3]: tile_x0, tile_y0, tile_geom */,
              // the routed kernel's stage-wise branch parks what its search carries from one iteration to the next here (gains of
@@ -41,6 +43,7 @@ enum : int { T_XTOL, T_EARLY, T_FINAL, T_FTOL, T_STALL, T_WTOL, T_KINK, T_KONST,
              T_GAIN1 = 28, T_GAIN2 = 29, T_ALPHA = 30,
              T_FSCAN = 31 /* the objective in front of a round of cell scans (the round decides whether the search is taken up again) */,
              kTolDoubles = 32, kHopLanes = 4 /* = NEO_RULE_HOP_LANES (solver_rules.h) */ };
+static_assert(T_MU < T_HOP_STAGE, "the stop tolerances and the cold constants end in front of the hop table");
 
 constexpr int kTileFree = 0x80;   // Ctx::tile_geom: every cell of the reach tile is free (raw cost 0)
 constexpr int kTileWall = 0x40;   // ... a lethal cell (raw 254) -- or the outside of the map -- among them: a wall in reach (solver_rules.h)

@@ -1,14 +1,17 @@
-/* solver_rules.h -- every constant and derived tolerance of the search, ONCE.
+/* solver_rules.h -- the rule book of the search: every constant and derived tolerance, ONCE, and the
+ * decisions that use them, ONCE -- does the Newton step test end the search or announce the last step, does the iteration
+ * that has taken its winner end it (the end of this file).
  *
- * Plain C: included by the host side of the library (neo_mpc_capi.cpp: derive()), by the device code
- * (k1_solve.h, costmap.h) and by the CPU mirror of the search that the test infrastructure keeps (mpc_oracle.c, part 2 --
- * the mirror follows the build's algorithm by construction and takes its rule book from here; the restatement of the
- * REFERENCE in the same file shares nothing with the product).  A threshold changed here changes on the GPU and in
- * the mirror at once. */
+ * Plain C: included by the host side of the library (neo_mpc_capi.cpp: derive()), by the device code (k1_solve.h, costmap.h;
+ * the decisions are __host__ __device__ there) and by the CPU mirror of the search that the test infrastructure keeps
+ * (mpc_oracle.c, part 2 -- the mirror follows the build's algorithm by construction and takes its rule book from here; the
+ * restatement of the REFERENCE in the same file shares nothing with the product).  A threshold or a rule changed here changes
+ * on the GPU and in the mirror at once. */
 #ifndef NEO_MPC_SOLVER_RULES_H_
 #define NEO_MPC_SOLVER_RULES_H_
 
 #include <math.h>
+#include <stdbool.h>
 
 #include "../../include/neo_mpc.h"
 
@@ -161,6 +164,129 @@ static inline void neo_rules_derive_routed(const neo_mpc_params* p, neo_rules* r
   neo_rules_derive_as(p, NEO_DIRECTION_STAGEWISE, r);
   r->btol_map = dense.btol_map;
   r->btol_free = dense.btol_free;
+}
+
+/* ---------------------------------------------------------------- the decisions of the search, in plain C: compiled into
+ * the device code (k1_solve.h solve_search, every K1 variant) and into the CPU mirror (mpc_oracle.c orc_pg_solve) from this
+ * one text.  How each side measures what goes in -- the maximum of |d|, the step taken, the costmap terms under a rollout --
+ * is its own business; what follows from the measurements is decided here. */
+#if defined(__HIPCC__)
+#define NEO_RULES_FN __host__ __device__ static inline
+#else
+#define NEO_RULES_FN static inline
+#endif
+
+/* ---- damping of the stage-wise direction beyond 8 control steps (Levenberg-Marquardt mu, start value mu0) */
+#define NEO_RULE_DAMP_RELAX_STEP 0.8    /* an iteration won by a Newton step of at least this length relaxes the damping ... */
+#define NEO_RULE_DAMP_RELAX 0.25        /* ... by this factor */
+#define NEO_RULE_DAMP_TIGHTEN_STEP 0.3  /* one won by a proximal lane or by a Newton step shorter than this tightens it ... */
+#define NEO_RULE_DAMP_TIGHTEN 4.0       /* ... by this factor */
+#define NEO_RULE_DAMP_RANGE 16.0        /* mu stays within [mu0 / this, mu0 x this] */
+
+/* The stop tolerances as a search reads them: a block of doubles -- the head of K1's tolerance block in LDS (solver_context.h;
+ * read where a rule needs one: as arguments they were all loaded up front and cost the kernels registers), an array in the mirror. */
+enum { NEO_TOL_XTOL, NEO_TOL_EARLY, NEO_TOL_FINAL, NEO_TOL_FTOL, NEO_TOL_STALL, NEO_TOL_WTOL, NEO_TOL_WTOL_LATE,
+       NEO_TOL_BTOL_MAP, NEO_TOL_BTOL_FREE, NEO_TOL_COUNT };
+static inline void neo_rules_stop_tolerances(const neo_rules* r, double* tol) {
+  tol[NEO_TOL_XTOL] = r->xtol; tol[NEO_TOL_EARLY] = r->xtol; tol[NEO_TOL_FINAL] = r->final_tol; tol[NEO_TOL_FTOL] = r->ftol;
+  tol[NEO_TOL_STALL] = r->stall_step; tol[NEO_TOL_WTOL] = r->wtol; tol[NEO_TOL_WTOL_LATE] = r->wtol_late;
+  tol[NEO_TOL_BTOL_MAP] = r->btol_map; tol[NEO_TOL_BTOL_FREE] = r->btol_free;
+}
+
+/* What a search carries from one iteration to the next about how it is doing. */
+typedef struct neo_search_run {
+  int stall;            /* consecutive iterations gaining < ftol (relative) or moving < stall_step */
+  int blocked_run;      /* consecutive iterations not won by a Newton step of at least NEO_RULE_BLOCKED_STEP */
+  int nblocked;         /* consecutive iterations not won by a Newton step of at least NEO_RULE_WINDOW_STEP (or won by a hop) */
+  double gain1, gain2;  /* objective decrease of the previous two iterations */
+  bool final_step;      /* the step test has announced this iteration as the last */
+} neo_search_run;
+/* at the start of a search, and again behind a cell scan that paid (the search is taken up from a new point) */
+NEO_RULES_FN void neo_search_run_init(neo_search_run* s) {
+  s->stall = 0; s->blocked_run = 0; s->nblocked = 1; s->final_step = false;
+  s->gain1 = INFINITY; s->gain2 = INFINITY;
+}
+
+/* The Newton step test in front of the candidate pass (second-order directions, not in the first iteration).  dm: the
+ * largest entry of the full step d; near_any: a block hovers next to the control norm's kink -- the prox step moves it, which d
+ * does not describe; nhops: hop candidates of this iteration; gauss_newton: d carries no second-order terms of the rollout. */
+enum { NEO_STEP_GOES_ON = 0, NEO_STEP_IS_LAST = 1, NEO_STEP_CONVERGED = 2 };
+NEO_RULES_FN int neo_rules_step_test(double dm, int near_any, int nhops, double early_tol, double final_tol, int gauss_newton) {
+  /* the full Newton step is already below the step tolerance: u is the answer
+   * (with a cheaper cell a hop away the search runs once more: its hop lanes decide) */
+  if (dm < early_tol && !near_any && nhops == 0) return NEO_STEP_CONVERGED;
+  /* a full Newton step below opt_tolerance (SLSQP's own step test) is the last one: searched and taken like any other, but
+   * nothing re-checks the point it lands on (the error left is of the order of the step squared)
+   * (a Gauss-Newton step converges linearly: it has to be shorter to be the last) */
+  if (dm < (gauss_newton ? NEO_RULE_FINAL_FRAC_GN : 1.0) * final_tol && !near_any) return NEO_STEP_IS_LAST;
+  return NEO_STEP_GOES_ON;
+}
+
+/* Does the iteration that has just taken its winner end the search?  Updates *s.
+ * The kind of search -- stagewise: the stage-wise direction; routed: ... with the control_steps-3 stop rules of the dense
+ * direction (neo_rules_derive_routed); blocked_rule: the blocked-run rule is on (dense direction, routed searches).
+ * tol: the stop tolerances (NEO_TOL_*).  The iteration -- newton_won: a lane of the second-order direction (32-63) won, with the
+ * step length won_step; hop_won: a hop candidate or the un-shifted start won; gain: f - fb; fb: the objective of the new iterate
+ * WITHOUT its constant terms; stepmax: the largest change of a control; free_now: the closing-in rule's free space (dense
+ * direction: no costmap term under the NEW iterate's rollout; stage-wise: under the rollout the iteration started from);
+ * free_rollout: no costmap term under the new iterate's rollout (read by the blocked-run rule only). */
+NEO_RULES_FN int neo_rules_iteration_ends(int stagewise, int routed, int blocked_rule, const double* tol, neo_search_run* s, int it,
+                                          int newton_won, double won_step, int hop_won, double gain, double fb, double stepmax,
+                                          int free_now, int free_rollout) {
+  /* (gain thresholds are relative to the u-dependent part of the objective: the constant terms -- the terminal distance term,
+   * py:266 -- can be 20 x the rest) */
+  const double fscale = fmax(1.0, fabs(fb));
+  /* iterations that gain next to nothing or barely move (creeping along a costmap cell edge, the slow tail next to the
+   * control norm's kink) end the search once NEO_RULE_STALL_ITERATIONS of them are in a row */
+  s->stall = (gain <= tol[NEO_TOL_FTOL] * fscale || stepmax <= tol[NEO_TOL_STALL]) ? s->stall + 1 : 0;
+  /* stage-wise direction: the window and closing-in rules only judge runs of BLOCKED iterations (none of the three won
+   * by a Newton step of at least half its length); iterations won by the Newton step end through the step test
+   * (the un-shifted start that won the first iteration says as little about step lengths as a hop) */
+  s->nblocked = (!newton_won || won_step < NEO_RULE_WINDOW_STEP || hop_won) ? s->nblocked + 1 : 0;
+  const int window_on = !stagewise || routed || s->nblocked >= 3;
+  /* three iterations that together gained less than wtol: creeping along a costmap cell edge
+   * (from NEO_RULE_LATE_ITERATION on the window is the control_steps-3 one again: a long-horizon search that has run twice
+   * its usual length is creeping, gaining 1e-8 of f per iteration up to the iteration cap -- a handful per 65 536 solves, but
+   * a launch lasts as long as its slowest wave) */
+  const double wtol0 = tol[NEO_TOL_WTOL];   /* (the closing-in rule below is on whenever the window rule is) */
+  const double wtol = it >= NEO_RULE_LATE_ITERATION ? tol[NEO_TOL_WTOL_LATE] : wtol0;
+  const double g1 = s->gain1, g2 = s->gain2;
+  int creeping = wtol > 0.0 && gain + g1 + g2 <= wtol * fscale && window_on;
+  /* ... and so does a step below stall_step whose gain halved twice in a row: the search is closing in on a costmap cell
+   * edge (or the kink) geometrically; what is left to gain is less than the last gain.  -3 % iterations at control_steps 3 and
+   * 32, no command moves by 1e-3.  In free space three gains it takes (round 5: the INFINITY the two older ones start at used
+   * to pass for a gain, and a warm search that began next to the kink ended after its second iteration, 2.4e-3 from the
+   * reference's converged first control on one G13 tick), and the geometric series the gains start has to be worth less than
+   * the stall threshold, gain r / (1 - r) <= ftol f~ with r = gain / gain1: the rule ended warm searches whose gains fell by
+   * a sixth per iteration with 3e-6 left to gain, which is 2.5e-3 in the first control along a direction of curvature 1.
+   * (dense and L-BFGS directions, routed searches: only behind NEO_RULE_CLOSING_RUN blocked iterations -- the gains of a Newton
+   * search that converges quadratically halve twice in a row as well, and one blocked iteration after them, a bound about to
+   * become active, is no sign of creeping: random parameter sets, 1 solve in 3000 stopped 5e-3 short)
+   * (free_now: where the first control is gated, not only the objective) */
+  creeping = creeping || (wtol0 > 0.0 && stepmax <= tol[NEO_TOL_STALL] && gain <= 0.5 * g1 && g1 <= 0.5 * g2 &&
+                          (!free_now || (g2 < INFINITY && gain * gain <= tol[NEO_TOL_FTOL] * fscale * (g1 - gain))) &&
+                          ((stagewise && !routed) ? window_on : s->nblocked >= NEO_RULE_CLOSING_RUN));
+  /* Blocked-run rule.  NEO_RULE_BLOCKED_RUN iterations in a row not won by a decent Newton step that together gain less
+   * than 0.1 x opt_tolerance (0.03 x with no costmap term under the new iterate's rollout): something the quadratic model
+   * does not see is in the way -- a costmap cell edge, or blocks hovering next to the control norm's kink -- and the search
+   * advances 1e-6 of f per iteration (SLSQP stops on ONE iteration gaining less than opt_tolerance).  In a closed 30 Hz loop of
+   * 4096 robots such searches set the duration of every launch: per-tick maximum 25 -> 13 iterations in the median, 100 -> 16
+   * at worst; cold solves and the zero-map drift check are untouched (4096 cold C2 solves: no objective more than 9e-6 higher;
+   * 8192 zero-map problems against solves run to the end: unchanged, max 5.8e-4).  Absolute, not scaled by |f|: f is
+   * dominated by the lethal term while a search is on its way out of a lethal cell.  A stage-wise search that is not routed does
+   * not take it: its wall model and hop candidates deal with cell edges, and its long shots need their blocked iterations to
+   * get out of lethal cells. */
+  int blocked_stop = 0;
+  if (blocked_rule) {
+    s->blocked_run = (!newton_won || won_step < NEO_RULE_BLOCKED_STEP) ? s->blocked_run + 1 : 0;
+    if (s->blocked_run >= NEO_RULE_BLOCKED_RUN)   /* (a tolerance of 0: the rule is off -- a gain is never <= 0 here) */
+      blocked_stop = gain + g1 + g2 <= (free_rollout ? tol[NEO_TOL_BTOL_FREE] : tol[NEO_TOL_BTOL_MAP]);
+  }
+  s->gain2 = g1; s->gain1 = gain;
+  /* the last-step rule rests on the Newton model having held: an iteration announced as the last but WON by a proximal
+   * step, a hop or a short Newton step (a bound about to become active, the kink) is not the last */
+  if (s->nblocked != 0) s->final_step = false;
+  return stepmax < tol[NEO_TOL_XTOL] || s->stall >= NEO_RULE_STALL_ITERATIONS || creeping || s->final_step || blocked_stop;
 }
 
 #endif /* NEO_MPC_SOLVER_RULES_H_ */

@@ -150,3 +150,38 @@ def select_carrots(plan_poses, plan_offsets, robot_poses, slow_down, footprint_c
         b.problems = problems.ctypes.data
     lib.orc_select_carrots(C.byref(lp), C.byref(b))
     return carrots
+
+
+# ---- the rule book's decisions on their own (solver_rules.h; tests/test_c_oracle.py)
+#: the block of stop tolerances, in the order of solver_rules.h NEO_TOL_*
+STOP_TOLERANCES = ("xtol", "early", "final", "ftol", "stall", "wtol", "wtol_late", "btol_map", "btol_free")
+STEP_GOES_ON, STEP_IS_LAST, STEP_CONVERGED = 0, 1, 2   # NEO_STEP_*
+
+
+class SearchRun(C.Structure):
+    """neo_search_run: what a search carries from one iteration to the next."""
+    _fields_ = [("stall", C.c_int), ("blocked_run", C.c_int), ("nblocked", C.c_int),
+                ("gain1", C.c_double), ("gain2", C.c_double), ("final_step", C.c_bool)]
+
+
+def search_run():
+    lib = load()
+    assert lib.orc_rules_tol_count() == len(STOP_TOLERANCES)
+    s = SearchRun()
+    lib.orc_search_run_init(C.byref(s))
+    return s
+
+
+def step_test(dm, near_any, nhops, early_tol, final_tol, gauss_newton):
+    return load().orc_rules_step_test(C.c_double(dm), int(near_any), int(nhops), C.c_double(early_tol), C.c_double(final_tol),
+                                      int(gauss_newton))
+
+
+def iteration_ends(run, tol, it=1, stagewise=False, routed=False, blocked_rule=False, newton_won=True, won_step=1.0,
+                   hop_won=False, gain=1.0, fb=0.0, stepmax=1.0, free_now=False, free_rollout=False):
+    """neo_rules_iteration_ends on `run` (updated in place); `tol`: dict of STOP_TOLERANCES (missing: 0)."""
+    t = (C.c_double * len(STOP_TOLERANCES))(*[tol.get(k, 0.0) for k in STOP_TOLERANCES])
+    assert not set(tol) - set(STOP_TOLERANCES)
+    return bool(load().orc_rules_iteration_ends(
+        int(stagewise), int(routed), int(blocked_rule), t, C.byref(run), int(it), int(newton_won), C.c_double(won_step),
+        int(hop_won), C.c_double(gain), C.c_double(fb), C.c_double(stepmax), int(free_now), int(free_rollout)))

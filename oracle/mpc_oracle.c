@@ -31,7 +31,6 @@
 #include "../neo_mpc_planner2_amd/csrc/solver_rules.h"
 
 #define ORC_LANES 64
-#define ORC_STALL_ITERATIONS NEO_RULE_STALL_ITERATIONS
 #define ORC_MAXN NEO_MPC_MAX_CONTROL_STEPS
 #define ORC_MAXV (3 * ORC_MAXN)
 
@@ -1152,8 +1151,6 @@ static int orc_capture_it = -1;
 static double* orc_capture_d = NULL;
 void orc_capture_direction(int it, double* d_out) { orc_capture_it = it; orc_capture_d = d_out; }
 #define ORC_TRIAL_RATIO NEO_RULE_TRIAL_RATIO
-#define ORC_BLOCKED_STEP NEO_RULE_BLOCKED_STEP
-#define ORC_LATE_ITERATION NEO_RULE_LATE_ITERATION
 static int orc_trial = 1;
 void orc_set_trial(int on) { orc_trial = on; }
 #define ORC_ALT_LANE 5   /* = kAltLane (solver_context.h) */
@@ -1166,19 +1163,7 @@ static double orc_term_sum(const orc_ctx* c, const double* u) {
   for (int i = 0; i < c->n; ++i) ts += orc_step_term(c, r.x[i], r.y[i]);
   return ts;
 }
-/* Blocked-run stop rule (dense Newton direction).  ORC_BLOCKED_RUN consecutive iterations NOT won by a decent Newton
- * step -- a proximal lane, or a Newton step cut below ORC_BLOCKED_STEP -- that together gain less than
- * ORC_BLOCKED_TOL_MAP * opt_tolerance (ORC_BLOCKED_TOL_FREE * opt_tolerance when no stage of the rollout has a costmap
- * term under it) end the search: something the quadratic model does not see is in the way -- a costmap cell edge, or
- * blocks hovering next to the control norm's kink -- and the search advances 1e-6 of f per iteration.  (SLSQP stops
- * on ONE iteration gaining less than opt_tolerance.)  Absolute, not scaled by |f|: f is dominated by the lethal term
- * while a search is on its way out of a lethal cell.  Closed 30 Hz loop of 4096 robots (warm ticks, where such
- * searches set a launch's duration): per-tick maximum 25 -> 13 iterations in the median, 100 -> 16 at worst; 4096 cold
- * C2 solves: no objective more than 9e-6 higher; 8192 zero-map problems against solves run to the end: unchanged (max
- * 5.8e-4).  Part of the window rule: off with it.  The stage-wise direction does not take it (its wall model and hop
- * candidates deal with cell edges, and its long shots need their blocked iterations to get out of lethal cells).
- * Beyond 3 control steps (run-time-sized dense kernel) the thresholds shrink with (3/N)^2 like the stall threshold. */
-#define ORC_BLOCKED_RUN NEO_RULE_BLOCKED_RUN
+/* A/B hook: 0 = the blocked-run rule (solver_rules.h neo_rules_iteration_ends) is off */
 static int orc_blocked_rule = 1;
 void orc_set_blocked_rule(int on) { orc_blocked_rule = on; }
 
@@ -1231,11 +1216,9 @@ int orc_pg_solve(const neo_mpc_params* p, const orc_map* m, const neo_mpc_proble
   const int max_it = rules.max_iterations;
   int mem = rules.lbfgs_memory;
   if (mem > NEO_MPC_MAX_LBFGS_MEMORY) mem = NEO_MPC_MAX_LBFGS_MEMORY;
-  const double xtol = rules.xtol, stall_step = rules.stall_step;
   /* search direction of lanes 32-63: stage-wise (Riccati) Newton, dense Newton (control_steps <= 8) or L-BFGS */
   const int riccati = rules.direction == NEO_DIRECTION_STAGEWISE;
   const int newton = riccati || (rules.direction == NEO_DIRECTION_DENSE && 3 * p->control_steps <= ORC_NEWTON_MAXV);
-  const double ftol = rules.ftol;
 
   double u[ORC_MAXV], gs[ORC_MAXV], gt[ORC_MAXV], gr[ORC_MAXV], d[ORC_MAXV];
   double u_prev[ORC_MAXV], gt_prev[ORC_MAXV], cand[ORC_MAXV], best_c[ORC_MAXV];
@@ -1293,17 +1276,17 @@ int orc_pg_solve(const neo_mpc_params* p, const orc_map* m, const neo_mpc_proble
    * Measured on 8192 cold starts: 12.6 -> 9.0 iterations at control_steps 32, 20.2 -> 10.3 at 64, 9.1 -> 8.1 at
    * 16; no gain at 8 and below (no damping there). */
   double alpha = riccati ? fmax(1.0, n / 8.0) : 1.0;
-  const double mu0 = (riccati && n > 8) ? (n - 8) / 8.0 : 0.0, mu_lo = mu0 / 16.0, mu_hi = 16.0 * mu0;
+  const double mu0 = (riccati && n > 8) ? (n - 8) / 8.0 : 0.0, mu_lo = mu0 / NEO_RULE_DAMP_RANGE, mu_hi = NEO_RULE_DAMP_RANGE * mu0;
   double mu = mu0;
-  int nfev = 1, it = 0, status = NEO_MPC_STATUS_MAX_ITER, stall = 0;
-  /* three iterations in a row that together gain less than wtol end the search (Newton only by default) */
-  const double wtol = rules.wtol, wtol_late = rules.wtol_late;
-  double gain1 = INFINITY, gain2 = INFINITY;
-  const double final_tol = rules.final_tol;
-  int final = 0;
-  int blocked_run = 0;   /* consecutive iterations not won by a decent Newton step */
+  int nfev = 1, it = 0, status = NEO_MPC_STATUS_MAX_ITER;
+  /* what ends a search: the rule book's decisions (solver_rules.h neo_rules_step_test, neo_rules_iteration_ends), the text
+   * the kernels compile, on the stop tolerances and on what the search carries from one iteration to the next */
+  double tol[NEO_TOL_COUNT];
+  neo_rules_stop_tolerances(&rules, tol);
+  neo_search_run run;
+  neo_search_run_init(&run);
+  const int blocked_rule = newton && (!riccati || routed) && orc_blocked_rule;   /* (dense direction, routed searches; the A/B hook) */
   int exact_step = 0;    /* this iteration's stage-wise direction carries the second-order terms */
-  int nblocked = 1;      /* consecutive iterations not won by a Newton step of at least half its length */
   int scanned = 0;   /* the cell scan has had its turn */
   it = 0;
 resume_search:
@@ -1324,7 +1307,7 @@ resume_search:
         /* second-order terms only behind an iteration won by a decent Newton step (the model held there): far from the
          * minimiser -- a search blocked by a wall, the first steps of a cold start -- the exact Hessian is indefinite
          * and the Gauss-Newton direction is the safer one */
-        exact_step = nblocked == 0;
+        exact_step = run.nblocked == 0;
         orc_riccati_direction_disp_tau(&c, u, gs, gt, &act, exact_step ? 1.0 : 0.0, mu, 1, d);
       }
       else orc_newton_direction(&c, u, gs, gr, &act, 0, d);
@@ -1367,21 +1350,16 @@ resume_search:
           orc_apply_active(&c, &act, d);
         }
       }
-      if (it > 0) { /* the full Newton step is already below the step tolerance: u is the answer
-                     * (the prox-moved blocks next to the kink are not covered by d) */
+      if (it > 0) {   /* the Newton step test */
         double dm = 0.0;
         int anynear = 0;
         for (int k = 0; k < nv; ++k) dm = fmax(dm, fabs(d[k]));
         /* (blocks next to the kink are moved by the prox step, which d does not describe -- unless they are at
          * rest on it) */
         for (int i = 0; i < n; ++i) anynear |= act.near[i] && !act.rest[i];
-        /* (with a cheaper cell a hop away the search runs once more: its hop lanes decide) */
-        if (dm < xtol && !anynear && nhops == 0) { status = NEO_MPC_STATUS_CONVERGED; goto exit_check; }
-        /* a full Newton step below opt_tolerance (SLSQP's own step test) is the last one: it is
-         * searched and taken like any other, but nothing re-checks the point it lands on (the
-         * error left is of the order of the step squared) */
-        /* (a Gauss-Newton step converges linearly: it has to be shorter to be the last) */
-        if (dm < (riccati && !exact_step ? NEO_RULE_FINAL_FRAC_GN : 1.0) * final_tol && !anynear) final = 1;
+        const int verdict = neo_rules_step_test(dm, anynear, nhops, tol[NEO_TOL_EARLY], tol[NEO_TOL_FINAL], riccati && !exact_step);
+        if (verdict == NEO_STEP_CONVERGED) { status = NEO_MPC_STATUS_CONVERGED; goto exit_check; }
+        if (verdict == NEO_STEP_IS_LAST) run.final_step = true;
       }
     }
     if (!newton && it > 0) {
@@ -1466,54 +1444,24 @@ resume_search:
       u_prev[k] = u[k]; gt_prev[k] = gt[k]; u[k] = best_c[k];
     }
     memcpy(near_prev, act.near, sizeof(near_prev));
-    const double decrease = f - fb;
+    const double decrease = f - fb, won_scale = orc_lane_scale(best, act.longshots);
     f = fb;
-    blocked_run = (best < 32 || orc_lane_scale(best, act.longshots) < ORC_BLOCKED_STEP) ? blocked_run + 1 : 0;
     /* (a hop that won says nothing about step lengths: damping and proximal step stay as they are) */
     const int hop_won = (best >= 1 && best <= nhops) || (it == 0 && best == ORC_ALT_LANE && alt_lane);
     if (!(it == 0 && cold) && !hop_won) {   /* (an iteration that had a Newton direction) */
-      if (best >= 32 && orc_lane_scale(best, act.longshots) >= 0.8) mu = fmax(0.25 * mu, mu_lo);
-      else if (best < 32 || orc_lane_scale(best, act.longshots) < 0.3) mu = fmin(4.0 * mu, mu_hi);
+      if (best >= 32 && won_scale >= NEO_RULE_DAMP_RELAX_STEP) mu = fmax(NEO_RULE_DAMP_RELAX * mu, mu_lo);
+      else if (best < 32 || won_scale < NEO_RULE_DAMP_TIGHTEN_STEP) mu = fmin(NEO_RULE_DAMP_TIGHTEN * mu, mu_hi);
     }
     if (best < 32 && !hop_won) {
-      alpha *= orc_lane_scale(best, act.longshots);
+      alpha *= won_scale;
       alpha = orc_clamp(alpha, 1e-6, 1e6);
     }
-    /* iterations that gain next to nothing or barely move (creeping along a costmap cell edge, the
-     * slow tail next to the control-norm kink) end the search once ORC_STALL_ITERATIONS of them
-     * are in a row */
-    /* (gain thresholds are relative to the u-dependent part of the objective: f without the constant terms) */
-    const double fsc = fmax(1.0, fabs(fb - c.konst));
-    stall = (decrease <= ftol * fsc || step <= stall_step) ? stall + 1 : 0;
-    /* (from ORC_LATE_ITERATION on the window is the control_steps-3 one again: a long-horizon search that has run
-     * twice its usual length is creeping, gaining 1e-8 of f per iteration up to the iteration cap -- a handful per
-     * 65 536 solves, but a launch lasts as long as its slowest wave) */
-    const double wnow = it >= ORC_LATE_ITERATION ? wtol_late : wtol;
-    /* stage-wise direction: the window and closing-in rules only judge runs of BLOCKED iterations (none of the three won
-     * by a Newton step of at least half its length); iterations won by the Newton step end through the step test */
-    nblocked = (best < 32 || orc_lane_scale(best, act.longshots) < NEO_RULE_WINDOW_STEP || hop_won) ? nblocked + 1 : 0;
-    const int creeping = wnow > 0.0 && decrease + gain1 + gain2 <= wnow * fsc && (!riccati || routed || nblocked >= 3);
-    /* ... and so does a step below stall_step whose gain halved twice in a row: the search is closing in on a
-     * costmap cell edge (or the kink) geometrically, what is left to gain is less than the last gain (part of the
-     * window rule: off with it).  -3 % iterations at control_steps 3 and 32, no command moves by 1e-3.
-     * (round 5) In free space three real gains it takes (the INFINITY the two older ones start at used to pass for one), and the
-     * geometric series they start has to be worth less than the stall threshold -- gain r / (1 - r) <= ftol f~ with r =
-     * gain / gain1 --: the rule ended warm searches whose gains fell by a sixth per iteration with 3e-6 left to gain, which
-     * along a flat direction (curvature 1) is 2.5e-3 in the first control. */
-    /* (in free space -- where the first control is gated, not only the objective: dense direction: no costmap term under the
-     * NEW iterate's rollout; stage-wise: under the rollout the iteration started from) */
-    const int free_now = riccati ? free_before : (newton ? orc_term_sum(&c, u) == 0.0 : 0);
-    const int closing_in = wtol > 0.0 && step <= stall_step && decrease <= 0.5 * gain1 && gain1 <= 0.5 * gain2 &&
-                           (!free_now || (gain2 < INFINITY && decrease * decrease <= ftol * fsc * (gain1 - decrease))) &&
-                           ((riccati && !routed) ? nblocked >= 3 : nblocked >= NEO_RULE_CLOSING_RUN);
-    int blocked_stop = 0;
-    if (newton && (!riccati || routed) && orc_blocked_rule && wtol > 0.0 && blocked_run >= ORC_BLOCKED_RUN)
-      blocked_stop = decrease + gain1 + gain2 <= (orc_term_sum(&c, u) == 0.0 ? rules.btol_free : rules.btol_map);
-    gain2 = gain1; gain1 = decrease;
-    /* (round 4) the last-step rule rests on the Newton model having held: an iteration announced as the last but WON by a
-     * proximal step or a short Newton step (the model was off: a bound about to become active, the kink) is not the last */
-    if (final && !(best >= 32 && orc_lane_scale(best, act.longshots) >= NEO_RULE_WINDOW_STEP)) final = 0;
-    if (step < xtol || stall >= ORC_STALL_ITERATIONS || creeping || closing_in || final || blocked_stop) { status = NEO_MPC_STATUS_CONVERGED; ++it; goto exit_check; }
+    /* does this iteration end the search?  (the objective without its constant terms; the closing-in rule's free space -- dense
+     * direction: no costmap term under the NEW iterate's rollout; stage-wise: under the rollout the iteration started from) */
+    const int free_rollout = ((newton && !riccati) || blocked_rule) ? orc_term_sum(&c, u) == 0.0 : 0;
+    const int free_now = riccati ? free_before : free_rollout;
+    if (neo_rules_iteration_ends(riccati, routed, blocked_rule, tol, &run, it, best >= 32, won_scale, hop_won, decrease, fb - c.konst, step,
+                                 free_now, free_rollout)) { status = NEO_MPC_STATUS_CONVERGED; ++it; goto exit_check; }
     continue;
   exit_check:
     break;
@@ -1531,7 +1479,8 @@ resume_search:
     for (int k = 1; k < NEO_RULE_SCAN_REPEATS && won && orc_term_sum(&c, u) != 0.0; ++k)
       if (!orc_cell_scan(&c, neo_rules_reach_cells(p, m->resolution), u, &f, rules.hop_min_drop, &nfev)) break;
     if (won && f_before - f > rules.scan_resume_gain && it < max_it) {
-      status = NEO_MPC_STATUS_MAX_ITER; stall = 0; final = 0; blocked_run = 0; nblocked = 1; gain1 = INFINITY; gain2 = INFINITY;
+      status = NEO_MPC_STATUS_MAX_ITER;
+      neo_search_run_init(&run);
       goto resume_search;
     }
   }
@@ -1542,6 +1491,18 @@ resume_search:
   if (nit_out) *nit_out = it;
   if (nfev_out) *nfev_out = nfev;
   return status;
+}
+
+/* test hooks (tests/test_c_oracle.py): the rule book's decisions on their own, the text orc_pg_solve and the kernels compile */
+int orc_rules_tol_count(void) { return NEO_TOL_COUNT; }
+void orc_search_run_init(neo_search_run* s) { neo_search_run_init(s); }
+int orc_rules_step_test(double dm, int near_any, int nhops, double early_tol, double final_tol, int gauss_newton) {
+  return neo_rules_step_test(dm, near_any, nhops, early_tol, final_tol, gauss_newton);
+}
+int orc_rules_iteration_ends(int stagewise, int routed, int blocked_rule, const double* tol, neo_search_run* s, int it, int newton_won,
+                             double won_step, int hop_won, double gain, double fb, double stepmax, int free_now, int free_rollout) {
+  return neo_rules_iteration_ends(stagewise, routed, blocked_rule, tol, s, it, newton_won, won_step, hop_won, gain, fb, stepmax, free_now,
+                                  free_rollout);
 }
 
 /* NEO_MPC_FLAG_WALL_IN_REACH of a request (K1's set-up: a lethal cell in the reach tile) */

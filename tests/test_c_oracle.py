@@ -401,6 +401,89 @@ def test_hop_candidates_never_hurt_and_find_the_cheaper_cell():
     assert (on["cost"] <= off["cost"] + 1e-9).mean() >= 0.95
 
 
+def test_rule_book_decisions_on_their_own():
+    """The two decisions of solver_rules.h that every K1 variant and the mirror compile (neo_rules_step_test,
+    neo_rules_iteration_ends), driven directly: the equivalences between the kernels' and the mirror's earlier hand-written
+    copies, which calling one text rests on."""
+    WINDOW_STEP, LATE_ITERATION, INF = 0.5, 20, float("inf")   # NEO_RULE_WINDOW_STEP, NEO_RULE_LATE_ITERATION
+    ends, run = c_oracle.iteration_ends, c_oracle.search_run
+    s = run()
+    assert (s.stall, s.blocked_run, s.nblocked, s.final_step, s.gain1, s.gain2) == (0, 0, 1, False, INF, INF)
+    # a blocked-run tolerance of 0 never fires, whatever positive gain; with a tolerance the third blocked iteration ends it
+    for btol, fired_at in ((0.0, None), (1.0, 3)):
+        s, fired = run(), None
+        for k, gain in enumerate((1e-300, 1e-12, 1e-300, 1.0, 1e-300, 1e-300), 1):
+            if ends(s, dict(btol_map=btol, btol_free=btol), it=k, blocked_rule=True, newton_won=False, gain=gain) and fired is None:
+                fired = k
+        assert fired == fired_at and s.blocked_run == 6
+    s = run()
+    for k in range(1, 5):   # ... and without the rule nothing is counted
+        assert not ends(s, dict(btol_map=1.0, btol_free=1.0), it=k, newton_won=False, gain=1e-9) and s.blocked_run == 0
+    # an announced last step survives only an iteration won by a Newton lane of at least NEO_RULE_WINDOW_STEP, not a hop
+    for stagewise in (False, True):
+        for newton_won, won_step, hop_won, last in ((True, WINDOW_STEP, False, True), (True, 1.0, False, True),
+                                                    (True, WINDOW_STEP - 1e-9, False, False), (False, 1.0, False, False),
+                                                    (True, 1.0, True, False)):
+            s = run()
+            s.final_step = True
+            assert ends(s, {}, stagewise=stagewise, newton_won=newton_won, won_step=won_step, hop_won=hop_won) == last
+            assert s.final_step == last and (s.nblocked == 0) == last
+    # closing-in with both older gains at INFINITY: not in free space, but on the costmap (behind two blocked iterations)
+    tol = dict(wtol=1e-3, stall=1.0)
+    for free_now, fires in ((True, False), (False, True)):
+        s = run()
+        assert ends(s, tol, newton_won=False, gain=1e-6, stepmax=0.5, free_now=free_now) == fires
+        assert (s.nblocked, s.gain1, s.gain2) == (2, 1e-6, INF)
+    s = run()   # (in free space three real gains it takes, and a geometric series worth less than ftol; the window itself too tight to fire)
+    s.gain1, s.gain2 = 4e-6, 1.6e-5
+    assert not ends(s, dict(tol, wtol=1e-9, ftol=1e-7), newton_won=False, gain=1e-6, stepmax=0.5, free_now=True)
+    s = run()
+    s.gain1, s.gain2 = 4e-6, 1.6e-5
+    assert ends(s, dict(tol, wtol=1e-9, ftol=1e-6), newton_won=False, gain=1e-6, stepmax=0.5, free_now=True)
+    # from NEO_RULE_LATE_ITERATION on the window uses the late tolerance
+    for it, fires in ((LATE_ITERATION - 1, False), (LATE_ITERATION, True)):
+        s = run()
+        s.gain1 = s.gain2 = 0.1
+        assert ends(s, dict(wtol=1e-9, wtol_late=1.0), it=it, gain=0.1) == fires
+    # a stage-wise search that is not routed needs three blocked iterations for the window ...
+    for routed, fired_at in ((False, 2), (True, 1)):
+        s, fired = run(), None
+        s.gain1 = s.gain2 = 0.1
+        for k in (1, 2):
+            if ends(s, dict(wtol=1.0), it=k, stagewise=True, routed=routed, newton_won=False, gain=0.1) and fired is None:
+                fired = k
+        assert fired == fired_at
+    # ... and for closing-in; a routed search takes the dense rules (two)
+    for stagewise, routed, fired_at in ((True, False, 2), (True, True, 1), (False, False, 1)):
+        s, fired = run(), None
+        s.gain1, s.gain2 = 0.2, 0.4
+        for k, gain in ((1, 0.1), (2, 0.05)):
+            if ends(s, dict(wtol=1e-12, stall=1.0), it=k, stagewise=stagewise, routed=routed, newton_won=False, gain=gain,
+                    stepmax=0.5) and fired is None:
+                fired = k
+        assert fired == fired_at
+    s = run()   # (an iteration won by a decent Newton step in between: the run of blocked iterations starts again)
+    s.gain1 = s.gain2 = 0.1
+    assert not ends(s, dict(wtol=1.0), stagewise=True, newton_won=False, gain=0.1) and s.nblocked == 2
+    assert not ends(s, dict(wtol=1.0), stagewise=True, newton_won=True, won_step=1.0, gain=0.1) and s.nblocked == 0
+    # the stall count and the step tolerance
+    s = run()
+    for k in range(1, 6):
+        assert ends(s, dict(ftol=1e-3), it=k, gain=1e-4, fb=-5.0) == (k == 5)   # (relative to |fb|: 1e-4 <= 1e-3 * 5)
+    s = run()
+    assert not ends(s, dict(ftol=1e-3), gain=2e-3, fb=0.5) and s.stall == 0     # (... but to no less than 1)
+    assert ends(run(), dict(xtol=1e-6), stepmax=0.9e-6) and not ends(run(), dict(xtol=1e-6), stepmax=1e-6)
+    # the step test: off when a hop candidate exists or a block hovers next to the kink; a Gauss-Newton step has to be shorter
+    st = c_oracle.step_test
+    assert st(1e-9, False, 0, 1e-6, 1e-3, False) == c_oracle.STEP_CONVERGED
+    assert st(1e-9, False, 1, 1e-6, 1e-3, False) == c_oracle.STEP_IS_LAST
+    assert st(1e-9, True, 0, 1e-6, 1e-3, False) == c_oracle.STEP_GOES_ON
+    assert st(5e-4, False, 0, 1e-6, 1e-3, False) == c_oracle.STEP_IS_LAST
+    assert st(5e-4, False, 0, 1e-6, 1e-3, True) == c_oracle.STEP_GOES_ON
+    assert st(2e-4, False, 0, 1e-6, 1e-3, True) == c_oracle.STEP_IS_LAST
+    assert st(float("nan"), False, 0, 1e-6, 1e-3, False) == c_oracle.STEP_GOES_ON
+
+
 def test_blocked_run_rule_only_shortens_creeping_searches():
     """The blocked-run stop rule of the dense Newton direction (three iterations in a row not won by a decent Newton
     step, gaining < 0.1 x opt_tolerance together -- 0.03 x in free space): cold solves end at the same objective (1e-4)
