@@ -39,6 +39,8 @@ extern "C" {
  * neo_mpc_get_costmap_pool) added a record and five entry points in the same way: still ABI 2, behaviour 6.
  * The fleet stamp (neo_mpc_stamp_batch, neo_mpc_stamp_fleet[_device], neo_mpc_inflation_costs) added a record and three
  * entry points in the same way: still ABI 2, behaviour 6.
+ * The world inflation (neo_mpc_inflate_world_map[_device], neo_mpc_get_world_map) added three entry points and no record:
+ * still ABI 2, behaviour 6.
  *
  * Behaviour history (iterates and iteration counts differ between versions, results stay inside the parity protocol of
  * DESIGN.md section 1; neo_mpc_behaviour_version() returns the number of the build that answers):
@@ -350,7 +352,8 @@ typedef struct neo_mpc_footprint_batch {
  *   float64, before any conversion); inside, its value is world[trunc(qy)][trunc(qx)]
  *   an outside cell gets `outside_value` (nav2's default_value: 255 with track_unknown_space, else 0).
  * Out of scope: a tf transform between the world map's frame and the windows' (they are one frame); `use_maximum`; further
- * layers (the world map IS the master grid the caller wants sampled, inflation included).  The other robots of the fleet
+ * layers (the world map IS the master grid the caller wants sampled, inflation included: a caller that holds a raw occupancy
+ * grid gets nav2's inflation from neo_mpc_inflate_world_map below, between neo_mpc_set_world_map and the rolls).  The other robots of the fleet
  * are stamped into the windows by the step behind the roll: neo_mpc_stamp_batch below (K8).
  * Pointers are host pointers for neo_mpc_roll_costmap_pool and device pointers for neo_mpc_roll_costmap_pool_device.
  * 56 bytes. */
@@ -601,6 +604,58 @@ int neo_mpc_set_world_map(neo_mpc_handle* handle, const uint8_t* cells, uint32_t
  * copy has an event of its own and a roll on another stream waits for it. */
 int neo_mpc_set_world_map_device(neo_mpc_handle* handle, const uint8_t* d_cells, uint32_t size_x, uint32_t size_y,
                                  double resolution, double origin_x, double origin_y, void* stream);
+
+/* nav2's inflation layer on the world map (K9): set -> inflate -> roll.  A fleet server usually holds an occupancy grid of
+ * 0 / 254 / 255; the solver's costmap term, the gate's `footprint_cost > 200` (cpp:225-228) and `w_costmap` want the slopes
+ * nav2's InflationLayer puts around the walls.  These calls rewrite the handle's OWN copy of the world map in place -- the
+ * caller's buffer was released by neo_mpc_set_world_map[_device] and is not involved -- and every later roll cuts its windows
+ * from the inflated map; when the world changes: set the raw map again, inflate again.  An inflation is not undone.
+ *
+ * Like neo_mpc_stamp_batch's, the contract is one by transcription (tests/world_inflation_reference.py is its executable
+ * form): the cost rule and the combination rule are the stamp's, word for word, which are nav2's with inflate_unknown
+ * false.  nav2's own InflationLayer is a queue-ordered wavefront; its result is this one up to the order in which it reaches
+ * the cells within a distance bin.  Neither is pinned against nav2 itself: nav2's layers are not available to the tests.
+ * Apart from the table T, which neo_mpc_inflation_costs builds on the host, the contract is integers only.
+ *
+ * Reach and table: the world map is WSX x WSY cells at resolution wres; R = ceil(inflation_radius / wres); T[0 .. R^2] is
+ * exactly what neo_mpc_inflation_costs(wres, inscribed_radius, inflation_radius, cost_scaling_factor, ...) returns.
+ * R > NEO_MPC_MAX_INFLATION_CELLS is refused with NEO_MPC_ERR_UNSUPPORTED.
+ *
+ * Seeds: the cells of the world map whose value is 254 (LETHAL_OBSTACLE) when the call starts.  Nothing else is a seed: not
+ * 253, not 255 (nav2's inflate_around_unknown is out of scope), and nothing beyond the map's edges.
+ *
+ * Distance: for cell (i, l), N = min (i - i')^2 + (l - l')^2 over the seeds (i', l'), an integer.  N > R^2 leaves the cell
+ * as it is; so does a map without seeds.
+ *
+ * Cost and combination: c = T[N], old = the cell's value: old == 255 becomes c when c >= 253 and stays 255 otherwise; any
+ * other old becomes max(old, c).
+ *
+ * Two consequences: the set of cells equal to 254 is the same before and after (T[n] <= 253 for n >= 1, and 254 stays 254);
+ * and the operation is idempotent -- inflating an inflated map with the same parameters changes nothing.
+ *
+ * neo_mpc_inflate_world_map is synchronous.  NEO_MPC_ERR_INVALID_ARGUMENT for a null handle and for a radius or scaling
+ * factor that is negative or not finite; NEO_MPC_ERR_NO_COSTMAP before neo_mpc_set_world_map; NEO_MPC_ERR_UNSUPPORTED for
+ * R > NEO_MPC_MAX_INFLATION_CELLS.  A refused call leaves the map as it was. */
+int neo_mpc_inflate_world_map(neo_mpc_handle* handle, double inscribed_radius, double inflation_radius,
+                              double cost_scaling_factor);
+/* Same, enqueued on `stream` (hipStream_t, may be NULL), returns without waiting.  Ordered exactly like
+ * neo_mpc_set_world_map_device's copy, which writes the same buffer: it waits on its stream for the last roll, which reads
+ * the copy, and for the previous copy or inflation when that ran on another stream; a roll on another stream waits for it.
+ * The cost table is kept in the handle, apart from the stamp's (windows and world may differ in resolution): when (wres,
+ * inscribed_radius, inflation_radius, cost_scaling_factor) differ from the previous call's it is rebuilt and uploaded
+ * synchronously; otherwise the call allocates nothing, copies nothing and does not synchronise, so set_world_map_device ->
+ * inflate_world_map_device -> roll -> stamp -> gate -> carrots -> solve can be captured on one stream in one HIP graph. */
+int neo_mpc_inflate_world_map_device(neo_mpc_handle* handle, double inscribed_radius, double inflation_radius,
+                                     double cost_scaling_factor, void* stream);
+/* Reads the handle's copy of the world map back, as the last neo_mpc_set_world_map or inflation left it: the cells,
+ * cells_out[size_y][size_x], and the geometry; any out pointer may be NULL (sizes first, then the cells).  Host pointers,
+ * synchronous; waits for the copy or inflation in flight -- one that was ENQUEUED by a call.  Work replayed from a HIP graph
+ * is not waited for: the handle's event was recorded while the graph was captured, and waiting for such an event does not
+ * wait for a replay (the same holds for neo_mpc_get_costmap_pool, and for the wait in front of a rebuilt cost table), so behind
+ * a replay synchronise the replay's stream first.  For display and logging: until a roll, the copy exists in device memory
+ * only.  NEO_MPC_ERR_NO_COSTMAP before neo_mpc_set_world_map. */
+int neo_mpc_get_world_map(neo_mpc_handle* handle, uint8_t* cells_out, uint32_t* size_x, uint32_t* size_y, double* resolution,
+                          double* origin_x, double* origin_y);
 
 /* Moves the windows to their robots and fills them from the world map (K7; the contract: neo_mpc_window_batch).  Afterwards
  * the handle's costmap IS this pool -- `count` maps of size_x x size_y cells, stored as neo_mpc_set_costmap_pool stores

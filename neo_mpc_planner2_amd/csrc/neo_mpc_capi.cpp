@@ -9,7 +9,7 @@
 // (the ordering of every launch that writes or reads the device map, and the host's wait for an idle map); the handle;
 // parameters and the term table; the shared checks; the device map (geometry, adoption, K3 ingest); the staging of host
 // batches by range; then the entry points -- costmaps, the solve paths of K1, K2 and the hooks, K4 carrots, K6 footprint
-// gate, K7 rolling windows, K8 fleet stamp.  A new entry point checks with the shared checks, stages with upload(), and
+// gate, K7 rolling windows, K8 fleet stamp, K9 world inflation.  A new entry point checks with the shared checks, stages with upload(), and
 // launches through fence.read() or between fence.begin_write() and end_write().
 #include <hip/hip_runtime.h>
 
@@ -233,13 +233,18 @@ struct __attribute__((visibility("hidden"))) neo_mpc_handle {
   bool has_world = false;
   int32_t world_size_x = 0, world_size_y = 0;
   double world_resolution = 0.0, world_origin_x = 0.0, world_origin_y = 0.0;
-  hipEvent_t world_ready = nullptr;         // recorded behind the copy into world_buf; a roll on another stream waits for it
+  hipEvent_t world_ready = nullptr;         // recorded behind every rewrite of world_buf, a copy or the inflation (K9); a roll on another stream waits for it
   hipStream_t world_ready_stream = nullptr;
   // K8 neo_mpc_stamp_fleet: the cost table and the key it was built for, the oriented polygons and their bounding boxes
   DeviceBuffer stamp_table, stamp_polys, stamp_boxes;
   bool has_stamp_table = false;
   double stamp_key[4] = {0.0, 0.0, 0.0, 0.0};   // resolution, inscribed_radius, inflation_radius, cost_scaling_factor
   int32_t stamp_reach = 0;
+  // K9 neo_mpc_inflate_world_map: its own cost table and key -- the world's resolution need not be the windows'
+  DeviceBuffer world_table;
+  bool has_world_table = false;
+  double world_key[4] = {0.0, 0.0, 0.0, 0.0};   // world resolution, inscribed_radius, inflation_radius, cost_scaling_factor
+  int32_t world_reach = 0;
 };
 constexpr size_t kLatencyPathMaxCount = 64;
 constexpr size_t kChunkedMinCount = 65536;   // staged host batches from here on go through in kChunks pieces on two streams
@@ -1227,6 +1232,30 @@ int neo_mpc_footprint_gate(neo_mpc_handle* h, const neo_mpc_footprint_batch* b) 
   return NEO_MPC_OK;
 }
 
+// K7, K9.  What every rewrite of world_buf -- a new copy, the inflation in place -- starts and ends with.  It runs behind the
+// last roll, which reads the copy that is about to change, and behind the previous rewrite.  The last roll is the fence's last
+// write or lies behind it -- every write runs behind the one before -- so the wait is for that write whatever it was:
+// `rolled` says nothing here, an ingest enqueued behind a roll that has not started clears it.  On `st` for the device
+// variants, on the host for the synchronous ones.
+static int begin_world_write(neo_mpc_handle* h, bool on_stream, hipStream_t st) {
+  int rc;
+  if (on_stream) {
+    if ((rc = h->fence.wait_writer(st))) return rc;
+    if (h->world_ready && h->world_ready_stream != st) HIP_TRY(hipStreamWaitEvent(st, h->world_ready, 0));
+  } else {
+    if ((rc = h->fence.wait_writer_host())) return rc;
+    if (h->world_ready) HIP_TRY(hipEventSynchronize(h->world_ready));
+  }
+  return NEO_MPC_OK;
+}
+// ... and the event a roll on another stream waits for
+static int end_world_write(neo_mpc_handle* h, hipStream_t st) {
+  if (!h->world_ready) HIP_TRY(hipEventCreateWithFlags(&h->world_ready, hipEventDisableTiming));
+  HIP_TRY(hipEventRecord(h->world_ready, st));
+  h->world_ready_stream = st;
+  return NEO_MPC_OK;
+}
+
 // K7.  The world map: the handle's own device copy, from host cells (stream == nullptr, blocking) or device cells (on `stream`).
 static int set_world_map(neo_mpc_handle* h, const uint8_t* cells, bool on_device, uint32_t sx, uint32_t sy, double res, double ox,
                          double oy, void* stream) {
@@ -1237,24 +1266,13 @@ static int set_world_map(neo_mpc_handle* h, const uint8_t* cells, bool on_device
   HIP_TRY(hipSetDevice(h->device));
   hipStream_t st = (hipStream_t)stream;
   const size_t bytes = (size_t)sx * sy;
-  // behind the last roll, which reads the copy that is about to be overwritten (and behind the previous copy).  The last
-  // roll is the fence's last write or lies behind it -- every write runs behind the one before -- so the wait is for that
-  // write whatever it was: `rolled` says nothing here, an ingest enqueued behind a roll that has not started clears it
-  int rc;
-  if (on_device) {
-    if ((rc = h->fence.wait_writer(st))) return rc;
-    if (h->world_ready && h->world_ready_stream != st) HIP_TRY(hipStreamWaitEvent(st, h->world_ready, 0));
-  } else {
-    if ((rc = h->fence.wait_writer_host())) return rc;
-    if (h->world_ready) HIP_TRY(hipEventSynchronize(h->world_ready));
-  }
+  int rc = begin_world_write(h, on_device, st);
+  if (rc) return rc;
   rc = h->world_buf.reserve(bytes);
   if (rc) { h->has_world = false; return rc; }   // (a failed re-allocation has let the old copy go)
   if (on_device) HIP_TRY(hipMemcpyAsync(h->world_buf.ptr, cells, bytes, hipMemcpyDeviceToDevice, st));
   else HIP_TRY(hipMemcpy(h->world_buf.ptr, cells, bytes, hipMemcpyHostToDevice));
-  if (!h->world_ready) HIP_TRY(hipEventCreateWithFlags(&h->world_ready, hipEventDisableTiming));
-  HIP_TRY(hipEventRecord(h->world_ready, st));
-  h->world_ready_stream = st;
+  if ((rc = end_world_write(h, st))) return rc;
   h->world_size_x = (int32_t)sx; h->world_size_y = (int32_t)sy;
   h->world_resolution = res; h->world_origin_x = ox; h->world_origin_y = oy;
   h->has_world = true;
@@ -1384,6 +1402,22 @@ int neo_mpc_get_costmap_pool(neo_mpc_handle* h, uint32_t first, uint32_t count, 
       HIP_TRY(hipMemcpy(origins_out, h->map.pool_origins + 2 * (size_t)first, (size_t)count * 16, hipMemcpyDeviceToHost));
     else { origins_out[0] = h->map.origin_x; origins_out[1] = h->map.origin_y; }
   }
+  return NEO_MPC_OK;
+}
+
+int neo_mpc_get_world_map(neo_mpc_handle* h, uint8_t* cells_out, uint32_t* size_x, uint32_t* size_y, double* resolution,
+                          double* origin_x, double* origin_y) {
+  if (!h) return fail(NEO_MPC_ERR_INVALID_ARGUMENT, "null handle");
+  if (!h->has_world) return fail(NEO_MPC_ERR_NO_COSTMAP, "neo_mpc_set_world_map has not been called");
+  if (size_x) *size_x = (uint32_t)h->world_size_x;
+  if (size_y) *size_y = (uint32_t)h->world_size_y;
+  if (resolution) *resolution = h->world_resolution;
+  if (origin_x) *origin_x = h->world_origin_x;
+  if (origin_y) *origin_y = h->world_origin_y;
+  if (!cells_out) return NEO_MPC_OK;
+  HIP_TRY(hipSetDevice(h->device));
+  HIP_TRY(hipEventSynchronize(h->world_ready));   // the copy or inflation in flight
+  HIP_TRY(hipMemcpy(cells_out, h->world_buf.ptr, (size_t)h->world_size_x * (size_t)h->world_size_y, hipMemcpyDeviceToHost));
   return NEO_MPC_OK;
 }
 
@@ -1521,6 +1555,58 @@ int neo_mpc_stamp_fleet(neo_mpc_handle* h, const neo_mpc_stamp_batch* b) {
     if (!d.poses && !d.problems) return NEO_MPC_ERR_DEVICE;
   }
   if ((rc = stamp(h, d, nullptr))) { (void)hipStreamSynchronize(nullptr); return rc; }   // (the staging is free again)
+  HIP_TRY(hipStreamSynchronize(nullptr));
+  return NEO_MPC_OK;
+}
+
+// K9.  nav2's inflation layer on the handle's copy of the world map, in place (the contract: include/neo_mpc.h).  Orders
+// itself like set_world_map's copy -- they write the same buffer -- on `stream`, or on the host and the null stream.
+static int inflate_world_map(neo_mpc_handle* h, double ins, double infl, double csf, bool on_device, void* stream) {
+  if (!h) return fail(NEO_MPC_ERR_INVALID_ARGUMENT, "null handle");
+  if (!stamp_radii_ok(ins, infl, csf))
+    return fail(NEO_MPC_ERR_INVALID_ARGUMENT, "inscribed_radius %g, inflation_radius %g and cost_scaling_factor %g must be finite and not negative", ins, infl, csf);
+  if (!h->has_world) return fail(NEO_MPC_ERR_NO_COSTMAP, "neo_mpc_set_world_map has not been called");
+  const double key[4] = {h->world_resolution, ins, infl, csf};
+  const int reach = stamp_reach_cells(key[0], infl);
+  if (reach < 0)
+    return fail(NEO_MPC_ERR_UNSUPPORTED, "inflation_radius %g at the world map's resolution %g is more than %d cells", infl, key[0],
+                NEO_MPC_MAX_INFLATION_CELLS);
+  HIP_TRY(hipSetDevice(h->device));
+  // the inflation behind every new copy of the map -- same parameters as the previous one -- finds its table in place: nothing is
+  // built, allocated or copied, so the call can be captured in a graph
+  int rc;
+  if (!(h->has_world_table && std::memcmp(key, h->world_key, sizeof(key)) == 0)) {
+    std::vector<uint8_t> table((size_t)reach * reach + 1);
+    stamp_costs(key[0], ins, csf, reach, table.data());
+    // (an inflation in flight reads the old table: every inflation records world_ready behind itself)
+    HIP_TRY(hipEventSynchronize(h->world_ready));
+    h->has_world_table = false;
+    if ((rc = h->world_table.reserve((size_t)NEO_MPC_MAX_INFLATION_CELLS * NEO_MPC_MAX_INFLATION_CELLS + 1))) return rc;   // (once)
+    if (!h->world_table.upload(table.data(), table.size())) return NEO_MPC_ERR_DEVICE;
+    std::memcpy(h->world_key, key, sizeof(key));
+    h->world_reach = reach;
+    h->has_world_table = true;
+  }
+  hipStream_t st = (hipStream_t)stream;
+  if ((rc = begin_world_write(h, on_device, st))) return rc;
+  InflateArgs a;
+  std::memset(&a, 0, sizeof(a));
+  a.world = h->world_buf.as<uint8_t>();
+  a.table = h->world_table.as<const uint8_t>();
+  a.wsx = h->world_size_x; a.wsy = h->world_size_y;
+  a.reach = h->world_reach;
+  launch_inflate_world(a, stream);
+  HIP_TRY(hipGetLastError());
+  return end_world_write(h, st);   // a roll behind it, on whatever stream, cuts its windows from the inflated map
+}
+
+int neo_mpc_inflate_world_map_device(neo_mpc_handle* h, double ins, double infl, double csf, void* stream) {
+  return inflate_world_map(h, ins, infl, csf, true, stream);
+}
+
+int neo_mpc_inflate_world_map(neo_mpc_handle* h, double ins, double infl, double csf) {
+  int rc = inflate_world_map(h, ins, infl, csf, false, nullptr);
+  if (rc) return rc;
   HIP_TRY(hipStreamSynchronize(nullptr));
   return NEO_MPC_OK;
 }

@@ -246,6 +246,14 @@ struct StampArgs {
   uint32_t per_robot;
 };
 
+// K9: nav2's inflation layer on the handle's copy of the world map (neo_mpc_inflate_world_map), in place
+struct InflateArgs {
+  uint8_t* world;                   // the world map, row-major wsx * wsy: read and rewritten
+  const uint8_t* table;             // [reach^2 + 1]: cost by squared cell distance (neo_mpc_inflation_costs at the world's resolution)
+  int32_t wsx, wsy;
+  int32_t reach;                    // R, cells: 0 .. NEO_MPC_MAX_INFLATION_CELLS
+};
+
 // A/B switches of the measurement tools: read from the environment ONCE, by neo_mpc_create (include/neo_mpc.h), kept in
 // the handle -- nothing on the solve path looks at the environment.
 struct LaunchTuning {
@@ -262,6 +270,7 @@ void launch_ingest(const IngestArgs& a, const LaunchTuning& t, void* stream);
 void launch_footprint_gate(const FootprintGateArgs& a, void* stream);
 void launch_roll(const RollArgs& a, void* stream);   // K7: k_roll_index, then k_roll_fill
 void launch_stamp(const StampArgs& a, void* stream); // K8: k_stamp_boxes, then k_stamp_fleet
+void launch_inflate_world(const InflateArgs& a, void* stream);   // K9: k_inflate_world
 // K5: dispatch order of the next launch from the iteration counts of the previous one (neo_mpc_balance_dispatch_device)
 void launch_dispatch_order(const neo_mpc_command* commands, float* load, uint32_t* order, uint32_t count, bool fresh, void* stream);
 constexpr uint32_t kDispatchSimds = 1024;   // a 4096-instance launch is one residency round: workgroups w, w + 1024, w + 2048, w + 3072 share a SIMD

@@ -18,10 +18,12 @@
 //   K6 k_footprint_gate  footprint_gate.h: the footprint gate in front of the carrot (cpp:218-219), one wave per robot.
 //   K7 k_roll_index, k_roll_fill  rolling_window.h: a fleet's rolling costmap windows cut from one world map, HBM-streaming.
 //   K8 k_stamp_boxes, k_stamp_fleet  fleet_stamp.h: the fleet's robots stamped into each other's windows, inflation ring included.
+//   K9 k_inflate_world  world_inflation.h: nav2's inflation layer on the world map the windows are cut from, in place.
 #include "k1_solve.h"
 #include "footprint_gate.h"
 #include "rolling_window.h"
 #include "fleet_stamp.h"
+#include "world_inflation.h"
 
 namespace neo_mpc {
 namespace {
@@ -404,6 +406,12 @@ void launch_stamp(const StampArgs& a, void* stream) {
   if (a.count == 0) return;
   hipLaunchKernelGGL(k_stamp_boxes, dim3((a.count + 255) / 256), dim3(256), 0, (hipStream_t)stream, a);
   hipLaunchKernelGGL(k_stamp_fleet, dim3(a.count), dim3(kLanes), 0, (hipStream_t)stream, a);
+}
+// K9: one workgroup per tile of 64 x 64 cells of the world map
+void launch_inflate_world(const InflateArgs& a, void* stream) {
+  if (a.wsx <= 0 || a.wsy <= 0) return;
+  hipLaunchKernelGGL(k_inflate_world, dim3((a.wsx + kInflateTile - 1) / kInflateTile, (a.wsy + kInflateTile - 1) / kInflateTile),
+                     dim3(kLanes * kInflateWaves), 0, (hipStream_t)stream, a);
 }
 void launch_ingest(const IngestArgs& a, const LaunchTuning& tuning, void* stream) {
   const long total = (long)a.rows * (a.pitch >> 4);

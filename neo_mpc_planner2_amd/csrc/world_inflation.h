@@ -1,0 +1,113 @@
+// world_inflation.h -- K9: nav2's inflation layer applied to the handle's copy of the world map, in place (the contract:
+// include/neo_mpc.h, neo_mpc_inflate_world_map).  Part of libneo_mpc.so's device code (included by neo_mpc_kernels.hip).
+#pragma once
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include "neo_mpc_device.h"
+#include "wave_ops.h"
+
+namespace neo_mpc {
+namespace {
+
+constexpr int kInflateTile = 64;    // a workgroup owns 64 x 64 cells: lane = column, one 64-bit word per row and 64 columns
+constexpr int kInflateWaves = 4;    // ... its waves take the rows in turn
+constexpr int kInflateLoads = 8;    // ... each with this many row words in flight
+constexpr int kInflateRows =kInflateTile + 2 * NEO_MPC_MAX_INFLATION_CELLS;   // the tile's rows and the largest halo
+constexpr int kInflateTableBytes = (NEO_MPC_MAX_INFLATION_CELLS * NEO_MPC_MAX_INFLATION_CELLS + 1 + 15) & ~15;
+constexpr int kInflateFar = 1 << 12;   // "no seed in this row": its square is beyond every R^2, and fits an int with d^2 added
+
+// Distance along a row from column 64 + c of a 192-column row (m0: columns 0 .. 63, m1: 64 .. 127, m2: 128 .. 191; bit b of
+// a word = its column b; 0 <= c < 64) to the row's nearest set bit -- K8's stamp_row_distance over three words.  Exact up to 64,
+// which is all a reach of at most 64 cells can ask for; kInflateFar where no bit is that near.
+__device__ __forceinline__ int inflate_row_distance(uint64_t m0, uint64_t m1, uint64_t m2, int c) {
+  // the 64 columns that end at the column, the nearest in bit 63; the 64 that start at it, the nearest in bit 0
+  const uint64_t left = (m1 << (63 - c)) | ((m0 >> c) >> 1);
+  const uint64_t right = (m1 >> c) | ((m2 << (63 - c)) << 1);
+  // (a distance of exactly 64 is the one column on either side that those windows leave out)
+  const int dl = left ? __clzll((long long)left) : ((m0 >> c) & 1 ? 64 : kInflateFar);
+  const int dr = right ? __ffsll((long long)right) - 1 : ((m2 >> c) & 1 ? 64 : kInflateFar);
+  return dl < dr ? dl : dr;
+}
+
+// K9: one workgroup of four waves per tile of 64 x 64 cells, one fused pass.
+//   1  The tile's halo -- the tile and R cells on every side, clipped to the map -- becomes a bitmask of seeds in LDS: a wave
+//      reads 64 consecutive bytes of a row and __ballot(cell == 254) is that row's word; three words per row (the tile's columns
+//      and the 64 on either side, of which the R nearest are read), at most 192 rows: 4.5 KB.
+//   2  A tile without a seed in its halo -- most of a yard -- is done: it reads nothing a second time and never loads the table.
+//   3  Otherwise T goes to LDS and every cell of the tile takes the minimum over the rows dy = 0, +-1, ... of dy^2 + hd^2, hd the
+//      distance to the row's nearest seed, the scan ending when dy^2 reaches the best so far and skipping rows without a seed;
+//      one byte read, combined by nav2's rule, written back where it changed.
+// IN PLACE, without a snapshot of the map.  A workgroup reads bytes of its neighbours' tiles (its halo) while their owners may
+// be rewriting them, and that is safe because the only thing it reads of a foreign byte is whether it equals 254, and no write
+// of this kernel changes that: a cell that is 254 has N = 0 and stays max(254, T[0]) = 254, and a cell that is not gets
+// T[N >= 1] <= 253, the maximum of that with a value other than 254, or keeps 255.  So step 1 sees the seeds of the map as it
+// was when the launch started whichever value of a foreign byte -- old or new, from whatever cache -- it is served: the kernel
+// depends on no visibility of another workgroup's write, on any XCD.  The value of a cell (step 3's `old`) is read by the one
+// lane that owns the cell, whose workgroup is the only writer of the tile: each byte has one reader of its value and one
+// writer, the same lane, once.  Byte stores merge into their line by byte mask; no two lanes write one byte.
+// No atomics; both barriers are unconditional; the trip counts of the loops that ballot are wave-uniform (all 64 lanes of a
+// wave run every turn of step 1's loop).
+__global__ __launch_bounds__(kLanes * kInflateWaves) void k_inflate_world(const InflateArgs a) {
+  __shared__ uint64_t masks[kInflateRows * 3];
+  __shared__ uint8_t table[kInflateTableBytes];
+  __shared__ int seen[kInflateWaves];
+  const int lane = threadIdx.x & (kLanes - 1), wave = uniform_int((int)(threadIdx.x >> 6));
+  const int R = a.reach, sx = a.wsx, sy = a.wsy;
+  const int tx = (int)blockIdx.x * kInflateTile, ty = (int)blockIdx.y * kInflateTile;   // the tile's first column and row
+  const int rows = kInflateTile + 2 * R;               // masks[3 * rr + w]: map row ty - R + rr, columns tx + 64 (w - 1) ...
+  const int c_lo = tx - R > 0 ? tx - R : 0;            // the halo's columns that exist: [c_lo, c_hi)
+  const int c_hi = tx + kInflateTile + R < sx ? tx + kInflateTile + R : sx;
+  bool any = false;
+  // (a wave's words, kInflateLoads at a time: the loads of a batch are in flight together -- one after the other, a tile
+  // without a seed, which does nothing else, is the sum of their latencies)
+  for (int t0 = wave; t0 < rows * 3; t0 += kInflateWaves * kInflateLoads) {
+    int cell[kInflateLoads];
+#pragma unroll
+    for (int u = 0; u < kInflateLoads; ++u) {
+      const int t = t0 + u * kInflateWaves, rr = t / 3, w = t - 3 * rr;
+      const int r = ty - R + rr, col = tx + (w - 1) * kInflateTile + lane;
+      cell[u] = 0;
+      if (t < rows * 3 && r >= 0 && r < sy && col >= c_lo && col < c_hi) cell[u] = a.world[(int64_t)r * sx + col];   // inside the map
+    }
+#pragma unroll
+    for (int u = 0; u < kInflateLoads; ++u) {
+      const int t = t0 + u * kInflateWaves;
+      const uint64_t m = __ballot(cell[u] == 254);
+      if (t < rows * 3 && lane == 0) masks[t] = m;     // (t < kInflateRows * 3: inside masks)
+      any = any || m != 0;
+    }
+  }
+  if (lane == 0) seen[wave] = any ? 1 : 0;
+  __syncthreads();
+  const bool some = (seen[0] | seen[1] | seen[2] | seen[3]) != 0;   // the same in every lane of the workgroup
+  if (some)
+    for (int t = (int)threadIdx.x; t <= R * R; t += kLanes * kInflateWaves) table[t] = a.table[t];
+  __syncthreads();
+  if (!some) return;
+  const int i = tx + lane, reach2 = R * R;
+  for (int k = wave; k < kInflateTile && ty + k < sy; k += kInflateWaves) {
+    const int l = ty + k, r0 = k + R;                  // the cell's row in the map and in the masks
+    int best = reach2 + 1;
+    for (int d = 0; d <= R && d * d < best; ++d) {     // (0 <= r0 - d and r0 + d < rows)
+      const uint64_t* up = masks + 3 * (r0 + d);
+      const uint64_t u0 = up[0], u1 = up[1], u2 = up[2];
+      if (u0 | u1 | u2) { const int hd = inflate_row_distance(u0, u1, u2, lane), v = d * d + hd * hd; best = v < best ? v : best; }
+      if (d > 0) {
+        const uint64_t* down = masks + 3 * (r0 - d);
+        const uint64_t d0 = down[0], d1 = down[1], d2 = down[2];
+        if (d0 | d1 | d2) { const int hd = inflate_row_distance(d0, d1, d2, lane), v = d * d + hd * hd; best = v < best ? v : best; }
+      }
+    }
+    if (best <= reach2 && i < sx) {
+      // nav2's inflation rule, inflate_unknown false
+      uint8_t* p = a.world + (int64_t)l * sx + i;      // 0 <= i < wsx, 0 <= l < wsy: this tile's own cell
+      const int cost = table[best], old = *p;
+      const int now = old == 255 ? (cost >= 253 ? cost : 255) : (cost > old ? cost : old);
+      if (now != old) *p = (uint8_t)now;
+    }
+  }
+}
+
+}  // namespace
+}  // namespace neo_mpc

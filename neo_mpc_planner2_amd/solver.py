@@ -33,6 +33,7 @@ class BatchSolver:
         self._last_call = None
         self._in_flight = {}    # ticket -> (batch struct, arrays): kept alive until solve_wait
         self._map_shape = None  # (maps, size_y, size_x) of the costmap(s) the handle holds (get_costmap_pool)
+        self._world_device = None   # the torch device the world map was set from (None: from host cells)
 
     # -- lifecycle ------------------------------------------------------------------
     def close(self):
@@ -119,6 +120,7 @@ class BatchSolver:
             sy, sx = cells.shape
             _lib.check(self._lib.neo_mpc_set_world_map(self._handle, C.c_void_p(cells.ctypes.data), sx, sy,
                                                       float(resolution), float(origin_x), float(origin_y)))
+            self._world_device = None
         else:
             import torch
             assert cells.is_cuda and cells.dtype == torch.uint8 and cells.is_contiguous()
@@ -127,6 +129,31 @@ class BatchSolver:
             _lib.check(self._lib.neo_mpc_set_world_map_device(
                 self._handle, C.c_void_p(cells.data_ptr()), sx, sy, float(resolution), float(origin_x),
                 float(origin_y), C.c_void_p(stream)))
+            self._world_device = cells.device
+
+    def inflate_world_map(self, inscribed_radius, inflation_radius, cost_scaling_factor):
+        """nav2's inflation layer on the handle's copy of the world map, in place (K9; the contract:
+        neo_mpc_inflate_world_map in include/neo_mpc.h): set_world_map(raw) -> inflate_world_map -> rolls.  Like
+        `set_world_map`: when the world map was set from a CUDA tensor the device call on torch's current stream,
+        otherwise the synchronous host call."""
+        args = (float(inscribed_radius), float(inflation_radius), float(cost_scaling_factor))
+        if self._world_device is None:
+            _lib.check(self._lib.neo_mpc_inflate_world_map(self._handle, *args))
+        else:
+            import torch
+            stream = torch.cuda.current_stream(self._world_device).cuda_stream
+            _lib.check(self._lib.neo_mpc_inflate_world_map_device(self._handle, *args, C.c_void_p(stream)))
+
+    def get_world_map(self):
+        """The handle's copy of the world map as the last `set_world_map` or `inflate_world_map` left it: (cells uint8
+        [size_y, size_x], resolution, origin_x, origin_y).  Synchronous; waits for the copy or inflation in flight."""
+        sx, sy = C.c_uint32(), C.c_uint32()
+        res, ox, oy = C.c_double(), C.c_double(), C.c_double()
+        _lib.check(self._lib.neo_mpc_get_world_map(self._handle, None, C.byref(sx), C.byref(sy), C.byref(res),
+                                                  C.byref(ox), C.byref(oy)))
+        cells = np.zeros((sy.value, sx.value), dtype=np.uint8)
+        _lib.check(self._lib.neo_mpc_get_world_map(self._handle, C.c_void_p(cells.ctypes.data), None, None, None, None, None))
+        return cells, res.value, ox.value, oy.value
 
     def roll_costmap_pool(self, size_x, size_y, resolution, origins, poses=None, problems=None, outside_value=255):
         """Moves `count` windows of size_x x size_y cells to their robots and fills them from the world map (K7;

@@ -9,7 +9,8 @@ solution shifted by one whole control step of 0.267 s although only 1/30 s has p
 tick needs about as many iterations as a cold one.
 --pool: every robot has a window of its own whose CONTENTS travel with it (origins rewritten, cells re-ingested by K3).
 --world: every robot has a rolling window (map_index = i) cut each tick from ONE fixed world map (K7,
-neo_mpc_roll_costmap_pool_device): the fleet drives past fixed obstacles with per-robot local costmaps."""
+neo_mpc_roll_costmap_pool_device): the fleet drives past fixed obstacles with per-robot local costmaps.
+--world --inflate INSCRIBED,RADIUS,FACTOR: the world map is inflated once before the loop (K9, neo_mpc_inflate_world_map_device)."""
 import json
 import math
 import os
@@ -29,6 +30,10 @@ TICKS, HZ = int(os.environ.get("NEO_MPC_TICKS", "60")), 30.0
 DUMP_TICK = int(os.environ.get("NEO_MPC_DUMP_TICK", "-1"))
 POOL = "--pool" in sys.argv   # every robot gets its own 200x200 rolling window (neo_mpc_set_costmap_pool)
 WORLD = "--world" in sys.argv  # ... cut every tick from the one 500x500 world map (neo_mpc_roll_costmap_pool)
+INFLATE = None                 # --inflate INSCRIBED,RADIUS,FACTOR (with --world): nav2's inflation on the world map, once
+if "--inflate" in sys.argv:
+    INFLATE = tuple(float(v) for v in sys.argv[sys.argv.index("--inflate") + 1].split(","))
+    assert WORLD and len(INFLATE) == 3, "--inflate INSCRIBED,RADIUS,FACTOR goes with --world"
 cfg, cmap, probs, st, warm = synthetic.make_workload("C2", seed=0)
 params = dict(README_PARAMS)
 params.update(control_steps=3)
@@ -39,6 +44,8 @@ with BatchSolver(params) as s:
     rolling = None
     if WORLD:
         s.set_world_map(torch.from_numpy(cmap[0]).to(dev), *cmap[1:])
+        if INFLATE:
+            s.inflate_world_map(*INFLATE)
         probs["map_index"] = np.arange(len(probs), dtype=np.int32)
         d_orig = torch.from_numpy(np.ascontiguousarray(probs["cur_xy"]) - 5.0).to(dev)
         rolling = (200, 200, cmap[1], d_orig)
@@ -90,6 +97,8 @@ extra = {}
 if WORLD:
     extra = {"pool": "4096 rolling windows of 200x200 cells cut from the one 500x500 world map every tick (K7)",
              "roll_ms_median": roll_ms}
+    if INFLATE:
+        extra["world_inflation"] = INFLATE
 elif POOL:
     extra = {"pool": "4096 rolling windows of 200x200 cells (160 MB raw), re-centred and re-ingested every tick",
              "ingest_ms_median": float(np.median([a.elapsed_time(e) for a, e in ing[5:]]))}
