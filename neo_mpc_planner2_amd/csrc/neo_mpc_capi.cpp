@@ -6,11 +6,12 @@
 // There is deliberately no CPU fallback: without a gfx950 device create() fails.
 //
 // In this order: the error setter; DeviceBuffer (device memory that frees itself, and the one-line uploads); MapFence
-// (the ordering of every launch that writes or reads the device map, and the host's wait for an idle map); the handle;
-// parameters and the term table; the shared checks; the device map (geometry, adoption, K3 ingest); the staging of host
-// batches by range; then the entry points -- costmaps, the solve paths of K1, K2 and the hooks, K4 carrots, K6 footprint
-// gate, K7 rolling windows, K8 fleet stamp, K9 world inflation.  A new entry point checks with the shared checks, stages with upload(), and
-// launches through fence.read() or between fence.begin_write() and end_write().
+// (the ordering of every launch that writes or reads the device map, and the host's wait for an idle map); WorldMap (the
+// world map's copy, geometry and ordering); the refusals of inflation parameters and InflationTable (K8's and K9's cached
+// cost table); the handle; parameters and the term table; the shared checks; the device map (geometry, adoption, K3
+// ingest); the staging of host batches by range; then the entry points -- costmaps, the solve paths of K1, K2 and the hooks,
+// K4 carrots, K6 footprint gate, K7 rolling windows, K8 fleet stamp, K9 world inflation.  A new entry point checks with the
+// shared checks, stages with upload(), and launches through fence.read() or between fence.begin_write() and end_write().
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -103,15 +104,29 @@ struct DeviceBuffer {
 };
 
 // ---------------------------------------------------------------------------------------------- the map fence
+// The event recorded behind the last write of a buffer, the stream it went to, and the waits for it: on a stream (skipped on
+// that stream itself: in order anyway) or on the host.  What MapFence and WorldMap both keep of their writer.
+struct WriteEvent {
+  hipEvent_t ready = nullptr;
+  hipStream_t ready_stream = nullptr;
+  int wait_writer(hipStream_t st) {
+    if (ready && ready_stream != st) HIP_TRY(hipStreamWaitEvent(st, ready, 0));
+    return NEO_MPC_OK;
+  }
+  int wait_writer_host() {
+    if (ready) HIP_TRY(hipEventSynchronize(ready));
+    return NEO_MPC_OK;
+  }
+  void destroy() { if (ready) (void)hipEventDestroy(ready); }
+};
+
 // Stream ordering around the device map (map_buf).  A WRITE -- ingest, roll, stamp: the kernels that rewrite the maps in
 // place -- runs behind the previous write and behind every launch still reading the maps, whatever stream it went to, and
 // records `ready` on its stream.  A READ -- every solve / postprocess / objective / gate launch -- waits for `ready` on its
 // own stream and records the in-use event OF ITS STREAM (one per distinct stream the caller has used), which the next
 // write waits for.  (Waits on the stream an event was recorded on are skipped: in order anyway.)
-struct MapFence {
+struct MapFence : WriteEvent {
   static constexpr size_t kMaxUsers = 64;   // distinct streams with a launch in flight between two writes
-  hipEvent_t ready = nullptr;
-  hipStream_t ready_stream = nullptr;
   struct User { hipStream_t stream; hipEvent_t done; bool pending; };
   std::vector<User> users;
 
@@ -139,16 +154,6 @@ struct MapFence {
     HIP_TRY(hipGetLastError());
     return release(st);
   }
-  // behind the last write, on a stream ...
-  int wait_writer(hipStream_t st) {
-    if (ready && ready_stream != st) HIP_TRY(hipStreamWaitEvent(st, ready, 0));
-    return NEO_MPC_OK;
-  }
-  // ... or on the host
-  int wait_writer_host() {
-    if (ready) HIP_TRY(hipEventSynchronize(ready));
-    return NEO_MPC_OK;
-  }
   // The host's wait for a map nobody is using: before the term table or the pool's origins are rewritten (blocking copies
   // on the null stream, which do not order against the non-blocking streams batches are in flight on) every launch that
   // may still read them has to have ENDED.  Those are the pending readers -- and the readers a write has already cleared:
@@ -161,7 +166,7 @@ struct MapFence {
     return wait_writer_host();
   }
   void destroy() {
-    if (ready) (void)hipEventDestroy(ready);
+    WriteEvent::destroy();
     for (auto& u : users) (void)hipEventDestroy(u.done);
   }
 
@@ -185,6 +190,87 @@ struct MapFence {
     }
     HIP_TRY(hipEventRecord(slot->done, st));
     slot->pending = true;
+    return NEO_MPC_OK;
+  }
+};
+
+// ---------------------------------------------------------------------------------------------- the world map
+// K7, K9.  The handle's own device copy of the world map the rolling windows are cut from, and its geometry.  Every rewrite
+// -- a new copy, the inflation in place -- runs behind the last roll, which reads the copy that is about to change, and
+// behind the previous rewrite.  The last roll is the fence's last write or lies behind it -- every write runs behind the one
+// before -- so the wait is for that write whatever it was: `rolled` says nothing here, an ingest enqueued behind a roll that
+// has not started clears it.  On `st` for the device variants, on the host for the synchronous ones.  Every rewrite ends
+// with `ready` recorded: a roll on another stream, the next rewrite and the host's read wait for it.
+struct WorldMap : WriteEvent {
+  DeviceBuffer buf;
+  bool has = false;
+  int32_t size_x = 0, size_y = 0;
+  double resolution = 0.0, origin_x = 0.0, origin_y = 0.0;
+  int begin_write(MapFence& fence, bool on_stream, hipStream_t st) {
+    if (int rc = on_stream ? fence.wait_writer(st) : fence.wait_writer_host()) return rc;
+    return on_stream ? wait_writer(st) : wait_writer_host();
+  }
+  int end_write(hipStream_t st) {
+    if (!ready) HIP_TRY(hipEventCreateWithFlags(&ready, hipEventDisableTiming));
+    HIP_TRY(hipEventRecord(ready, st));
+    ready_stream = st;
+    return NEO_MPC_OK;
+  }
+};
+
+// ---------------------------------------------------------------------------------------------- inflation parameters
+// K8, K9.  The cost table of the contract (neo_mpc_stamp_batch): nav2's InflationLayer::computeCost by squared cell distance.
+void stamp_costs(double res, double ins, double csf, int reach, uint8_t* table) {
+  table[0] = 254;
+  for (int n = 1; n <= reach * reach; ++n) {
+    const double dist = std::sqrt((double)n) * res;
+    if (dist <= ins) table[n] = 253;
+    else {
+      const double factor = std::exp(-csf * (dist - ins));
+      table[n] = (uint8_t)(252.0 * factor);
+    }
+  }
+}
+// The refusals of inflation parameters, once: the radii alone (what an entry point refuses before it looks at its map) ...
+int check_inflation_radii(double ins, double infl, double csf) {
+  if (std::isfinite(ins) && std::isfinite(infl) && std::isfinite(csf) && ins >= 0.0 && infl >= 0.0 && csf >= 0.0) return NEO_MPC_OK;
+  return fail(NEO_MPC_ERR_INVALID_ARGUMENT, "inscribed_radius %g, inflation_radius %g and cost_scaling_factor %g must be finite and not negative", ins, infl, csf);
+}
+// ... and all of them at a resolution (`whose` map's: "" or "the world map's ") -> R = ceil(inflation_radius / res) in
+// `reach` (if asked for), refused beyond NEO_MPC_MAX_INFLATION_CELLS (compared in float64, before the conversion)
+int inflation_reach(double res, double ins, double infl, double csf, const char* whose, int* reach) {
+  if (int rc = check_inflation_radii(ins, infl, csf)) return rc;
+  const double r = std::ceil(infl / res);
+  if (!(r <= (double)NEO_MPC_MAX_INFLATION_CELLS))
+    return fail(NEO_MPC_ERR_UNSUPPORTED, "inflation_radius %g at %sresolution %g is more than %d cells", infl, whose, res, NEO_MPC_MAX_INFLATION_CELLS);
+  if (reach) *reach = (int)r;
+  return NEO_MPC_OK;
+}
+
+// The table on the device and the parameters it was built for.  A call with the parameters of the previous one -- the stamp
+// of every tick, the inflation behind every new world map -- finds it in place: nothing is built, allocated or copied, so
+// the call can be captured in a graph.  build(): for parameters inflation_reach() has passed;
+// `readers`: the writer whose launches read the table -- those in flight read the old one to their end.
+struct InflationTable {
+  DeviceBuffer buf;
+  bool valid = false;
+  double key[4] = {0.0, 0.0, 0.0, 0.0};   // resolution, inscribed_radius, inflation_radius, cost_scaling_factor
+  int32_t reach = 0;
+  int build(double res, double ins, double infl, double csf, WriteEvent& readers) {
+    const double now[4] = {res, ins, infl, csf};
+    if (valid && std::memcmp(now, key, sizeof(key)) == 0) return NEO_MPC_OK;
+    const int r = (int)std::ceil(infl / res);   // (inflation_reach() has passed these parameters: R <= NEO_MPC_MAX_INFLATION_CELLS)
+    int rc;
+    std::vector<uint8_t> table((size_t)r * r + 1);
+    stamp_costs(res, ins, csf, r, table.data());
+    if ((rc = readers.wait_writer_host())) return rc;
+    valid = false;
+    // (the largest table, once: a change of parameters never re-allocates)
+    if ((rc = buf.reserve((size_t)NEO_MPC_MAX_INFLATION_CELLS * NEO_MPC_MAX_INFLATION_CELLS + 1))) return rc;
+    if (!buf.upload(table.data(), table.size())) return NEO_MPC_ERR_DEVICE;
+    std::memcpy(key, now, sizeof(key));
+    reach = r;
+    valid = true;
     return NEO_MPC_OK;
   }
 };
@@ -228,23 +314,14 @@ struct __attribute__((visibility("hidden"))) neo_mpc_handle {
   // K4 neo_mpc_select_carrots (its robot poses: poses) and K6 neo_mpc_footprint_gate (its polygon: verts; fp_costs: both)
   DeviceBuffer plan_poses, plan_offsets, fp_costs, slow_down, carrots;
   DeviceBuffer gate_indices, gate_polygons_out;
-  // K7 neo_mpc_set_world_map / neo_mpc_roll_costmap_pool: the handle's own copy of the world map and the fill's index tables
-  DeviceBuffer world_buf, roll_tables;
-  bool has_world = false;
-  int32_t world_size_x = 0, world_size_y = 0;
-  double world_resolution = 0.0, world_origin_x = 0.0, world_origin_y = 0.0;
-  hipEvent_t world_ready = nullptr;         // recorded behind every rewrite of world_buf, a copy or the inflation (K9); a roll on another stream waits for it
-  hipStream_t world_ready_stream = nullptr;
-  // K8 neo_mpc_stamp_fleet: the cost table and the key it was built for, the oriented polygons and their bounding boxes
-  DeviceBuffer stamp_table, stamp_polys, stamp_boxes;
-  bool has_stamp_table = false;
-  double stamp_key[4] = {0.0, 0.0, 0.0, 0.0};   // resolution, inscribed_radius, inflation_radius, cost_scaling_factor
-  int32_t stamp_reach = 0;
-  // K9 neo_mpc_inflate_world_map: its own cost table and key -- the world's resolution need not be the windows'
-  DeviceBuffer world_table;
-  bool has_world_table = false;
-  double world_key[4] = {0.0, 0.0, 0.0, 0.0};   // world resolution, inscribed_radius, inflation_radius, cost_scaling_factor
-  int32_t world_reach = 0;
+  // K7 neo_mpc_set_world_map / neo_mpc_roll_costmap_pool: the world map and the fill's index tables
+  WorldMap world;
+  DeviceBuffer roll_tables;
+  // K8 neo_mpc_stamp_fleet: the cost table at the windows' resolution, the oriented polygons and their bounding boxes
+  InflationTable stamp_table;
+  DeviceBuffer stamp_polys, stamp_boxes;
+  // K9 neo_mpc_inflate_world_map: its own cost table -- the world's resolution need not be the windows'
+  InflationTable world_table;
 };
 constexpr size_t kLatencyPathMaxCount = 64;
 constexpr size_t kChunkedMinCount = 65536;   // staged host batches from here on go through in kChunks pieces on two streams
@@ -686,7 +763,7 @@ void neo_mpc_destroy(neo_mpc_handle* h) {
   }
   for (hipStream_t cs : h->chunk_streams) if (cs) (void)hipStreamDestroy(cs);
   h->fence.destroy();
-  if (h->world_ready) (void)hipEventDestroy(h->world_ready);
+  h->world.destroy();
   if (h->pin) (void)hipHostFree(h->pin);
   delete h;   // (every DeviceBuffer frees its own memory, on the device set above)
 }
@@ -1232,30 +1309,6 @@ int neo_mpc_footprint_gate(neo_mpc_handle* h, const neo_mpc_footprint_batch* b) 
   return NEO_MPC_OK;
 }
 
-// K7, K9.  What every rewrite of world_buf -- a new copy, the inflation in place -- starts and ends with.  It runs behind the
-// last roll, which reads the copy that is about to change, and behind the previous rewrite.  The last roll is the fence's last
-// write or lies behind it -- every write runs behind the one before -- so the wait is for that write whatever it was:
-// `rolled` says nothing here, an ingest enqueued behind a roll that has not started clears it.  On `st` for the device
-// variants, on the host for the synchronous ones.
-static int begin_world_write(neo_mpc_handle* h, bool on_stream, hipStream_t st) {
-  int rc;
-  if (on_stream) {
-    if ((rc = h->fence.wait_writer(st))) return rc;
-    if (h->world_ready && h->world_ready_stream != st) HIP_TRY(hipStreamWaitEvent(st, h->world_ready, 0));
-  } else {
-    if ((rc = h->fence.wait_writer_host())) return rc;
-    if (h->world_ready) HIP_TRY(hipEventSynchronize(h->world_ready));
-  }
-  return NEO_MPC_OK;
-}
-// ... and the event a roll on another stream waits for
-static int end_world_write(neo_mpc_handle* h, hipStream_t st) {
-  if (!h->world_ready) HIP_TRY(hipEventCreateWithFlags(&h->world_ready, hipEventDisableTiming));
-  HIP_TRY(hipEventRecord(h->world_ready, st));
-  h->world_ready_stream = st;
-  return NEO_MPC_OK;
-}
-
 // K7.  The world map: the handle's own device copy, from host cells (stream == nullptr, blocking) or device cells (on `stream`).
 static int set_world_map(neo_mpc_handle* h, const uint8_t* cells, bool on_device, uint32_t sx, uint32_t sy, double res, double ox,
                          double oy, void* stream) {
@@ -1266,16 +1319,17 @@ static int set_world_map(neo_mpc_handle* h, const uint8_t* cells, bool on_device
   HIP_TRY(hipSetDevice(h->device));
   hipStream_t st = (hipStream_t)stream;
   const size_t bytes = (size_t)sx * sy;
-  int rc = begin_world_write(h, on_device, st);
+  WorldMap& w = h->world;
+  int rc = w.begin_write(h->fence, on_device, st);
   if (rc) return rc;
-  rc = h->world_buf.reserve(bytes);
-  if (rc) { h->has_world = false; return rc; }   // (a failed re-allocation has let the old copy go)
-  if (on_device) HIP_TRY(hipMemcpyAsync(h->world_buf.ptr, cells, bytes, hipMemcpyDeviceToDevice, st));
-  else HIP_TRY(hipMemcpy(h->world_buf.ptr, cells, bytes, hipMemcpyHostToDevice));
-  if ((rc = end_world_write(h, st))) return rc;
-  h->world_size_x = (int32_t)sx; h->world_size_y = (int32_t)sy;
-  h->world_resolution = res; h->world_origin_x = ox; h->world_origin_y = oy;
-  h->has_world = true;
+  rc = w.buf.reserve(bytes);
+  if (rc) { w.has = false; return rc; }   // (a failed re-allocation has let the old copy go)
+  if (on_device) HIP_TRY(hipMemcpyAsync(w.buf.ptr, cells, bytes, hipMemcpyDeviceToDevice, st));
+  else HIP_TRY(hipMemcpy(w.buf.ptr, cells, bytes, hipMemcpyHostToDevice));
+  if ((rc = w.end_write(st))) return rc;
+  w.size_x = (int32_t)sx; w.size_y = (int32_t)sy;
+  w.resolution = res; w.origin_x = ox; w.origin_y = oy;
+  w.has = true;
   return NEO_MPC_OK;
 }
 
@@ -1291,7 +1345,7 @@ int neo_mpc_set_world_map_device(neo_mpc_handle* h, const uint8_t* d_cells, uint
 // What both roll entry points check: the record's shape, never a value behind a pointer.
 static int check_window_batch(const neo_mpc_handle* h, const neo_mpc_window_batch* w) {
   if (!h || !w) return fail(NEO_MPC_ERR_INVALID_ARGUMENT, "null argument");
-  if (!h->has_world) return fail(NEO_MPC_ERR_NO_COSTMAP, "neo_mpc_set_world_map has not been called");
+  if (!h->world.has) return fail(NEO_MPC_ERR_NO_COSTMAP, "neo_mpc_set_world_map has not been called");
   if (w->reserved != 0) return fail(NEO_MPC_ERR_INVALID_ARGUMENT, "neo_mpc_window_batch.reserved must be zero (got %u)", w->reserved);
   if (w->outside_value > 255) return fail(NEO_MPC_ERR_INVALID_ARGUMENT, "outside_value %u is no cell value (0 .. 255)", w->outside_value);
   if (w->count > NEO_MPC_MAX_POOL_MAPS)
@@ -1322,15 +1376,15 @@ static int roll(neo_mpc_handle* h, const neo_mpc_window_batch& d, void* stream) 
   // behind the previous ingest or roll, every launch still reading the old map (it reads `origins` too: the device variant
   // rewrites them in-stream behind these waits) and the world map's copy
   if ((rc = h->fence.begin_write(st))) return rc;
-  if (h->world_ready_stream != st) HIP_TRY(hipStreamWaitEvent(st, h->world_ready, 0));
+  if ((rc = h->world.wait_writer(st))) return rc;
   RollArgs a;
   std::memset(&a, 0, sizeof(a));
   a.poses = d.poses; a.problems = d.poses ? nullptr : d.problems; a.origins = d.origins;
   a.tables = h->roll_tables.as<int32_t>();
-  a.world = h->world_buf.as<const uint8_t>(); a.dst = h->map_buf.as<uint8_t>();
-  a.res = d.resolution; a.wres = h->world_resolution; a.wox = h->world_origin_x; a.woy = h->world_origin_y;
+  a.world = h->world.buf.as<const uint8_t>(); a.dst = h->map_buf.as<uint8_t>();
+  a.res = d.resolution; a.wres = h->world.resolution; a.wox = h->world.origin_x; a.woy = h->world.origin_y;
   a.dst_stride = (int64_t)g.stride;
-  a.wsx = h->world_size_x; a.wsy = h->world_size_y;
+  a.wsx = h->world.size_x; a.wsy = h->world.size_y;
   a.size_x = sx; a.size_y = sy; a.pitch = g.pitch; a.rows = g.rows; a.border = g.border;
   a.tab_x = tab_x; a.tab_stride = tab_stride;
   a.count = (uint32_t)count; a.outside = d.outside_value;
@@ -1408,49 +1462,26 @@ int neo_mpc_get_costmap_pool(neo_mpc_handle* h, uint32_t first, uint32_t count, 
 int neo_mpc_get_world_map(neo_mpc_handle* h, uint8_t* cells_out, uint32_t* size_x, uint32_t* size_y, double* resolution,
                           double* origin_x, double* origin_y) {
   if (!h) return fail(NEO_MPC_ERR_INVALID_ARGUMENT, "null handle");
-  if (!h->has_world) return fail(NEO_MPC_ERR_NO_COSTMAP, "neo_mpc_set_world_map has not been called");
-  if (size_x) *size_x = (uint32_t)h->world_size_x;
-  if (size_y) *size_y = (uint32_t)h->world_size_y;
-  if (resolution) *resolution = h->world_resolution;
-  if (origin_x) *origin_x = h->world_origin_x;
-  if (origin_y) *origin_y = h->world_origin_y;
+  if (!h->world.has) return fail(NEO_MPC_ERR_NO_COSTMAP, "neo_mpc_set_world_map has not been called");
+  WorldMap& w = h->world;
+  if (size_x) *size_x = (uint32_t)w.size_x;
+  if (size_y) *size_y = (uint32_t)w.size_y;
+  if (resolution) *resolution = w.resolution;
+  if (origin_x) *origin_x = w.origin_x;
+  if (origin_y) *origin_y = w.origin_y;
   if (!cells_out) return NEO_MPC_OK;
   HIP_TRY(hipSetDevice(h->device));
-  HIP_TRY(hipEventSynchronize(h->world_ready));   // the copy or inflation in flight
-  HIP_TRY(hipMemcpy(cells_out, h->world_buf.ptr, (size_t)h->world_size_x * (size_t)h->world_size_y, hipMemcpyDeviceToHost));
+  if (int rc = w.wait_writer_host()) return rc;   // the copy or inflation in flight
+  HIP_TRY(hipMemcpy(cells_out, w.buf.ptr, (size_t)w.size_x * (size_t)w.size_y, hipMemcpyDeviceToHost));
   return NEO_MPC_OK;
-}
-
-// K8.  The cost table of the contract (neo_mpc_stamp_batch): nav2's InflationLayer::computeCost by squared cell distance.
-static bool stamp_radii_ok(double ins, double infl, double csf) {
-  return std::isfinite(ins) && std::isfinite(infl) && std::isfinite(csf) && ins >= 0.0 && infl >= 0.0 && csf >= 0.0;
-}
-// R = ceil(inflation_radius / res), or -1 beyond NEO_MPC_MAX_INFLATION_CELLS (compared in float64, before the conversion)
-static int stamp_reach_cells(double res, double infl) {
-  const double r = std::ceil(infl / res);
-  return r <= (double)NEO_MPC_MAX_INFLATION_CELLS ? (int)r : -1;
-}
-static void stamp_costs(double res, double ins, double csf, int reach, uint8_t* table) {
-  table[0] = 254;
-  for (int n = 1; n <= reach * reach; ++n) {
-    const double dist = std::sqrt((double)n) * res;
-    if (dist <= ins) table[n] = 253;
-    else {
-      const double factor = std::exp(-csf * (dist - ins));
-      table[n] = (uint8_t)(252.0 * factor);
-    }
-  }
 }
 
 int neo_mpc_inflation_costs(double res, double ins, double infl, double csf, uint8_t* table_out, size_t capacity,
                             uint32_t* cells_out) {
   if (!(res > 0.0) || !std::isfinite(res))
     return fail(NEO_MPC_ERR_INVALID_ARGUMENT, "resolution %g must be positive and finite", res);
-  if (!stamp_radii_ok(ins, infl, csf))
-    return fail(NEO_MPC_ERR_INVALID_ARGUMENT, "inscribed_radius %g, inflation_radius %g and cost_scaling_factor %g must be finite and not negative", ins, infl, csf);
-  const int reach = stamp_reach_cells(res, infl);
-  if (reach < 0)
-    return fail(NEO_MPC_ERR_UNSUPPORTED, "inflation_radius %g at resolution %g is more than %d cells", infl, res, NEO_MPC_MAX_INFLATION_CELLS);
+  int reach;
+  if (int rc = inflation_reach(res, ins, infl, csf, "", &reach)) return rc;
   if (cells_out) *cells_out = (uint32_t)reach;
   if (table_out) {
     if (capacity < (size_t)reach * reach + 1)
@@ -1465,41 +1496,22 @@ static int check_stamp_batch(const neo_mpc_handle* h, const neo_mpc_stamp_batch*
   if (!h || !b) return fail(NEO_MPC_ERR_INVALID_ARGUMENT, "null argument");
   if (b->reserved != 0) return fail(NEO_MPC_ERR_INVALID_ARGUMENT, "neo_mpc_stamp_batch.reserved must be zero");
   if (int rc = check_footprint_shape(b->footprint_points, b->per_robot_footprints)) return rc;
-  if (!stamp_radii_ok(b->inscribed_radius, b->inflation_radius, b->cost_scaling_factor))
-    return fail(NEO_MPC_ERR_INVALID_ARGUMENT, "inscribed_radius %g, inflation_radius %g and cost_scaling_factor %g must be finite and not negative",
-                b->inscribed_radius, b->inflation_radius, b->cost_scaling_factor);
+  if (int rc = check_inflation_radii(b->inscribed_radius, b->inflation_radius, b->cost_scaling_factor)) return rc;
   if (b->count > 0 && !b->polygons && (!b->footprint || (!b->poses && !b->problems)))
     return fail(NEO_MPC_ERR_INVALID_ARGUMENT, "neither polygons nor a footprint with poses or problems");
   if (!h->has_map) return fail(NEO_MPC_ERR_NO_COSTMAP, "the handle holds no costmap");
   if (h->map.pool_count <= 0) return fail(NEO_MPC_ERR_UNSUPPORTED, "the handle holds a single costmap, not a pool");
   if (b->count > 0 && b->count != (size_t)h->map.pool_count)
     return fail(NEO_MPC_ERR_INVALID_ARGUMENT, "%zu robots for a pool of %d windows: they are one to one", b->count, h->map.pool_count);
-  if (stamp_reach_cells(h->map.resolution, b->inflation_radius) < 0)
-    return fail(NEO_MPC_ERR_UNSUPPORTED, "inflation_radius %g at resolution %g is more than %d cells", b->inflation_radius,
-                h->map.resolution, NEO_MPC_MAX_INFLATION_CELLS);
-  return NEO_MPC_OK;
+  return inflation_reach(h->map.resolution, b->inscribed_radius, b->inflation_radius, b->cost_scaling_factor, "", nullptr);
 }
 
 // `d`: the record with device pointers.  Orders itself like roll(): it rewrites the device maps in place.
 static int stamp(neo_mpc_handle* h, const neo_mpc_stamp_batch& d, void* stream) {
   const size_t n = d.count, np = d.footprint_points;
-  const double key[4] = {h->map.resolution, d.inscribed_radius, d.inflation_radius, d.cost_scaling_factor};
-  // the stamp of every tick -- same parameters as the previous one -- finds its table in place: nothing is built, allocated
-  // or copied, so the call can be captured in a graph
-  const bool same = h->has_stamp_table && std::memcmp(key, h->stamp_key, sizeof(key)) == 0;
-  int rc;
-  if (!same) {
-    const int reach = stamp_reach_cells(key[0], key[2]);
-    std::vector<uint8_t> table((size_t)reach * reach + 1);
-    stamp_costs(key[0], key[1], key[3], reach, table.data());
-    // (a stamp in flight reads the old table: every stamp ends a write of the fence)
-    if ((rc = h->fence.wait_writer_host())) return rc;
-    h->has_stamp_table = false;
-    if (!h->stamp_table.upload(table.data(), table.size())) return NEO_MPC_ERR_DEVICE;
-    std::memcpy(h->stamp_key, key, sizeof(key));
-    h->stamp_reach = reach;
-    h->has_stamp_table = true;
-  }
+  // (every stamp ends a write of the fence)
+  int rc = h->stamp_table.build(h->map.resolution, d.inscribed_radius, d.inflation_radius, d.cost_scaling_factor, h->fence);
+  if (rc) return rc;
   // (no-ops from the second call with this count and footprint_points on)
   if ((rc = h->stamp_boxes.reserve(n * 32))) return rc;
   if (!d.polygons && (rc = h->stamp_polys.reserve(n * np * 16))) return rc;
@@ -1511,13 +1523,13 @@ static int stamp(neo_mpc_handle* h, const neo_mpc_stamp_batch& d, void* stream) 
   a.polygons = d.polygons;
   if (!d.polygons) { a.footprint = d.footprint; a.poses = d.poses; a.problems = d.poses ? nullptr : d.problems; }
   a.polys = h->stamp_polys.as<double>(); a.boxes = h->stamp_boxes.as<double>();
-  a.table = h->stamp_table.as<const uint8_t>();
+  a.table = h->stamp_table.buf.as<const uint8_t>();
   a.cells = const_cast<uint8_t*>(h->map.cells);   // (cell (0, 0) of the first map of map_buf, the handle's own)
   a.origins = h->map.pool_origins;
   a.res = h->map.resolution;
   a.stride = h->map.pool_stride;
   a.size_x = h->map.size_x; a.size_y = h->map.size_y; a.pitch = h->map.pitch;
-  a.reach = h->stamp_reach;
+  a.reach = h->stamp_table.reach;
   a.count = (uint32_t)n; a.points = d.footprint_points; a.per_robot = d.per_robot_footprints;
   launch_stamp(a, stream);
   HIP_TRY(hipGetLastError());
@@ -1563,41 +1575,24 @@ int neo_mpc_stamp_fleet(neo_mpc_handle* h, const neo_mpc_stamp_batch* b) {
 // itself like set_world_map's copy -- they write the same buffer -- on `stream`, or on the host and the null stream.
 static int inflate_world_map(neo_mpc_handle* h, double ins, double infl, double csf, bool on_device, void* stream) {
   if (!h) return fail(NEO_MPC_ERR_INVALID_ARGUMENT, "null handle");
-  if (!stamp_radii_ok(ins, infl, csf))
-    return fail(NEO_MPC_ERR_INVALID_ARGUMENT, "inscribed_radius %g, inflation_radius %g and cost_scaling_factor %g must be finite and not negative", ins, infl, csf);
-  if (!h->has_world) return fail(NEO_MPC_ERR_NO_COSTMAP, "neo_mpc_set_world_map has not been called");
-  const double key[4] = {h->world_resolution, ins, infl, csf};
-  const int reach = stamp_reach_cells(key[0], infl);
-  if (reach < 0)
-    return fail(NEO_MPC_ERR_UNSUPPORTED, "inflation_radius %g at the world map's resolution %g is more than %d cells", infl, key[0],
-                NEO_MPC_MAX_INFLATION_CELLS);
+  int rc = check_inflation_radii(ins, infl, csf);
+  if (rc) return rc;
+  WorldMap& w = h->world;
+  if (!w.has) return fail(NEO_MPC_ERR_NO_COSTMAP, "neo_mpc_set_world_map has not been called");
+  if ((rc = inflation_reach(w.resolution, ins, infl, csf, "the world map's ", nullptr))) return rc;
   HIP_TRY(hipSetDevice(h->device));
-  // the inflation behind every new copy of the map -- same parameters as the previous one -- finds its table in place: nothing is
-  // built, allocated or copied, so the call can be captured in a graph
-  int rc;
-  if (!(h->has_world_table && std::memcmp(key, h->world_key, sizeof(key)) == 0)) {
-    std::vector<uint8_t> table((size_t)reach * reach + 1);
-    stamp_costs(key[0], ins, csf, reach, table.data());
-    // (an inflation in flight reads the old table: every inflation records world_ready behind itself)
-    HIP_TRY(hipEventSynchronize(h->world_ready));
-    h->has_world_table = false;
-    if ((rc = h->world_table.reserve((size_t)NEO_MPC_MAX_INFLATION_CELLS * NEO_MPC_MAX_INFLATION_CELLS + 1))) return rc;   // (once)
-    if (!h->world_table.upload(table.data(), table.size())) return NEO_MPC_ERR_DEVICE;
-    std::memcpy(h->world_key, key, sizeof(key));
-    h->world_reach = reach;
-    h->has_world_table = true;
-  }
+  if ((rc = h->world_table.build(w.resolution, ins, infl, csf, w))) return rc;   // (every inflation records the world's event)
   hipStream_t st = (hipStream_t)stream;
-  if ((rc = begin_world_write(h, on_device, st))) return rc;
+  if ((rc = w.begin_write(h->fence, on_device, st))) return rc;
   InflateArgs a;
   std::memset(&a, 0, sizeof(a));
-  a.world = h->world_buf.as<uint8_t>();
-  a.table = h->world_table.as<const uint8_t>();
-  a.wsx = h->world_size_x; a.wsy = h->world_size_y;
-  a.reach = h->world_reach;
+  a.world = w.buf.as<uint8_t>();
+  a.table = h->world_table.buf.as<const uint8_t>();
+  a.wsx = w.size_x; a.wsy = w.size_y;
+  a.reach = h->world_table.reach;
   launch_inflate_world(a, stream);
   HIP_TRY(hipGetLastError());
-  return end_world_write(h, st);   // a roll behind it, on whatever stream, cuts its windows from the inflated map
+  return w.end_write(st);   // a roll behind it, on whatever stream, cuts its windows from the inflated map
 }
 
 int neo_mpc_inflate_world_map_device(neo_mpc_handle* h, double ins, double infl, double csf, void* stream) {

@@ -9,8 +9,8 @@
 //
 //   K1 k_solve        k1_solve.h; this unit holds its dense-Newton and L-BFGS variants, neo_mpc_riccati.hip the others.
 //   K2 postprocess    py:365-403, fused as the epilogue of K1 and launchable on its own.
-//   K3 k_ingest       raw nav2 costmap -> device map with a lethal border and 128-byte
-//                     row pitch (16 B per lane, HBM-streaming).
+//   K3 k_ingest       costmap_ingest.h: raw nav2 costmap -> device map with a lethal border and 128-byte row pitch (16 B per
+//                     lane, HBM-streaming); the stream over a padded map and its grid, which K7's fill shares.
 //   K4 k_carrot       the step before the solver: plan pruning + look-ahead point
 //                     (src/NeoMpcPlanner.cpp:83-104, 157-189, 221-232), HBM-streaming.
 //   k_objective       py:204-269 for given controls (parity checks of the objective).
@@ -18,8 +18,9 @@
 //   K6 k_footprint_gate  footprint_gate.h: the footprint gate in front of the carrot (cpp:218-219), one wave per robot.
 //   K7 k_roll_index, k_roll_fill  rolling_window.h: a fleet's rolling costmap windows cut from one world map, HBM-streaming.
 //   K8 k_stamp_boxes, k_stamp_fleet  fleet_stamp.h: the fleet's robots stamped into each other's windows, inflation ring included.
-//   K9 k_inflate_world  world_inflation.h: nav2's inflation layer on the world map the windows are cut from, in place.
+//   K9 k_inflate_world  world_inflation.h: nav2's inflation layer on the world map, in place (inflation.h: what it shares with K8).
 #include "k1_solve.h"
+#include "costmap_ingest.h"
 #include "footprint_gate.h"
 #include "rolling_window.h"
 #include "fleet_stamp.h"
@@ -112,63 +113,6 @@ __global__ __launch_bounds__(256) void k_objective(const ObjectiveArgs a) {
   const double eth = final_yaw - z;                                       // py:267
   total += ((w_trans * (gdist * gdist)) + (w_orient * (eth * eth))) * a.w_terminal;   // py:268
   a.cost[b] = total;
-}
-
-// K3: raw nav2 costmap -> bordered, pitched device map.  One 16-byte store per lane and chunk; kIngestUnroll chunks per
-// thread with every load issued before the first store (memory-level parallelism: the kernel is a pure stream).
-constexpr int kIngestUnroll = 4;
-typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-__device__ __forceinline__ u32x4 ingest_chunk(const IngestArgs& a, unsigned idx, unsigned chunks_per_row) {
-  const int row = (int)(idx / chunks_per_row), chunk = (int)(idx - (unsigned)row * chunks_per_row);
-  const int my = row - a.border;
-  const int mx0 = chunk * 16 - a.border;
-  u32x4 v = {0xFEFEFEFEu, 0xFEFEFEFEu, 0xFEFEFEFEu, 0xFEFEFEFEu};
-  if (my >= 0 && my < a.size_y && mx0 >= 0 && mx0 + 16 <= a.size_x && (a.size_x & 7) == 0) {
-    // interior chunk of a map whose rows are 8-byte aligned (mx0 is a multiple of 16): two 8-byte loads
-    typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
-    const u32x2* src8 = reinterpret_cast<const u32x2*>(a.src + (long)my * a.size_x + mx0);
-    const u32x2 lo = __builtin_nontemporal_load(src8), hi = __builtin_nontemporal_load(src8 + 1);
-    v = u32x4{lo.x, lo.y, hi.x, hi.y};
-  } else if (my >= 0 && my < a.size_y && mx0 >= 0 && mx0 + 16 <= a.size_x && (a.size_x & 3) == 0) {
-    const uint32_t* src4 = reinterpret_cast<const uint32_t*>(a.src + (long)my * a.size_x + mx0);
-    v = u32x4{src4[0], src4[1], src4[2], src4[3]};
-  } else if (my >= 0 && my < a.size_y && mx0 >= 0 && mx0 < a.size_x && (a.size_x & 3) == 0) {
-    // the chunk that straddles the right edge of a map whose width is a multiple of 4 (200-cell windows: 8 of its 16
-    // bytes): whole dwords, lethal beyond the edge
-    const uint32_t* src4 = reinterpret_cast<const uint32_t*>(a.src + (long)my * a.size_x + mx0);
-    const int valid = (a.size_x - mx0) >> 2;   // 1..3 dwords
-    v = u32x4{src4[0], valid > 1 ? src4[1] : 0xFEFEFEFEu, valid > 2 ? src4[2] : 0xFEFEFEFEu, 0xFEFEFEFEu};
-  } else if (my >= 0 && my < a.size_y && mx0 + 16 > 0 && mx0 < a.size_x) {
-    uint8_t bytes[16];
-    const uint8_t* src = a.src + (long)my * a.size_x;
-#pragma unroll
-    for (int k = 0; k < 16; ++k) {
-      const int mx = mx0 + k;
-      bytes[k] = (mx >= 0 && mx < a.size_x) ? src[mx] : (uint8_t)254;
-    }
-    v = *reinterpret_cast<const u32x4*>(bytes);
-  }
-  return v;
-}
-__global__ __launch_bounds__(256) void k_ingest(const IngestArgs args) {
-  IngestArgs a = args;   // blockIdx.y: which map of a pool
-  a.src += (long)blockIdx.y * a.size_x * a.size_y;
-  a.dst += (long)blockIdx.y * a.dst_stride;
-  const unsigned chunks_per_row = (unsigned)a.pitch >> 4;
-  const unsigned total = (unsigned)a.rows * chunks_per_row;   // (< 2^31: rows, pitch <= 2^20 + 256 and pitch/16 per row)
-  const unsigned stride = gridDim.x * blockDim.x;
-  for (unsigned base = blockIdx.x * blockDim.x + threadIdx.x; base < total; base += kIngestUnroll * stride) {
-    u32x4 v[kIngestUnroll];
-#pragma unroll
-    for (int k = 0; k < kIngestUnroll; ++k)
-      if (base + k * stride < total) v[k] = ingest_chunk(a, base + k * stride, chunks_per_row);
-    // streamed once, read back sparsely (reach tiles): non-temporal, so the stream does not wait for
-    // L2 lines to be allocated (measured: 3.0 -> 4.3 TB/s over a pool of 4096 windows)
-#pragma unroll
-    for (int k = 0; k < kIngestUnroll; ++k)
-      if (base + k * stride < total)
-        __builtin_nontemporal_store(v[k], reinterpret_cast<u32x4*>(a.dst) + (base + k * stride));
-  }
 }
 
 // K4: carrot selection, one wavefront per robot.  Lanes stride over the plan poses (24 B each,
@@ -395,10 +339,7 @@ void launch_roll(const RollArgs& a, void* stream) {
   if (a.count == 0) return;
   hipLaunchKernelGGL(k_roll_index, dim3((a.count + kRollWaves - 1) / kRollWaves), dim3(kLanes * kRollWaves), 0,
                      (hipStream_t)stream, a);
-  const long total = (long)a.rows * (a.pitch >> 4);
-  int blocks = (int)((total + 256L * kRollUnroll - 1) / (256L * kRollUnroll));
-  if (blocks > 2048) blocks = 2048;
-  hipLaunchKernelGGL(k_roll_fill, dim3(blocks, a.count), dim3(256), 0, (hipStream_t)stream, a);
+  hipLaunchKernelGGL(k_roll_fill, padded_map_grid(a.rows, a.pitch, kRollUnroll, a.count), dim3(256), 0, (hipStream_t)stream, a);
 }
 // K8: polygons and bounding boxes first (one thread per robot), then one wave per window -- two launches, so that every box is
 // final before any window searches the fleet
@@ -414,12 +355,8 @@ void launch_inflate_world(const InflateArgs& a, void* stream) {
                      dim3(kLanes * kInflateWaves), 0, (hipStream_t)stream, a);
 }
 void launch_ingest(const IngestArgs& a, const LaunchTuning& tuning, void* stream) {
-  const long total = (long)a.rows * (a.pitch >> 4);
-  // a few 16-byte chunks per thread: one-chunk threads make the launch dispatch-bound for pools of small maps
-  const int per_thread = kIngestUnroll;
-  int blocks = (int)((total + 256L * per_thread - 1) / (256L * per_thread));
-  if (blocks > 2048) blocks = 2048;
-  hipLaunchKernelGGL(k_ingest, dim3(blocks, a.maps > 0 ? a.maps : 1), dim3(256), 0, (hipStream_t)stream, a);
+  hipLaunchKernelGGL(k_ingest, padded_map_grid(a.rows, a.pitch, kIngestUnroll, a.maps > 0 ? a.maps : 1), dim3(256), 0,
+                     (hipStream_t)stream, a);
 }
 
 }  // namespace neo_mpc

@@ -6,6 +6,7 @@
 #include <math.h>
 #include <stdint.h>
 
+#include "costmap_ingest.h"
 #include "neo_mpc_device.h"
 #include "wave_ops.h"
 
@@ -13,7 +14,7 @@ namespace neo_mpc {
 namespace {
 
 constexpr int kRollWaves = 4;        // windows per workgroup of k_roll_index: one wave each, no LDS, no barrier
-constexpr int kRollUnroll = 4;       // 16-byte chunks per thread of k_roll_fill, every load in front of the first store
+constexpr int kRollUnroll = 4;       // 16-byte chunks per thread of k_roll_fill
 constexpr int kRollOutside = -1;     // index table: worldToMap refuses this column / row -> outside_value
 constexpr int kRollLethal = -2;      // index table: a column beyond the window's right edge (table padding) -> 254
 
@@ -62,15 +63,12 @@ __global__ __launch_bounds__(kLanes * kRollWaves) void k_roll_index(const RollAr
   for (int j = lane; j < a.size_y; j += kLanes) ty[j] = roll_cell(oy, j, a.res, a.woy, a.wres, a.wsy);
 }
 
-// K7b: the fill, K3's shape -- one 16-byte non-temporal store per lane and chunk over the whole padded map, 254 in the border
-// and the pitch padding -- with gathered bytes of the world map (a few MB: it stays in cache) as the source.
-typedef uint32_t roll_u32x4 __attribute__((ext_vector_type(4)));
+// K7b: the fill, K3's stream (costmap_ingest.h: stream_padded_map) -- 254 in the border and the pitch padding -- with gathered
+// bytes of the world map (a few MB: it stays in cache) as the source.
 typedef int32_t roll_i32x4 __attribute__((ext_vector_type(4)));
-__device__ __forceinline__ roll_u32x4 roll_chunk(const RollArgs& a, const int32_t* tx, unsigned idx, unsigned chunks_per_row) {
-  const int row = (int)(idx / chunks_per_row), chunk = (int)(idx - (unsigned)row * chunks_per_row);
-  const int my = row - a.border;
-  const int mx0 = chunk * 16 - a.border;               // (the border is a multiple of 16: a chunk never straddles column 0)
-  roll_u32x4 v = {0xFEFEFEFEu, 0xFEFEFEFEu, 0xFEFEFEFEu, 0xFEFEFEFEu};
+__device__ __forceinline__ u32x4 roll_chunk(const RollArgs& a, const int32_t* tx, int my, int mx0) {
+  // (the border is a multiple of 16: a chunk never straddles column 0)
+  u32x4 v = {0xFEFEFEFEu, 0xFEFEFEFEu, 0xFEFEFEFEu, 0xFEFEFEFEu};
   if (my >= 0 && my < a.size_y && mx0 >= 0 && mx0 < a.size_x) {
     const int wy = tx[a.tab_x + my];
     const uint8_t* wrow = a.world + (int64_t)(wy < 0 ? 0 : wy) * a.wsx;
@@ -89,27 +87,13 @@ __device__ __forceinline__ roll_u32x4 roll_chunk(const RollArgs& a, const int32_
       }
       w[g] = word;
     }
-    v = roll_u32x4{w[0], w[1], w[2], w[3]};
+    v = u32x4{w[0], w[1], w[2], w[3]};
   }
   return v;
 }
-__global__ __launch_bounds__(256) void k_roll_fill(const RollArgs args) {
-  RollArgs a = args;   // blockIdx.y: which window
-  const int32_t* tx = a.tables + (size_t)blockIdx.y * a.tab_stride;
-  a.dst += (int64_t)blockIdx.y * a.dst_stride;
-  const unsigned chunks_per_row = (unsigned)a.pitch >> 4;
-  const unsigned total = (unsigned)a.rows * chunks_per_row;   // (< 2^31: checked on the host, like K3's)
-  const unsigned stride = gridDim.x * blockDim.x;
-  for (unsigned base = blockIdx.x * blockDim.x + threadIdx.x; base < total; base += kRollUnroll * stride) {
-    roll_u32x4 v[kRollUnroll];
-#pragma unroll
-    for (int k = 0; k < kRollUnroll; ++k)
-      if (base + k * stride < total) v[k] = roll_chunk(a, tx, base + k * stride, chunks_per_row);
-#pragma unroll
-    for (int k = 0; k < kRollUnroll; ++k)
-      if (base + k * stride < total)
-        __builtin_nontemporal_store(v[k], reinterpret_cast<roll_u32x4*>(a.dst) + (base + k * stride));
-  }
+__global__ __launch_bounds__(256) void k_roll_fill(const RollArgs a) {
+  const int32_t* tx = a.tables + (size_t)blockIdx.y * a.tab_stride;   // blockIdx.y: which window
+  stream_padded_map<kRollUnroll>(a, blockDim.x, [&](int my, int mx0) { return roll_chunk(a, tx, my, mx0); });
 }
 
 }  // namespace

@@ -4,18 +4,18 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "inflation.h"
 #include "neo_mpc_device.h"
 #include "wave_ops.h"
 
 namespace neo_mpc {
 namespace {
 
+constexpr int kInflateFar = 1 << 12;   // "no seed in this row": its square is beyond every R^2, and fits an int with d^2 added
 constexpr int kInflateTile = 64;    // a workgroup owns 64 x 64 cells: lane = column, one 64-bit word per row and 64 columns
 constexpr int kInflateWaves = 4;    // ... its waves take the rows in turn
 constexpr int kInflateLoads = 8;    // ... each with this many row words in flight
 constexpr int kInflateRows =kInflateTile + 2 * NEO_MPC_MAX_INFLATION_CELLS;   // the tile's rows and the largest halo
-constexpr int kInflateTableBytes = (NEO_MPC_MAX_INFLATION_CELLS * NEO_MPC_MAX_INFLATION_CELLS + 1 + 15) & ~15;
-constexpr int kInflateFar = 1 << 12;   // "no seed in this row": its square is beyond every R^2, and fits an int with d^2 added
 
 // Distance along a row from column 64 + c of a 192-column row (m0: columns 0 .. 63, m1: 64 .. 127, m2: 128 .. 191; bit b of
 // a word = its column b; 0 <= c < 64) to the row's nearest set bit -- K8's stamp_row_distance over three words.  Exact up to 64,
@@ -50,7 +50,7 @@ __device__ __forceinline__ int inflate_row_distance(uint64_t m0, uint64_t m1, ui
 // wave run every turn of step 1's loop).
 __global__ __launch_bounds__(kLanes * kInflateWaves) void k_inflate_world(const InflateArgs a) {
   __shared__ uint64_t masks[kInflateRows * 3];
-  __shared__ uint8_t table[kInflateTableBytes];
+  __shared__ uint8_t table[kInflationTableBytes];
   __shared__ int seen[kInflateWaves];
   const int lane = threadIdx.x & (kLanes - 1), wave = uniform_int((int)(threadIdx.x >> 6));
   const int R = a.reach, sx = a.wsx, sy = a.wsy;
@@ -81,31 +81,19 @@ __global__ __launch_bounds__(kLanes * kInflateWaves) void k_inflate_world(const 
   if (lane == 0) seen[wave] = any ? 1 : 0;
   __syncthreads();
   const bool some = (seen[0] | seen[1] | seen[2] | seen[3]) != 0;   // the same in every lane of the workgroup
-  if (some)
-    for (int t = (int)threadIdx.x; t <= R * R; t += kLanes * kInflateWaves) table[t] = a.table[t];
+  if (some) inflation_stage_table(table, a.table, R, (int)threadIdx.x, kLanes * kInflateWaves);
   __syncthreads();
   if (!some) return;
-  const int i = tx + lane, reach2 = R * R;
+  const int i = tx + lane;
   for (int k = wave; k < kInflateTile && ty + k < sy; k += kInflateWaves) {
     const int l = ty + k, r0 = k + R;                  // the cell's row in the map and in the masks
-    int best = reach2 + 1;
-    for (int d = 0; d <= R && d * d < best; ++d) {     // (0 <= r0 - d and r0 + d < rows)
-      const uint64_t* up = masks + 3 * (r0 + d);
-      const uint64_t u0 = up[0], u1 = up[1], u2 = up[2];
-      if (u0 | u1 | u2) { const int hd = inflate_row_distance(u0, u1, u2, lane), v = d * d + hd * hd; best = v < best ? v : best; }
-      if (d > 0) {
-        const uint64_t* down = masks + 3 * (r0 - d);
-        const uint64_t d0 = down[0], d1 = down[1], d2 = down[2];
-        if (d0 | d1 | d2) { const int hd = inflate_row_distance(d0, d1, d2, lane), v = d * d + hd * hd; best = v < best ? v : best; }
-      }
-    }
-    if (best <= reach2 && i < sx) {
-      // nav2's inflation rule, inflate_unknown false
-      uint8_t* p = a.world + (int64_t)l * sx + i;      // 0 <= i < wsx, 0 <= l < wsy: this tile's own cell
-      const int cost = table[best], old = *p;
-      const int now = old == 255 ? (cost >= 253 ? cost : 255) : (cost > old ? cost : old);
-      if (now != old) *p = (uint8_t)now;
-    }
+    const int best = inflation_scan(R, [&](int dy, auto&& found) {   // (0 <= r0 - R and r0 + R < rows)
+      const uint64_t* m = masks + 3 * (r0 + dy);
+      const uint64_t m0 = m[0], m1 = m[1], m2 = m[2];
+      if (m0 | m1 | m2) found(inflate_row_distance(m0, m1, m2, lane));   // (a row without a seed is skipped)
+    });
+    // 0 <= i < wsx, 0 <= l < wsy: this tile's own cell
+    if (best <= R * R && i < sx) inflation_combine(a.world + (int64_t)l * sx + i, table, best);
   }
 }
 

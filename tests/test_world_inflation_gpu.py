@@ -1,13 +1,16 @@
 """The world inflation (K9) on the GPU: neo_mpc_inflate_world_map[_device] and neo_mpc_get_world_map against the
 transcription of tests/world_inflation_reference.py -- exact equality of uint8 cells, no tolerance, no dropped case -- and
-the call's place in the chain: set -> inflate -> roll, its refusals, a HIP graph on one stream, and its order against a roll
-on another stream (the delay and its validity conditions are those of tests/test_stream_ordering.py, imported)."""
+the call's place in the chain: set -> inflate -> roll, its refusals, a HIP graph on one stream, its order against a roll
+on another stream (the delay and its validity conditions are those of tests/test_stream_ordering.py, imported), and K9 and
+the fleet stamp (K8) on one handle, each with a cost table of its own that changes between the calls."""
 import ctypes as C
 import functools
 
 import numpy as np
 import pytest
 
+from tests import fleet_stamp_reference as stamp_ref
+from tests import footprint_gate_reference as gate_ref
 from tests import rolling_window_reference as roll_ref
 from tests import test_stream_ordering as so          # helpers only: the module object holds its tests, this one collects none
 from tests import test_world_inflation as cpu
@@ -248,3 +251,63 @@ def test_the_inflation_waits_for_the_held_roll(rig):
 
     so.run(r, prepare, [so.Step("H", r.roll), so.Step("A", lambda: r.s.inflate_world_map(*PARAMS))] + r.readback("raw windows"),
            [("raw windows", "inflated windows", "any")], check=check)
+
+
+# ------------------------------------------------------------------------------------------ 10: K9 and K8 on one handle
+CHAIN_WORLD = ((0.45, 0.9, 3.0), (0.2, 0.3, 5.0))             # the inflation's parameters by round: R = 18, 6 at 5 cm
+CHAIN_STAMP = ((0.3, 0.6, 4.0), (0.45, 1.2, 2.0))             # the stamp's: R = 6, 12 at 0.1 m
+CHAIN_RECT = ((0.3, 0.2), (-0.3, 0.2), (-0.3, -0.2), (0.3, -0.2))       # the shared footprint, 0.6 x 0.4 m
+CHAIN_WINDOW = (36, 20, 0.1)
+
+
+@functools.lru_cache(maxsize=None)
+def chain_case():
+    """(world, resolution, poses, start origins, [(origins, pool) after each round]) by the chain of the three transcriptions
+    -- inflate_world, roll, stamp_pool -- with the asserts that the case tells the two cost tables apart: every stage changes
+    cells, and either kernel with the other's table gives another result."""
+    _, world, res, _, _ = cpu.cases()[16]
+    assert world.shape == (75, 130) and res == 0.05 and (world == 254).sum() == 24
+    wox, woy = GEOMETRY
+    poses = np.array([(wox + 2.0, woy + 1.6, 0.3), (wox + 2.9, woy + 2.0, 1.0), (wox + 3.6, woy + 1.5, -2.0)])
+    start = poses[:, :2] - (1.8, 1.0) + 0.013
+    polygons = np.array([gate_ref.oriented(pose, CHAIN_RECT) for pose in poses])
+    origins, rounds, counts = start, [], []
+    for world_params, stamp_params in zip(CHAIN_WORLD, CHAIN_STAMP):
+        world_table, stamp_table = ref.table_for(res, *world_params), stamp_ref.inflation_costs(CHAIN_WINDOW[2], *stamp_params)
+        inflated = ref.inflate(world, *world_table)
+        origins, cut = roll_ref.roll(inflated, res, wox, woy, origins, *CHAIN_WINDOW, poses=poses, outside_value=255)
+        pool = stamp_ref.stamp_pool(cut, origins, CHAIN_WINDOW[2], polygons, *stamp_params)
+        changed = [int((pool[k] != cut[k]).sum()) for k in range(3)]
+        crossed = np.stack([stamp_ref.stamp_window(cut[k], origins[k], CHAIN_WINDOW[2], np.delete(polygons, k, axis=0), *world_table)[0]
+                            for k in range(3)])
+        print("R = %d, %d: the inflation changes %d cells (%d others with the stamp's table), the stamp %s (%d others with the "
+              "world's table)" % (world_table[1], stamp_table[1], (inflated != world).sum(),
+                                  (ref.inflate(world, *stamp_table) != inflated).sum(), changed, (crossed != pool).sum()))
+        assert (inflated != world).any() and all(changed)
+        assert (crossed != pool).any() and (ref.inflate(world, *stamp_table) != inflated).any()
+        counts.append(((inflated != world).sum(), changed, (crossed != pool).sum(), (ref.inflate(world, *stamp_table) != inflated).sum()))
+        pool.setflags(write=False)
+        rounds.append((origins, pool))
+    assert not np.array_equal(rounds[0][1], rounds[1][1])
+    assert counts == [(8519, [98, 209, 116], 675, 7962), (2204, [334, 552, 355], 683, 4484)]        # the case, pinned down
+    return world, res, poses, start, rounds
+
+
+@pytest.mark.parametrize("where", ("host", "device"))
+def test_inflation_and_stamp_on_one_handle_keep_their_tables_apart(where):
+    """set -> inflate -> roll -> stamp twice on one handle, the inflation's and the stamp's parameters -- and reach --
+    different from each other and changed between the rounds: after each round the pool is the chain of the three
+    transcriptions, exactly.  NumPy arrays through the host calls, CUDA tensors through the device calls."""
+    import torch
+    world, res, poses, start, rounds = chain_case()
+    put = (lambda a: np.array(a)) if where == "host" else (lambda a: torch.from_numpy(np.array(a)).to(DEV))
+    footprint, d_poses, origins = put(np.asarray(CHAIN_RECT)), put(poses), put(start)
+    with solver() as s:
+        for world_params, stamp_params, (want_origins, want) in zip(CHAIN_WORLD, CHAIN_STAMP, rounds):
+            s.set_world_map(put(world), res, *GEOMETRY)
+            s.inflate_world_map(*world_params)
+            s.roll_costmap_pool(*CHAIN_WINDOW, origins, poses=d_poses)
+            s.stamp_fleet(*stamp_params, footprint=footprint, poses=d_poses)
+            got, back = s.get_costmap_pool()
+            assert back.tolist() == want_origins.tolist()
+            assert np.array_equal(got, want), (where, world_params, stamp_params, int((got != want).sum()))
