@@ -41,6 +41,9 @@ extern "C" {
  * entry points in the same way: still ABI 2, behaviour 6.
  * The world inflation (neo_mpc_inflate_world_map[_device], neo_mpc_get_world_map) added three entry points and no record:
  * still ABI 2, behaviour 6.
+ * The scan obstacle layer (neo_mpc_scan_batch, neo_mpc_update_scan_layer[_device], neo_mpc_get_scan_layer,
+ * neo_mpc_reset_scan_layer, NEO_MPC_MAX_SCAN_POINTS) added a record, four entry points and a constant in the same way: still
+ * ABI 2, behaviour 6.
  *
  * Behaviour history (iterates and iteration counts differ between versions, results stay inside the parity protocol of
  * DESIGN.md section 1; neo_mpc_behaviour_version() returns the number of the build that answers):
@@ -354,7 +357,8 @@ typedef struct neo_mpc_footprint_batch {
  * Out of scope: a tf transform between the world map's frame and the windows' (they are one frame); `use_maximum`; further
  * layers (the world map IS the master grid the caller wants sampled, inflation included: a caller that holds a raw occupancy
  * grid gets nav2's inflation from neo_mpc_inflate_world_map below, between neo_mpc_set_world_map and the rolls).  The other robots of the fleet
- * are stamped into the windows by the step behind the roll: neo_mpc_stamp_batch below (K8).
+ * are stamped into the windows by the step behind the roll: neo_mpc_stamp_batch below (K8); what the sensors see, by
+ * neo_mpc_scan_batch (K10).
  * Pointers are host pointers for neo_mpc_roll_costmap_pool and device pointers for neo_mpc_roll_costmap_pool_device.
  * 56 bytes. */
 typedef struct neo_mpc_window_batch {
@@ -431,6 +435,110 @@ typedef struct neo_mpc_stamp_batch {
   double cost_scaling_factor;      /* 1/m; >= 0, finite */
   uint64_t reserved;               /* MUST be zero */
 } neo_mpc_stamp_batch;
+
+/* ---- the step between the roll and the stamp: an obstacle layer fed from sensor points (K10) ---------- */
+
+#define NEO_MPC_MAX_SCAN_POINTS 8192u
+#define NEO_MPC_SCAN_CLEAR 1u   /* raytrace the layer free from the sensor origin to every point */
+#define NEO_MPC_SCAN_MARK  2u   /* mark the points' cells lethal in the layer */
+
+/* What is neither on the world map nor a member of the fleet -- a pallet left in an aisle, a person, another vendor's robot --
+ * reaches a window through nav2's obstacle layer.  neo_mpc_update_scan_layer keeps one such layer per window in the handle:
+ * it rolls with its window, is cleared along this tick's sensor rays and marked at their end points (nav2 Humble's
+ * ObstacleLayer::raytraceFreespace, Costmap2D::raytraceLine, bresenham2D and the marking loop of
+ * ObstacleLayer::updateBounds), is combined into the window with updateWithMax and inflated around its own lethal cells
+ * with the cost table and combination rule of neo_mpc_stamp_batch.  The tick is roll -> scan -> stamp -> gate -> carrots ->
+ * solve.  The scan step comes BEFORE the stamp: a ray that turns an unknown cell free would otherwise erase a stamp ring that
+ * left it at 255.
+ *
+ * Input: points, not ranges.  nav2's obstacle layer consumes Observations: a sensor origin and a cloud of hit points already
+ * in the costmap's global frame; the projection of a LaserScan and the tf transform happen in front of it (laser_geometry,
+ * ObservationBuffer).  The record takes the same thing, one observation per robot and tick.  Out of scope: projecting ranges
+ * to points; a z coordinate (min / max_obstacle_height); more than one observation per robot and tick;
+ * observation_persistence; footprint_clearing_enabled -- obstacle_min_range is the stand-in for a scanner that sees its own
+ * robot.
+ *
+ * Like neo_mpc_stamp_batch's, the contract is one by transcription: nav2 cannot be built next to this library, so the text
+ * below is the contract (tests/scan_layer_reference.py is its executable form).  Neither is pinned against nav2 itself: nav2's
+ * layers are not available to the tests.  Everything below is float64 + - * /, one sqrt of an exact integer, comparisons and
+ * integer arithmetic; every floating-point operation is ONE correctly rounded operation in the order written (nothing fused,
+ * no reciprocal).
+ *
+ * Window k of the handle's pool has sx x sy cells, resolution res and origin (ox, oy), as the last roll or
+ * neo_mpc_set_costmap_pool left them.  `count` must equal the pool's map count.  The layer of window k is a grid of the same
+ * size with values in {255, 0, 254} plus an origin (lx, ly).  It is kept by the handle.
+ *
+ * Reset.  The layer is unknown_value everywhere with (lx, ly) = (ox, oy): on the first update; after
+ * neo_mpc_reset_scan_layer; whenever sx, sy, res, the map count or unknown_value differ from the previous update's.  A pool
+ * replaced with the same geometry keeps its layers.
+ *
+ * 1. Roll the layer.  This library's own rule: the layer follows its window instead of recomputing nav2's updateOrigin, so the
+ * two cannot drift apart.  qx = (ox - lx) / res, and cx = qx rounded to the nearest integer, ties to even.  If qx is not
+ * finite or |qx| >= sx, the whole layer becomes unknown_value.  cy is computed likewise.  New cell (i, l) = old cell
+ * (i + cx, l + cy) where that lies inside the grid, else unknown_value.  Then (lx, ly) <- (ox, oy).
+ *
+ * worldToMap(wx, wy).  It fails when a coordinate is not finite, or wx < ox, or wy < oy.  Else mx = trunc((wx - ox) / res)
+ * and my likewise.  It fails unless mx < sx and my < sy, compared in float64 before conversion.
+ *
+ * cellDistance(d) = (unsigned) max(0.0, ceil(d / res)), compared and clamped in float64 (above at 2^31 - 1, which no grid
+ * reaches).
+ *
+ * 2. Clear (with NEO_MPC_SCAN_CLEAR).  The sensor origin is (sx0, sy0).  If worldToMap of it fails, nothing of this robot is
+ * cleared.  Otherwise its cell is (x0, y0).  ex = ox + sx res and ey = oy + sy res.  M = cellDistance(raytrace_max_range) and
+ * m = cellDistance(raytrace_min_range).  For every point (wx, wy), skipped when a coordinate is not finite:
+ *   1. a = wx - sx0 and b = wy - sy0, once.
+ *   2. Four clips in order:
+ *        if wx < ox: t = (ox - sx0) / a; wx = ox; wy = sy0 + b t
+ *        if wy < oy: t = (oy - sy0) / b; wx = sx0 + a t; wy = oy
+ *        if wx > ex: t = (ex - sx0) / a; wx = ex - 0.001; wy = sy0 + b t
+ *        if wy > ey: t = (ey - sy0) / b; wx = sx0 + a t; wy = ey - 0.001
+ *   3. (x1, y1) = worldToMap of the result.  The point is skipped when it fails.
+ *   4. The line walk (raytraceLine): Dx = x1 - x0, Dy = y1 - y0, and dist = sqrt((double)(Dx^2 + Dy^2)) -- the argument of
+ *      the square root is the exact integer; nav2 calls hypot here.  If dist < m, nothing is cleared.  If dist > 0:
+ *      u0 = (unsigned)(x0 + Dx / dist m) and v0 likewise; else (u0, v0) = (x0, y0).  dx = x1 - u0 and dy = y1 - v0; the
+ *      signs are +1 when the difference is > 0, else -1.  scale = dist == 0 ? 1.0 : min(1.0, M / dist).  Major axis:
+ *      A = max(|dx|, |dy|) and B is the other; x is the major axis on a tie.  n = min(M, (unsigned)(scale A)).  Start at
+ *      (u0, v0) with e = A / 2 (integer division) and repeat n times: clear the cell; step one cell along the major axis;
+ *      e += B; if (unsigned)e >= A, step one cell along the minor axis and e -= A.  Then clear the cell reached.
+ *      "Clear" means layer cell <- 0.  Every cell the walk touches lies inside the grid.
+ *
+ * 3. Mark (with NEO_MPC_SCAN_MARK).  It runs after every clear of this update.  For every point, with the original
+ * coordinates and skipped when not finite: s = (wx - sx0) (wx - sx0) + (wy - sy0) (wy - sy0).  The point is skipped when
+ * s >= obstacle_max_range obstacle_max_range, or s < obstacle_min_range obstacle_min_range, or worldToMap fails.  Else layer
+ * cell <- 254.  A sensor origin off the map still marks.
+ *
+ * 4. Combine into the window (updateWithMax).  For every cell, v = layer value and old = window value.  v == 255 leaves the
+ * cell alone.  Else the cell becomes v when old == 255 or old < v.  Consequences: a cleared cell turns an unknown window
+ * cell free; with unknown_value 0 every unknown window cell becomes free, as nav2 does without track_unknown_space.
+ *
+ * 5. Inflate.  Seeds are the layer's cells equal to 254, inside the window only.  R, the table T and the combination are word
+ * for word those of neo_mpc_stamp_batch; T comes from neo_mpc_inflation_costs at res.  They are applied to the window values
+ * step 4 left.  Stated difference from nav2: the inflation of the world's own walls came with the roll (K9); a cell that
+ * step 4 turned from unknown to free does not get that inflation back; nav2 inflates after all layers have merged, so it
+ * would give it back.
+ *
+ * Not touched: the lethal border and pitch padding of the device maps, and the pool's `origins`.  The window part is not
+ * undone: the next roll cuts the windows afresh, and the layer persists.
+ *
+ * Idempotence.  An update repeated with the same batch, with no roll in between, changes neither layer nor pool.
+ *
+ * flags == 0 is a real use: scans arrive at 10 Hz and ticks run at 30 Hz; a roll cuts the windows afresh, so the layer has to
+ * be put into them again on the ticks between scans.
+ * Pointers are host pointers for neo_mpc_update_scan_layer and device pointers for neo_mpc_update_scan_layer_device.
+ * 104 bytes. */
+typedef struct neo_mpc_scan_batch {
+  size_t count;                   /* robots = windows: the pool's map count (0: nothing happens) */
+  const double* points;           /* [count][max_points][2] hit points, global frame; may be NULL when flags == 0 */
+  const uint32_t* point_counts;   /* optional [count]: robot k has point_counts[k] <= max_points points; NULL: max_points each */
+  const double* sensor_origins;   /* [count][2] Observation.origin_, global frame; may be NULL when flags == 0 */
+  uint32_t max_points;            /* 0 .. NEO_MPC_MAX_SCAN_POINTS */
+  uint32_t flags;                 /* NEO_MPC_SCAN_*; 0: no new observation -- the layer is rolled and applied again */
+  double obstacle_max_range, obstacle_min_range;   /* m, finite, >= 0 */
+  double raytrace_max_range, raytrace_min_range;   /* m, finite, >= 0 */
+  double inscribed_radius, inflation_radius, cost_scaling_factor;   /* as neo_mpc_stamp_batch */
+  uint32_t unknown_value;         /* the layer's default: 255 (nav2's track_unknown_space) or 0; anything else is refused */
+  uint32_t reserved;              /* MUST be zero */
+} neo_mpc_scan_batch;
 
 typedef struct neo_mpc_handle neo_mpc_handle;
 
@@ -706,6 +814,37 @@ int neo_mpc_stamp_fleet(neo_mpc_handle* handle, const neo_mpc_stamp_batch* batch
  * so like a roll it waits on its stream for the previous ingest, roll or stamp and for every launch still reading the maps,
  * and the gates and solves behind it wait for it. */
 int neo_mpc_stamp_fleet_device(neo_mpc_handle* handle, const neo_mpc_stamp_batch* batch, void* stream);
+
+/* Updates the windows' obstacle layers from one observation per robot and puts them into the windows (K10; the contract:
+ * neo_mpc_scan_batch).  Host pointers, synchronous.  Refusals, all of which leave pool and layers as they were:
+ * NEO_MPC_ERR_INVALID_ARGUMENT for a null handle or batch, a non-zero `reserved`, flag bits beyond the two, an unknown_value
+ * other than 0 or 255, max_points > NEO_MPC_MAX_SCAN_POINTS, a null `points` or `sensor_origins` with non-zero flags, a
+ * range, radius or scaling factor that is negative or not finite, a `count` that is not the pool's map count, and -- in this
+ * variant only -- a point_counts[k] > max_points or a sensor origin that is not finite; NEO_MPC_ERR_NO_COSTMAP without a
+ * costmap; NEO_MPC_ERR_UNSUPPORTED for a single costmap instead of a pool, and for R > NEO_MPC_MAX_INFLATION_CELLS.
+ * count == 0 is NEO_MPC_OK and does nothing. */
+int neo_mpc_update_scan_layer(neo_mpc_handle* handle, const neo_mpc_scan_batch* batch);
+/* Same with every pointer in device memory; enqueued on `stream`, returns without waiting; no value behind a pointer is
+ * looked at on the host: a point_counts[k] beyond max_points is clamped to it, and a sensor origin that is not finite fails
+ * worldToMap.  Ordering, both variants: an update is a write of the device maps exactly like a stamp -- it waits on its
+ * stream for the previous ingest, roll, stamp or update and for every launch still reading the maps, and the gates and solves
+ * behind it wait for it; the layer buffers are touched only inside such writes, so the same chain orders them.
+ * Memory: the layers cost the handle up to two more pools' worth of device memory (the layers, and those of the update in
+ * flight).  They are allocated on the first update and reallocated only on a reset by geometry.  The cost table is kept in
+ * the handle, apart from the stamp's and the world's, and rebuilt and uploaded synchronously when (res, inscribed_radius,
+ * inflation_radius, cost_scaling_factor) differ from the previous update's.  A device update with the geometry, count and
+ * inflation parameters of the previous one allocates nothing, copies nothing and does not synchronise, so roll -> scan ->
+ * stamp -> gate -> carrots -> solve can be captured on one stream in one HIP graph and replayed with new points. */
+int neo_mpc_update_scan_layer_device(neo_mpc_handle* handle, const neo_mpc_scan_batch* batch, void* stream);
+/* Reads layers [first, first + count) back as the last update left them: cells_out[count][size_y][size_x] and their origins,
+ * origins_out[count][2] (either may be NULL).  Host pointers, synchronous; waits for the write of the device maps in flight
+ * -- one that was ENQUEUED by a call: behind a graph replay synchronise the replay's stream first (neo_mpc_get_world_map says
+ * why).  NEO_MPC_ERR_NO_COSTMAP when there is no layer -- before the first update and behind neo_mpc_reset_scan_layer;
+ * NEO_MPC_ERR_INVALID_ARGUMENT for a null handle and a range outside the layers. */
+int neo_mpc_get_scan_layer(neo_mpc_handle* handle, uint32_t first, uint32_t count, uint8_t* cells_out, double* origins_out);
+/* The next update starts from a layer of unknown_value.  Touches no device memory.  NEO_MPC_ERR_INVALID_ARGUMENT for a null
+ * handle. */
+int neo_mpc_reset_scan_layer(neo_mpc_handle* handle);
 
 /* ---- multi-GPU fleets: the one exchange step ------------------------------------------------
  * Instances of one tick shard embarrassingly over the GPUs of a node (one handle per GPU, costmap and parameters

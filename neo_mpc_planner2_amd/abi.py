@@ -156,6 +156,32 @@ class NeoMpcStampBatch(_C.Structure):
 MAX_INFLATION_CELLS = 64
 
 
+class NeoMpcScanBatch(_C.Structure):
+    """`neo_mpc_scan_batch` (include/neo_mpc.h): one update of the windows' obstacle layers from sensor points."""
+    _fields_ = [("count", _C.c_size_t), ("points", _C.c_void_p), ("point_counts", _C.c_void_p),
+                ("sensor_origins", _C.c_void_p), ("max_points", _C.c_uint32), ("flags", _C.c_uint32),
+                ("obstacle_max_range", _C.c_double), ("obstacle_min_range", _C.c_double),
+                ("raytrace_max_range", _C.c_double), ("raytrace_min_range", _C.c_double),
+                ("inscribed_radius", _C.c_double), ("inflation_radius", _C.c_double), ("cost_scaling_factor", _C.c_double),
+                ("unknown_value", _C.c_uint32), ("reserved", _C.c_uint32)]
+
+
+#: the same record as a NumPy dtype (104 bytes; the pointers as addresses)
+SCAN_BATCH_DTYPE = np.dtype([
+    ("count", "<u8"), ("points", "<u8"), ("point_counts", "<u8"), ("sensor_origins", "<u8"),
+    ("max_points", "<u4"), ("flags", "<u4"),
+    ("obstacle_max_range", "<f8"), ("obstacle_min_range", "<f8"),
+    ("raytrace_max_range", "<f8"), ("raytrace_min_range", "<f8"),
+    ("inscribed_radius", "<f8"), ("inflation_radius", "<f8"), ("cost_scaling_factor", "<f8"),
+    ("unknown_value", "<u4"), ("reserved", "<u4"),
+], align=False)
+assert SCAN_BATCH_DTYPE.itemsize == 104 == _C.sizeof(NeoMpcScanBatch)
+
+MAX_SCAN_POINTS = 8192
+SCAN_CLEAR = 1           # NEO_MPC_SCAN_CLEAR: raytrace the layer free from the sensor origin to every point
+SCAN_MARK = 2            # NEO_MPC_SCAN_MARK: mark the points' cells lethal in the layer
+
+
 def params_struct(params=None, **over):
     """dict of ROS parameter names (+ solver options) -> NeoMpcParams.  Missing names take
     the reference node's declared defaults (py:49-75)."""

@@ -1,6 +1,7 @@
-// inflation.h -- what K8 (fleet_stamp.h) and K9 (world_inflation.h) share of nav2's inflation by squared cell distance: the cost
+// inflation.h -- what K8 (fleet_stamp.h), K9 (world_inflation.h) and K10 (scan_layer.h) share of nav2's inflation by squared cell distance: the cost
 // table T in LDS, the rule that combines T[N] with a cell, and the scan over rows of seeds for N, a cell's squared distance to
-// the nearest one -- K9's; K8 keeps a written-out copy that measured faster there.  What a row looks like stays with the kernels.
+// the nearest one -- K9's and K10's; K8 keeps a written-out copy that measured faster there -- and the distance along a row of
+// three 64-bit words of seeds, which K9 (world_inflation.h) and K10 (scan_layer.h) share.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -29,6 +30,21 @@ __device__ __forceinline__ int inflation_scan(int R, Row&& row) {
     if (d > 0) row(-d, found);
   }
   return best;
+}
+
+constexpr int kInflateFar = 1 << 12;   // "no seed in this row": its square is beyond every R^2, and fits an int with d^2 added
+
+// Distance along a row from column 64 + c of a 192-column row (m0: columns 0 .. 63, m1: 64 .. 127, m2: 128 .. 191; bit b of
+// a word = its column b; 0 <= c < 64) to the row's nearest set bit -- K8's stamp_row_distance over three words.  Exact up to 64,
+// which is all a reach of at most 64 cells can ask for; kInflateFar where no bit is that near.
+__device__ __forceinline__ int inflate_row_distance(uint64_t m0, uint64_t m1, uint64_t m2, int c) {
+  // the 64 columns that end at the column, the nearest in bit 63; the 64 that start at it, the nearest in bit 0
+  const uint64_t left = (m1 << (63 - c)) | ((m0 >> c) >> 1);
+  const uint64_t right = (m1 >> c) | ((m2 << (63 - c)) << 1);
+  // (a distance of exactly 64 is the one column on either side that those windows leave out)
+  const int dl = left ? __clzll((long long)left) : ((m0 >> c) & 1 ? 64 : kInflateFar);
+  const int dr = right ? __ffsll((long long)right) - 1 : ((m2 >> c) & 1 ? 64 : kInflateFar);
+  return dl < dr ? dl : dr;
 }
 
 // nav2's inflation rule, inflate_unknown false, on the cell at `p` for the squared distance `best` <= R^2: one byte read,

@@ -7,10 +7,10 @@
 //
 // In this order: the error setter; DeviceBuffer (device memory that frees itself, and the one-line uploads); MapFence
 // (the ordering of every launch that writes or reads the device map, and the host's wait for an idle map); WorldMap (the
-// world map's copy, geometry and ordering); the refusals of inflation parameters and InflationTable (K8's and K9's cached
+// world map's copy, geometry and ordering); the refusals of inflation parameters and InflationTable (K8's, K9's and K10's cached
 // cost table); the handle; parameters and the term table; the shared checks; the device map (geometry, adoption, K3
 // ingest); the staging of host batches by range; then the entry points -- costmaps, the solve paths of K1, K2 and the hooks,
-// K4 carrots, K6 footprint gate, K7 rolling windows, K8 fleet stamp, K9 world inflation.  A new entry point checks with the
+// K4 carrots, K6 footprint gate, K7 rolling windows, K8 fleet stamp, K9 world inflation, K10 scan layer.  A new entry point checks with the
 // shared checks, stages with upload(), and launches through fence.read() or between fence.begin_write() and end_write().
 #include <hip/hip_runtime.h>
 
@@ -322,6 +322,15 @@ struct __attribute__((visibility("hidden"))) neo_mpc_handle {
   DeviceBuffer stamp_polys, stamp_boxes;
   // K9 neo_mpc_inflate_world_map: its own cost table -- the world's resolution need not be the windows'
   InflationTable world_table;
+  // K10 neo_mpc_update_scan_layer: the layers between updates, those of the update in flight, the layers' origins, a cost
+  // table of its own, what the previous update was made for (a difference resets the layers), and the host variant's staging
+  InflationTable scan_table;
+  DeviceBuffer scan_layer, scan_work, scan_origins;
+  bool scan_valid = false;
+  int32_t scan_sx = 0, scan_sy = 0, scan_count = 0;
+  uint32_t scan_unknown = 0;
+  double scan_res = 0.0;
+  DeviceBuffer scan_points, scan_point_counts, scan_sensors;
 };
 constexpr size_t kLatencyPathMaxCount = 64;
 constexpr size_t kChunkedMinCount = 65536;   // staged host batches from here on go through in kChunks pieces on two streams
@@ -1603,6 +1612,131 @@ int neo_mpc_inflate_world_map(neo_mpc_handle* h, double ins, double infl, double
   int rc = inflate_world_map(h, ins, infl, csf, false, nullptr);
   if (rc) return rc;
   HIP_TRY(hipStreamSynchronize(nullptr));
+  return NEO_MPC_OK;
+}
+
+// K10.  What both update entry points check: the record's shape and the handle's pool, never a value behind a pointer.
+static int check_scan_batch(const neo_mpc_handle* h, const neo_mpc_scan_batch* b) {
+  if (!h || !b) return fail(NEO_MPC_ERR_INVALID_ARGUMENT, "null argument");
+  if (b->reserved != 0) return fail(NEO_MPC_ERR_INVALID_ARGUMENT, "neo_mpc_scan_batch.reserved must be zero");
+  if (b->flags & ~(NEO_MPC_SCAN_CLEAR | NEO_MPC_SCAN_MARK)) return fail(NEO_MPC_ERR_INVALID_ARGUMENT, "unknown flags 0x%x", b->flags);
+  if (b->unknown_value != 0 && b->unknown_value != 255)
+    return fail(NEO_MPC_ERR_INVALID_ARGUMENT, "unknown_value %u is neither 0 nor 255", b->unknown_value);
+  if (b->max_points > NEO_MPC_MAX_SCAN_POINTS)
+    return fail(NEO_MPC_ERR_INVALID_ARGUMENT, "max_points %u: at most %u", b->max_points, NEO_MPC_MAX_SCAN_POINTS);
+  if (b->flags != 0 && b->count > 0 && (!b->points || !b->sensor_origins))
+    return fail(NEO_MPC_ERR_INVALID_ARGUMENT, "points and sensor_origins must not be null with flags 0x%x", b->flags);
+  for (const double r : {b->obstacle_max_range, b->obstacle_min_range, b->raytrace_max_range, b->raytrace_min_range})
+    if (!std::isfinite(r) || r < 0.0) return fail(NEO_MPC_ERR_INVALID_ARGUMENT, "range %g must be finite and not negative", r);
+  if (int rc = check_inflation_radii(b->inscribed_radius, b->inflation_radius, b->cost_scaling_factor)) return rc;
+  if (!h->has_map) return fail(NEO_MPC_ERR_NO_COSTMAP, "the handle holds no costmap");
+  if (h->map.pool_count <= 0) return fail(NEO_MPC_ERR_UNSUPPORTED, "the handle holds a single costmap, not a pool");
+  if (b->count > 0 && b->count != (size_t)h->map.pool_count)
+    return fail(NEO_MPC_ERR_INVALID_ARGUMENT, "%zu robots for a pool of %d windows: they are one to one", b->count, h->map.pool_count);
+  return inflation_reach(h->map.resolution, b->inscribed_radius, b->inflation_radius, b->cost_scaling_factor, "", nullptr);
+}
+
+// `d`: the record with device pointers.  Orders itself like stamp(): it rewrites the device maps in place, and the layer
+// buffers inside the same write.
+static int scan(neo_mpc_handle* h, const neo_mpc_scan_batch& d, void* stream) {
+  const DevMap& m = h->map;
+  // (every update ends a write of the fence)
+  int rc = h->scan_table.build(m.resolution, d.inscribed_radius, d.inflation_radius, d.cost_scaling_factor, h->fence);
+  if (rc) return rc;
+  const int layer_pitch = (m.size_x + 63) & ~63;
+  const size_t layer_stride = (size_t)layer_pitch * (size_t)m.size_y;
+  const bool same = h->scan_valid && h->scan_sx == m.size_x && h->scan_sy == m.size_y && h->scan_count == m.pool_count &&
+                    h->scan_res == m.resolution && h->scan_unknown == d.unknown_value;
+  if (!same) {
+    // a reset: the buffers are re-allocated only where the geometry asks for more (a re-allocation synchronises)
+    h->scan_valid = false;
+    if ((rc = h->scan_layer.reserve(layer_stride * d.count))) return rc;
+    if ((rc = h->scan_work.reserve(layer_stride * d.count))) return rc;
+    if ((rc = h->scan_origins.reserve(d.count * 16))) return rc;
+  }
+  hipStream_t st = (hipStream_t)stream;
+  if ((rc = h->fence.begin_write(st))) return rc;
+  ScanArgs a;
+  std::memset(&a, 0, sizeof(a));
+  if (d.flags != 0) { a.points = d.points; a.point_counts = d.point_counts; a.sensor_origins = d.sensor_origins; }
+  a.table = h->scan_table.buf.as<const uint8_t>();
+  a.layer = h->scan_layer.as<uint8_t>(); a.work = h->scan_work.as<uint8_t>(); a.layer_origins = h->scan_origins.as<double>();
+  a.cells = const_cast<uint8_t*>(m.cells);   // (cell (0, 0) of the first map of map_buf, the handle's own)
+  a.origins = m.pool_origins;
+  a.res = m.resolution;
+  a.obstacle_max = d.obstacle_max_range; a.obstacle_min = d.obstacle_min_range;
+  a.raytrace_max = d.raytrace_max_range; a.raytrace_min = d.raytrace_min_range;
+  a.stride = m.pool_stride; a.layer_stride = (int64_t)layer_stride;
+  a.size_x = m.size_x; a.size_y = m.size_y; a.pitch = m.pitch; a.layer_pitch = layer_pitch;
+  a.reach = h->scan_table.reach;
+  a.count = (uint32_t)d.count; a.max_points = d.max_points; a.flags = d.flags; a.unknown = d.unknown_value;
+  a.reset = same ? 0u : 1u;
+  launch_scan_layer(a, stream);
+  HIP_TRY(hipGetLastError());
+  if ((rc = h->fence.end_write(st))) return rc;   // a stamp, gate or solve behind it sees the windows with the layer in them
+  h->scan_valid = true;
+  h->scan_sx = m.size_x; h->scan_sy = m.size_y; h->scan_count = m.pool_count; h->scan_res = m.resolution;
+  h->scan_unknown = d.unknown_value;
+  return NEO_MPC_OK;
+}
+
+int neo_mpc_update_scan_layer_device(neo_mpc_handle* h, const neo_mpc_scan_batch* b, void* stream) {
+  int rc = check_scan_batch(h, b);
+  if (rc) return rc;
+  if (b->count == 0) return NEO_MPC_OK;
+  HIP_TRY(hipSetDevice(h->device));
+  return scan(h, *b, stream);
+}
+
+int neo_mpc_update_scan_layer(neo_mpc_handle* h, const neo_mpc_scan_batch* b) {
+  int rc = check_scan_batch(h, b);
+  if (rc) return rc;
+  if (b->count == 0) return NEO_MPC_OK;
+  const size_t n = b->count;
+  neo_mpc_scan_batch d = *b;
+  d.points = nullptr; d.point_counts = nullptr; d.sensor_origins = nullptr;
+  if (b->flags != 0) {
+    // the values the device variant takes as they come are looked at here
+    for (size_t k = 0; k < n; ++k) {
+      if (b->point_counts && b->point_counts[k] > b->max_points)
+        return fail(NEO_MPC_ERR_INVALID_ARGUMENT, "point_counts[%zu] = %u is more than max_points %u", k, b->point_counts[k], b->max_points);
+      if (!std::isfinite(b->sensor_origins[2 * k]) || !std::isfinite(b->sensor_origins[2 * k + 1]))
+        return fail(NEO_MPC_ERR_INVALID_ARGUMENT, "the sensor origin of robot %zu is not finite", k);
+    }
+    HIP_TRY(hipSetDevice(h->device));
+    if (!(d.sensor_origins = h->scan_sensors.upload(b->sensor_origins, n * 16))) return NEO_MPC_ERR_DEVICE;
+    if (b->max_points > 0 && !(d.points = h->scan_points.upload(b->points, n * b->max_points * 16))) return NEO_MPC_ERR_DEVICE;
+    if (b->point_counts && !(d.point_counts = h->scan_point_counts.upload(b->point_counts, n * 4))) return NEO_MPC_ERR_DEVICE;
+  }
+  HIP_TRY(hipSetDevice(h->device));
+  if ((rc = scan(h, d, nullptr))) { (void)hipStreamSynchronize(nullptr); return rc; }   // (the staging is free again)
+  HIP_TRY(hipStreamSynchronize(nullptr));
+  return NEO_MPC_OK;
+}
+
+int neo_mpc_get_scan_layer(neo_mpc_handle* h, uint32_t first, uint32_t count, uint8_t* cells_out, double* origins_out) {
+  if (!h) return fail(NEO_MPC_ERR_INVALID_ARGUMENT, "null handle");
+  if (!h->scan_valid) return fail(NEO_MPC_ERR_NO_COSTMAP, "no scan layer: neo_mpc_update_scan_layer has not been called since the last reset");
+  const uint32_t maps = (uint32_t)h->scan_count;
+  if (first > maps || count > maps - first)
+    return fail(NEO_MPC_ERR_INVALID_ARGUMENT, "layers [%u, %u + %u) outside the %u there are", first, first, count, maps);
+  if (count == 0) return NEO_MPC_OK;
+  HIP_TRY(hipSetDevice(h->device));
+  int rc = h->fence.wait_writer_host();   // the update in flight
+  if (rc) return rc;
+  const size_t sx = (size_t)h->scan_sx, sy = (size_t)h->scan_sy, pitch = (sx + 63) & ~(size_t)63;
+  if (cells_out)
+    for (uint32_t k = 0; k < count; ++k)   // a strided copy per layer: the pitch stays behind
+      HIP_TRY(hipMemcpy2D(cells_out + (size_t)k * sx * sy, sx, h->scan_layer.as<uint8_t>() + (size_t)(first + k) * pitch * sy,
+                          pitch, sx, sy, hipMemcpyDeviceToHost));
+  if (origins_out)
+    HIP_TRY(hipMemcpy(origins_out, h->scan_origins.as<double>() + 2 * (size_t)first, (size_t)count * 16, hipMemcpyDeviceToHost));
+  return NEO_MPC_OK;
+}
+
+int neo_mpc_reset_scan_layer(neo_mpc_handle* h) {
+  if (!h) return fail(NEO_MPC_ERR_INVALID_ARGUMENT, "null handle");
+  h->scan_valid = false;
   return NEO_MPC_OK;
 }
 

@@ -254,6 +254,31 @@ struct InflateArgs {
   int32_t reach;                    // R, cells: 0 .. NEO_MPC_MAX_INFLATION_CELLS
 };
 
+// K10: the scan obstacle layer (neo_mpc_scan_batch, device pointers) -- the handle's map pool and its two layer buffers
+struct ScanArgs {
+  const double* points;             // [count][max_points][2] global frame (read with NEO_MPC_SCAN_CLEAR / _MARK only)
+  const uint32_t* point_counts;     // optional [count]
+  const double* sensor_origins;     // [count][2]
+  const uint8_t* table;             // [reach^2 + 1]: cost by squared cell distance (neo_mpc_inflation_costs)
+  uint8_t* layer;                   // handle-owned: the layers between updates, layer_pitch bytes a row, no border
+  uint8_t* work;                    // handle-owned: this update's layers, same shape
+  double* layer_origins;            // [count][2] handle-owned: where the layers of `layer` lie
+  uint8_t* cells;                   // cell (0, 0) of the first window
+  const double* origins;            // [count][2]
+  double res;
+  double obstacle_max, obstacle_min, raytrace_max, raytrace_min;
+  int64_t stride;                   // bytes between windows
+  int64_t layer_stride;             // bytes between layers
+  int32_t size_x, size_y, pitch;
+  int32_t layer_pitch;              // size_x rounded up to 64
+  int32_t reach;                    // R, cells: 0 .. NEO_MPC_MAX_INFLATION_CELLS
+  uint32_t count;
+  uint32_t max_points;
+  uint32_t flags;                   // NEO_MPC_SCAN_*
+  uint32_t unknown;                 // 0 or 255
+  uint32_t reset;                   // 1: the layers start from `unknown` at the windows' origins
+};
+
 // A/B switches of the measurement tools: read from the environment ONCE, by neo_mpc_create (include/neo_mpc.h), kept in
 // the handle -- nothing on the solve path looks at the environment.
 struct LaunchTuning {
@@ -271,6 +296,7 @@ void launch_footprint_gate(const FootprintGateArgs& a, void* stream);
 void launch_roll(const RollArgs& a, void* stream);   // K7: k_roll_index, then k_roll_fill
 void launch_stamp(const StampArgs& a, void* stream); // K8: k_stamp_boxes, then k_stamp_fleet
 void launch_inflate_world(const InflateArgs& a, void* stream);   // K9: k_inflate_world
+void launch_scan_layer(const ScanArgs& a, void* stream);         // K10: k_scan_shift, k_scan_rays (clear, mark), k_scan_apply
 // K5: dispatch order of the next launch from the iteration counts of the previous one (neo_mpc_balance_dispatch_device)
 void launch_dispatch_order(const neo_mpc_command* commands, float* load, uint32_t* order, uint32_t count, bool fresh, void* stream);
 constexpr uint32_t kDispatchSimds = 1024;   // a 4096-instance launch is one residency round: workgroups w, w + 1024, w + 2048, w + 3072 share a SIMD

@@ -11,24 +11,10 @@
 namespace neo_mpc {
 namespace {
 
-constexpr int kInflateFar = 1 << 12;   // "no seed in this row": its square is beyond every R^2, and fits an int with d^2 added
 constexpr int kInflateTile = 64;    // a workgroup owns 64 x 64 cells: lane = column, one 64-bit word per row and 64 columns
 constexpr int kInflateWaves = 4;    // ... its waves take the rows in turn
 constexpr int kInflateLoads = 8;    // ... each with this many row words in flight
 constexpr int kInflateRows =kInflateTile + 2 * NEO_MPC_MAX_INFLATION_CELLS;   // the tile's rows and the largest halo
-
-// Distance along a row from column 64 + c of a 192-column row (m0: columns 0 .. 63, m1: 64 .. 127, m2: 128 .. 191; bit b of
-// a word = its column b; 0 <= c < 64) to the row's nearest set bit -- K8's stamp_row_distance over three words.  Exact up to 64,
-// which is all a reach of at most 64 cells can ask for; kInflateFar where no bit is that near.
-__device__ __forceinline__ int inflate_row_distance(uint64_t m0, uint64_t m1, uint64_t m2, int c) {
-  // the 64 columns that end at the column, the nearest in bit 63; the 64 that start at it, the nearest in bit 0
-  const uint64_t left = (m1 << (63 - c)) | ((m0 >> c) >> 1);
-  const uint64_t right = (m1 >> c) | ((m2 << (63 - c)) << 1);
-  // (a distance of exactly 64 is the one column on either side that those windows leave out)
-  const int dl = left ? __clzll((long long)left) : ((m0 >> c) & 1 ? 64 : kInflateFar);
-  const int dr = right ? __ffsll((long long)right) - 1 : ((m2 >> c) & 1 ? 64 : kInflateFar);
-  return dl < dr ? dl : dr;
-}
 
 // K9: one workgroup of four waves per tile of 64 x 64 cells, one fused pass.
 //   1  The tile's halo -- the tile and R cells on every side, clipped to the map -- becomes a bitmask of seeds in LDS: a wave

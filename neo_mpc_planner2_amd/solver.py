@@ -290,6 +290,76 @@ class BatchSolver:
             stream = torch.cuda.current_stream(shape.device).cuda_stream
             _lib.check(self._lib.neo_mpc_stamp_fleet_device(self._handle, C.byref(b), C.c_void_p(stream)))
 
+    # -- scan obstacle layer (the step between the roll and the stamp) --------------------
+    def update_scan_layer(self, inscribed_radius, inflation_radius, cost_scaling_factor, points=None, sensor_origins=None,
+                          point_counts=None, flags=None, obstacle_max_range=2.5, obstacle_min_range=0.0,
+                          raytrace_max_range=3.0, raytrace_min_range=0.0, unknown_value=255, on_device=None):
+        """Updates the obstacle layer of every window of the pool from one observation per robot and puts the layers into
+        the windows (K10; the contract: neo_mpc_scan_batch in include/neo_mpc.h).  `points` [count, max_points, 2] hit
+        points and `sensor_origins` [count, 2], global frame; `point_counts` (uint32 [count]) for ragged clouds; `flags`
+        abi.SCAN_CLEAR | abi.SCAN_MARK (the default with points) or 0 (the default without: no new observation, the layer
+        is rolled and applied again; the range defaults are nav2's).  NumPy arrays go through the synchronous host call;
+        CUDA tensors (float64, `point_counts` int32 holding the uint32 counts) through the device call on torch's current
+        stream.  Without points `on_device` picks the variant (a torch device, or True for this solver's)."""
+        assert self._map_shape is not None, "no costmap has been set through this BatchSolver"
+        b = abi.NeoMpcScanBatch()
+        b.count = self._map_shape[0]
+        b.obstacle_max_range, b.obstacle_min_range = float(obstacle_max_range), float(obstacle_min_range)
+        b.raytrace_max_range, b.raytrace_min_range = float(raytrace_max_range), float(raytrace_min_range)
+        b.inscribed_radius, b.inflation_radius = float(inscribed_radius), float(inflation_radius)
+        b.cost_scaling_factor, b.unknown_value = float(cost_scaling_factor), int(unknown_value)
+        if flags is None:
+            flags = (abi.SCAN_CLEAR | abi.SCAN_MARK) if points is not None else 0
+        b.flags = int(flags)
+        device = None
+        if points is not None and hasattr(points, "data_ptr"):
+            device = points.device
+        elif points is None and on_device is not None and on_device is not False:
+            import torch
+            device = torch.device("cuda", self.device) if on_device is True else torch.device(on_device)
+        if device is None:
+            if points is not None:
+                points = np.ascontiguousarray(points, dtype=np.float64)
+                sensor_origins = np.ascontiguousarray(sensor_origins, dtype=np.float64)
+                assert points.ndim == 3 and points.shape[0] == b.count and points.shape[2] == 2
+                assert sensor_origins.shape == (b.count, 2)
+                b.points, b.sensor_origins, b.max_points = points.ctypes.data, sensor_origins.ctypes.data, points.shape[1]
+                if point_counts is not None:
+                    point_counts = np.ascontiguousarray(point_counts, dtype=np.uint32)
+                    assert point_counts.shape == (b.count,)
+                    b.point_counts = point_counts.ctypes.data
+            _lib.check(self._lib.neo_mpc_update_scan_layer(self._handle, C.byref(b)))
+        else:
+            import torch
+            if points is not None:
+                for a in (points, sensor_origins, point_counts):
+                    assert a is None or (a.is_cuda and a.is_contiguous())
+                assert points.dtype == torch.float64 and points.dim() == 3 and points.shape[0] == b.count and points.shape[2] == 2
+                assert sensor_origins.dtype == torch.float64 and tuple(sensor_origins.shape) == (b.count, 2)
+                b.points, b.sensor_origins, b.max_points = points.data_ptr(), sensor_origins.data_ptr(), points.shape[1]
+                if point_counts is not None:
+                    assert point_counts.dtype == torch.int32 and tuple(point_counts.shape) == (b.count,)
+                    b.point_counts = point_counts.data_ptr()
+            stream = torch.cuda.current_stream(device).cuda_stream
+            _lib.check(self._lib.neo_mpc_update_scan_layer_device(self._handle, C.byref(b), C.c_void_p(stream)))
+
+    def get_scan_layer(self, first=0, count=None):
+        """Layers [first, first + count) as the last `update_scan_layer` left them: uint8 [count, size_y, size_x] with
+        values in {255, 0, 254}, and their origins, float64 [count, 2].  Synchronous; waits for the update in flight."""
+        assert self._map_shape is not None, "no costmap has been set through this BatchSolver"
+        maps, sy, sx = self._map_shape
+        if count is None:
+            count = maps - first
+        cells = np.zeros((count, sy, sx), dtype=np.uint8)
+        origins = np.zeros((count, 2), dtype=np.float64)
+        _lib.check(self._lib.neo_mpc_get_scan_layer(self._handle, int(first), int(count), C.c_void_p(cells.ctypes.data),
+                                                   C.c_void_p(origins.ctypes.data)))
+        return cells, origins
+
+    def reset_scan_layer(self):
+        """The next `update_scan_layer` starts from a layer of `unknown_value`."""
+        _lib.check(self._lib.neo_mpc_reset_scan_layer(self._handle))
+
     HOST_PATHS = {"auto": 0, "staged": 1, "zerocopy": 2, "zerocopy_out": 3}
 
     def set_host_path(self, mode):
