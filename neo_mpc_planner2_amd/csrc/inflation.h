@@ -1,7 +1,7 @@
 // inflation.h -- what K8 (fleet_stamp.h), K9 (world_inflation.h) and K10 (scan_layer.h) share of nav2's inflation by squared cell distance: the cost
 // table T in LDS, the rule that combines T[N] with a cell, and the scan over rows of seeds for N, a cell's squared distance to
-// the nearest one -- K9's and K10's; K8 keeps a written-out copy that measured faster there -- and the distance along a row of
-// three 64-bit words of seeds, which K9 (world_inflation.h) and K10 (scan_layer.h) share.
+// the nearest one -- K9's and K10's; K8 keeps a written-out copy that measured faster there -- and K9's and K10's tiled pass:
+// the tile constants, a tile's halo as rows of three 64-bit words of seeds in LDS, and a cell's N from those rows.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -45,6 +45,61 @@ __device__ __forceinline__ int inflate_row_distance(uint64_t m0, uint64_t m1, ui
   const int dl = left ? __clzll((long long)left) : ((m0 >> c) & 1 ? 64 : kInflateFar);
   const int dr = right ? __ffsll((long long)right) - 1 : ((m2 >> c) & 1 ? 64 : kInflateFar);
   return dl < dr ? dl : dr;
+}
+
+constexpr int kInflateTile = 64;    // a workgroup owns 64 x 64 cells: lane = column, one 64-bit word per row and 64 columns
+constexpr int kInflateWaves = 4;    // ... its waves take the rows in turn
+constexpr int kInflateLoads = 8;    // ... each with this many row words in flight
+constexpr int kInflateRows = kInflateTile + 2 * NEO_MPC_MAX_INFLATION_CELLS;   // the tile's rows and the largest halo
+
+// Step 1 of K9 and K10, by a workgroup of kInflateWaves waves (`lane`, `wave`: this thread's) for the tile at column tx, row ty
+// of the sx x sy map at `src`, rows `pitch` bytes apart.  The tile's halo -- the tile and R cells on every side, clipped to the
+// map -- becomes a bitmask of seeds in LDS: a wave reads 64 consecutive bytes of a row and __ballot(cell == 254) is that row's
+// word; masks[3 * rr + w] is map row ty - R + rr, columns tx + 64 (w - 1) ... (the tile's columns and the 64 on either side, of
+// which the R nearest are read), at most kInflateRows rows: 4.5 KB.  Then, if any wave saw a seed (`seen`: a vote per wave), T
+// goes to `lds_table`.  Returns whether one did, the same in every lane of the workgroup, behind the second of two barriers.
+// Both barriers are unconditional, and the trip counts of the loops that ballot are wave-uniform: all 64 lanes of a wave run
+// every turn.  A wave's words go kInflateLoads at a time: the loads of a batch are in flight together -- one after the other,
+// a tile without a seed, which does little else, is the sum of their latencies.
+__device__ __forceinline__ bool inflation_tile_seeds(uint64_t* masks, uint8_t* lds_table, int* seen, const uint8_t* src, int pitch,
+                                                     int sx, int sy, int tx, int ty, int R, const uint8_t* table, int lane, int wave) {
+  const int rows = kInflateTile + 2 * R;
+  const int c_lo = tx - R > 0 ? tx - R : 0;            // the halo's columns that exist: [c_lo, c_hi)
+  const int c_hi = tx + kInflateTile + R < sx ? tx + kInflateTile + R : sx;
+  bool any = false;
+  for (int t0 = wave; t0 < rows * 3; t0 += kInflateWaves * kInflateLoads) {
+    int cell[kInflateLoads];
+#pragma unroll
+    for (int u = 0; u < kInflateLoads; ++u) {
+      const int t = t0 + u * kInflateWaves, rr = t / 3, w = t - 3 * rr;
+      const int r = ty - R + rr, col = tx + (w - 1) * kInflateTile + lane;
+      cell[u] = 0;
+      if (t < rows * 3 && r >= 0 && r < sy && col >= c_lo && col < c_hi) cell[u] = src[(int64_t)r * pitch + col];   // inside the map
+    }
+#pragma unroll
+    for (int u = 0; u < kInflateLoads; ++u) {
+      const int t = t0 + u * kInflateWaves;
+      const uint64_t m = __ballot(cell[u] == 254);
+      if (t < rows * 3 && lane == 0) masks[t] = m;     // (t < kInflateRows * 3: inside masks)
+      any = any || m != 0;
+    }
+  }
+  if (lane == 0) seen[wave] = any ? 1 : 0;
+  __syncthreads();
+  const bool some = (seen[0] | seen[1] | seen[2] | seen[3]) != 0;
+  if (some) inflation_stage_table(lds_table, table, R, (int)threadIdx.x, kLanes * kInflateWaves);
+  __syncthreads();
+  return some;
+}
+
+// The squared distance from the cell in column `lane` of the tile, row r0 of `masks` (R <= r0 < R + kInflateTile, so that
+// 0 <= r0 - R and r0 + R < the halo's rows), to the nearest seed of the halo, or R^2 + 1; a row without a seed is skipped
+__device__ __forceinline__ int inflation_tile_distance(const uint64_t* masks, int R, int r0, int lane) {
+  return inflation_scan(R, [&](int dy, auto&& found) {
+    const uint64_t* m = masks + 3 * (r0 + dy);
+    const uint64_t m0 = m[0], m1 = m[1], m2 = m[2];
+    if (m0 | m1 | m2) found(inflate_row_distance(m0, m1, m2, lane));
+  });
 }
 
 // nav2's inflation rule, inflate_unknown false, on the cell at `p` for the squared distance `best` <= R^2: one byte read,

@@ -275,6 +275,34 @@ struct InflationTable {
   }
 };
 
+// ---------------------------------------------------------------------------------------------- the scan layers
+// K10.  An obstacle layer per window of the pool, rows padded to 64 bytes: `layer` holds the layers between updates, `work`
+// those of the update in flight, `origins` the layers' origins; a cost table of their own; and what the layers were made
+// for -- an update that meets another geometry or unknown_value resets them.
+struct ScanLayers {
+  InflationTable table;
+  DeviceBuffer layer, work, origins;
+  bool valid = false;
+  int32_t size_x = 0, size_y = 0, count = 0;
+  double resolution = 0.0;
+  uint32_t unknown = 0;
+  DeviceBuffer points, point_counts, sensors;   // (the host variant's staging)
+  int pitch() const { return (size_x + 63) & ~63; }
+  size_t stride() const { return (size_t)pitch() * (size_t)size_y; }
+  bool matches(const DevMap& m, uint32_t u) const {
+    return valid && size_x == m.size_x && size_y == m.size_y && count == m.pool_count && resolution == m.resolution && unknown == u;
+  }
+  // A reset: the pool's geometry, nobody's until adopt(); re-allocated only where that asks for more (which synchronises)
+  int resize(const DevMap& m, uint32_t unknown_value) {
+    valid = false;
+    size_x = m.size_x; size_y = m.size_y; count = m.pool_count; resolution = m.resolution; unknown = unknown_value;
+    if (int rc = layer.reserve(stride() * (size_t)count)) return rc;
+    if (int rc = work.reserve(stride() * (size_t)count)) return rc;
+    return origins.reserve((size_t)count * 16);
+  }
+  void adopt() { valid = true; }   // behind the update's end_write: its launches are enqueued
+};
+
 }  // namespace
 
 // (hidden: its destructor, no longer trivial, is no export)
@@ -322,15 +350,7 @@ struct __attribute__((visibility("hidden"))) neo_mpc_handle {
   DeviceBuffer stamp_polys, stamp_boxes;
   // K9 neo_mpc_inflate_world_map: its own cost table -- the world's resolution need not be the windows'
   InflationTable world_table;
-  // K10 neo_mpc_update_scan_layer: the layers between updates, those of the update in flight, the layers' origins, a cost
-  // table of its own, what the previous update was made for (a difference resets the layers), and the host variant's staging
-  InflationTable scan_table;
-  DeviceBuffer scan_layer, scan_work, scan_origins;
-  bool scan_valid = false;
-  int32_t scan_sx = 0, scan_sy = 0, scan_count = 0;
-  uint32_t scan_unknown = 0;
-  double scan_res = 0.0;
-  DeviceBuffer scan_points, scan_point_counts, scan_sensors;
+  ScanLayers scan;   // K10 neo_mpc_update_scan_layer
 };
 constexpr size_t kLatencyPathMaxCount = 64;
 constexpr size_t kChunkedMinCount = 65536;   // staged host batches from here on go through in kChunks pieces on two streams
@@ -1445,6 +1465,15 @@ int neo_mpc_roll_costmap_pool(neo_mpc_handle* h, const neo_mpc_window_batch* w) 
   return NEO_MPC_OK;
 }
 
+// Maps first .. first + count - 1 of those at `base` (rows `pitch` bytes apart, maps `stride`) -> cells_out (if asked for),
+// sx * sy bytes each: a strided copy per map, border and pitch stay behind
+static int download_maps(const uint8_t* base, size_t pitch, size_t stride, size_t sx, size_t sy, uint32_t first, uint32_t count,
+                         uint8_t* cells_out) {
+  for (uint32_t k = 0; cells_out && k < count; ++k)
+    HIP_TRY(hipMemcpy2D(cells_out + (size_t)k * sx * sy, sx, base + (size_t)(first + k) * stride, pitch, sx, sy, hipMemcpyDeviceToHost));
+  return NEO_MPC_OK;
+}
+
 int neo_mpc_get_costmap_pool(neo_mpc_handle* h, uint32_t first, uint32_t count, uint8_t* cells_out, double* origins_out) {
   if (!h) return fail(NEO_MPC_ERR_INVALID_ARGUMENT, "null handle");
   if (!h->has_map) return fail(NEO_MPC_ERR_NO_COSTMAP, "neo_mpc_set_costmap has not been called");
@@ -1455,11 +1484,8 @@ int neo_mpc_get_costmap_pool(neo_mpc_handle* h, uint32_t first, uint32_t count, 
   HIP_TRY(hipSetDevice(h->device));
   int rc = h->fence.wait_writer_host();   // the ingest, roll or stamp in flight
   if (rc) return rc;
-  const size_t sx = (size_t)h->map.size_x, sy = (size_t)h->map.size_y;
-  if (cells_out)
-    for (uint32_t k = 0; k < count; ++k)   // a strided copy per map: border and pitch stay behind
-      HIP_TRY(hipMemcpy2D(cells_out + (size_t)k * sx * sy, sx, h->map.cells + (size_t)(first + k) * h->map.pool_stride,
-                          (size_t)h->map.pitch, sx, sy, hipMemcpyDeviceToHost));
+  const DevMap& m = h->map;
+  if ((rc = download_maps(m.cells, m.pitch, m.pool_stride, m.size_x, m.size_y, first, count, cells_out))) return rc;
   if (origins_out) {
     if (h->map.pool_count > 0)
       HIP_TRY(hipMemcpy(origins_out, h->map.pool_origins + 2 * (size_t)first, (size_t)count * 16, hipMemcpyDeviceToHost));
@@ -1500,6 +1526,22 @@ int neo_mpc_inflation_costs(double res, double ins, double infl, double csf, uin
   return NEO_MPC_OK;
 }
 
+// The refusals K8 and K10 share, behind each one's own: the handle's pool, one robot per window, the reach
+static int check_pool_batch(const neo_mpc_handle* h, size_t count, double ins, double infl, double csf) {
+  if (!h->has_map) return fail(NEO_MPC_ERR_NO_COSTMAP, "the handle holds no costmap");
+  if (h->map.pool_count <= 0) return fail(NEO_MPC_ERR_UNSUPPORTED, "the handle holds a single costmap, not a pool");
+  if (count > 0 && count != (size_t)h->map.pool_count)
+    return fail(NEO_MPC_ERR_INVALID_ARGUMENT, "%zu robots for a pool of %d windows: they are one to one", count, h->map.pool_count);
+  return inflation_reach(h->map.resolution, ins, infl, csf, "", nullptr);
+}
+
+// The end of a synchronous variant of K8, K9 or K10: the null stream is waited for whether or not the enqueue failed (`rc`) -> the first error
+static int finish_on_null_stream(int rc) {
+  if (rc) { (void)hipStreamSynchronize(nullptr); return rc; }
+  HIP_TRY(hipStreamSynchronize(nullptr));
+  return NEO_MPC_OK;
+}
+
 // What both stamp entry points check: the record's shape and the handle's pool, never a value behind a pointer.
 static int check_stamp_batch(const neo_mpc_handle* h, const neo_mpc_stamp_batch* b) {
   if (!h || !b) return fail(NEO_MPC_ERR_INVALID_ARGUMENT, "null argument");
@@ -1508,11 +1550,7 @@ static int check_stamp_batch(const neo_mpc_handle* h, const neo_mpc_stamp_batch*
   if (int rc = check_inflation_radii(b->inscribed_radius, b->inflation_radius, b->cost_scaling_factor)) return rc;
   if (b->count > 0 && !b->polygons && (!b->footprint || (!b->poses && !b->problems)))
     return fail(NEO_MPC_ERR_INVALID_ARGUMENT, "neither polygons nor a footprint with poses or problems");
-  if (!h->has_map) return fail(NEO_MPC_ERR_NO_COSTMAP, "the handle holds no costmap");
-  if (h->map.pool_count <= 0) return fail(NEO_MPC_ERR_UNSUPPORTED, "the handle holds a single costmap, not a pool");
-  if (b->count > 0 && b->count != (size_t)h->map.pool_count)
-    return fail(NEO_MPC_ERR_INVALID_ARGUMENT, "%zu robots for a pool of %d windows: they are one to one", b->count, h->map.pool_count);
-  return inflation_reach(h->map.resolution, b->inscribed_radius, b->inflation_radius, b->cost_scaling_factor, "", nullptr);
+  return check_pool_batch(h, b->count, b->inscribed_radius, b->inflation_radius, b->cost_scaling_factor);
 }
 
 // `d`: the record with device pointers.  Orders itself like roll(): it rewrites the device maps in place.
@@ -1575,24 +1613,24 @@ int neo_mpc_stamp_fleet(neo_mpc_handle* h, const neo_mpc_stamp_batch* b) {
     else d.problems = h->problems.upload(b->problems, n * sizeof(neo_mpc_problem));
     if (!d.poses && !d.problems) return NEO_MPC_ERR_DEVICE;
   }
-  if ((rc = stamp(h, d, nullptr))) { (void)hipStreamSynchronize(nullptr); return rc; }   // (the staging is free again)
-  HIP_TRY(hipStreamSynchronize(nullptr));
-  return NEO_MPC_OK;
+  return finish_on_null_stream(stamp(h, d, nullptr));
 }
 
+// K9.  What both inflation entry points refuse, before any HIP call
+static int check_inflate_world_map(const neo_mpc_handle* h, double ins, double infl, double csf) {
+  if (!h) return fail(NEO_MPC_ERR_INVALID_ARGUMENT, "null handle");
+  if (int rc = check_inflation_radii(ins, infl, csf)) return rc;
+  if (!h->world.has) return fail(NEO_MPC_ERR_NO_COSTMAP, "neo_mpc_set_world_map has not been called");
+  return inflation_reach(h->world.resolution, ins, infl, csf, "the world map's ", nullptr);
+}
 // K9.  nav2's inflation layer on the handle's copy of the world map, in place (the contract: include/neo_mpc.h).  Orders
 // itself like set_world_map's copy -- they write the same buffer -- on `stream`, or on the host and the null stream.
 static int inflate_world_map(neo_mpc_handle* h, double ins, double infl, double csf, bool on_device, void* stream) {
-  if (!h) return fail(NEO_MPC_ERR_INVALID_ARGUMENT, "null handle");
-  int rc = check_inflation_radii(ins, infl, csf);
-  if (rc) return rc;
   WorldMap& w = h->world;
-  if (!w.has) return fail(NEO_MPC_ERR_NO_COSTMAP, "neo_mpc_set_world_map has not been called");
-  if ((rc = inflation_reach(w.resolution, ins, infl, csf, "the world map's ", nullptr))) return rc;
   HIP_TRY(hipSetDevice(h->device));
-  if ((rc = h->world_table.build(w.resolution, ins, infl, csf, w))) return rc;   // (every inflation records the world's event)
+  if (int rc = h->world_table.build(w.resolution, ins, infl, csf, w)) return rc;   // (every inflation records the world's event)
   hipStream_t st = (hipStream_t)stream;
-  if ((rc = w.begin_write(h->fence, on_device, st))) return rc;
+  if (int rc = w.begin_write(h->fence, on_device, st)) return rc;
   InflateArgs a;
   std::memset(&a, 0, sizeof(a));
   a.world = w.buf.as<uint8_t>();
@@ -1605,14 +1643,13 @@ static int inflate_world_map(neo_mpc_handle* h, double ins, double infl, double 
 }
 
 int neo_mpc_inflate_world_map_device(neo_mpc_handle* h, double ins, double infl, double csf, void* stream) {
+  if (int rc = check_inflate_world_map(h, ins, infl, csf)) return rc;
   return inflate_world_map(h, ins, infl, csf, true, stream);
 }
 
 int neo_mpc_inflate_world_map(neo_mpc_handle* h, double ins, double infl, double csf) {
-  int rc = inflate_world_map(h, ins, infl, csf, false, nullptr);
-  if (rc) return rc;
-  HIP_TRY(hipStreamSynchronize(nullptr));
-  return NEO_MPC_OK;
+  if (int rc = check_inflate_world_map(h, ins, infl, csf)) return rc;
+  return finish_on_null_stream(inflate_world_map(h, ins, infl, csf, false, nullptr));
 }
 
 // K10.  What both update entry points check: the record's shape and the handle's pool, never a value behind a pointer.
@@ -1629,54 +1666,40 @@ static int check_scan_batch(const neo_mpc_handle* h, const neo_mpc_scan_batch* b
   for (const double r : {b->obstacle_max_range, b->obstacle_min_range, b->raytrace_max_range, b->raytrace_min_range})
     if (!std::isfinite(r) || r < 0.0) return fail(NEO_MPC_ERR_INVALID_ARGUMENT, "range %g must be finite and not negative", r);
   if (int rc = check_inflation_radii(b->inscribed_radius, b->inflation_radius, b->cost_scaling_factor)) return rc;
-  if (!h->has_map) return fail(NEO_MPC_ERR_NO_COSTMAP, "the handle holds no costmap");
-  if (h->map.pool_count <= 0) return fail(NEO_MPC_ERR_UNSUPPORTED, "the handle holds a single costmap, not a pool");
-  if (b->count > 0 && b->count != (size_t)h->map.pool_count)
-    return fail(NEO_MPC_ERR_INVALID_ARGUMENT, "%zu robots for a pool of %d windows: they are one to one", b->count, h->map.pool_count);
-  return inflation_reach(h->map.resolution, b->inscribed_radius, b->inflation_radius, b->cost_scaling_factor, "", nullptr);
+  return check_pool_batch(h, b->count, b->inscribed_radius, b->inflation_radius, b->cost_scaling_factor);
 }
 
 // `d`: the record with device pointers.  Orders itself like stamp(): it rewrites the device maps in place, and the layer
 // buffers inside the same write.
 static int scan(neo_mpc_handle* h, const neo_mpc_scan_batch& d, void* stream) {
   const DevMap& m = h->map;
+  ScanLayers& l = h->scan;
   // (every update ends a write of the fence)
-  int rc = h->scan_table.build(m.resolution, d.inscribed_radius, d.inflation_radius, d.cost_scaling_factor, h->fence);
+  int rc = l.table.build(m.resolution, d.inscribed_radius, d.inflation_radius, d.cost_scaling_factor, h->fence);
   if (rc) return rc;
-  const int layer_pitch = (m.size_x + 63) & ~63;
-  const size_t layer_stride = (size_t)layer_pitch * (size_t)m.size_y;
-  const bool same = h->scan_valid && h->scan_sx == m.size_x && h->scan_sy == m.size_y && h->scan_count == m.pool_count &&
-                    h->scan_res == m.resolution && h->scan_unknown == d.unknown_value;
-  if (!same) {
-    // a reset: the buffers are re-allocated only where the geometry asks for more (a re-allocation synchronises)
-    h->scan_valid = false;
-    if ((rc = h->scan_layer.reserve(layer_stride * d.count))) return rc;
-    if ((rc = h->scan_work.reserve(layer_stride * d.count))) return rc;
-    if ((rc = h->scan_origins.reserve(d.count * 16))) return rc;
-  }
+  const bool same = l.matches(m, d.unknown_value);
+  if (!same && (rc = l.resize(m, d.unknown_value))) return rc;   // (d.count is the pool's: check_pool_batch)
   hipStream_t st = (hipStream_t)stream;
   if ((rc = h->fence.begin_write(st))) return rc;
   ScanArgs a;
   std::memset(&a, 0, sizeof(a));
   if (d.flags != 0) { a.points = d.points; a.point_counts = d.point_counts; a.sensor_origins = d.sensor_origins; }
-  a.table = h->scan_table.buf.as<const uint8_t>();
-  a.layer = h->scan_layer.as<uint8_t>(); a.work = h->scan_work.as<uint8_t>(); a.layer_origins = h->scan_origins.as<double>();
+  a.table = l.table.buf.as<const uint8_t>();
+  a.layer = l.layer.as<uint8_t>(); a.work = l.work.as<uint8_t>(); a.layer_origins = l.origins.as<double>();
   a.cells = const_cast<uint8_t*>(m.cells);   // (cell (0, 0) of the first map of map_buf, the handle's own)
   a.origins = m.pool_origins;
   a.res = m.resolution;
   a.obstacle_max = d.obstacle_max_range; a.obstacle_min = d.obstacle_min_range;
   a.raytrace_max = d.raytrace_max_range; a.raytrace_min = d.raytrace_min_range;
-  a.stride = m.pool_stride; a.layer_stride = (int64_t)layer_stride;
-  a.size_x = m.size_x; a.size_y = m.size_y; a.pitch = m.pitch; a.layer_pitch = layer_pitch;
-  a.reach = h->scan_table.reach;
+  a.stride = m.pool_stride; a.layer_stride = (int64_t)l.stride();
+  a.size_x = m.size_x; a.size_y = m.size_y; a.pitch = m.pitch; a.layer_pitch = l.pitch();
+  a.reach = l.table.reach;
   a.count = (uint32_t)d.count; a.max_points = d.max_points; a.flags = d.flags; a.unknown = d.unknown_value;
   a.reset = same ? 0u : 1u;
   launch_scan_layer(a, stream);
   HIP_TRY(hipGetLastError());
   if ((rc = h->fence.end_write(st))) return rc;   // a stamp, gate or solve behind it sees the windows with the layer in them
-  h->scan_valid = true;
-  h->scan_sx = m.size_x; h->scan_sy = m.size_y; h->scan_count = m.pool_count; h->scan_res = m.resolution;
-  h->scan_unknown = d.unknown_value;
+  l.adopt();
   return NEO_MPC_OK;
 }
 
@@ -1703,40 +1726,36 @@ int neo_mpc_update_scan_layer(neo_mpc_handle* h, const neo_mpc_scan_batch* b) {
       if (!std::isfinite(b->sensor_origins[2 * k]) || !std::isfinite(b->sensor_origins[2 * k + 1]))
         return fail(NEO_MPC_ERR_INVALID_ARGUMENT, "the sensor origin of robot %zu is not finite", k);
     }
-    HIP_TRY(hipSetDevice(h->device));
-    if (!(d.sensor_origins = h->scan_sensors.upload(b->sensor_origins, n * 16))) return NEO_MPC_ERR_DEVICE;
-    if (b->max_points > 0 && !(d.points = h->scan_points.upload(b->points, n * b->max_points * 16))) return NEO_MPC_ERR_DEVICE;
-    if (b->point_counts && !(d.point_counts = h->scan_point_counts.upload(b->point_counts, n * 4))) return NEO_MPC_ERR_DEVICE;
   }
   HIP_TRY(hipSetDevice(h->device));
-  if ((rc = scan(h, d, nullptr))) { (void)hipStreamSynchronize(nullptr); return rc; }   // (the staging is free again)
-  HIP_TRY(hipStreamSynchronize(nullptr));
-  return NEO_MPC_OK;
+  if (b->flags != 0) {
+    if (!(d.sensor_origins = h->scan.sensors.upload(b->sensor_origins, n * 16))) return NEO_MPC_ERR_DEVICE;
+    if (b->max_points > 0 && !(d.points = h->scan.points.upload(b->points, n * b->max_points * 16))) return NEO_MPC_ERR_DEVICE;
+    if (b->point_counts && !(d.point_counts = h->scan.point_counts.upload(b->point_counts, n * 4))) return NEO_MPC_ERR_DEVICE;
+  }
+  return finish_on_null_stream(scan(h, d, nullptr));
 }
 
 int neo_mpc_get_scan_layer(neo_mpc_handle* h, uint32_t first, uint32_t count, uint8_t* cells_out, double* origins_out) {
   if (!h) return fail(NEO_MPC_ERR_INVALID_ARGUMENT, "null handle");
-  if (!h->scan_valid) return fail(NEO_MPC_ERR_NO_COSTMAP, "no scan layer: neo_mpc_update_scan_layer has not been called since the last reset");
-  const uint32_t maps = (uint32_t)h->scan_count;
+  const ScanLayers& l = h->scan;
+  if (!l.valid) return fail(NEO_MPC_ERR_NO_COSTMAP, "no scan layer: neo_mpc_update_scan_layer has not been called since the last reset");
+  const uint32_t maps = (uint32_t)l.count;
   if (first > maps || count > maps - first)
     return fail(NEO_MPC_ERR_INVALID_ARGUMENT, "layers [%u, %u + %u) outside the %u there are", first, first, count, maps);
   if (count == 0) return NEO_MPC_OK;
   HIP_TRY(hipSetDevice(h->device));
   int rc = h->fence.wait_writer_host();   // the update in flight
   if (rc) return rc;
-  const size_t sx = (size_t)h->scan_sx, sy = (size_t)h->scan_sy, pitch = (sx + 63) & ~(size_t)63;
-  if (cells_out)
-    for (uint32_t k = 0; k < count; ++k)   // a strided copy per layer: the pitch stays behind
-      HIP_TRY(hipMemcpy2D(cells_out + (size_t)k * sx * sy, sx, h->scan_layer.as<uint8_t>() + (size_t)(first + k) * pitch * sy,
-                          pitch, sx, sy, hipMemcpyDeviceToHost));
+  if ((rc = download_maps(l.layer.as<uint8_t>(), l.pitch(), l.stride(), l.size_x, l.size_y, first, count, cells_out))) return rc;
   if (origins_out)
-    HIP_TRY(hipMemcpy(origins_out, h->scan_origins.as<double>() + 2 * (size_t)first, (size_t)count * 16, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(origins_out, l.origins.as<double>() + 2 * (size_t)first, (size_t)count * 16, hipMemcpyDeviceToHost));
   return NEO_MPC_OK;
 }
 
 int neo_mpc_reset_scan_layer(neo_mpc_handle* h) {
   if (!h) return fail(NEO_MPC_ERR_INVALID_ARGUMENT, "null handle");
-  h->scan_valid = false;
+  h->scan.valid = false;
   return NEO_MPC_OK;
 }
 

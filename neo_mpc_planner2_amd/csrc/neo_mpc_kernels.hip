@@ -18,7 +18,7 @@
 //   K6 k_footprint_gate  footprint_gate.h: the footprint gate in front of the carrot (cpp:218-219), one wave per robot.
 //   K7 k_roll_index, k_roll_fill  rolling_window.h: a fleet's rolling costmap windows cut from one world map, HBM-streaming.
 //   K8 k_stamp_boxes, k_stamp_fleet  fleet_stamp.h: the fleet's robots stamped into each other's windows, inflation ring included.
-//   K9 k_inflate_world  world_inflation.h: nav2's inflation layer on the world map, in place (inflation.h: what it shares with K8).
+//   K9 k_inflate_world  world_inflation.h: nav2's inflation layer on the world map, in place (inflation.h: what it shares with K8 and K10).
 //   K10 k_scan_shift, k_scan_rays, k_scan_apply  scan_layer.h: the obstacle layer of every window, fed from sensor points.
 #include "k1_solve.h"
 #include "costmap_ingest.h"
@@ -365,8 +365,8 @@ void launch_scan_layer(const ScanArgs& a, void* stream) {
   const dim3 rays((a.max_points + kScanRayThreads - 1) / kScanRayThreads, a.count);
   if (a.max_points > 0 && (a.flags & NEO_MPC_SCAN_CLEAR)) hipLaunchKernelGGL(k_scan_rays<false>, rays, dim3(kScanRayThreads), 0, st, a);
   if (a.max_points > 0 && (a.flags & NEO_MPC_SCAN_MARK)) hipLaunchKernelGGL(k_scan_rays<true>, rays, dim3(kScanRayThreads), 0, st, a);
-  hipLaunchKernelGGL(k_scan_apply, dim3((a.size_x + kScanTile - 1) / kScanTile, (a.size_y + kScanTile - 1) / kScanTile, a.count),
-                     dim3(kLanes * kScanWaves), 0, st, a);
+  hipLaunchKernelGGL(k_scan_apply, dim3((a.size_x + kInflateTile - 1) / kInflateTile, (a.size_y + kInflateTile - 1) / kInflateTile, a.count),
+                     dim3(kLanes * kInflateWaves), 0, st, a);
 }
 void launch_ingest(const IngestArgs& a, const LaunchTuning& tuning, void* stream) {
   hipLaunchKernelGGL(k_ingest, padded_map_grid(a.rows, a.pitch, kIngestUnroll, a.maps > 0 ? a.maps : 1), dim3(256), 0,

@@ -19,10 +19,6 @@ namespace {
 
 constexpr int kScanShiftRows = 16;  // rows of one window a workgroup of k_scan_shift moves
 constexpr int kScanRayThreads = 256;
-constexpr int kScanTile = 64;       // k_scan_apply, K9's scheme: a workgroup owns 64 x 64 cells, lane = column
-constexpr int kScanWaves = 4;
-constexpr int kScanLoads = 8;
-constexpr int kScanRows = kScanTile + 2 * NEO_MPC_MAX_INFLATION_CELLS;
 
 // K10a, step 1 of the contract (and its reset): grid (row chunks, window), four cells per thread and store.  A workgroup
 // reads `layer` and the two origins, which no launch of this update has written yet, and writes rows of `work` that are its
@@ -147,55 +143,29 @@ __global__ __launch_bounds__(kScanRayThreads) void k_scan_rays(const ScanArgs a)
 
 // K10c, steps 4 and 5 of the contract, K9's scheme per window: grid (tile column, tile row, window), one workgroup of four
 // waves per tile of 64 x 64 cells.
-//   1  The tile's halo of `work` -- the tile and R cells on every side, clipped to the window -- becomes a bitmask of seeds in
-//      LDS: __ballot(layer == 254), three words per row.
+//   1  The tile's halo of `work` becomes a bitmask of seeds in LDS (inflation_tile_seeds).
 //   2  Every cell of the tile: the layer's value goes back to `layer`, and into the window by updateWithMax.
-//   3  A tile with a seed in its halo loads T and every cell takes T[N] by nav2's rule (inflation_scan / inflation_combine);
-//      a tile without one never loads T.
+//   3  A tile with a seed in its halo has T in LDS and every cell takes T[N] by nav2's rule (inflation_tile_distance,
+//      inflation_combine); a tile without one never loads T.
 // Seeds are read from `work`, which this launch does not write, so the in-place hazard K9 argues away does not arise here.
 // `layer` is written and not read.  A window byte is read and written by the one lane that owns its cell, step 2 before
 // step 3 in program order.  The layer's new origin is the window's: written by the window's first tile, read by nobody in
-// this launch.  No atomics; both barriers are unconditional; the loops that ballot have wave-uniform trip counts.
-__global__ __launch_bounds__(kLanes * kScanWaves) void k_scan_apply(const ScanArgs a) {
-  __shared__ uint64_t masks[kScanRows * 3];
+// this launch.  No atomics.
+__global__ __launch_bounds__(kLanes * kInflateWaves) void k_scan_apply(const ScanArgs a) {
+  __shared__ uint64_t masks[kInflateRows * 3];
   __shared__ uint8_t table[kInflationTableBytes];
-  __shared__ int seen[kScanWaves];
+  __shared__ int seen[kInflateWaves];
   const int lane = threadIdx.x & (kLanes - 1), wave = uniform_int((int)(threadIdx.x >> 6));
   const uint32_t k = blockIdx.z;
   const int R = a.reach, sx = a.size_x, sy = a.size_y, lp = a.layer_pitch;
-  const int tx = (int)blockIdx.x * kScanTile, ty = (int)blockIdx.y * kScanTile;
+  const int tx = (int)blockIdx.x * kInflateTile, ty = (int)blockIdx.y * kInflateTile;
   const uint8_t* work = a.work + (int64_t)k * a.layer_stride;
   uint8_t* keep = a.layer + (int64_t)k * a.layer_stride;
   uint8_t* cells = a.cells + (int64_t)k * a.stride;
   if (blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x < 2) a.layer_origins[2 * (size_t)k + threadIdx.x] = a.origins[2 * (size_t)k + threadIdx.x];
-  const int rows = kScanTile + 2 * R;                 // masks[3 * rr + w]: layer row ty - R + rr, columns tx + 64 (w - 1) ...
-  const int c_lo = tx - R > 0 ? tx - R : 0;
-  const int c_hi = tx + kScanTile + R < sx ? tx + kScanTile + R : sx;
-  bool any = false;
-  for (int t0 = wave; t0 < rows * 3; t0 += kScanWaves * kScanLoads) {
-    int cell[kScanLoads];
-#pragma unroll
-    for (int u = 0; u < kScanLoads; ++u) {
-      const int t = t0 + u * kScanWaves, rr = t / 3, w = t - 3 * rr;
-      const int r = ty - R + rr, col = tx + (w - 1) * kScanTile + lane;
-      cell[u] = 0;
-      if (t < rows * 3 && r >= 0 && r < sy && col >= c_lo && col < c_hi) cell[u] = work[(int64_t)r * lp + col];   // inside the layer
-    }
-#pragma unroll
-    for (int u = 0; u < kScanLoads; ++u) {
-      const int t = t0 + u * kScanWaves;
-      const uint64_t m = __ballot(cell[u] == 254);
-      if (t < rows * 3 && lane == 0) masks[t] = m;    // (t < kScanRows * 3: inside masks)
-      any = any || m != 0;
-    }
-  }
-  if (lane == 0) seen[wave] = any ? 1 : 0;
-  __syncthreads();
-  const bool some = (seen[0] | seen[1] | seen[2] | seen[3]) != 0;   // the same in every lane of the workgroup
-  if (some) inflation_stage_table(table, a.table, R, (int)threadIdx.x, kLanes * kScanWaves);
-  __syncthreads();
+  const bool some = inflation_tile_seeds(masks, table, seen, work, lp, sx, sy, tx, ty, R, a.table, lane, wave);
   const int i = tx + lane;
-  for (int j = wave; j < kScanTile && ty + j < sy; j += kScanWaves) {
+  for (int j = wave; j < kInflateTile && ty + j < sy; j += kInflateWaves) {
     const int l = ty + j, r0 = j + R;
     if (i >= sx) continue;                             // (nothing below is a wave operation)
     // 0 <= i < size_x, 0 <= l < size_y: this tile's own cell, in the layers and in the window
@@ -207,11 +177,7 @@ __global__ __launch_bounds__(kLanes * kScanWaves) void k_scan_apply(const ScanAr
       if (old == 255 || old < v) *p = (uint8_t)v;
     }
     if (!some) continue;
-    const int best = inflation_scan(R, [&](int dy, auto&& found) {   // (0 <= r0 - R and r0 + R < rows)
-      const uint64_t* m = masks + 3 * (r0 + dy);
-      const uint64_t m0 = m[0], m1 = m[1], m2 = m[2];
-      if (m0 | m1 | m2) found(inflate_row_distance(m0, m1, m2, lane));
-    });
+    const int best = inflation_tile_distance(masks, R, r0, lane);
     if (best <= R * R) inflation_combine(p, table, best);
   }
 }

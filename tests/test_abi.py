@@ -10,6 +10,7 @@ import numpy as np
 import pytest
 
 from neo_mpc_planner2_amd import _lib, abi
+from tests.c_probe import kernel_resources, run_c_probe
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HEADER = os.path.join(ROOT, "include", "neo_mpc.h")
@@ -36,8 +37,7 @@ def test_library_exports_every_declared_symbol():
 
 
 def test_record_layouts_match_the_header(tmp_path):
-    src = tmp_path / "probe.c"
-    src.write_text(r'''
+    got = run_c_probe(tmp_path, r'''
 #include <stdio.h>
 #include <stddef.h>
 #include "neo_mpc.h"
@@ -56,9 +56,6 @@ int main(void) {
   P(neo_mpc_batch, footprints); P(neo_mpc_batch, footprint_points); P(neo_mpc_batch, velocities);
   return 0;
 }''')
-    exe = tmp_path / "probe"
-    subprocess.check_call(["gcc", "-I", os.path.join(ROOT, "include"), str(src), "-o", str(exe)])
-    got = dict(line.split() for line in subprocess.check_output([str(exe)]).decode().splitlines())
     got = {k: int(v) for k, v in got.items()}
     assert got["sizeof.params"] == C.sizeof(abi.NeoMpcParams)
     assert got["sizeof.problem"] == abi.PROBLEM_DTYPE.itemsize == 256
@@ -240,31 +237,14 @@ def test_bench_dump_outputs_layout_and_cap(tmp_path):
     assert np.array_equal(np.load(str(tmp_path / "s1" / "state_old_goal.npy")), st["old_goal"][rows])
 
 
-def test_baseline_kernels_are_scratch_free():
+def test_baseline_kernels_are_scratch_free(tmp_path):
     """The kernels of the BASELINE configs -- k_solve_routed<4, tame, static tile> (config 2 / 4: control_steps 3, AUTO) and
     k_solve<4, 0, stage-wise, tame> (configs 3 and 5) -- spill no vector register: 0 bytes of scratch per lane at their four
     waves per SIMD (round 5's config-3 / 5 kernel had picked up 24 bytes per lane unnoticed: its HBM writes doubled).  The
     compiler's own resource remarks for the translation unit both live in, with the flags of the Makefile; no GPU needed."""
-    import os
-    import re
-    import subprocess
-    csrc = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "neo_mpc_planner2_amd", "csrc")
-    mk = open(os.path.join(csrc, "Makefile")).read()
+    mk = open(os.path.join(ROOT, "neo_mpc_planner2_amd", "csrc", "Makefile")).read()
     flags = re.search(r"^RICCATI_FLAGS := (.*)$", mk, re.M).group(1).split()
-    out = subprocess.run(["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wno-unused-function",
-                          "-Wno-pass-failed"] + flags + ["-Rpass-analysis=kernel-resource-usage", "-x", "hip", "-c",
-                          "neo_mpc_riccati.hip", "-o", os.devnull], cwd=csrc, capture_output=True, text=True, timeout=900)
-    assert out.returncode == 0, out.stderr[-2000:]
-    rows, cur = {}, None
-    for line in out.stderr.splitlines():
-        m = re.search(r"Function Name: (\S+)", line)
-        if m:
-            cur = m.group(1)
-            rows[cur] = {}
-            continue
-        m = re.search(r"remark:\s+([A-Za-z ]+)(?: \[[^\]]*\])?: (\d+)", line)
-        if m and cur:
-            rows[cur][m.group(1).strip()] = int(m.group(2))
+    rows = kernel_resources(tmp_path, '#include "neo_mpc_riccati.hip"\n', flags)
     wanted = {"k_solve_routedILi4ELb1ELi1024E": "config 2 / 4", "7k_solveILi4ELi0ELi2ELb1ELi0E": "configs 3, 5"}
     for key, what in wanted.items():
         hit = [v for k, v in rows.items() if key in k]

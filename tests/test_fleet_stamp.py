@@ -10,9 +10,7 @@ cannot move a cell."""
 import ctypes as C
 import functools
 import math
-import os
 import re
-import subprocess
 
 import numpy as np
 import pytest
@@ -21,9 +19,8 @@ from neo_mpc_planner2_amd import _lib, abi, synthetic
 from tests import fleet_stamp_reference as ref
 from tests import footprint_gate_reference as gate_ref
 from tests import rolling_window_reference as roll_ref
+from tests.c_probe import HEADER, run_c_probe
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HEADER = os.path.join(ROOT, "include", "neo_mpc.h")
 ENTRY_POINTS = ("neo_mpc_stamp_fleet", "neo_mpc_stamp_fleet_device", "neo_mpc_inflation_costs")
 WRES, WOX, WOY, WSIZE = synthetic.RESOLUTION, -1.5, -1.5, 300         # the world: 15 m around a 12 m yard
 PARAMS = (0.45, 0.9, 3.0)           # inscribed_radius, inflation_radius, cost_scaling_factor
@@ -94,22 +91,14 @@ def test_the_fast_transcription_equals_the_definition():
 # ------------------------------------------------------------------------------------------ 2: record and entry points
 def test_stamp_batch_layout_and_entry_points(tmp_path):
     fields = [f for f, _ in abi.NeoMpcStampBatch._fields_]
-    src = tmp_path / "probe.c"
-    src.write_text('#include <stdio.h>\n#include <stddef.h>\n#include "neo_mpc.h"\n'
-                   '#define P(f) printf(#f " %zu\\n", offsetof(neo_mpc_stamp_batch, f))\n'
-                   'int main(void) {\n  printf("sizeof %zu\\n", sizeof(neo_mpc_stamp_batch));\n'
-                   '  printf("cells %d\\n", NEO_MPC_MAX_INFLATION_CELLS);\n'
-                   + "".join("  P(%s);\n" % f for f in fields) +
-                   '  void* volatile f[3] = {' + ", ".join("(void*)%s" % n for n in ENTRY_POINTS) + '};\n'
-                   '  return f[0] == 0 || f[1] == 0 || f[2] == 0;\n}\n')
-    obj = tmp_path / "probe.o"
-    exe = tmp_path / "probe"
-    # (compiled against the header and linked against the library: the entry points are declared AND exported)
-    subprocess.check_call(["gcc", "-Wall", "-Werror=implicit-function-declaration", "-I", os.path.join(ROOT, "include"), "-c", str(src), "-o", str(obj)])
-    subprocess.check_call(["gcc", str(obj), "-L", os.path.join(ROOT, "neo_mpc_planner2_amd"), "-lneo_mpc",
-                           "-Wl,-rpath," + os.path.join(ROOT, "neo_mpc_planner2_amd"), "-Wl,-rpath,/opt/rocm/lib",
-                           "-o", str(exe)])
-    got = {k: int(v) for k, v in (line.split() for line in subprocess.check_output([str(exe)]).decode().splitlines())}
+    got = run_c_probe(tmp_path, '#include <stdio.h>\n#include <stddef.h>\n#include "neo_mpc.h"\n'
+                      '#define P(f) printf(#f " %zu\\n", offsetof(neo_mpc_stamp_batch, f))\n'
+                      'int main(void) {\n  printf("sizeof %zu\\n", sizeof(neo_mpc_stamp_batch));\n'
+                      '  printf("cells %d\\n", NEO_MPC_MAX_INFLATION_CELLS);\n'
+                      + "".join("  P(%s);\n" % f for f in fields) +
+                      '  void* volatile f[3] = {' + ", ".join("(void*)%s" % n for n in ENTRY_POINTS) + '};\n'
+                      '  return f[0] == 0 || f[1] == 0 || f[2] == 0;\n}\n')
+    got = {k: int(v) for k, v in got.items()}
     assert got["sizeof"] == C.sizeof(abi.NeoMpcStampBatch) == 80
     assert got["cells"] == abi.MAX_INFLATION_CELLS == 64
     for f in fields:

@@ -11,18 +11,15 @@ condition on the inputs (fixed seeds), not a tolerance; no robot is dropped."""
 import ctypes as C
 import functools
 import math
-import os
 import re
-import subprocess
 
 import numpy as np
 import pytest
 
 from neo_mpc_planner2_amd import _lib, abi, synthetic
 from tests import footprint_gate_reference as ref
+from tests.c_probe import HEADER, run_c_probe
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HEADER = os.path.join(ROOT, "include", "neo_mpc.h")
 RES = synthetic.RESOLUTION
 RECT = synthetic.RECT_FOOTPRINT
 TRIANGLE = ((0.4, 0.0), (-0.3, 0.3), (-0.3, -0.3))
@@ -81,21 +78,13 @@ def test_closed_form_equals_the_iterative_walk_exhaustively():
 
 def test_footprint_batch_layout_and_entry_points(tmp_path):
     fields = [f for f, _ in abi.NeoMpcFootprintBatch._fields_]
-    src = tmp_path / "probe.c"
-    src.write_text('#include <stdio.h>\n#include <stddef.h>\n#include "neo_mpc.h"\n'
-                   '#define P(f) printf(#f " %zu\\n", offsetof(neo_mpc_footprint_batch, f))\n'
-                   'int main(void) {\n  printf("sizeof %zu\\n", sizeof(neo_mpc_footprint_batch));\n'
-                   + "".join("  P(%s);\n" % f for f in fields) +
-                   '  void* volatile f[2] = {(void*)neo_mpc_footprint_gate, (void*)neo_mpc_footprint_gate_device};\n'
-                   '  return f[0] == 0 || f[1] == 0;\n}\n')
-    obj = tmp_path / "probe.o"
-    exe = tmp_path / "probe"
-    # (compiled against the header and linked against the library: both entry points are declared AND exported)
-    subprocess.check_call(["gcc", "-Wall", "-Werror=implicit-function-declaration", "-I", os.path.join(ROOT, "include"), "-c", str(src), "-o", str(obj)])
-    subprocess.check_call(["gcc", str(obj), "-L", os.path.join(ROOT, "neo_mpc_planner2_amd"), "-lneo_mpc",
-                           "-Wl,-rpath," + os.path.join(ROOT, "neo_mpc_planner2_amd"), "-Wl,-rpath,/opt/rocm/lib",
-                           "-o", str(exe)])
-    got = {k: int(v) for k, v in (line.split() for line in subprocess.check_output([str(exe)]).decode().splitlines())}
+    got = run_c_probe(tmp_path, '#include <stdio.h>\n#include <stddef.h>\n#include "neo_mpc.h"\n'
+                      '#define P(f) printf(#f " %zu\\n", offsetof(neo_mpc_footprint_batch, f))\n'
+                      'int main(void) {\n  printf("sizeof %zu\\n", sizeof(neo_mpc_footprint_batch));\n'
+                      + "".join("  P(%s);\n" % f for f in fields) +
+                      '  void* volatile f[2] = {(void*)neo_mpc_footprint_gate, (void*)neo_mpc_footprint_gate_device};\n'
+                      '  return f[0] == 0 || f[1] == 0;\n}\n')
+    got = {k: int(v) for k, v in got.items()}
     assert got["sizeof"] == C.sizeof(abi.NeoMpcFootprintBatch) == 64
     for f in fields:
         assert got[f] == getattr(abi.NeoMpcFootprintBatch, f).offset, f

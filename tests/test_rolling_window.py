@@ -6,18 +6,15 @@ identically on both sides, so every comparison with the transcription is exact e
 origins: no tolerance, no dropped case, no condition on the inputs."""
 import ctypes as C
 import functools
-import os
 import re
-import subprocess
 
 import numpy as np
 import pytest
 
 from neo_mpc_planner2_amd import _lib, abi, synthetic
 from tests import rolling_window_reference as ref
+from tests.c_probe import HEADER, run_c_probe
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HEADER = os.path.join(ROOT, "include", "neo_mpc.h")
 WRES = synthetic.RESOLUTION
 WOX, WOY = -1.0, -1.5
 ENTRY_POINTS = ("neo_mpc_set_world_map", "neo_mpc_set_world_map_device", "neo_mpc_roll_costmap_pool",
@@ -57,21 +54,13 @@ def test_transcription_on_a_hand_worked_map():
 # ------------------------------------------------------------------------------------------ 2: record and entry points
 def test_window_batch_layout_and_entry_points(tmp_path):
     fields = [f for f, _ in abi.NeoMpcWindowBatch._fields_]
-    src = tmp_path / "probe.c"
-    src.write_text('#include <stdio.h>\n#include <stddef.h>\n#include "neo_mpc.h"\n'
-                   '#define P(f) printf(#f " %zu\\n", offsetof(neo_mpc_window_batch, f))\n'
-                   'int main(void) {\n  printf("sizeof %zu\\n", sizeof(neo_mpc_window_batch));\n'
-                   + "".join("  P(%s);\n" % f for f in fields) +
-                   '  void* volatile f[5] = {' + ", ".join("(void*)%s" % n for n in ENTRY_POINTS) + '};\n'
-                   '  return f[0] == 0 || f[1] == 0 || f[2] == 0 || f[3] == 0 || f[4] == 0;\n}\n')
-    obj = tmp_path / "probe.o"
-    exe = tmp_path / "probe"
-    # (compiled against the header and linked against the library: the entry points are declared AND exported)
-    subprocess.check_call(["gcc", "-Wall", "-Werror=implicit-function-declaration", "-I", os.path.join(ROOT, "include"), "-c", str(src), "-o", str(obj)])
-    subprocess.check_call(["gcc", str(obj), "-L", os.path.join(ROOT, "neo_mpc_planner2_amd"), "-lneo_mpc",
-                           "-Wl,-rpath," + os.path.join(ROOT, "neo_mpc_planner2_amd"), "-Wl,-rpath,/opt/rocm/lib",
-                           "-o", str(exe)])
-    got = {k: int(v) for k, v in (line.split() for line in subprocess.check_output([str(exe)]).decode().splitlines())}
+    got = run_c_probe(tmp_path, '#include <stdio.h>\n#include <stddef.h>\n#include "neo_mpc.h"\n'
+                      '#define P(f) printf(#f " %zu\\n", offsetof(neo_mpc_window_batch, f))\n'
+                      'int main(void) {\n  printf("sizeof %zu\\n", sizeof(neo_mpc_window_batch));\n'
+                      + "".join("  P(%s);\n" % f for f in fields) +
+                      '  void* volatile f[5] = {' + ", ".join("(void*)%s" % n for n in ENTRY_POINTS) + '};\n'
+                      '  return f[0] == 0 || f[1] == 0 || f[2] == 0 || f[3] == 0 || f[4] == 0;\n}\n')
+    got = {k: int(v) for k, v in got.items()}
     assert got["sizeof"] == C.sizeof(abi.NeoMpcWindowBatch) == 56
     for f in fields:
         assert got[f] == getattr(abi.NeoMpcWindowBatch, f).offset, f

@@ -8,9 +8,7 @@ transcription is exact equality of uint8 cells and float64 origins -- no toleran
 import collections
 import ctypes as C
 import functools
-import os
 import re
-import subprocess
 
 import numpy as np
 import pytest
@@ -20,9 +18,9 @@ from tests import fleet_stamp_reference as stamp_ref
 from tests import footprint_gate_reference as gate_ref
 from tests import rolling_window_reference as roll_ref
 from tests import scan_layer_reference as ref
+from tests import world_inflation_reference as world_ref
+from tests.c_probe import HEADER, run_c_probe
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HEADER = os.path.join(ROOT, "include", "neo_mpc.h")
 ENTRY_POINTS = ("neo_mpc_update_scan_layer", "neo_mpc_update_scan_layer_device", "neo_mpc_get_scan_layer",
                 "neo_mpc_reset_scan_layer")
 #: wider than one 64-cell tile, not square, no multiples of 64
@@ -87,23 +85,15 @@ def test_the_line_walk_on_a_hand_worked_map():
 # ------------------------------------------------------------------------------------------ 2: record and entry points
 def test_scan_batch_layout_and_entry_points(tmp_path):
     fields = [f for f, _ in abi.NeoMpcScanBatch._fields_]
-    src = tmp_path / "probe.c"
-    src.write_text('#include <stdio.h>\n#include <stddef.h>\n#include "neo_mpc.h"\n'
-                   '#define P(f) printf(#f " %zu\\n", offsetof(neo_mpc_scan_batch, f))\n'
-                   'int main(void) {\n  printf("sizeof %zu\\n", sizeof(neo_mpc_scan_batch));\n'
-                   '  printf("MAX_SCAN_POINTS %u\\n", NEO_MPC_MAX_SCAN_POINTS);\n'
-                   '  printf("SCAN_CLEAR %u\\n", NEO_MPC_SCAN_CLEAR);\n  printf("SCAN_MARK %u\\n", NEO_MPC_SCAN_MARK);\n'
-                   + "".join("  P(%s);\n" % f for f in fields) +
-                   '  void* volatile f[4] = {' + ", ".join("(void*)%s" % n for n in ENTRY_POINTS) + '};\n'
-                   '  return f[0] == 0 || f[1] == 0 || f[2] == 0 || f[3] == 0;\n}\n')
-    obj = tmp_path / "probe.o"
-    exe = tmp_path / "probe"
-    # (compiled against the header and linked against the library: the entry points are declared AND exported)
-    subprocess.check_call(["gcc", "-Wall", "-Werror=implicit-function-declaration", "-I", os.path.join(ROOT, "include"), "-c", str(src), "-o", str(obj)])
-    subprocess.check_call(["gcc", str(obj), "-L", os.path.join(ROOT, "neo_mpc_planner2_amd"), "-lneo_mpc",
-                           "-Wl,-rpath," + os.path.join(ROOT, "neo_mpc_planner2_amd"), "-Wl,-rpath,/opt/rocm/lib",
-                           "-o", str(exe)])
-    got = {k: int(v) for k, v in (line.split() for line in subprocess.check_output([str(exe)]).decode().splitlines())}
+    got = run_c_probe(tmp_path, '#include <stdio.h>\n#include <stddef.h>\n#include "neo_mpc.h"\n'
+                      '#define P(f) printf(#f " %zu\\n", offsetof(neo_mpc_scan_batch, f))\n'
+                      'int main(void) {\n  printf("sizeof %zu\\n", sizeof(neo_mpc_scan_batch));\n'
+                      '  printf("MAX_SCAN_POINTS %u\\n", NEO_MPC_MAX_SCAN_POINTS);\n'
+                      '  printf("SCAN_CLEAR %u\\n", NEO_MPC_SCAN_CLEAR);\n  printf("SCAN_MARK %u\\n", NEO_MPC_SCAN_MARK);\n'
+                      + "".join("  P(%s);\n" % f for f in fields) +
+                      '  void* volatile f[4] = {' + ", ".join("(void*)%s" % n for n in ENTRY_POINTS) + '};\n'
+                      '  return f[0] == 0 || f[1] == 0 || f[2] == 0 || f[3] == 0;\n}\n')
+    got = {k: int(v) for k, v in got.items()}
     assert got["sizeof"] == C.sizeof(abi.NeoMpcScanBatch) == abi.SCAN_BATCH_DTYPE.itemsize == 104
     assert got["MAX_SCAN_POINTS"] == abi.MAX_SCAN_POINTS == 8192 and got["SCAN_CLEAR"] == abi.SCAN_CLEAR == 1 and got["SCAN_MARK"] == abi.SCAN_MARK == 2
     assert list(abi.SCAN_BATCH_DTYPE.names) == fields
@@ -702,3 +692,48 @@ def test_closed_loop_with_a_scan_and_without():
     assert free > wall_x, "the control run: the robot did not reach the wall"
     assert stopped < wall_x - 0.45
     assert ((runs["scan"][1]["flags"] & abi.FLAG_STOPPED) != 0).any(axis=0).all()
+
+
+# ------------------------------------------------------------------------------------------ 13: a seed exactly 64 cells away
+@functools.lru_cache(maxsize=None)
+def distance_64_case():
+    """193 x 66 free cells of 1/16 m (a layer pitch of 256), seeds at (64, 1) and (64, 65), R = 64: K9's and K10's shared pass
+    where a seed is exactly 64 columns away across a tile border on either side, and 64 rows.  -> (world, inflated world,
+    parameters, the two scan points [1, 2, 2], sensor origin [1, 2], layers, pool), the cell values asserted by hand."""
+    params = inflation_for(64, 0.0625)
+    table, reach = world_ref.table_for(0.0625, *params)
+    assert reach == 64 and table[4096] >= 1                              # (or the arm could not be seen)
+    world = np.zeros((66, 193), dtype=np.uint8)
+    world[1, 64] = world[65, 64] = 254
+    want = world_ref.inflate_world(world, 0.0625, *params)
+    # the centres of the seeds' cells, seen from the centre of cell (64, 33): 2 m either way, inside the default ranges
+    points, sensor = np.array([[(4.03125, 0.09375), (4.03125, 4.09375)]]), np.array([(4.03125, 2.09375)])
+    model = ref.ScanLayers()
+    pool = model.update(world[None] * 0, np.zeros((1, 2)), 0.0625, *params, points=points, sensor_origins=sensor)
+    assert np.argwhere(model.layers[0] == 254).tolist() == [[1, 64], [65, 64]]
+    for got in (want, pool[0]):
+        # 64 columns to the left and to the right of either seed: T[4096], in those two rows alone; from column 129 on: untouched
+        assert got[1, 0] == got[1, 128] == got[65, 0] == got[65, 128] == table[4096] and not got[:, 129:].any()
+        assert np.flatnonzero(got[:, 0]).tolist() == np.flatnonzero(got[:, 128]).tolist() == [1, 65]
+        # 64 rows from the other seed: each is a seed itself and keeps 254 from there, max(254, T[4096])
+        assert got[1, 64] == got[65, 64] == 254 and (got == 254).sum() == 2
+    return world, want, params, points, sensor, model.layers, pool
+
+
+def test_a_seed_exactly_64_cells_away_in_the_transcriptions():
+    assert np.array_equal(distance_64_case()[1], distance_64_case()[6][0])    # unknown layer cells leave a free window alone
+
+
+@pytest.mark.gpu
+def test_a_seed_exactly_64_cells_away_on_the_gpu():
+    from neo_mpc_planner2_amd.solver import BatchSolver
+    world, want, params, points, sensor, layers, pool = distance_64_case()
+    with BatchSolver({}) as s:
+        for put in (np.array, gpu):                                       # the host and the device variants
+            s.set_world_map(put(world), 0.0625, 0.0, 0.0)
+            s.inflate_world_map(*params)
+            assert np.array_equal(s.get_world_map()[0], want), put.__name__
+            s.set_costmap_pool(world[None] * 0, 0.0625, np.zeros((1, 2)))
+            s.update_scan_layer(*params, points=put(points), sensor_origins=put(sensor))
+            got = state_of(s)
+            assert np.array_equal(got[0], layers) and np.array_equal(got[2], pool), put.__name__

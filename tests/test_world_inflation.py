@@ -7,17 +7,14 @@ table, so every comparison is exact equality of uint8 cells: no tolerance, no dr
 `cases()` are what tests/test_world_inflation_gpu.py holds the library to."""
 import ctypes as C
 import functools
-import os
 import re
-import subprocess
 
 import numpy as np
 
 from neo_mpc_planner2_amd import _lib
 from tests import world_inflation_reference as ref
+from tests.c_probe import HEADER, kernel_resources, run_c_probe
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HEADER = os.path.join(ROOT, "include", "neo_mpc.h")
 ENTRY_POINTS = ("neo_mpc_inflate_world_map", "neo_mpc_inflate_world_map_device", "neo_mpc_get_world_map")
 SIZES = ((13, 11), (70, 67), (130, 75))                 # size_x, size_y: below one tile, just over one, 3 x 2 tiles
 DENSITIES = (0.002, 0.03)                               # seeds
@@ -96,25 +93,15 @@ def test_the_fast_transcription_equals_the_definition():
 
 # ------------------------------------------------------------------------------------------ 3: the entry points
 def test_entry_points_are_declared_and_exported(tmp_path):
-    src = tmp_path / "probe.c"
-    src.write_text('#include <stdio.h>\n#include "neo_mpc.h"\n'
-                   'int main(void) {\n'
-                   '  int (*host)(neo_mpc_handle*, double, double, double) = neo_mpc_inflate_world_map;\n'
-                   '  int (*device)(neo_mpc_handle*, double, double, double, void*) = neo_mpc_inflate_world_map_device;\n'
-                   '  int (*get)(neo_mpc_handle*, uint8_t*, uint32_t*, uint32_t*, double*, double*, double*) = neo_mpc_get_world_map;\n'
-                   '  void* volatile f[3] = {(void*)host, (void*)device, (void*)get};\n'
-                   '  printf("abi %d\\nbehaviour %d\\ncells %d\\n", NEO_MPC_ABI_VERSION, NEO_MPC_BEHAVIOUR_VERSION, NEO_MPC_MAX_INFLATION_CELLS);\n'
-                   '  printf("null %d %d %d\\n", host(0, 0.45, 0.9, 3.0), device(0, 0.45, 0.9, 3.0, 0), get(0, 0, 0, 0, 0, 0, 0));\n'
-                   '  return f[0] == 0 || f[1] == 0 || f[2] == 0;\n}\n')
-    obj = tmp_path / "probe.o"
-    exe = tmp_path / "probe"
-    # (compiled against the header and linked against the library: the entry points are declared AND exported)
-    subprocess.check_call(["gcc", "-Wall", "-Werror=implicit-function-declaration", "-Werror=incompatible-pointer-types", "-I",
-                           os.path.join(ROOT, "include"), "-c", str(src), "-o", str(obj)])
-    subprocess.check_call(["gcc", str(obj), "-L", os.path.join(ROOT, "neo_mpc_planner2_amd"), "-lneo_mpc",
-                           "-Wl,-rpath," + os.path.join(ROOT, "neo_mpc_planner2_amd"), "-Wl,-rpath,/opt/rocm/lib",
-                           "-o", str(exe)])
-    got = dict(line.split(None, 1) for line in subprocess.check_output([str(exe)]).decode().splitlines())
+    got = run_c_probe(tmp_path, '#include <stdio.h>\n#include "neo_mpc.h"\n'
+                      'int main(void) {\n'
+                      '  int (*host)(neo_mpc_handle*, double, double, double) = neo_mpc_inflate_world_map;\n'
+                      '  int (*device)(neo_mpc_handle*, double, double, double, void*) = neo_mpc_inflate_world_map_device;\n'
+                      '  int (*get)(neo_mpc_handle*, uint8_t*, uint32_t*, uint32_t*, double*, double*, double*) = neo_mpc_get_world_map;\n'
+                      '  void* volatile f[3] = {(void*)host, (void*)device, (void*)get};\n'
+                      '  printf("abi %d\\nbehaviour %d\\ncells %d\\n", NEO_MPC_ABI_VERSION, NEO_MPC_BEHAVIOUR_VERSION, NEO_MPC_MAX_INFLATION_CELLS);\n'
+                      '  printf("null %d %d %d\\n", host(0, 0.45, 0.9, 3.0), device(0, 0.45, 0.9, 3.0, 0), get(0, 0, 0, 0, 0, 0, 0));\n'
+                      '  return f[0] == 0 || f[1] == 0 || f[2] == 0;\n}\n', werror=("incompatible-pointer-types",))
     assert got["abi"] == "2" and got["behaviour"] == "6" and got["cells"] == "64"
     assert got["null"] == "-1 -1 -1"                                                # a null handle: NEO_MPC_ERR_INVALID_ARGUMENT
     text = re.sub(r"/\*.*?\*/", "", open(HEADER).read(), flags=re.S)
@@ -138,25 +125,9 @@ def test_the_inflation_kernel_is_scratch_free(tmp_path):
     """k_inflate_world spills nothing: the compiler's own resource remarks for a translation unit that holds this kernel
     alone, with the flags of the Makefile; no GPU needed.  Held to the figures DESIGN.md states: 8 waves per SIMD and 8736
     bytes of LDS (masks 4608, table 4112, flags 16)."""
-    csrc = os.path.join(ROOT, "neo_mpc_planner2_amd", "csrc")
-    src = tmp_path / "k9.hip"
-    src.write_text('#include "world_inflation.h"\n'
-                   'void launch(const neo_mpc::InflateArgs& a) {\n'
-                   '  hipLaunchKernelGGL(neo_mpc::k_inflate_world, dim3(1, 1), dim3(256), 0, nullptr, a);\n}\n')
-    out = subprocess.run(["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wno-unused-function",
-                          "-Wno-pass-failed", "-Rpass-analysis=kernel-resource-usage", "-I", csrc, "-x", "hip", "-c",
-                          str(src), "-o", os.devnull], capture_output=True, text=True, timeout=900)
-    assert out.returncode == 0, out.stderr[-2000:]
-    rows, cur = {}, None
-    for line in out.stderr.splitlines():
-        m = re.search(r"Function Name: (\S+)", line)
-        if m:
-            cur = m.group(1)
-            rows[cur] = {}
-            continue
-        m = re.search(r"remark:\s+([A-Za-z ]+)(?: \[[^\]]*\])?: (\d+)", line)
-        if m and cur:
-            rows[cur][m.group(1).strip()] = int(m.group(2))
+    rows = kernel_resources(tmp_path, '#include "world_inflation.h"\n'
+                            'void launch(const neo_mpc::InflateArgs& a) {\n'
+                            '  hipLaunchKernelGGL(neo_mpc::k_inflate_world, dim3(1, 1), dim3(256), 0, nullptr, a);\n}\n')
     hit = [v for k, v in rows.items() if "k_inflate_world" in k]
     assert len(hit) == 1, list(rows)
     print("k_inflate_world:", hit[0])
