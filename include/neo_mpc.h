@@ -44,6 +44,9 @@ extern "C" {
  * The scan obstacle layer (neo_mpc_scan_batch, neo_mpc_update_scan_layer[_device], neo_mpc_get_scan_layer,
  * neo_mpc_reset_scan_layer, NEO_MPC_MAX_SCAN_POINTS) added a record, four entry points and a constant in the same way: still
  * ABI 2, behaviour 6.
+ * The laser projection (neo_mpc_scanner, neo_mpc_laser_batch, neo_mpc_laser_beam_table, neo_mpc_project_laser[_device],
+ * neo_mpc_update_scan_layer_from_ranges[_device], NEO_MPC_MAX_SCAN_SOURCES, NEO_MPC_LASER_INF_IS_VALID) added two records,
+ * five entry points and two constants in the same way: still ABI 2, behaviour 6.
  *
  * Behaviour history (iterates and iteration counts differ between versions, results stay inside the parity protocol of
  * DESIGN.md section 1; neo_mpc_behaviour_version() returns the number of the build that answers):
@@ -447,15 +450,15 @@ typedef struct neo_mpc_stamp_batch {
  * it rolls with its window, is cleared along this tick's sensor rays and marked at their end points (nav2 Humble's
  * ObstacleLayer::raytraceFreespace, Costmap2D::raytraceLine, bresenham2D and the marking loop of
  * ObstacleLayer::updateBounds), is combined into the window with updateWithMax and inflated around its own lethal cells
- * with the cost table and combination rule of neo_mpc_stamp_batch.  The tick is roll -> scan -> stamp -> gate -> carrots ->
- * solve.  The scan step comes BEFORE the stamp: a ray that turns an unknown cell free would otherwise erase a stamp ring that
+ * with the cost table and combination rule of neo_mpc_stamp_batch.  The tick is roll -> scan (points or ranges) -> stamp ->
+ * gate -> carrots -> solve.  The scan step comes BEFORE the stamp: a ray that turns an unknown cell free would otherwise erase a stamp ring that
  * left it at 255.
  *
  * Input: points, not ranges.  nav2's obstacle layer consumes Observations: a sensor origin and a cloud of hit points already
  * in the costmap's global frame; the projection of a LaserScan and the tf transform happen in front of it (laser_geometry,
- * ObservationBuffer).  The record takes the same thing, one observation per robot and tick.  Out of scope: projecting ranges
- * to points; a z coordinate (min / max_obstacle_height); more than one observation per robot and tick;
- * observation_persistence; footprint_clearing_enabled -- obstacle_min_range is the stand-in for a scanner that sees its own
+ * ObservationBuffer).  The record takes the same thing, one observation per robot and tick; LaserScan ranges and several
+ * scanners per robot go through neo_mpc_laser_batch (K11, below), which projects them and runs this update over all of
+ * them.  Out of scope: a z coordinate (min / max_obstacle_height); observation_persistence; footprint_clearing_enabled -- obstacle_min_range is the stand-in for a scanner that sees its own
  * robot.
  *
  * Like neo_mpc_stamp_batch's, the contract is one by transcription: nav2 cannot be built next to this library, so the text
@@ -539,6 +542,73 @@ typedef struct neo_mpc_scan_batch {
   uint32_t unknown_value;         /* the layer's default: 255 (nav2's track_unknown_space) or 0; anything else is refused */
   uint32_t reserved;              /* MUST be zero */
 } neo_mpc_scan_batch;
+
+/* ---- the scan step fed from LaserScan ranges, several scanners per robot (K11) ------------------------- */
+
+#define NEO_MPC_MAX_SCAN_SOURCES 4u
+#define NEO_MPC_LASER_INF_IS_VALID 1u   /* neo_mpc_scanner.flags: a range of +inf is a beam that met nothing (nav2's inf_is_valid) */
+
+/* A fleet server receives sensor_msgs/LaserScan messages, not points: float32 ranges, an angle geometry shared by every
+ * scan of a scanner model, one robot pose per scan, and usually two scanners a robot, front and rear.  K11 projects the
+ * ranges of every scanner of every robot into global-frame points and sensor origins on the device, and
+ * neo_mpc_update_scan_layer_from_ranges runs the update of neo_mpc_scan_batch over all of them: every clear of every
+ * scanner first, every mark of every scanner afterwards, as nav2's ObstacleLayer::updateBounds raytraces all clearing
+ * observations before it marks any.  Two successive neo_mpc_update_scan_layer calls cannot give that order: the second
+ * scanner's rays would erase the cells the first one marked in the same tick.
+ *
+ * The model is laser_geometry::LaserProjection::projectLaser -- a table of cos / sin per scan geometry, a range valid when
+ * range_min <= r < range_max -- and, for +inf, ObstacleLayer::laserScanValidInfCallback.  Like neo_mpc_scan_batch's, the
+ * contract is one by transcription: laser_geometry and nav2 cannot be built next to this library, so the text below is the
+ * contract (tests/laser_scan_reference.py is its executable form) and neither is pinned against them.  Stated differences
+ * from nav2: float64 throughout (nav2's cloud and tf transform are float32); one planar pose per scan -- no per-beam time
+ * interpolation as in transformLaserScanToPointCloud, no z coordinate; range_max - 1e-4 is formed in float64.  Every float64
+ * + - * / is ONE correctly rounded operation in the order written (nothing fused).
+ *
+ * A scanner: configuration, shared by the whole fleet.  64 bytes. */
+typedef struct neo_mpc_scanner {
+  double mount_x, mount_y, mount_yaw;   /* the scanner's pose in the robot's base frame */
+  double angle_min, angle_increment;    /* LaserScan's, widened from float32 by the caller */
+  double range_min, range_max;          /* LaserScan's: finite, 0 <= range_min <= range_max */
+  uint32_t flags;                       /* NEO_MPC_LASER_INF_IS_VALID or 0; other bits are refused */
+  uint32_t reserved;                    /* MUST be zero */
+} neo_mpc_scanner;
+
+/* Projection of beam i of source (scanner) s of robot k, with the robot at (x_k, y_k, yaw_k):
+ *   1. r = (double)ranges[k][s][i].  If r == +inf and the scanner has NEO_MPC_LASER_INF_IS_VALID, r = range_max - 1e-4.
+ *   2. The beam is valid iff r >= range_min && r < range_max.  NaN, -inf, and +inf without the flag fail this test.
+ *   3. An invalid beam writes the point (NaN, NaN), which steps 2 and 3 of neo_mpc_scan_batch skip.  Nothing is compacted.
+ *   4. The beam table, built on the host with libm (neo_mpc_laser_beam_table; the device never evaluates a beam's cos or sin):
+ *        a = mount_yaw + (angle_min + (double)i * angle_increment);   Tb[s][i] = (c, sn) = (cos(a), sin(a))
+ *   5. Base frame: bx = mount_x + r * c and by = mount_y + r * sn.
+ *   6. Global frame, with (S, C) = (sin(yaw_k), cos(yaw_k)) evaluated on the device (the one step that is not pinned to the
+ *      bit: the device's sincos is within 1 ulp, exact at yaw 0):
+ *        gx = (x_k + bx * C) - by * S;   gy = (y_k + bx * S) + by * C
+ *   7. The sensor origin of (k, s) is the same two formulas at (bx, by) = (mount_x, mount_y).
+ *
+ * The layer update over `sources` scanners: reset, roll (step 1), combine (4) and inflate (5) are neo_mpc_scan_batch's,
+ * unchanged.  Step 2 (clear) runs for every source with that source's own origin; a source whose origin fails worldToMap
+ * clears nothing.  Step 3 (mark) runs for every source, after every clear of every source; the squared distance of its
+ * range test is taken to the point's own source's origin.
+ *
+ * Pointers: `scanners` is ALWAYS a host pointer and is consumed before the call returns.  The others are host pointers for
+ * neo_mpc_project_laser / neo_mpc_update_scan_layer_from_ranges and device pointers for the _device variants; a device
+ * `points_out` must be 16-byte aligned.  128 bytes. */
+typedef struct neo_mpc_laser_batch {
+  size_t count;                      /* robots; for the update: = windows, the pool's map count (0: nothing happens) */
+  const float* ranges;               /* [count][sources][beams] LaserScan.ranges as on the wire */
+  const double* poses;               /* [count][3] robot x, y, yaw, global frame: the roll's and the gate's array */
+  const neo_mpc_scanner* scanners;   /* [sources], host memory */
+  uint32_t sources;                  /* 1 .. NEO_MPC_MAX_SCAN_SOURCES */
+  uint32_t beams;                    /* >= 1; sources * beams <= NEO_MPC_MAX_SCAN_POINTS */
+  double* points_out;                /* [count][sources][beams][2]; the update: optional, NULL = a buffer of the handle's */
+  double* origins_out;               /* [count][sources][2]; the update: optional, NULL = a buffer of the handle's */
+  uint32_t scan_flags;               /* NEO_MPC_SCAN_*, not 0: a tick without a new scan is neo_mpc_scan_batch's flags == 0 */
+  uint32_t unknown_value;            /* as neo_mpc_scan_batch */
+  double obstacle_max_range, obstacle_min_range;   /* as neo_mpc_scan_batch */
+  double raytrace_max_range, raytrace_min_range;
+  double inscribed_radius, inflation_radius, cost_scaling_factor;
+  uint64_t reserved;                 /* MUST be zero */
+} neo_mpc_laser_batch;
 
 typedef struct neo_mpc_handle neo_mpc_handle;
 
@@ -845,6 +915,40 @@ int neo_mpc_get_scan_layer(neo_mpc_handle* handle, uint32_t first, uint32_t coun
 /* The next update starts from a layer of unknown_value.  Touches no device memory.  NEO_MPC_ERR_INVALID_ARGUMENT for a null
  * handle. */
 int neo_mpc_reset_scan_layer(neo_mpc_handle* handle);
+
+/* The beam table of one scanner (K11; the contract: neo_mpc_laser_batch, step 4): table_out[beams][2] = (cos, sin) of every
+ * beam's angle in the base frame.  Pure host code: no handle, no device.  NEO_MPC_ERR_INVALID_ARGUMENT for a null argument,
+ * beams outside 1 .. NEO_MPC_MAX_SCAN_POINTS and a scanner the projection refuses (below). */
+int neo_mpc_laser_beam_table(const neo_mpc_scanner* scanner, uint32_t beams, double* table_out);
+/* Projects LaserScan ranges into global-frame points and sensor origins (K11), and nothing else: for display, logging and
+ * tests.  `points_out` and `origins_out` are required; scan_flags, unknown_value and the range and inflation fields are
+ * ignored; no costmap is needed, layers and pool are not touched and `count` is free.  Host pointers, synchronous.
+ * Refusals, which leave the out buffers alone: NEO_MPC_ERR_INVALID_ARGUMENT for a null handle, batch or array, a non-zero
+ * `reserved` of the batch or of a scanner, `sources` outside 1 .. NEO_MPC_MAX_SCAN_SOURCES, beams == 0 or
+ * sources * beams > NEO_MPC_MAX_SCAN_POINTS, unknown scanner flag bits, a mount, angle or range of a scanner that is not
+ * finite, range_min < 0, range_max < range_min, and -- in the host variants only -- a pose that is not finite.
+ * count == 0 is NEO_MPC_OK and does nothing. */
+int neo_mpc_project_laser(neo_mpc_handle* handle, const neo_mpc_laser_batch* batch);
+/* Same with `ranges`, `poses` and the two out arrays in device memory (`scanners` stays a host pointer); enqueued on
+ * `stream`, returns without waiting; no value behind the device pointers is looked at: a pose that is not finite yields
+ * points that are not finite, which the layer update skips.  A `points_out` that is not 16-byte aligned is refused.  The
+ * beam tables are kept in the handle, keyed by the scanners' bytes and `beams`: when they differ from the previous call's
+ * the tables are rebuilt and uploaded synchronously; otherwise the call allocates nothing, copies nothing and does not
+ * synchronise. */
+int neo_mpc_project_laser_device(neo_mpc_handle* handle, const neo_mpc_laser_batch* batch, void* stream);
+/* Projects the ranges (K11) and updates the windows' obstacle layers from all sources (the contract: neo_mpc_laser_batch).
+ * Host pointers, synchronous; `points_out` / `origins_out`, when given, receive what was projected.  Refusals, all of which
+ * leave pool, layers and out buffers as they were: those of neo_mpc_project_laser; scan_flags == 0 or with bits beyond the
+ * two; and every refusal of neo_mpc_update_scan_layer that concerns unknown_value, the ranges, the inflation parameters,
+ * `count` and the pool, with the same codes.  count == 0 is NEO_MPC_OK and does nothing. */
+int neo_mpc_update_scan_layer_from_ranges(neo_mpc_handle* handle, const neo_mpc_laser_batch* batch);
+/* Same with device pointers, enqueued on `stream`.  Ordering: the projection and the update are one write of the device
+ * maps, fenced exactly like neo_mpc_update_scan_layer_device.  Memory: without `points_out` / `origins_out` the handle
+ * keeps count * sources * beams * 16 bytes of points and count * sources * 16 bytes of origins, allocated on the first use
+ * and on a change of (count, sources, beams).  A call with the scanners, count, sources, beams, geometry and inflation
+ * parameters of the previous one allocates nothing, copies nothing and does not synchronise, so roll -> scan from ranges ->
+ * stamp -> gate -> carrots -> solve can be captured on one stream in one HIP graph and replayed with new ranges and poses. */
+int neo_mpc_update_scan_layer_from_ranges_device(neo_mpc_handle* handle, const neo_mpc_laser_batch* batch, void* stream);
 
 /* ---- multi-GPU fleets: the one exchange step ------------------------------------------------
  * Instances of one tick shard embarrassingly over the GPUs of a node (one handle per GPU, costmap and parameters

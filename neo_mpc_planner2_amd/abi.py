@@ -182,6 +182,68 @@ SCAN_CLEAR = 1           # NEO_MPC_SCAN_CLEAR: raytrace the layer free from the 
 SCAN_MARK = 2            # NEO_MPC_SCAN_MARK: mark the points' cells lethal in the layer
 
 
+class NeoMpcScanner(_C.Structure):
+    """`neo_mpc_scanner` (include/neo_mpc.h): one scanner of a robot -- its mount and its LaserScan geometry."""
+    _fields_ = [("mount_x", _C.c_double), ("mount_y", _C.c_double), ("mount_yaw", _C.c_double),
+                ("angle_min", _C.c_double), ("angle_increment", _C.c_double),
+                ("range_min", _C.c_double), ("range_max", _C.c_double),
+                ("flags", _C.c_uint32), ("reserved", _C.c_uint32)]
+
+
+#: the same record as a NumPy dtype (64 bytes)
+SCANNER_DTYPE = np.dtype([
+    ("mount_x", "<f8"), ("mount_y", "<f8"), ("mount_yaw", "<f8"), ("angle_min", "<f8"), ("angle_increment", "<f8"),
+    ("range_min", "<f8"), ("range_max", "<f8"), ("flags", "<u4"), ("reserved", "<u4"),
+], align=False)
+assert SCANNER_DTYPE.itemsize == 64 == _C.sizeof(NeoMpcScanner)
+
+
+class NeoMpcLaserBatch(_C.Structure):
+    """`neo_mpc_laser_batch` (include/neo_mpc.h): LaserScan ranges of every scanner of every robot, projected and -- for
+    the update -- put into the windows' obstacle layers."""
+    _fields_ = [("count", _C.c_size_t), ("ranges", _C.c_void_p), ("poses", _C.c_void_p), ("scanners", _C.c_void_p),
+                ("sources", _C.c_uint32), ("beams", _C.c_uint32), ("points_out", _C.c_void_p), ("origins_out", _C.c_void_p),
+                ("scan_flags", _C.c_uint32), ("unknown_value", _C.c_uint32),
+                ("obstacle_max_range", _C.c_double), ("obstacle_min_range", _C.c_double),
+                ("raytrace_max_range", _C.c_double), ("raytrace_min_range", _C.c_double),
+                ("inscribed_radius", _C.c_double), ("inflation_radius", _C.c_double), ("cost_scaling_factor", _C.c_double),
+                ("reserved", _C.c_uint64)]
+
+
+#: the same record as a NumPy dtype (128 bytes; the pointers as addresses)
+LASER_BATCH_DTYPE = np.dtype([
+    ("count", "<u8"), ("ranges", "<u8"), ("poses", "<u8"), ("scanners", "<u8"), ("sources", "<u4"), ("beams", "<u4"),
+    ("points_out", "<u8"), ("origins_out", "<u8"), ("scan_flags", "<u4"), ("unknown_value", "<u4"),
+    ("obstacle_max_range", "<f8"), ("obstacle_min_range", "<f8"),
+    ("raytrace_max_range", "<f8"), ("raytrace_min_range", "<f8"),
+    ("inscribed_radius", "<f8"), ("inflation_radius", "<f8"), ("cost_scaling_factor", "<f8"), ("reserved", "<u8"),
+], align=False)
+assert LASER_BATCH_DTYPE.itemsize == 128 == _C.sizeof(NeoMpcLaserBatch)
+
+MAX_SCAN_SOURCES = 4
+LASER_INF_IS_VALID = 1   # NEO_MPC_LASER_INF_IS_VALID: a range of +inf is a beam that met nothing, at range_max - 1e-4
+
+
+def scanner_array(scanners):
+    """One scanner or a sequence of them -> a NumPy array of SCANNER_DTYPE.  A scanner is a mapping with the record's field
+    names (flags and reserved default to 0), a NeoMpcScanner, or an element of such an array already."""
+    if isinstance(scanners, np.ndarray) and scanners.dtype == SCANNER_DTYPE:
+        return np.ascontiguousarray(scanners).reshape(-1)
+    if isinstance(scanners, (dict, NeoMpcScanner)):
+        scanners = [scanners]
+    out = np.zeros(len(scanners), dtype=SCANNER_DTYPE)
+    for k, sc in enumerate(scanners):
+        for name in SCANNER_DTYPE.names:
+            if isinstance(sc, dict):
+                if name in sc:
+                    out[k][name] = sc[name]
+                else:
+                    assert name in ("flags", "reserved"), "scanner %d lacks %s" % (k, name)
+            else:
+                out[k][name] = getattr(sc, name) if hasattr(sc, name) else sc[name]
+    return out
+
+
 def params_struct(params=None, **over):
     """dict of ROS parameter names (+ solver options) -> NeoMpcParams.  Missing names take
     the reference node's declared defaults (py:49-75)."""

@@ -10,7 +10,8 @@
 // world map's copy, geometry and ordering); the refusals of inflation parameters and InflationTable (K8's, K9's and K10's cached
 // cost table); the handle; parameters and the term table; the shared checks; the device map (geometry, adoption, K3
 // ingest); the staging of host batches by range; then the entry points -- costmaps, the solve paths of K1, K2 and the hooks,
-// K4 carrots, K6 footprint gate, K7 rolling windows, K8 fleet stamp, K9 world inflation, K10 scan layer.  A new entry point checks with the
+// K4 carrots, K6 footprint gate, K7 rolling windows, K8 fleet stamp, K9 world inflation, K10 scan layer,
+// K11 laser projection.  A new entry point checks with the
 // shared checks, stages with upload(), and launches through fence.read() or between fence.begin_write() and end_write().
 #include <hip/hip_runtime.h>
 
@@ -303,6 +304,51 @@ struct ScanLayers {
   void adopt() { valid = true; }   // behind the update's end_write: its launches are enqueued
 };
 
+// K11.  The beam table of one scanner (the contract: neo_mpc_laser_batch, step 4), with libm
+void laser_beam_table(const neo_mpc_scanner& sc, uint32_t beams, double* table) {
+#pragma clang fp contract(off)
+  for (uint32_t i = 0; i < beams; ++i) {
+    const double a = sc.mount_yaw + (sc.angle_min + (double)i * sc.angle_increment);
+    table[2 * (size_t)i] = std::cos(a);
+    table[2 * (size_t)i + 1] = std::sin(a);
+  }
+}
+
+// K11.  The beam tables on the device and the scanners they were built for, the handle's own points and origins -- what an
+// update without points_out / origins_out projects into -- and the host variants' staging of the ranges.  A call with the
+// scanners, beams and count of the previous one finds all of it in place: nothing is built, allocated or copied, so the call
+// can be captured in a graph.
+struct LaserProjection {
+  DeviceBuffer table, points, origins;
+  DeviceBuffer ranges;                    // (the host variants' staging)
+  std::vector<unsigned char> key;         // the scanners' bytes, then `beams`
+  bool valid = false;
+  // for scanners check_scanner() has passed.  The launches in flight, on whatever stream, read the old tables to their end:
+  // a change of scanners is configuration, and waits for the device.
+  int build(const neo_mpc_scanner* scanners, uint32_t sources, uint32_t beams) {
+    std::vector<unsigned char> now(sources * sizeof(neo_mpc_scanner) + sizeof(beams));
+    std::memcpy(now.data(), scanners, sources * sizeof(neo_mpc_scanner));
+    std::memcpy(now.data() + sources * sizeof(neo_mpc_scanner), &beams, sizeof(beams));
+    if (valid && now == key) return NEO_MPC_OK;
+    std::vector<double> host((size_t)sources * beams * 2);
+    for (uint32_t s = 0; s < sources; ++s) laser_beam_table(scanners[s], beams, host.data() + (size_t)s * beams * 2);
+    HIP_TRY(hipDeviceSynchronize());
+    valid = false;
+    // (the largest table, once: a change of scanners never re-allocates)
+    if (int rc = table.reserve((size_t)NEO_MPC_MAX_SCAN_POINTS * 16)) return rc;
+    if (!table.upload(host.data(), host.size() * 8)) return NEO_MPC_ERR_DEVICE;
+    key.swap(now);
+    valid = true;
+    return NEO_MPC_OK;
+  }
+  // the handle's own out buffers: no-ops from the second call with this shape on (a re-allocation frees, which synchronises)
+  int reserve_out(size_t count, uint32_t sources, uint32_t beams, bool want_points, bool want_origins) {
+    if (want_points) if (int rc = points.reserve(count * sources * beams * 16)) return rc;
+    if (want_origins) if (int rc = origins.reserve(count * sources * 16)) return rc;
+    return NEO_MPC_OK;
+  }
+};
+
 }  // namespace
 
 // (hidden: its destructor, no longer trivial, is no export)
@@ -351,6 +397,7 @@ struct __attribute__((visibility("hidden"))) neo_mpc_handle {
   // K9 neo_mpc_inflate_world_map: its own cost table -- the world's resolution need not be the windows'
   InflationTable world_table;
   ScanLayers scan;   // K10 neo_mpc_update_scan_layer
+  LaserProjection laser;   // K11 neo_mpc_project_laser, neo_mpc_update_scan_layer_from_ranges
 };
 constexpr size_t kLatencyPathMaxCount = 64;
 constexpr size_t kChunkedMinCount = 65536;   // staged host batches from here on go through in kChunks pieces on two streams
@@ -1671,7 +1718,10 @@ static int check_scan_batch(const neo_mpc_handle* h, const neo_mpc_scan_batch* b
 
 // `d`: the record with device pointers.  Orders itself like stamp(): it rewrites the device maps in place, and the layer
 // buffers inside the same write.
-static int scan(neo_mpc_handle* h, const neo_mpc_scan_batch& d, void* stream) {
+// `laser`: K11's projection of `sources` scanners a robot into d.points and d.sensor_origins, enqueued inside the same write,
+// in front of the layers' launches (the rays of the previous update, which read the handle's own points, lie behind the
+// previous write's end).
+static int scan(neo_mpc_handle* h, const neo_mpc_scan_batch& d, void* stream, const LaserArgs* laser = nullptr) {
   const DevMap& m = h->map;
   ScanLayers& l = h->scan;
   // (every update ends a write of the fence)
@@ -1695,7 +1745,11 @@ static int scan(neo_mpc_handle* h, const neo_mpc_scan_batch& d, void* stream) {
   a.size_x = m.size_x; a.size_y = m.size_y; a.pitch = m.pitch; a.layer_pitch = l.pitch();
   a.reach = l.table.reach;
   a.count = (uint32_t)d.count; a.max_points = d.max_points; a.flags = d.flags; a.unknown = d.unknown_value;
+  // (without K11 every point of a robot is its one source's: the address arithmetic of one observation per robot)
+  a.sources = laser ? laser->sources : 1u;
+  a.points_per_source = laser ? laser->beams : (d.max_points > 0 ? d.max_points : 1u);
   a.reset = same ? 0u : 1u;
+  if (laser) launch_laser_project(*laser, stream);
   launch_scan_layer(a, stream);
   HIP_TRY(hipGetLastError());
   if ((rc = h->fence.end_write(st))) return rc;   // a stamp, gate or solve behind it sees the windows with the layer in them
@@ -1735,6 +1789,136 @@ int neo_mpc_update_scan_layer(neo_mpc_handle* h, const neo_mpc_scan_batch* b) {
   }
   return finish_on_null_stream(scan(h, d, nullptr));
 }
+
+// K11.  What the projection refuses of one scanner
+static int check_scanner(const neo_mpc_scanner& sc, uint32_t s) {
+  if (sc.reserved != 0) return fail(NEO_MPC_ERR_INVALID_ARGUMENT, "neo_mpc_scanner.reserved of scanner %u must be zero", s);
+  if (sc.flags & ~NEO_MPC_LASER_INF_IS_VALID) return fail(NEO_MPC_ERR_INVALID_ARGUMENT, "unknown flags 0x%x of scanner %u", sc.flags, s);
+  for (const double v : {sc.mount_x, sc.mount_y, sc.mount_yaw, sc.angle_min, sc.angle_increment, sc.range_min, sc.range_max})
+    if (!std::isfinite(v)) return fail(NEO_MPC_ERR_INVALID_ARGUMENT, "a mount, angle or range of scanner %u is not finite", s);
+  if (sc.range_min < 0.0 || sc.range_max < sc.range_min)
+    return fail(NEO_MPC_ERR_INVALID_ARGUMENT, "scanner %u: range_min %g, range_max %g", s, sc.range_min, sc.range_max);
+  return NEO_MPC_OK;
+}
+
+// K11.  What the four entry points check: the record's shape, the scanners (host configuration) and, for an update, what
+// check_scan_batch checks of the handle's pool -- never a value behind ranges, poses or the out pointers.
+static int check_laser_batch(const neo_mpc_handle* h, const neo_mpc_laser_batch* b, bool update, bool device) {
+  if (!h || !b) return fail(NEO_MPC_ERR_INVALID_ARGUMENT, "null argument");
+  if (b->reserved != 0) return fail(NEO_MPC_ERR_INVALID_ARGUMENT, "neo_mpc_laser_batch.reserved must be zero");
+  if (b->sources < 1 || b->sources > NEO_MPC_MAX_SCAN_SOURCES)
+    return fail(NEO_MPC_ERR_INVALID_ARGUMENT, "sources %u outside [1, %u]", b->sources, NEO_MPC_MAX_SCAN_SOURCES);
+  if (b->beams < 1 || b->beams > NEO_MPC_MAX_SCAN_POINTS / b->sources)
+    return fail(NEO_MPC_ERR_INVALID_ARGUMENT, "beams %u: at least 1, and with %u sources at most %u points", b->beams, b->sources, NEO_MPC_MAX_SCAN_POINTS);
+  if (!b->scanners) return fail(NEO_MPC_ERR_INVALID_ARGUMENT, "scanners must not be null");
+  if (b->count > 0 && (!b->ranges || !b->poses)) return fail(NEO_MPC_ERR_INVALID_ARGUMENT, "ranges and poses must not be null");
+  if (!update && b->count > 0 && (!b->points_out || !b->origins_out))
+    return fail(NEO_MPC_ERR_INVALID_ARGUMENT, "points_out and origins_out must not be null");
+  if (device && ((uintptr_t)b->points_out & 15)) return fail(NEO_MPC_ERR_INVALID_ARGUMENT, "points_out is not 16-byte aligned");
+  if (update) {
+    if (b->scan_flags == 0 || (b->scan_flags & ~(NEO_MPC_SCAN_CLEAR | NEO_MPC_SCAN_MARK)))
+      return fail(NEO_MPC_ERR_INVALID_ARGUMENT, "scan_flags 0x%x: NEO_MPC_SCAN_CLEAR, NEO_MPC_SCAN_MARK or both", b->scan_flags);
+    if (b->unknown_value != 0 && b->unknown_value != 255)
+      return fail(NEO_MPC_ERR_INVALID_ARGUMENT, "unknown_value %u is neither 0 nor 255", b->unknown_value);
+  }
+  for (uint32_t s = 0; s < b->sources; ++s)
+    if (int rc = check_scanner(b->scanners[s], s)) return rc;
+  if (!update) return NEO_MPC_OK;
+  for (const double r : {b->obstacle_max_range, b->obstacle_min_range, b->raytrace_max_range, b->raytrace_min_range})
+    if (!std::isfinite(r) || r < 0.0) return fail(NEO_MPC_ERR_INVALID_ARGUMENT, "range %g must be finite and not negative", r);
+  if (int rc = check_inflation_radii(b->inscribed_radius, b->inflation_radius, b->cost_scaling_factor)) return rc;
+  return check_pool_batch(h, b->count, b->inscribed_radius, b->inflation_radius, b->cost_scaling_factor);
+}
+
+// `d`: the record with device pointers (points_out / origins_out null: the handle's own) -> the kernel's arguments, the beam
+// tables and the handle's buffers in place
+static int laser_args(neo_mpc_handle* h, const neo_mpc_laser_batch& d, LaserArgs& a) {
+  LaserProjection& l = h->laser;
+  if (int rc = l.build(d.scanners, d.sources, d.beams)) return rc;
+  if (int rc = l.reserve_out(d.count, d.sources, d.beams, !d.points_out, !d.origins_out)) return rc;
+  std::memset(&a, 0, sizeof(a));
+  a.ranges = d.ranges; a.poses = d.poses;
+  a.table = l.table.as<const double>();
+  a.points = d.points_out ? d.points_out : l.points.as<double>();
+  a.origins = d.origins_out ? d.origins_out : l.origins.as<double>();
+  for (uint32_t s = 0; s < d.sources; ++s) {
+    const neo_mpc_scanner& sc = d.scanners[s];
+    LaserSource& o = a.source[s];
+    o.mount_x = sc.mount_x; o.mount_y = sc.mount_y; o.range_min = sc.range_min; o.range_max = sc.range_max;
+    o.inf_range = sc.range_max - 1e-4;
+    o.inf_is_valid = sc.flags & NEO_MPC_LASER_INF_IS_VALID;
+  }
+  a.count = (uint32_t)d.count; a.sources = d.sources; a.beams = d.beams;
+  return NEO_MPC_OK;
+}
+
+// The projection alone: it touches neither maps nor layers, so it is in order on its stream and nothing else
+static int project_laser(neo_mpc_handle* h, const neo_mpc_laser_batch& d, void* stream) {
+  LaserArgs a;
+  if (int rc = laser_args(h, d, a)) return rc;
+  launch_laser_project(a, stream);
+  HIP_TRY(hipGetLastError());
+  return NEO_MPC_OK;
+}
+
+// The projection and the update over all sources, one write of the device maps
+static int scan_from_ranges(neo_mpc_handle* h, const neo_mpc_laser_batch& d, void* stream) {
+  LaserArgs a;
+  if (int rc = laser_args(h, d, a)) return rc;
+  neo_mpc_scan_batch sb;
+  std::memset(&sb, 0, sizeof(sb));
+  sb.count = d.count; sb.points = a.points; sb.sensor_origins = a.origins;
+  sb.max_points = d.sources * d.beams; sb.flags = d.scan_flags;
+  sb.obstacle_max_range = d.obstacle_max_range; sb.obstacle_min_range = d.obstacle_min_range;
+  sb.raytrace_max_range = d.raytrace_max_range; sb.raytrace_min_range = d.raytrace_min_range;
+  sb.inscribed_radius = d.inscribed_radius; sb.inflation_radius = d.inflation_radius; sb.cost_scaling_factor = d.cost_scaling_factor;
+  sb.unknown_value = d.unknown_value;
+  return scan(h, sb, stream, &a);
+}
+
+int neo_mpc_laser_beam_table(const neo_mpc_scanner* scanner, uint32_t beams, double* table_out) {
+  if (!scanner || !table_out) return fail(NEO_MPC_ERR_INVALID_ARGUMENT, "null argument");
+  if (beams < 1 || beams > NEO_MPC_MAX_SCAN_POINTS) return fail(NEO_MPC_ERR_INVALID_ARGUMENT, "beams %u outside [1, %u]", beams, NEO_MPC_MAX_SCAN_POINTS);
+  if (int rc = check_scanner(*scanner, 0)) return rc;
+  laser_beam_table(*scanner, beams, table_out);
+  return NEO_MPC_OK;
+}
+
+int neo_mpc_project_laser_device(neo_mpc_handle* h, const neo_mpc_laser_batch* b, void* stream) {
+  if (int rc = check_laser_batch(h, b, false, true)) return rc;
+  if (b->count == 0) return NEO_MPC_OK;
+  HIP_TRY(hipSetDevice(h->device));
+  return project_laser(h, *b, stream);
+}
+
+int neo_mpc_update_scan_layer_from_ranges_device(neo_mpc_handle* h, const neo_mpc_laser_batch* b, void* stream) {
+  if (int rc = check_laser_batch(h, b, true, true)) return rc;
+  if (b->count == 0) return NEO_MPC_OK;
+  HIP_TRY(hipSetDevice(h->device));
+  return scan_from_ranges(h, *b, stream);
+}
+
+// The host variants: ranges and poses staged, projected into the handle's own buffers, and those read back where asked for
+static int laser_from_host(neo_mpc_handle* h, const neo_mpc_laser_batch* b, bool update) {
+  if (int rc = check_laser_batch(h, b, update, false)) return rc;
+  if (b->count == 0) return NEO_MPC_OK;
+  const size_t n = b->count, scans = n * b->sources;
+  // the values the device variants take as they come are looked at here
+  if (int rc = check_poses_finite(b->poses, nullptr, n)) return rc;
+  HIP_TRY(hipSetDevice(h->device));
+  neo_mpc_laser_batch d = *b;
+  d.points_out = nullptr; d.origins_out = nullptr;
+  if (!(d.ranges = h->laser.ranges.upload(b->ranges, scans * b->beams * 4))) return NEO_MPC_ERR_DEVICE;
+  if (!(d.poses = h->poses.upload(b->poses, n * 24))) return NEO_MPC_ERR_DEVICE;
+  if (int rc = finish_on_null_stream(update ? scan_from_ranges(h, d, nullptr) : project_laser(h, d, nullptr))) return rc;
+  if (b->points_out) HIP_TRY(hipMemcpy(b->points_out, h->laser.points.ptr, scans * b->beams * 16, hipMemcpyDeviceToHost));
+  if (b->origins_out) HIP_TRY(hipMemcpy(b->origins_out, h->laser.origins.ptr, scans * 16, hipMemcpyDeviceToHost));
+  return NEO_MPC_OK;
+}
+
+int neo_mpc_project_laser(neo_mpc_handle* h, const neo_mpc_laser_batch* b) { return laser_from_host(h, b, false); }
+
+int neo_mpc_update_scan_layer_from_ranges(neo_mpc_handle* h, const neo_mpc_laser_batch* b) { return laser_from_host(h, b, true); }
 
 int neo_mpc_get_scan_layer(neo_mpc_handle* h, uint32_t first, uint32_t count, uint8_t* cells_out, double* origins_out) {
   if (!h) return fail(NEO_MPC_ERR_INVALID_ARGUMENT, "null handle");

@@ -258,7 +258,7 @@ struct InflateArgs {
 struct ScanArgs {
   const double* points;             // [count][max_points][2] global frame (read with NEO_MPC_SCAN_CLEAR / _MARK only)
   const uint32_t* point_counts;     // optional [count]
-  const double* sensor_origins;     // [count][2]
+  const double* sensor_origins;     // [count][sources][2]: point p of a robot was seen from its source p / points_per_source
   const uint8_t* table;             // [reach^2 + 1]: cost by squared cell distance (neo_mpc_inflation_costs)
   uint8_t* layer;                   // handle-owned: the layers between updates, layer_pitch bytes a row, no border
   uint8_t* work;                    // handle-owned: this update's layers, same shape
@@ -274,9 +274,29 @@ struct ScanArgs {
   int32_t reach;                    // R, cells: 0 .. NEO_MPC_MAX_INFLATION_CELLS
   uint32_t count;
   uint32_t max_points;
+  uint32_t sources;                 // K10: 1; K11: the scanners of a robot
+  uint32_t points_per_source;       // K10: max_points (every point is source 0's); K11: beams, max_points = sources * beams
   uint32_t flags;                   // NEO_MPC_SCAN_*
   uint32_t unknown;                 // 0 or 255
   uint32_t reset;                   // 1: the layers start from `unknown` at the windows' origins
+};
+
+// K11: LaserScan ranges projected into global-frame points and sensor origins (neo_mpc_laser_batch, device pointers)
+struct LaserSource {                // one neo_mpc_scanner as the kernel needs it
+  double mount_x, mount_y;
+  double range_min, range_max;
+  double inf_range;                 // range_max - 1e-4, formed on the host in float64
+  uint32_t inf_is_valid;            // NEO_MPC_LASER_INF_IS_VALID
+  uint32_t pad;
+};
+struct LaserArgs {
+  const float* ranges;              // [count][sources][beams]
+  const double* poses;              // [count][3]
+  const double* table;              // [sources][beams][2] handle-owned: cos, sin of every beam's angle in the base frame
+  double* points;                   // [count][sources][beams][2], 16-byte aligned
+  double* origins;                  // [count][sources][2]
+  LaserSource source[NEO_MPC_MAX_SCAN_SOURCES];
+  uint32_t count, sources, beams;
 };
 
 // A/B switches of the measurement tools: read from the environment ONCE, by neo_mpc_create (include/neo_mpc.h), kept in
@@ -297,6 +317,7 @@ void launch_roll(const RollArgs& a, void* stream);   // K7: k_roll_index, then k
 void launch_stamp(const StampArgs& a, void* stream); // K8: k_stamp_boxes, then k_stamp_fleet
 void launch_inflate_world(const InflateArgs& a, void* stream);   // K9: k_inflate_world
 void launch_scan_layer(const ScanArgs& a, void* stream);         // K10: k_scan_shift, k_scan_rays (clear, mark), k_scan_apply
+void launch_laser_project(const LaserArgs& a, void* stream);     // K11: k_laser_project
 // K5: dispatch order of the next launch from the iteration counts of the previous one (neo_mpc_balance_dispatch_device)
 void launch_dispatch_order(const neo_mpc_command* commands, float* load, uint32_t* order, uint32_t count, bool fresh, void* stream);
 constexpr uint32_t kDispatchSimds = 1024;   // a 4096-instance launch is one residency round: workgroups w, w + 1024, w + 2048, w + 3072 share a SIMD

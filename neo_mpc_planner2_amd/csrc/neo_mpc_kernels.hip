@@ -20,6 +20,7 @@
 //   K8 k_stamp_boxes, k_stamp_fleet  fleet_stamp.h: the fleet's robots stamped into each other's windows, inflation ring included.
 //   K9 k_inflate_world  world_inflation.h: nav2's inflation layer on the world map, in place (inflation.h: what it shares with K8 and K10).
 //   K10 k_scan_shift, k_scan_rays, k_scan_apply  scan_layer.h: the obstacle layer of every window, fed from sensor points.
+//   K11 k_laser_project  laser_projection.h: LaserScan ranges of every scanner of every robot -> those points, HBM-streaming.
 #include "k1_solve.h"
 #include "costmap_ingest.h"
 #include "footprint_gate.h"
@@ -27,6 +28,7 @@
 #include "fleet_stamp.h"
 #include "world_inflation.h"
 #include "scan_layer.h"
+#include "laser_projection.h"
 
 namespace neo_mpc {
 namespace {
@@ -367,6 +369,11 @@ void launch_scan_layer(const ScanArgs& a, void* stream) {
   if (a.max_points > 0 && (a.flags & NEO_MPC_SCAN_MARK)) hipLaunchKernelGGL(k_scan_rays<true>, rays, dim3(kScanRayThreads), 0, st, a);
   hipLaunchKernelGGL(k_scan_apply, dim3((a.size_x + kInflateTile - 1) / kInflateTile, (a.size_y + kInflateTile - 1) / kInflateTile, a.count),
                      dim3(kLanes * kInflateWaves), 0, st, a);
+}
+// K11: one workgroup per robot and source
+void launch_laser_project(const LaserArgs& a, void* stream) {
+  if (a.count == 0) return;
+  hipLaunchKernelGGL(k_laser_project, dim3(a.count, a.sources), dim3(kLaserThreads), 0, (hipStream_t)stream, a);
 }
 void launch_ingest(const IngestArgs& a, const LaunchTuning& tuning, void* stream) {
   hipLaunchKernelGGL(k_ingest, padded_map_grid(a.rows, a.pitch, kIngestUnroll, a.maps > 0 ? a.maps : 1), dim3(256), 0,

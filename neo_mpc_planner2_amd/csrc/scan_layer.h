@@ -77,6 +77,9 @@ __device__ __forceinline__ uint32_t scan_cell_distance(double d, double res) {
 // what puts every mark behind every clear), grid (point chunks, window), a lane per ray.  No atomics: within a launch every
 // writer of a byte writes the same value -- 0 in the clearing launch, 254 in the marking one -- so whichever of two colliding
 // byte stores lands last the byte is the same; byte stores merge into their line by byte mask and touch no neighbour.
+// With several sources (K11) a window's points are those of all its sources, point p seen from source p / points_per_source,
+// and the argument still holds: one clearing launch over all sources, then one marking launch over all sources, puts every
+// mark of every source behind every clear of every source with no new synchronisation.
 // Nothing is read back from the layer.  The trip counts of the walk diverge between lanes; nothing ballots inside it.
 template <bool kMark>
 __global__ __launch_bounds__(kScanRayThreads) void k_scan_rays(const ScanArgs a) {
@@ -88,7 +91,8 @@ __global__ __launch_bounds__(kScanRayThreads) void k_scan_rays(const ScanArgs a)
   if (p >= np) return;
   const int sx = a.size_x, sy = a.size_y, lp = a.layer_pitch;
   const double res = a.res, ox = a.origins[2 * (size_t)k], oy = a.origins[2 * (size_t)k + 1];
-  const double sx0 = a.sensor_origins[2 * (size_t)k], sy0 = a.sensor_origins[2 * (size_t)k + 1];
+  const size_t src = (size_t)k * a.sources + p / a.points_per_source;   // (K10: sources 1, points_per_source max_points: k)
+  const double sx0 = a.sensor_origins[2 * src], sy0 = a.sensor_origins[2 * src + 1];
   const double* pt = a.points + ((size_t)k * a.max_points + p) * 2;
   double wx = pt[0], wy = pt[1];
   if (!isfinite(wx) || !isfinite(wy)) return;

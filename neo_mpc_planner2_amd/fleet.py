@@ -14,7 +14,7 @@ from . import abi
 
 
 def closed_loop(solver, batch, ticks, hz=30.0, before_tick=None, after_tick=None, balance_every=0, footprint=None,
-                rolling=None, stamp=None, scan=None):
+                rolling=None, stamp=None, scan=None, laser=None):
     """Run `ticks` control ticks of `batch` (a solver.DeviceBatch) through `solver` (a BatchSolver with its costmap
     set).  Returns per-tick lists: kernel_ms (HIP events around the K1 launch), mean_iterations, max_iterations,
     stopped_fraction.  `before_tick(t, pos)` runs before tick t's launch (e.g. re-centre a costmap pool),
@@ -36,9 +36,14 @@ def closed_loop(solver, batch, ticks, hz=30.0, before_tick=None, after_tick=None
     tick t -- the inflation parameters, and on a tick with a new observation `points` and `sensor_origins` as CUDA tensors
     (without them: flags 0, the layer is rolled and applied again; pass on_device=True then) -- and the update (K10,
     neo_mpc_update_scan_layer_device) runs between the roll and the stamp, so the gate and K1 see what the sensors saw.
-    None: no scan layer, the loop is unchanged."""
+    None: no scan layer, the loop is unchanged.  `laser` = a callable, with `rolling` and instead of `scan`: `laser(t, poses)`
+    returns the keyword arguments of BatchSolver.update_scan_layer_from_ranges for tick t -- the inflation parameters, `ranges`
+    as a CUDA float32 tensor, `poses` (the loop's own, handed through, or the caller's) and `scanners` -- and the projection
+    and the update over all scanners (K11, neo_mpc_update_scan_layer_from_ranges_device) run where `scan` runs.  None: the
+    loop is unchanged."""
     assert stamp is None or (rolling is not None and footprint is not None), "stamp needs rolling and footprint"
     assert scan is None or rolling is not None, "scan needs rolling"
+    assert laser is None or (rolling is not None and scan is None), "laser needs rolling and excludes scan"
     import torch
     b = batch
     P = b.problems.view(torch.float64).reshape(b.count, -1)          # the 32 doubles of each request
@@ -77,6 +82,8 @@ def closed_loop(solver, batch, ticks, hz=30.0, before_tick=None, after_tick=None
             solver.roll_costmap_pool(rolling[0], rolling[1], rolling[2], rolling[3], poses=poses)
         if scan is not None:
             solver.update_scan_layer(**scan(t, poses))
+        if laser is not None:
+            solver.update_scan_layer_from_ranges(**laser(t, poses))
         if stamp is not None:
             solver.stamp_fleet(stamp[0], stamp[1], stamp[2], footprint=base, poses=poses)
         if footprint is not None:

@@ -12,6 +12,18 @@ import numpy as np
 from . import _lib, abi
 
 
+def laser_beam_table(scanner, beams):
+    """The beam table of one scanner (neo_mpc_laser_beam_table; the contract: neo_mpc_laser_batch in include/neo_mpc.h,
+    step 4): float64 [beams, 2], (cos, sin) of every beam's angle in the base frame.  Pure host code.  `scanner`: what
+    abi.scanner_array takes."""
+    sc = abi.scanner_array(scanner)
+    assert sc.shape == (1,), "one scanner"
+    table = np.zeros((int(beams), 2), dtype=np.float64)
+    _lib.check(_lib.load().neo_mpc_laser_beam_table(C.cast(sc.ctypes.data, C.POINTER(abi.NeoMpcScanner)), int(beams),
+                                                    C.c_void_p(table.ctypes.data)))
+    return table
+
+
 class BatchSolver:
     """One solver configuration + one costmap on one GPU (a `neo_mpc_handle`)."""
 
@@ -342,6 +354,81 @@ class BatchSolver:
                     b.point_counts = point_counts.data_ptr()
             stream = torch.cuda.current_stream(device).cuda_stream
             _lib.check(self._lib.neo_mpc_update_scan_layer_device(self._handle, C.byref(b), C.c_void_p(stream)))
+
+    # -- the scan step fed from LaserScan ranges -----------------------------------------
+    def _laser_batch(self, ranges, poses, scanners, points_out, origins_out, need_out):
+        """-> (the record with everything but the update's fields, what must stay alive, points_out, origins_out, the
+        stream or None for the host variant)."""
+        b = abi.NeoMpcLaserBatch()
+        sc = abi.scanner_array(scanners)
+        b.scanners, b.sources = sc.ctypes.data, sc.shape[0]
+        if not hasattr(ranges, "data_ptr"):
+            ranges = np.ascontiguousarray(ranges, dtype=np.float32)
+            poses = np.ascontiguousarray(poses, dtype=np.float64)
+            assert ranges.ndim == 3 and ranges.shape[1] == b.sources and poses.shape == (ranges.shape[0], 3)
+            count, _, beams = ranges.shape
+            if points_out is None and need_out:
+                points_out = np.zeros((count, b.sources, beams, 2), dtype=np.float64)
+            if origins_out is None and need_out:
+                origins_out = np.zeros((count, b.sources, 2), dtype=np.float64)
+            for a, shape in ((points_out, (count, b.sources, beams, 2)), (origins_out, (count, b.sources, 2))):
+                assert a is None or (isinstance(a, np.ndarray) and a.dtype == np.float64 and a.flags.c_contiguous and a.shape == shape)
+            b.ranges, b.poses = ranges.ctypes.data, poses.ctypes.data
+            b.points_out = points_out.ctypes.data if points_out is not None else None
+            b.origins_out = origins_out.ctypes.data if origins_out is not None else None
+            stream = None
+        else:
+            import torch
+            assert ranges.is_cuda and ranges.is_contiguous() and ranges.dtype == torch.float32 and ranges.dim() == 3
+            assert ranges.shape[1] == b.sources
+            count, _, beams = ranges.shape
+            assert poses.is_cuda and poses.is_contiguous() and poses.dtype == torch.float64 and tuple(poses.shape) == (count, 3)
+            if points_out is None and need_out:
+                points_out = torch.zeros((count, b.sources, beams, 2), dtype=torch.float64, device=ranges.device)
+            if origins_out is None and need_out:
+                origins_out = torch.zeros((count, b.sources, 2), dtype=torch.float64, device=ranges.device)
+            for a, shape in ((points_out, (count, b.sources, beams, 2)), (origins_out, (count, b.sources, 2))):
+                assert a is None or (a.is_cuda and a.is_contiguous() and a.dtype == torch.float64 and tuple(a.shape) == shape)
+            b.ranges, b.poses = ranges.data_ptr(), poses.data_ptr()
+            b.points_out = points_out.data_ptr() if points_out is not None else None
+            b.origins_out = origins_out.data_ptr() if origins_out is not None else None
+            stream = torch.cuda.current_stream(ranges.device).cuda_stream
+        b.count, b.beams = count, beams
+        return b, (sc, ranges, poses), points_out, origins_out, stream
+
+    def project_laser(self, ranges, poses, scanners, points_out=None, origins_out=None):
+        """Projects LaserScan `ranges` (float32 [count, sources, beams], as on the wire) of robots at `poses` (float64
+        [count, 3]: x, y, yaw) into global-frame hit points [count, sources, beams, 2] -- (NaN, NaN) for a beam that is not
+        valid -- and sensor origins [count, sources, 2], and returns the two (K11; the contract: neo_mpc_laser_batch in
+        include/neo_mpc.h).  `scanners`: what abi.scanner_array takes, host configuration.  NumPy arrays go through the
+        synchronous host call; CUDA tensors through the device call on torch's current stream.  Needs no costmap."""
+        b, keep, points_out, origins_out, stream = self._laser_batch(ranges, poses, scanners, points_out, origins_out, True)
+        if stream is None:
+            _lib.check(self._lib.neo_mpc_project_laser(self._handle, C.byref(b)))
+        else:
+            _lib.check(self._lib.neo_mpc_project_laser_device(self._handle, C.byref(b), C.c_void_p(stream)))
+        return points_out, origins_out
+
+    def update_scan_layer_from_ranges(self, inscribed_radius, inflation_radius, cost_scaling_factor, ranges, poses, scanners,
+                                      flags=None, points_out=None, origins_out=None, obstacle_max_range=2.5,
+                                      obstacle_min_range=0.0, raytrace_max_range=3.0, raytrace_min_range=0.0,
+                                      unknown_value=255):
+        """Projects the ranges as `project_laser` does and updates the obstacle layer of every window of the pool from all
+        scanners: every clear of every scanner, then every mark (K11 and K10; the contract: neo_mpc_laser_batch).  `flags`
+        abi.SCAN_CLEAR | abi.SCAN_MARK (the default) or one of them; a tick without a new scan is `update_scan_layer`
+        without points.  `points_out` / `origins_out` receive what was projected when given.  NumPy arrays go through the
+        synchronous host call; CUDA tensors through the device call on torch's current stream."""
+        b, keep, _, _, stream = self._laser_batch(ranges, poses, scanners, points_out, origins_out, False)
+        b.scan_flags = int(abi.SCAN_CLEAR | abi.SCAN_MARK if flags is None else flags)
+        b.unknown_value = int(unknown_value)
+        b.obstacle_max_range, b.obstacle_min_range = float(obstacle_max_range), float(obstacle_min_range)
+        b.raytrace_max_range, b.raytrace_min_range = float(raytrace_max_range), float(raytrace_min_range)
+        b.inscribed_radius, b.inflation_radius = float(inscribed_radius), float(inflation_radius)
+        b.cost_scaling_factor = float(cost_scaling_factor)
+        if stream is None:
+            _lib.check(self._lib.neo_mpc_update_scan_layer_from_ranges(self._handle, C.byref(b)))
+        else:
+            _lib.check(self._lib.neo_mpc_update_scan_layer_from_ranges_device(self._handle, C.byref(b), C.c_void_p(stream)))
 
     def get_scan_layer(self, first=0, count=None):
         """Layers [first, first + count) as the last `update_scan_layer` left them: uint8 [count, size_y, size_x] with
