@@ -610,6 +610,74 @@ typedef struct neo_mpc_laser_batch {
   uint64_t reserved;                 /* MUST be zero */
 } neo_mpc_laser_batch;
 
+/* ---- one obstacle layer for the whole fleet, on the world map (K12) ------------------------------------ */
+
+/* neo_mpc_update_scan_layer gives every window a layer of its own: what robot A sees never reaches robot B's window, the
+ * same pallet is inflated again in every window that overlaps it, and the layers cost two more pools of memory.  A fleet
+ * server holds every robot's scans and poses, so it can keep ONE layer on the world map's lattice, feed it from all robots,
+ * merge and inflate it into a copy of the world map once per update and let the roll cut the windows from that copy:
+ *   world scan (points or ranges) -> roll -> stamp -> gate -> carrots -> solve.
+ * The path is additive: the per-window layers (K10, K11) stay as they are and may be used in the same tick, behind the roll.
+ *
+ * State, kept by the handle next to its world map, on the world map's geometry -- WSX x WSY cells of wres at (wox, woy):
+ *   `layer`  values in {255, 0, 254}, persistent; the lattice is fixed, so nothing rolls.  It is unknown_value everywhere on
+ *            the first update, after neo_mpc_reset_world_scan_layer, and whenever the world map's size, resolution or origin
+ *            or unknown_value differ from the previous update's.  neo_mpc_set_world_map with unchanged geometry keeps it.
+ *   `live`   the world map with the layer merged in and inflated.  neo_mpc_roll_costmap_pool[_device] cuts its windows from
+ *            `live` while it is VALID and from the world map otherwise.  `live` becomes valid at the end of every update and
+ *            invalid with every neo_mpc_set_world_map[_device], neo_mpc_inflate_world_map[_device] and
+ *            neo_mpc_reset_world_scan_layer; the next update composes it afresh from the map as it then is, and an update
+ *            with flags == 0 is enough for that.  A handle on which no update was ever called behaves bit for bit as before.
+ *            neo_mpc_get_world_map keeps returning the static map.
+ *
+ * An update, over `count` robots (free of the pool's map count; no pool is needed), each step one or more launches on the
+ * caller's stream, the launch boundary being the order; no atomics:
+ *   1. Clear (with NEO_MPC_SCAN_CLEAR).  Every ray of every source of every robot by step 2 of neo_mpc_scan_batch's contract,
+ *      word for word, with the world's geometry in place of the window's: (ox, oy, res, sx, sy) = (wox, woy, wres, WSX, WSY)
+ *      in worldToMap, the four clips and cellDistance.  Layer cell <- 0, in place.
+ *   2. Mark (with NEO_MPC_SCAN_MARK).  After every clear of every robot, step 3 of that contract on the world's geometry:
+ *      layer cell <- 254.  Robot A's mark therefore survives robot B's ray of the same update -- nav2's order for several
+ *      observation sources in one costmap.
+ *   3. Fleet footprint clearing (with a neo_mpc_fleet_clear record).  The layer is shared, so A's scanner marks B's hull, and
+ *      without this step B's own footprint gate would read 254 and abort (cpp:234-236).  After the marks every robot's
+ *      outline is set free in the layer -- the fleet form of nav2's footprint_clearing_enabled; the other robots still reach
+ *      the windows through neo_mpc_stamp_fleet.  Polygons as in neo_mpc_stamp_batch: `polygons`, or `footprint` placed at
+ *      `poses` / `problems` by the device routine of the footprint gate -- for the same inputs the gate's footprints_out is
+ *      bit for bit what is cleared.  The rule, float64, ONE correctly rounded operation at a time in the order written
+ *      (nothing fused): the world cell (i, l), 0 <= i < WSX, 0 <= l < WSY, has the centre cx = wox + (i + 0.5) wres,
+ *      cy = woy + (l + 0.5) wres; for the edge from a = P[e] to b = P[(e + 1) % n]: ex = b.x - a.x, ey = b.y - a.y,
+ *      c_e = ex (cy - a.y) - ey (cx - a.x) (neo_mpc_stamp_batch's edge function), L_e = sqrt(ex ex + ey ey).  The cell becomes
+ *      0 when every c_e >= -(padding L_e) or every c_e <= padding L_e.  With padding == 0 this is the stamp rule exactly.  A
+ *      polygon with a vertex that is not finite clears nothing; cells outside the world do not exist.  For a convex polygon
+ *      with an area the cleared cells lie within padding / sin(theta / 2) of its bounding box, theta its sharpest interior
+ *      angle: that box is what the device walks.
+ *      `padding` is in metres.  It exists because a hit on a hull lies ON the polygon's boundary: the centre of its cell may lie
+ *      just outside the polygon while the gate's edge walk crosses that very cell.  Callers want padding >= one cell
+ *      diagonal (sqrt(2) wres) plus the scanner's noise.
+ *   4. Compose.  live = the world map combined with the layer by step 4 of neo_mpc_scan_batch's contract (updateWithMax: 255
+ *      in the layer leaves the cell alone), then inflated around the layer's cells equal to 254 by its step 5, with
+ *      R = ceil(inflation_radius / wres) <= NEO_MPC_MAX_INFLATION_CELLS and T from neo_mpc_inflation_costs at wres.  The
+ *      stated difference from nav2 carries over: a cell the layer turns from unknown to free does not get the world's own
+ *      inflation back.
+ * flags == 0 runs steps 3 (if given) and 4 only.  An update repeated with the same inputs changes neither layer nor live.
+ * Out of scope: recomposing only the tiles a scan touched; decaying old marks (observation_persistence); a z coordinate.
+ *
+ * The clear record.  Pointers are host pointers for the synchronous calls and device pointers for the _device variants.
+ * 64 bytes. */
+typedef struct neo_mpc_fleet_clear {
+  size_t count;                    /* robots: must equal the scan or laser batch's count */
+  const double* polygons;          /* optional [count][footprint_points][2], global frame; when given, footprint, poses and
+                                      problems are not read */
+  const double* footprint;         /* used when `polygons` is NULL: [footprint_points][2] base frame, or with
+                                      per_robot_footprints [count][footprint_points][2] */
+  uint32_t footprint_points;       /* 3 .. NEO_MPC_MAX_FOOTPRINT_POINTS */
+  uint32_t per_robot_footprints;   /* 0: one footprint for all; 1: one per robot; anything else is refused */
+  const double* poses;             /* with `footprint`: optional [count][3] x, y, yaw */
+  const neo_mpc_problem* problems; /* with `footprint`, used when `poses` is NULL: cur_xy and the yaw of cur_q */
+  double padding;                  /* m; >= 0, finite */
+  uint64_t reserved;               /* MUST be zero */
+} neo_mpc_fleet_clear;
+
 typedef struct neo_mpc_handle neo_mpc_handle;
 
 /* library / ABI */
@@ -949,6 +1017,49 @@ int neo_mpc_update_scan_layer_from_ranges(neo_mpc_handle* handle, const neo_mpc_
  * parameters of the previous one allocates nothing, copies nothing and does not synchronise, so roll -> scan from ranges ->
  * stamp -> gate -> carrots -> solve can be captured on one stream in one HIP graph and replayed with new ranges and poses. */
 int neo_mpc_update_scan_layer_from_ranges_device(neo_mpc_handle* handle, const neo_mpc_laser_batch* batch, void* stream);
+
+/* Updates the fleet's shared obstacle layer on the world map from one observation per robot and composes `live` (K12; the
+ * contract: neo_mpc_fleet_clear above).  `batch` is neo_mpc_scan_batch's record with `count` = the number of robots, 1 ..
+ * NEO_MPC_MAX_POOL_MAPS (0 does nothing); `clear` may be NULL.  Host pointers, synchronous.  Refusals, all of which leave
+ * layer, live and their validity as they were: those of neo_mpc_update_scan_layer that concern `reserved`, the flags,
+ * unknown_value, max_points, null arrays with non-zero flags, the ranges and radii, point_counts and sensor origins, with the
+ * same codes and texts; NEO_MPC_ERR_NO_COSTMAP before neo_mpc_set_world_map; NEO_MPC_ERR_UNSUPPORTED for
+ * R > NEO_MPC_MAX_INFLATION_CELLS at the world's resolution; NEO_MPC_ERR_INVALID_ARGUMENT for count > NEO_MPC_MAX_POOL_MAPS
+ * and, of the clear record, the refusals of neo_mpc_stamp_fleet (reserved, footprint_points, per_robot_footprints, neither
+ * polygons nor a footprint with poses or problems, a pose or vertex that is not finite), a `padding` that is negative or not
+ * finite, and a `count` other than the batch's. */
+int neo_mpc_update_world_scan_layer(neo_mpc_handle* handle, const neo_mpc_scan_batch* batch, const neo_mpc_fleet_clear* clear);
+/* Same with every pointer of both records in device memory; enqueued on `stream`, returns without waiting; no value behind a
+ * pointer is looked at on the host.  Ordering: an update reads the world map and rewrites what the roll reads, so it is fenced
+ * exactly like neo_mpc_inflate_world_map_device -- it waits on its stream for the last roll and the previous copy, inflation
+ * or update, and a roll on another stream waits for it.  Memory: two more world maps' worth, allocated on the first update
+ * and on a larger world.  The cost table is kept in the handle, apart from K8's, K9's and K10's, and rebuilt synchronously
+ * when (wres, inscribed_radius, inflation_radius, cost_scaling_factor) differ from the previous update's.  A device update
+ * with the shapes and inflation parameters of the previous one allocates nothing, copies nothing and does not synchronise, so
+ * world scan -> roll -> stamp -> gate -> carrots -> solve can be captured on one stream in one HIP graph and replayed with
+ * new points and poses.  The roll's source -- `live` or the world map -- is a pointer fixed when the roll is CAPTURED: capture
+ * the roll behind an update, and capture again after a call that invalidates `live`. */
+int neo_mpc_update_world_scan_layer_device(neo_mpc_handle* handle, const neo_mpc_scan_batch* batch, const neo_mpc_fleet_clear* clear,
+                                           void* stream);
+/* K11's projection, unchanged, in front of steps 1 to 4 over all sources (the contract: neo_mpc_laser_batch, with the
+ * world's layer in place of the windows').  Refusals: those of neo_mpc_update_scan_layer_from_ranges with the pool's replaced
+ * by the world's as above, and those of the clear record. */
+int neo_mpc_update_world_scan_layer_from_ranges(neo_mpc_handle* handle, const neo_mpc_laser_batch* batch,
+                                                const neo_mpc_fleet_clear* clear);
+/* Same with device pointers (`scanners` stays a host pointer), enqueued on `stream`: the projection and the update are one
+ * rewrite of what the roll reads, fenced like neo_mpc_update_world_scan_layer_device; a call with the scanners, shapes and
+ * inflation parameters of the previous one allocates nothing, copies nothing and does not synchronise. */
+int neo_mpc_update_world_scan_layer_from_ranges_device(neo_mpc_handle* handle, const neo_mpc_laser_batch* batch,
+                                                       const neo_mpc_fleet_clear* clear, void* stream);
+/* Reads the layer and `live` back as the last update left them, layer_out[WSY][WSX] and live_out[WSY][WSX] on the geometry of
+ * the world map of that update (either may be NULL); `live` is returned whether or not it is still valid.  Host pointers,
+ * synchronous; waits for the update in flight -- one that was ENQUEUED by a call (neo_mpc_get_world_map says why).
+ * NEO_MPC_ERR_NO_COSTMAP before the first update, behind neo_mpc_reset_world_scan_layer and behind a neo_mpc_set_world_map of
+ * another size (the next update resets the layer in that case anyway). */
+int neo_mpc_get_world_scan_layer(neo_mpc_handle* handle, uint8_t* layer_out, uint8_t* live_out);
+/* The next update starts from a layer of unknown_value, and until then the roll reads the world map.  Touches no device
+ * memory.  NEO_MPC_ERR_INVALID_ARGUMENT for a null handle. */
+int neo_mpc_reset_world_scan_layer(neo_mpc_handle* handle);
 
 /* ---- multi-GPU fleets: the one exchange step ------------------------------------------------
  * Instances of one tick shard embarrassingly over the GPUs of a node (one handle per GPU, costmap and parameters

@@ -31,6 +31,9 @@ EXPORTS = (
     "neo_mpc_update_scan_layer", "neo_mpc_update_scan_layer_device", "neo_mpc_get_scan_layer", "neo_mpc_reset_scan_layer",
     "neo_mpc_laser_beam_table", "neo_mpc_project_laser", "neo_mpc_project_laser_device",
     "neo_mpc_update_scan_layer_from_ranges", "neo_mpc_update_scan_layer_from_ranges_device",
+    "neo_mpc_update_world_scan_layer", "neo_mpc_update_world_scan_layer_device",
+    "neo_mpc_update_world_scan_layer_from_ranges", "neo_mpc_update_world_scan_layer_from_ranges_device",
+    "neo_mpc_get_world_scan_layer", "neo_mpc_reset_world_scan_layer",
     "neo_mpc_rccl_available", "neo_mpc_comm_init_all", "neo_mpc_comm_destroy", "neo_mpc_group_start",
     "neo_mpc_group_end", "neo_mpc_allgather_velocities", "neo_mpc_broadcast_costmap",
 )
@@ -135,6 +138,13 @@ def load():
         lib.neo_mpc_project_laser_device.argtypes = [C.c_void_p, P(abi.NeoMpcLaserBatch), C.c_void_p]
         lib.neo_mpc_update_scan_layer_from_ranges.argtypes = [C.c_void_p, P(abi.NeoMpcLaserBatch)]
         lib.neo_mpc_update_scan_layer_from_ranges_device.argtypes = [C.c_void_p, P(abi.NeoMpcLaserBatch), C.c_void_p]
+        lib.neo_mpc_update_world_scan_layer.argtypes = [C.c_void_p, P(abi.NeoMpcScanBatch), P(abi.NeoMpcFleetClear)]
+        lib.neo_mpc_update_world_scan_layer_device.argtypes = [C.c_void_p, P(abi.NeoMpcScanBatch), P(abi.NeoMpcFleetClear), C.c_void_p]
+        lib.neo_mpc_update_world_scan_layer_from_ranges.argtypes = [C.c_void_p, P(abi.NeoMpcLaserBatch), P(abi.NeoMpcFleetClear)]
+        lib.neo_mpc_update_world_scan_layer_from_ranges_device.argtypes = [C.c_void_p, P(abi.NeoMpcLaserBatch),
+                                                                          P(abi.NeoMpcFleetClear), C.c_void_p]
+        lib.neo_mpc_get_world_scan_layer.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+        lib.neo_mpc_reset_world_scan_layer.argtypes = [C.c_void_p]
     _lib = lib
     return lib
 

@@ -224,6 +224,21 @@ MAX_SCAN_SOURCES = 4
 LASER_INF_IS_VALID = 1   # NEO_MPC_LASER_INF_IS_VALID: a range of +inf is a beam that met nothing, at range_max - 1e-4
 
 
+class NeoMpcFleetClear(_C.Structure):
+    """`neo_mpc_fleet_clear` (include/neo_mpc.h): the robots' outlines set free in the fleet's shared obstacle layer."""
+    _fields_ = [("count", _C.c_size_t), ("polygons", _C.c_void_p), ("footprint", _C.c_void_p),
+                ("footprint_points", _C.c_uint32), ("per_robot_footprints", _C.c_uint32), ("poses", _C.c_void_p),
+                ("problems", _C.c_void_p), ("padding", _C.c_double), ("reserved", _C.c_uint64)]
+
+
+#: the same record as a NumPy dtype (64 bytes; the pointers as addresses)
+FLEET_CLEAR_DTYPE = np.dtype([
+    ("count", "<u8"), ("polygons", "<u8"), ("footprint", "<u8"), ("footprint_points", "<u4"), ("per_robot_footprints", "<u4"),
+    ("poses", "<u8"), ("problems", "<u8"), ("padding", "<f8"), ("reserved", "<u8"),
+], align=False)
+assert FLEET_CLEAR_DTYPE.itemsize == 64 == _C.sizeof(NeoMpcFleetClear)
+
+
 def scanner_array(scanners):
     """One scanner or a sequence of them -> a NumPy array of SCANNER_DTYPE.  A scanner is a mapping with the record's field
     names (flags and reserved default to 0), a NeoMpcScanner, or an element of such an array already."""

@@ -11,7 +11,7 @@
 // cost table); the handle; parameters and the term table; the shared checks; the device map (geometry, adoption, K3
 // ingest); the staging of host batches by range; then the entry points -- costmaps, the solve paths of K1, K2 and the hooks,
 // K4 carrots, K6 footprint gate, K7 rolling windows, K8 fleet stamp, K9 world inflation, K10 scan layer,
-// K11 laser projection.  A new entry point checks with the
+// K11 laser projection, K12 world scan layer.  A new entry point checks with the
 // shared checks, stages with upload(), and launches through fence.read() or between fence.begin_write() and end_write().
 #include <hip/hip_runtime.h>
 
@@ -304,6 +304,34 @@ struct ScanLayers {
   void adopt() { valid = true; }   // behind the update's end_write: its launches are enqueued
 };
 
+// K12.  The fleet's shared obstacle layer on the world map's lattice: `layer` persists between updates, `live` is the world
+// map with the layer merged in and inflated -- what the roll reads while `live_valid` --, both WSX bytes a row; a cost table of
+// their own at the world's resolution; and what the layer was made for -- an update that meets another geometry or
+// unknown_value resets it.  Ordered by the world map's own event (WorldMap): an update is a rewrite of what the roll reads.
+struct WorldScanLayer {
+  InflationTable table;
+  DeviceBuffer layer, live;
+  bool valid = false;        // the layer holds what the updates since the last reset put there
+  bool live_valid = false;   // `live` is the current world map with the layer in it
+  int32_t size_x = 0, size_y = 0;
+  double resolution = 0.0, origin_x = 0.0, origin_y = 0.0;
+  uint32_t unknown = 0;
+  DeviceBuffer verts, poses, problems;   // (the host variants' staging of the clear record)
+  size_t bytes() const { return (size_t)size_x * (size_t)size_y; }
+  bool matches(const WorldMap& w, uint32_t u) const {
+    return valid && size_x == w.size_x && size_y == w.size_y && resolution == w.resolution && origin_x == w.origin_x &&
+           origin_y == w.origin_y && unknown == u;
+  }
+  // A reset: the world's geometry; re-allocated only where that asks for more (which synchronises)
+  int resize(const WorldMap& w, uint32_t unknown_value) {
+    valid = false; live_valid = false;
+    size_x = w.size_x; size_y = w.size_y; resolution = w.resolution; origin_x = w.origin_x; origin_y = w.origin_y;
+    unknown = unknown_value;
+    if (int rc = layer.reserve(bytes())) return rc;
+    return live.reserve(bytes());
+  }
+};
+
 // K11.  The beam table of one scanner (the contract: neo_mpc_laser_batch, step 4), with libm
 void laser_beam_table(const neo_mpc_scanner& sc, uint32_t beams, double* table) {
 #pragma clang fp contract(off)
@@ -398,6 +426,7 @@ struct __attribute__((visibility("hidden"))) neo_mpc_handle {
   InflationTable world_table;
   ScanLayers scan;   // K10 neo_mpc_update_scan_layer
   LaserProjection laser;   // K11 neo_mpc_project_laser, neo_mpc_update_scan_layer_from_ranges
+  WorldScanLayer world_scan;   // K12 neo_mpc_update_world_scan_layer
 };
 constexpr size_t kLatencyPathMaxCount = 64;
 constexpr size_t kChunkedMinCount = 65536;   // staged host batches from here on go through in kChunks pieces on two streams
@@ -1398,6 +1427,7 @@ static int set_world_map(neo_mpc_handle* h, const uint8_t* cells, bool on_device
   WorldMap& w = h->world;
   int rc = w.begin_write(h->fence, on_device, st);
   if (rc) return rc;
+  h->world_scan.live_valid = false;   // (K12: the next update composes the new map; until then the roll reads this one)
   rc = w.buf.reserve(bytes);
   if (rc) { w.has = false; return rc; }   // (a failed re-allocation has let the old copy go)
   if (on_device) HIP_TRY(hipMemcpyAsync(w.buf.ptr, cells, bytes, hipMemcpyDeviceToDevice, st));
@@ -1406,6 +1436,9 @@ static int set_world_map(neo_mpc_handle* h, const uint8_t* cells, bool on_device
   w.size_x = (int32_t)sx; w.size_y = (int32_t)sy;
   w.resolution = res; w.origin_x = ox; w.origin_y = oy;
   w.has = true;
+  // (K12: a layer of another size is no layer of this world -- the next update resets it anyway, and until then
+  // neo_mpc_get_world_scan_layer has nothing of the size its caller expects)
+  if (h->world_scan.size_x != w.size_x || h->world_scan.size_y != w.size_y) h->world_scan.valid = false;
   return NEO_MPC_OK;
 }
 
@@ -1457,7 +1490,9 @@ static int roll(neo_mpc_handle* h, const neo_mpc_window_batch& d, void* stream) 
   std::memset(&a, 0, sizeof(a));
   a.poses = d.poses; a.problems = d.poses ? nullptr : d.problems; a.origins = d.origins;
   a.tables = h->roll_tables.as<int32_t>();
-  a.world = h->world.buf.as<const uint8_t>(); a.dst = h->map_buf.as<uint8_t>();
+  // (K12: while an update's composition is current the windows are cut from it -- same geometry, same event)
+  a.world = h->world_scan.live_valid ? h->world_scan.live.as<const uint8_t>() : h->world.buf.as<const uint8_t>();
+  a.dst = h->map_buf.as<uint8_t>();
   a.res = d.resolution; a.wres = h->world.resolution; a.wox = h->world.origin_x; a.woy = h->world.origin_y;
   a.dst_stride = (int64_t)g.stride;
   a.wsx = h->world.size_x; a.wsy = h->world.size_y;
@@ -1678,6 +1713,7 @@ static int inflate_world_map(neo_mpc_handle* h, double ins, double infl, double 
   if (int rc = h->world_table.build(w.resolution, ins, infl, csf, w)) return rc;   // (every inflation records the world's event)
   hipStream_t st = (hipStream_t)stream;
   if (int rc = w.begin_write(h->fence, on_device, st)) return rc;
+  h->world_scan.live_valid = false;   // (K12, as in set_world_map)
   InflateArgs a;
   std::memset(&a, 0, sizeof(a));
   a.world = w.buf.as<uint8_t>();
@@ -1699,8 +1735,17 @@ int neo_mpc_inflate_world_map(neo_mpc_handle* h, double ins, double infl, double
   return finish_on_null_stream(inflate_world_map(h, ins, infl, csf, false, nullptr));
 }
 
-// K10.  What both update entry points check: the record's shape and the handle's pool, never a value behind a pointer.
-static int check_scan_batch(const neo_mpc_handle* h, const neo_mpc_scan_batch* b) {
+// K12.  What a world-scan update refuses behind the record's own refusals, in place of check_pool_batch: the world map, the
+// number of robots (free of the pool's), the reach at the world's resolution
+static int check_world_scan(const neo_mpc_handle* h, size_t count, double ins, double infl, double csf) {
+  if (!h->world.has) return fail(NEO_MPC_ERR_NO_COSTMAP, "neo_mpc_set_world_map has not been called");
+  if (count > NEO_MPC_MAX_POOL_MAPS) return fail(NEO_MPC_ERR_INVALID_ARGUMENT, "%zu robots: at most %u per call", count, NEO_MPC_MAX_POOL_MAPS);
+  return inflation_reach(h->world.resolution, ins, infl, csf, "the world map's ", nullptr);
+}
+
+// K10, K12 (`world`).  What the update entry points check: the record's shape and the handle's pool -- or its world map --,
+// never a value behind a pointer.
+static int check_scan_batch(const neo_mpc_handle* h, const neo_mpc_scan_batch* b, bool world = false) {
   if (!h || !b) return fail(NEO_MPC_ERR_INVALID_ARGUMENT, "null argument");
   if (b->reserved != 0) return fail(NEO_MPC_ERR_INVALID_ARGUMENT, "neo_mpc_scan_batch.reserved must be zero");
   if (b->flags & ~(NEO_MPC_SCAN_CLEAR | NEO_MPC_SCAN_MARK)) return fail(NEO_MPC_ERR_INVALID_ARGUMENT, "unknown flags 0x%x", b->flags);
@@ -1713,6 +1758,7 @@ static int check_scan_batch(const neo_mpc_handle* h, const neo_mpc_scan_batch* b
   for (const double r : {b->obstacle_max_range, b->obstacle_min_range, b->raytrace_max_range, b->raytrace_min_range})
     if (!std::isfinite(r) || r < 0.0) return fail(NEO_MPC_ERR_INVALID_ARGUMENT, "range %g must be finite and not negative", r);
   if (int rc = check_inflation_radii(b->inscribed_radius, b->inflation_radius, b->cost_scaling_factor)) return rc;
+  if (world) return check_world_scan(h, b->count, b->inscribed_radius, b->inflation_radius, b->cost_scaling_factor);
   return check_pool_batch(h, b->count, b->inscribed_radius, b->inflation_radius, b->cost_scaling_factor);
 }
 
@@ -1803,7 +1849,7 @@ static int check_scanner(const neo_mpc_scanner& sc, uint32_t s) {
 
 // K11.  What the four entry points check: the record's shape, the scanners (host configuration) and, for an update, what
 // check_scan_batch checks of the handle's pool -- never a value behind ranges, poses or the out pointers.
-static int check_laser_batch(const neo_mpc_handle* h, const neo_mpc_laser_batch* b, bool update, bool device) {
+static int check_laser_batch(const neo_mpc_handle* h, const neo_mpc_laser_batch* b, bool update, bool device, bool world = false) {
   if (!h || !b) return fail(NEO_MPC_ERR_INVALID_ARGUMENT, "null argument");
   if (b->reserved != 0) return fail(NEO_MPC_ERR_INVALID_ARGUMENT, "neo_mpc_laser_batch.reserved must be zero");
   if (b->sources < 1 || b->sources > NEO_MPC_MAX_SCAN_SOURCES)
@@ -1827,6 +1873,7 @@ static int check_laser_batch(const neo_mpc_handle* h, const neo_mpc_laser_batch*
   for (const double r : {b->obstacle_max_range, b->obstacle_min_range, b->raytrace_max_range, b->raytrace_min_range})
     if (!std::isfinite(r) || r < 0.0) return fail(NEO_MPC_ERR_INVALID_ARGUMENT, "range %g must be finite and not negative", r);
   if (int rc = check_inflation_radii(b->inscribed_radius, b->inflation_radius, b->cost_scaling_factor)) return rc;
+  if (world) return check_world_scan(h, b->count, b->inscribed_radius, b->inflation_radius, b->cost_scaling_factor);
   return check_pool_batch(h, b->count, b->inscribed_radius, b->inflation_radius, b->cost_scaling_factor);
 }
 
@@ -1861,10 +1908,8 @@ static int project_laser(neo_mpc_handle* h, const neo_mpc_laser_batch& d, void* 
   return NEO_MPC_OK;
 }
 
-// The projection and the update over all sources, one write of the device maps
-static int scan_from_ranges(neo_mpc_handle* h, const neo_mpc_laser_batch& d, void* stream) {
-  LaserArgs a;
-  if (int rc = laser_args(h, d, a)) return rc;
+// The update's record for the points `a` projects
+static neo_mpc_scan_batch scan_batch_of(const neo_mpc_laser_batch& d, const LaserArgs& a) {
   neo_mpc_scan_batch sb;
   std::memset(&sb, 0, sizeof(sb));
   sb.count = d.count; sb.points = a.points; sb.sensor_origins = a.origins;
@@ -1873,7 +1918,14 @@ static int scan_from_ranges(neo_mpc_handle* h, const neo_mpc_laser_batch& d, voi
   sb.raytrace_max_range = d.raytrace_max_range; sb.raytrace_min_range = d.raytrace_min_range;
   sb.inscribed_radius = d.inscribed_radius; sb.inflation_radius = d.inflation_radius; sb.cost_scaling_factor = d.cost_scaling_factor;
   sb.unknown_value = d.unknown_value;
-  return scan(h, sb, stream, &a);
+  return sb;
+}
+
+// The projection and the update over all sources, one write of the device maps
+static int scan_from_ranges(neo_mpc_handle* h, const neo_mpc_laser_batch& d, void* stream) {
+  LaserArgs a;
+  if (int rc = laser_args(h, d, a)) return rc;
+  return scan(h, scan_batch_of(d, a), stream, &a);
 }
 
 int neo_mpc_laser_beam_table(const neo_mpc_scanner* scanner, uint32_t beams, double* table_out) {
@@ -1940,6 +1992,179 @@ int neo_mpc_get_scan_layer(neo_mpc_handle* h, uint32_t first, uint32_t count, ui
 int neo_mpc_reset_scan_layer(neo_mpc_handle* h) {
   if (!h) return fail(NEO_MPC_ERR_INVALID_ARGUMENT, "null handle");
   h->scan.valid = false;
+  return NEO_MPC_OK;
+}
+
+// ---------------------------------------------------------------------------------------------- K12: the world scan layer
+// What the update entry points check of the clear record: its shape, never a value behind a pointer
+static int check_fleet_clear(const neo_mpc_fleet_clear* c, size_t count) {
+  if (!c) return NEO_MPC_OK;
+  if (c->reserved != 0) return fail(NEO_MPC_ERR_INVALID_ARGUMENT, "neo_mpc_fleet_clear.reserved must be zero");
+  if (int rc = check_footprint_shape(c->footprint_points, c->per_robot_footprints)) return rc;
+  if (!std::isfinite(c->padding) || c->padding < 0.0)
+    return fail(NEO_MPC_ERR_INVALID_ARGUMENT, "padding %g must be finite and not negative", c->padding);
+  if (c->count != count)
+    return fail(NEO_MPC_ERR_INVALID_ARGUMENT, "%zu outlines for %zu robots: they are one to one", c->count, count);
+  if (c->count > 0 && !c->polygons && (!c->footprint || (!c->poses && !c->problems)))
+    return fail(NEO_MPC_ERR_INVALID_ARGUMENT, "neither polygons nor a footprint with poses or problems");
+  return NEO_MPC_OK;
+}
+
+// `d`, `c`: the records with device pointers (`c` may be null).  Orders itself like inflate_world_map(): it reads the world map
+// and rewrites what the roll reads -- on `stream`, or on the host and the null stream.  `laser`: K11's projection into d.points
+// and d.sensor_origins, enqueued inside the same write, in front of the rays.
+static int world_scan(neo_mpc_handle* h, const neo_mpc_scan_batch& d, const neo_mpc_fleet_clear* c, bool on_device, void* stream,
+                      const LaserArgs* laser = nullptr) {
+  WorldMap& w = h->world;
+  WorldScanLayer& l = h->world_scan;
+  int rc = l.table.build(w.resolution, d.inscribed_radius, d.inflation_radius, d.cost_scaling_factor, w);   // (every update records the world's event)
+  if (rc) return rc;
+  const bool same = l.matches(w, d.unknown_value);
+  if (!same && (rc = l.resize(w, d.unknown_value))) return rc;
+  hipStream_t st = (hipStream_t)stream;
+  // behind the last roll, which reads `live` or the world map, and the previous copy, inflation or update
+  if ((rc = w.begin_write(h->fence, on_device, st))) return rc;
+  WorldScanArgs a;
+  std::memset(&a, 0, sizeof(a));
+  if (d.flags != 0) { a.s.points = d.points; a.s.point_counts = d.point_counts; a.s.sensor_origins = d.sensor_origins; }
+  a.s.table = l.table.buf.as<const uint8_t>();
+  a.s.res = w.resolution;
+  a.s.obstacle_max = d.obstacle_max_range; a.s.obstacle_min = d.obstacle_min_range;
+  a.s.raytrace_max = d.raytrace_max_range; a.s.raytrace_min = d.raytrace_min_range;
+  a.s.reach = l.table.reach;
+  a.s.count = (uint32_t)d.count; a.s.max_points = d.flags != 0 ? d.max_points : 0u; a.s.flags = d.flags; a.s.unknown = d.unknown_value;
+  a.s.sources = laser ? laser->sources : 1u;
+  a.s.points_per_source = laser ? laser->beams : (d.max_points > 0 ? d.max_points : 1u);
+  a.layer = l.layer.as<uint8_t>(); a.world = w.buf.as<const uint8_t>(); a.live = l.live.as<uint8_t>();
+  if (c && c->count > 0) {
+    a.polygons = c->polygons;
+    if (!c->polygons) { a.footprint = c->footprint; a.poses = c->poses; a.problems = c->poses ? nullptr : c->problems; }
+    a.padding = c->padding; a.points = c->footprint_points; a.per_robot = c->per_robot_footprints; a.clear = 1u;
+  }
+  a.wres = w.resolution; a.wox = w.origin_x; a.woy = w.origin_y;
+  a.wsx = w.size_x; a.wsy = w.size_y;
+  a.reset = same ? 0u : 1u;
+  if (laser) launch_laser_project(*laser, stream);
+  launch_world_scan(a, stream);
+  HIP_TRY(hipGetLastError());
+  if ((rc = w.end_write(st))) return rc;   // a roll behind it, on whatever stream, cuts its windows from `live`
+  l.valid = true; l.live_valid = true;
+  return NEO_MPC_OK;
+}
+
+// The clear record's host arrays staged -> `d` with device pointers (the values the device variants take as they come are
+// looked at here)
+static int stage_fleet_clear(neo_mpc_handle* h, const neo_mpc_fleet_clear* c, neo_mpc_fleet_clear& d) {
+  const size_t n = c->count, np = c->footprint_points;
+  const double* verts = c->polygons ? c->polygons : c->footprint;
+  const size_t polygons = c->polygons || c->per_robot_footprints ? n : 1;
+  if (int rc = check_vertices_finite(verts, polygons, np, "vertex", "polygon")) return rc;
+  if (!c->polygons) if (int rc = check_poses_finite(c->poses, c->problems, n)) return rc;
+  HIP_TRY(hipSetDevice(h->device));
+  WorldScanLayer& l = h->world_scan;
+  d = *c;
+  d.polygons = nullptr; d.footprint = nullptr; d.poses = nullptr; d.problems = nullptr;
+  const double* d_verts = l.verts.upload(verts, polygons * np * 16);
+  if (!d_verts) return NEO_MPC_ERR_DEVICE;
+  if (c->polygons) d.polygons = d_verts;
+  else {
+    d.footprint = d_verts;
+    if (c->poses) d.poses = l.poses.upload(c->poses, n * 24);
+    else d.problems = l.problems.upload(c->problems, n * sizeof(neo_mpc_problem));
+    if (!d.poses && !d.problems) return NEO_MPC_ERR_DEVICE;
+  }
+  return NEO_MPC_OK;
+}
+
+int neo_mpc_update_world_scan_layer_device(neo_mpc_handle* h, const neo_mpc_scan_batch* b, const neo_mpc_fleet_clear* c, void* stream) {
+  int rc = check_scan_batch(h, b, true);
+  if (rc || (rc = check_fleet_clear(c, b->count))) return rc;
+  if (b->count == 0) return NEO_MPC_OK;
+  HIP_TRY(hipSetDevice(h->device));
+  return world_scan(h, *b, c, true, stream);
+}
+
+int neo_mpc_update_world_scan_layer(neo_mpc_handle* h, const neo_mpc_scan_batch* b, const neo_mpc_fleet_clear* c) {
+  int rc = check_scan_batch(h, b, true);
+  if (rc || (rc = check_fleet_clear(c, b->count))) return rc;
+  if (b->count == 0) return NEO_MPC_OK;
+  const size_t n = b->count;
+  neo_mpc_scan_batch d = *b;
+  d.points = nullptr; d.point_counts = nullptr; d.sensor_origins = nullptr;
+  if (b->flags != 0) {
+    // the values the device variant takes as they come are looked at here
+    for (size_t k = 0; k < n; ++k) {
+      if (b->point_counts && b->point_counts[k] > b->max_points)
+        return fail(NEO_MPC_ERR_INVALID_ARGUMENT, "point_counts[%zu] = %u is more than max_points %u", k, b->point_counts[k], b->max_points);
+      if (!std::isfinite(b->sensor_origins[2 * k]) || !std::isfinite(b->sensor_origins[2 * k + 1]))
+        return fail(NEO_MPC_ERR_INVALID_ARGUMENT, "the sensor origin of robot %zu is not finite", k);
+    }
+  }
+  neo_mpc_fleet_clear dc;
+  if (c && c->count > 0 && (rc = stage_fleet_clear(h, c, dc))) return rc;
+  HIP_TRY(hipSetDevice(h->device));
+  if (b->flags != 0) {
+    if (!(d.sensor_origins = h->scan.sensors.upload(b->sensor_origins, n * 16))) return NEO_MPC_ERR_DEVICE;
+    if (b->max_points > 0 && !(d.points = h->scan.points.upload(b->points, n * b->max_points * 16))) return NEO_MPC_ERR_DEVICE;
+    if (b->point_counts && !(d.point_counts = h->scan.point_counts.upload(b->point_counts, n * 4))) return NEO_MPC_ERR_DEVICE;
+  }
+  return finish_on_null_stream(world_scan(h, d, c && c->count > 0 ? &dc : nullptr, false, nullptr));
+}
+
+// The projection and the world's update over all sources, one write of what the roll reads
+static int world_scan_from_ranges(neo_mpc_handle* h, const neo_mpc_laser_batch& d, const neo_mpc_fleet_clear* c, bool on_device,
+                                  void* stream) {
+  LaserArgs a;
+  if (int rc = laser_args(h, d, a)) return rc;
+  return world_scan(h, scan_batch_of(d, a), c, on_device, stream, &a);
+}
+
+int neo_mpc_update_world_scan_layer_from_ranges_device(neo_mpc_handle* h, const neo_mpc_laser_batch* b, const neo_mpc_fleet_clear* c,
+                                                       void* stream) {
+  int rc = check_laser_batch(h, b, true, true, true);
+  if (rc || (rc = check_fleet_clear(c, b->count))) return rc;
+  if (b->count == 0) return NEO_MPC_OK;
+  HIP_TRY(hipSetDevice(h->device));
+  return world_scan_from_ranges(h, *b, c, true, stream);
+}
+
+int neo_mpc_update_world_scan_layer_from_ranges(neo_mpc_handle* h, const neo_mpc_laser_batch* b, const neo_mpc_fleet_clear* c) {
+  int rc = check_laser_batch(h, b, true, false, true);
+  if (rc || (rc = check_fleet_clear(c, b->count))) return rc;
+  if (b->count == 0) return NEO_MPC_OK;
+  const size_t n = b->count, scans = n * b->sources;
+  // the values the device variants take as they come are looked at here
+  if ((rc = check_poses_finite(b->poses, nullptr, n))) return rc;
+  neo_mpc_fleet_clear dc;
+  if (c && c->count > 0 && (rc = stage_fleet_clear(h, c, dc))) return rc;
+  HIP_TRY(hipSetDevice(h->device));
+  neo_mpc_laser_batch d = *b;
+  d.points_out = nullptr; d.origins_out = nullptr;
+  if (!(d.ranges = h->laser.ranges.upload(b->ranges, scans * b->beams * 4))) return NEO_MPC_ERR_DEVICE;
+  if (!(d.poses = h->poses.upload(b->poses, n * 24))) return NEO_MPC_ERR_DEVICE;
+  if ((rc = finish_on_null_stream(world_scan_from_ranges(h, d, c && c->count > 0 ? &dc : nullptr, false, nullptr)))) return rc;
+  if (b->points_out) HIP_TRY(hipMemcpy(b->points_out, h->laser.points.ptr, scans * b->beams * 16, hipMemcpyDeviceToHost));
+  if (b->origins_out) HIP_TRY(hipMemcpy(b->origins_out, h->laser.origins.ptr, scans * 16, hipMemcpyDeviceToHost));
+  return NEO_MPC_OK;
+}
+
+int neo_mpc_get_world_scan_layer(neo_mpc_handle* h, uint8_t* layer_out, uint8_t* live_out) {
+  if (!h) return fail(NEO_MPC_ERR_INVALID_ARGUMENT, "null handle");
+  WorldScanLayer& l = h->world_scan;
+  if (!l.valid)
+    return fail(NEO_MPC_ERR_NO_COSTMAP, "no world scan layer: neo_mpc_update_world_scan_layer has not been called since the last reset");
+  if (!layer_out && !live_out) return NEO_MPC_OK;
+  HIP_TRY(hipSetDevice(h->device));
+  if (int rc = h->world.wait_writer_host()) return rc;   // the update in flight
+  if (layer_out) HIP_TRY(hipMemcpy(layer_out, l.layer.ptr, l.bytes(), hipMemcpyDeviceToHost));
+  if (live_out) HIP_TRY(hipMemcpy(live_out, l.live.ptr, l.bytes(), hipMemcpyDeviceToHost));
+  return NEO_MPC_OK;
+}
+
+int neo_mpc_reset_world_scan_layer(neo_mpc_handle* h) {
+  if (!h) return fail(NEO_MPC_ERR_INVALID_ARGUMENT, "null handle");
+  h->world_scan.valid = false;
+  h->world_scan.live_valid = false;
   return NEO_MPC_OK;
 }
 

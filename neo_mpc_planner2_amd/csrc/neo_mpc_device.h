@@ -281,6 +281,26 @@ struct ScanArgs {
   uint32_t reset;                   // 1: the layers start from `unknown` at the windows' origins
 };
 
+// K12: the fleet's shared obstacle layer on the world map (neo_mpc_update_world_scan_layer, device pointers) -- the handle's
+// world map, its layer and the map the roll reads; every row of the three is wsx bytes
+struct WorldScanArgs {
+  ScanArgs s;                       // the rays as K10 takes them (count: robots; flags, ranges, sources) and table / reach at wres
+  uint8_t* layer;                   // handle-owned: the layer, {255, 0, 254}, persistent
+  const uint8_t* world;             // the static world map
+  uint8_t* live;                    // handle-owned: the world map with the layer merged in and inflated
+  const double* polygons;           // fleet footprint clearing (neo_mpc_fleet_clear): as StampArgs; all null with clear == 0
+  const double* footprint;
+  const double* poses;
+  const neo_mpc_problem* problems;
+  double padding;                   // m
+  double wres, wox, woy;
+  int32_t wsx, wsy;
+  uint32_t points;                  // footprint_points
+  uint32_t per_robot;
+  uint32_t clear;                   // 1: step 3 runs
+  uint32_t reset;                   // 1: the layer starts from s.unknown
+};
+
 // K11: LaserScan ranges projected into global-frame points and sensor origins (neo_mpc_laser_batch, device pointers)
 struct LaserSource {                // one neo_mpc_scanner as the kernel needs it
   double mount_x, mount_y;
@@ -318,6 +338,7 @@ void launch_stamp(const StampArgs& a, void* stream); // K8: k_stamp_boxes, then 
 void launch_inflate_world(const InflateArgs& a, void* stream);   // K9: k_inflate_world
 void launch_scan_layer(const ScanArgs& a, void* stream);         // K10: k_scan_shift, k_scan_rays (clear, mark), k_scan_apply
 void launch_laser_project(const LaserArgs& a, void* stream);     // K11: k_laser_project
+void launch_world_scan(const WorldScanArgs& a, void* stream);    // K12: k_world_scan_rays (clear, mark), k_world_scan_footprints, k_world_scan_compose
 // K5: dispatch order of the next launch from the iteration counts of the previous one (neo_mpc_balance_dispatch_device)
 void launch_dispatch_order(const neo_mpc_command* commands, float* load, uint32_t* order, uint32_t count, bool fresh, void* stream);
 constexpr uint32_t kDispatchSimds = 1024;   // a 4096-instance launch is one residency round: workgroups w, w + 1024, w + 2048, w + 3072 share a SIMD

@@ -21,6 +21,7 @@
 //   K9 k_inflate_world  world_inflation.h: nav2's inflation layer on the world map, in place (inflation.h: what it shares with K8 and K10).
 //   K10 k_scan_shift, k_scan_rays, k_scan_apply  scan_layer.h: the obstacle layer of every window, fed from sensor points.
 //   K11 k_laser_project  laser_projection.h: LaserScan ranges of every scanner of every robot -> those points, HBM-streaming.
+//   K12 k_world_scan_rays, k_world_scan_footprints, k_world_scan_compose  world_scan_layer.h: one obstacle layer for the fleet on the world map.
 #include "k1_solve.h"
 #include "costmap_ingest.h"
 #include "footprint_gate.h"
@@ -29,6 +30,7 @@
 #include "world_inflation.h"
 #include "scan_layer.h"
 #include "laser_projection.h"
+#include "world_scan_layer.h"
 
 namespace neo_mpc {
 namespace {
@@ -374,6 +376,20 @@ void launch_scan_layer(const ScanArgs& a, void* stream) {
 void launch_laser_project(const LaserArgs& a, void* stream) {
   if (a.count == 0) return;
   hipLaunchKernelGGL(k_laser_project, dim3(a.count, a.sources), dim3(kLaserThreads), 0, (hipStream_t)stream, a);
+}
+// K12: the reset (a fill), every clear of every robot, every mark, the footprints, then the composition -- each behind the one
+// before on one stream: every mark lies behind every clear, the footprints behind every mark, the seeds are final when read
+void launch_world_scan(const WorldScanArgs& a, void* stream) {
+  if (a.wsx <= 0 || a.wsy <= 0) return;
+  hipStream_t st = (hipStream_t)stream;
+  if (a.reset) (void)hipMemsetAsync(a.layer, (int)a.s.unknown, (size_t)a.wsx * (size_t)a.wsy, st);
+  const dim3 rays((a.s.max_points + kScanRayThreads - 1) / kScanRayThreads, a.s.count);
+  const bool any = a.s.count > 0 && a.s.max_points > 0;
+  if (any && (a.s.flags & NEO_MPC_SCAN_CLEAR)) hipLaunchKernelGGL(k_world_scan_rays<false>, rays, dim3(kScanRayThreads), 0, st, a);
+  if (any && (a.s.flags & NEO_MPC_SCAN_MARK)) hipLaunchKernelGGL(k_world_scan_rays<true>, rays, dim3(kScanRayThreads), 0, st, a);
+  if (a.clear && a.s.count > 0) hipLaunchKernelGGL(k_world_scan_footprints, dim3(a.s.count), dim3(kLanes), 0, st, a);
+  hipLaunchKernelGGL(k_world_scan_compose, dim3((a.wsx + kInflateTile - 1) / kInflateTile, (a.wsy + kInflateTile - 1) / kInflateTile),
+                     dim3(kLanes * kInflateWaves), 0, st, a);
 }
 void launch_ingest(const IngestArgs& a, const LaunchTuning& tuning, void* stream) {
   hipLaunchKernelGGL(k_ingest, padded_map_grid(a.rows, a.pitch, kIngestUnroll, a.maps > 0 ? a.maps : 1), dim3(256), 0,

@@ -73,36 +73,27 @@ __device__ __forceinline__ uint32_t scan_cell_distance(double d, double res) {
   return (uint32_t)fmin(fmax(0.0, ceil(d / res)), 2147483647.0);
 }
 
-// K10b, steps 2 and 3 of the contract: one launch per phase (kMark false: clear, then true: mark -- the launch boundary is
-// what puts every mark behind every clear), grid (point chunks, window), a lane per ray.  No atomics: within a launch every
-// writer of a byte writes the same value -- 0 in the clearing launch, 254 in the marking one -- so whichever of two colliding
-// byte stores lands last the byte is the same; byte stores merge into their line by byte mask and touch no neighbour.
-// With several sources (K11) a window's points are those of all its sources, point p seen from source p / points_per_source,
-// and the argument still holds: one clearing launch over all sources, then one marking launch over all sources, puts every
-// mark of every source behind every clear of every source with no new synchronisation.
-// Nothing is read back from the layer.  The trip counts of the walk diverge between lanes; nothing ballots inside it.
+// One ray of steps 2 and 3 of the contract: point p of robot k of the batch `a`, on a grid of sx x sy cells of `res` at (ox, oy)
+// whose cell (0, 0) is at `layer`, rows lp bytes apart (kMark false: the clearing walk; true: the mark).  The one copy of the
+// clips, raytraceLine and the mark test: K10b runs it on a window's geometry and layer, K12a (world_scan_layer.h) on the world's.
 template <bool kMark>
-__global__ __launch_bounds__(kScanRayThreads) void k_scan_rays(const ScanArgs a) {
+__device__ __forceinline__ void scan_ray(const ScanArgs& a, uint32_t k, uint32_t p, double ox, double oy, double res, int sx,
+                                         int sy, int lp, uint8_t* layer) {
 #pragma clang fp contract(off)
-  const uint32_t k = blockIdx.y;
-  const uint32_t p = blockIdx.x * kScanRayThreads + threadIdx.x;
   uint32_t np = a.max_points;
   if (a.point_counts) { const uint32_t c = a.point_counts[k]; np = c < np ? c : np; }
   if (p >= np) return;
-  const int sx = a.size_x, sy = a.size_y, lp = a.layer_pitch;
-  const double res = a.res, ox = a.origins[2 * (size_t)k], oy = a.origins[2 * (size_t)k + 1];
   const size_t src = (size_t)k * a.sources + p / a.points_per_source;   // (K10: sources 1, points_per_source max_points: k)
   const double sx0 = a.sensor_origins[2 * src], sy0 = a.sensor_origins[2 * src + 1];
   const double* pt = a.points + ((size_t)k * a.max_points + p) * 2;
   double wx = pt[0], wy = pt[1];
   if (!isfinite(wx) || !isfinite(wy)) return;
-  uint8_t* layer = a.work + (int64_t)k * a.layer_stride;
   if (kMark) {
     const double s = (wx - sx0) * (wx - sx0) + (wy - sy0) * (wy - sy0);
     if (s >= a.obstacle_max * a.obstacle_max || s < a.obstacle_min * a.obstacle_min) return;
     int mx, my;
     if (!scan_world_to_map(wx, wy, ox, oy, res, sx, sy, mx, my)) return;
-    layer[(int64_t)my * lp + mx] = 254;   // 0 <= mx < size_x, 0 <= my < size_y by worldToMap
+    layer[(int64_t)my * lp + mx] = 254;   // 0 <= mx < sx, 0 <= my < sy by worldToMap
     return;
   }
   int x0, y0, x1, y1;
@@ -133,7 +124,7 @@ __global__ __launch_bounds__(kScanRayThreads) void k_scan_rays(const ScanArgs a)
   const uint32_t reach = (uint32_t)(scale * (double)A), n = M < reach ? M : reach;
   int x = u0, y = v0, e = (int)(A / 2);
   for (uint32_t t = 0; t < n; ++t) {
-    // (the contract's walk stays inside the grid; the comparison keeps a store inside this window's layer whatever comes)
+    // (the contract's walk stays inside the grid; the comparison keeps a store inside the layer whatever comes)
     if ((unsigned)x < (unsigned)sx && (unsigned)y < (unsigned)sy) layer[(int64_t)y * lp + x] = 0;
     if (x_major) x += step_x; else y += step_y;
     e += (int)B;
@@ -143,6 +134,21 @@ __global__ __launch_bounds__(kScanRayThreads) void k_scan_rays(const ScanArgs a)
     }
   }
   if ((unsigned)x < (unsigned)sx && (unsigned)y < (unsigned)sy) layer[(int64_t)y * lp + x] = 0;
+}
+
+// K10b, steps 2 and 3 of the contract: one launch per phase (kMark false: clear, then true: mark -- the launch boundary is
+// what puts every mark behind every clear), grid (point chunks, window), a lane per ray.  No atomics: within a launch every
+// writer of a byte writes the same value -- 0 in the clearing launch, 254 in the marking one -- so whichever of two colliding
+// byte stores lands last the byte is the same; byte stores merge into their line by byte mask and touch no neighbour.
+// With several sources (K11) a window's points are those of all its sources, point p seen from source p / points_per_source,
+// and the argument still holds: one clearing launch over all sources, then one marking launch over all sources, puts every
+// mark of every source behind every clear of every source with no new synchronisation.
+// Nothing is read back from the layer.  The trip counts of the walk diverge between lanes; nothing ballots inside it.
+template <bool kMark>
+__global__ __launch_bounds__(kScanRayThreads) void k_scan_rays(const ScanArgs a) {
+  const uint32_t k = blockIdx.y;
+  scan_ray<kMark>(a, k, blockIdx.x * kScanRayThreads + threadIdx.x, a.origins[2 * (size_t)k], a.origins[2 * (size_t)k + 1], a.res,
+                  a.size_x, a.size_y, a.layer_pitch, a.work + (int64_t)k * a.layer_stride);
 }
 
 // K10c, steps 4 and 5 of the contract, K9's scheme per window: grid (tile column, tile row, window), one workgroup of four

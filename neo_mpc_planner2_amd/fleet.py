@@ -14,7 +14,7 @@ from . import abi
 
 
 def closed_loop(solver, batch, ticks, hz=30.0, before_tick=None, after_tick=None, balance_every=0, footprint=None,
-                rolling=None, stamp=None, scan=None, laser=None):
+                rolling=None, stamp=None, scan=None, laser=None, world_scan=None):
     """Run `ticks` control ticks of `batch` (a solver.DeviceBatch) through `solver` (a BatchSolver with its costmap
     set).  Returns per-tick lists: kernel_ms (HIP events around the K1 launch), mean_iterations, max_iterations,
     stopped_fraction.  `before_tick(t, pos)` runs before tick t's launch (e.g. re-centre a costmap pool),
@@ -40,10 +40,14 @@ def closed_loop(solver, batch, ticks, hz=30.0, before_tick=None, after_tick=None
     returns the keyword arguments of BatchSolver.update_scan_layer_from_ranges for tick t -- the inflation parameters, `ranges`
     as a CUDA float32 tensor, `poses` (the loop's own, handed through, or the caller's) and `scanners` -- and the projection
     and the update over all scanners (K11, neo_mpc_update_scan_layer_from_ranges_device) run where `scan` runs.  None: the
-    loop is unchanged."""
+    loop is unchanged.  `world_scan` = a callable, with `rolling`; it excludes nothing: `world_scan(t, poses)` returns the
+    keyword arguments of BatchSolver.update_world_scan_layer -- or, when `ranges` is among them, of
+    update_world_scan_layer_from_ranges -- and the update of the fleet's shared layer on the world map (K12) runs BEFORE the
+    roll, so every window is cut from what the whole fleet saw.  None: the loop is unchanged."""
     assert stamp is None or (rolling is not None and footprint is not None), "stamp needs rolling and footprint"
     assert scan is None or rolling is not None, "scan needs rolling"
     assert laser is None or (rolling is not None and scan is None), "laser needs rolling and excludes scan"
+    assert world_scan is None or rolling is not None, "world_scan needs rolling"
     import torch
     b = batch
     P = b.problems.view(torch.float64).reshape(b.count, -1)          # the 32 doubles of each request
@@ -78,6 +82,9 @@ def closed_loop(solver, batch, ticks, hz=30.0, before_tick=None, after_tick=None
             before_tick(t, pos)
         if rolling is not None or footprint is not None:
             poses = torch.cat([pos, yaw[:, None]], 1).contiguous()   # one array serves the roll and the gate
+        if world_scan is not None:
+            kw = world_scan(t, poses)
+            (solver.update_world_scan_layer_from_ranges if "ranges" in kw else solver.update_world_scan_layer)(**kw)
         if rolling is not None:
             solver.roll_costmap_pool(rolling[0], rolling[1], rolling[2], rolling[3], poses=poses)
         if scan is not None:

@@ -314,8 +314,20 @@ class BatchSolver:
         CUDA tensors (float64, `point_counts` int32 holding the uint32 counts) through the device call on torch's current
         stream.  Without points `on_device` picks the variant (a torch device, or True for this solver's)."""
         assert self._map_shape is not None, "no costmap has been set through this BatchSolver"
+        b, stream, _ = self._scan_batch(self._map_shape[0], inscribed_radius, inflation_radius, cost_scaling_factor, points,
+                                        sensor_origins, point_counts, flags, obstacle_max_range, obstacle_min_range,
+                                        raytrace_max_range, raytrace_min_range, unknown_value, on_device)
+        if stream is None:
+            _lib.check(self._lib.neo_mpc_update_scan_layer(self._handle, C.byref(b)))
+        else:
+            _lib.check(self._lib.neo_mpc_update_scan_layer_device(self._handle, C.byref(b), C.c_void_p(stream)))
+
+    def _scan_batch(self, count, inscribed_radius, inflation_radius, cost_scaling_factor, points, sensor_origins, point_counts,
+                    flags, obstacle_max_range, obstacle_min_range, raytrace_max_range, raytrace_min_range, unknown_value,
+                    on_device):
+        """-> (neo_mpc_scan_batch over `count` robots, the stream or None for the host variant, what must stay alive)."""
         b = abi.NeoMpcScanBatch()
-        b.count = self._map_shape[0]
+        b.count = int(count)
         b.obstacle_max_range, b.obstacle_min_range = float(obstacle_max_range), float(obstacle_min_range)
         b.raytrace_max_range, b.raytrace_min_range = float(raytrace_max_range), float(raytrace_min_range)
         b.inscribed_radius, b.inflation_radius = float(inscribed_radius), float(inflation_radius)
@@ -340,20 +352,18 @@ class BatchSolver:
                     point_counts = np.ascontiguousarray(point_counts, dtype=np.uint32)
                     assert point_counts.shape == (b.count,)
                     b.point_counts = point_counts.ctypes.data
-            _lib.check(self._lib.neo_mpc_update_scan_layer(self._handle, C.byref(b)))
-        else:
-            import torch
-            if points is not None:
-                for a in (points, sensor_origins, point_counts):
-                    assert a is None or (a.is_cuda and a.is_contiguous())
-                assert points.dtype == torch.float64 and points.dim() == 3 and points.shape[0] == b.count and points.shape[2] == 2
-                assert sensor_origins.dtype == torch.float64 and tuple(sensor_origins.shape) == (b.count, 2)
-                b.points, b.sensor_origins, b.max_points = points.data_ptr(), sensor_origins.data_ptr(), points.shape[1]
-                if point_counts is not None:
-                    assert point_counts.dtype == torch.int32 and tuple(point_counts.shape) == (b.count,)
-                    b.point_counts = point_counts.data_ptr()
-            stream = torch.cuda.current_stream(device).cuda_stream
-            _lib.check(self._lib.neo_mpc_update_scan_layer_device(self._handle, C.byref(b), C.c_void_p(stream)))
+            return b, None, (points, sensor_origins, point_counts)
+        import torch
+        if points is not None:
+            for a in (points, sensor_origins, point_counts):
+                assert a is None or (a.is_cuda and a.is_contiguous())
+            assert points.dtype == torch.float64 and points.dim() == 3 and points.shape[0] == b.count and points.shape[2] == 2
+            assert sensor_origins.dtype == torch.float64 and tuple(sensor_origins.shape) == (b.count, 2)
+            b.points, b.sensor_origins, b.max_points = points.data_ptr(), sensor_origins.data_ptr(), points.shape[1]
+            if point_counts is not None:
+                assert point_counts.dtype == torch.int32 and tuple(point_counts.shape) == (b.count,)
+                b.point_counts = point_counts.data_ptr()
+        return b, torch.cuda.current_stream(device).cuda_stream, (points, sensor_origins, point_counts)
 
     # -- the scan step fed from LaserScan ranges -----------------------------------------
     def _laser_batch(self, ranges, poses, scanners, points_out, origins_out, need_out):
@@ -446,6 +456,112 @@ class BatchSolver:
     def reset_scan_layer(self):
         """The next `update_scan_layer` starts from a layer of `unknown_value`."""
         _lib.check(self._lib.neo_mpc_reset_scan_layer(self._handle))
+
+    # -- the fleet's shared obstacle layer on the world map (in front of the roll) ---------
+    @staticmethod
+    def _fleet_clear(clear, count, on_host):
+        """`clear` = None, or a mapping with `padding` (m) and either `polygons` [count, points, 2] or `footprint` ([points, 2]
+        or [count, points, 2]) with `poses` [count, 3] or `problems` -> (neo_mpc_fleet_clear or None, what must stay alive)."""
+        if clear is None:
+            return None, None
+        assert set(clear) <= {"padding", "polygons", "footprint", "poses", "problems"}, sorted(clear)
+        c = abi.NeoMpcFleetClear()
+        c.count, c.padding = int(count), float(clear.get("padding", 0.0))
+        keep = []
+
+        def ptr(a, dim, records=False):
+            if on_host:
+                a = a if records else np.ascontiguousarray(a, dtype=np.float64)
+                assert a.flags.c_contiguous and (records or a.ndim in dim)
+                keep.append(a)
+                return a, a.ctypes.data
+            import torch
+            assert a.is_cuda and a.is_contiguous() and (records or (a.dtype == torch.float64 and a.dim() in dim))
+            keep.append(a)
+            return a, a.data_ptr()
+
+        if clear.get("polygons") is not None:
+            polygons, c.polygons = ptr(clear["polygons"], (3,))
+            assert polygons.shape[0] == count and polygons.shape[2] == 2
+            c.footprint_points = polygons.shape[1]
+        else:
+            footprint, c.footprint = ptr(clear["footprint"], (2, 3))
+            assert footprint.shape[-1] == 2 and (len(footprint.shape) == 2 or footprint.shape[0] == count)
+            c.footprint_points = footprint.shape[-2]
+            c.per_robot_footprints = 1 if len(footprint.shape) == 3 else 0
+            if clear.get("poses") is not None:
+                poses, c.poses = ptr(clear["poses"], (2,))
+                assert tuple(poses.shape) == (count, 3)
+            elif clear.get("problems") is not None:
+                problems, c.problems = ptr(clear["problems"], (), records=True)
+                assert problems.shape[0] == count
+        return c, keep
+
+    def update_world_scan_layer(self, inscribed_radius, inflation_radius, cost_scaling_factor, points=None, sensor_origins=None,
+                                point_counts=None, flags=None, clear=None, count=None, obstacle_max_range=2.5,
+                                obstacle_min_range=0.0, raytrace_max_range=3.0, raytrace_min_range=0.0, unknown_value=255,
+                                on_device=None):
+        """Updates the fleet's shared obstacle layer on the world map from one observation per robot and composes the map
+        the next `roll_costmap_pool` cuts its windows from (K12; the contract: neo_mpc_fleet_clear in include/neo_mpc.h):
+        world scan -> roll -> stamp -> gate -> carrots -> solve.  Points, flags, ranges and `on_device` as
+        `update_scan_layer`; the number of robots is that of `points`, else of `clear`'s arrays, else `count` (default 1),
+        and is not tied to the pool's.  `clear` = a mapping with `padding` (metres) and either `polygons` or `footprint`
+        with `poses` or `problems`, as `stamp_fleet` takes them: the robots' own outlines are set free in the layer."""
+        if points is not None:
+            count = points.shape[0]
+        elif clear is not None:
+            count = next(clear[k].shape[0] for k in ("polygons", "poses", "problems") if clear.get(k) is not None)
+        elif count is None:
+            count = 1
+        b, stream, keep = self._scan_batch(count, inscribed_radius, inflation_radius, cost_scaling_factor, points,
+                                           sensor_origins, point_counts, flags, obstacle_max_range, obstacle_min_range,
+                                           raytrace_max_range, raytrace_min_range, unknown_value, on_device)
+        c, keep_c = self._fleet_clear(clear, count, stream is None)
+        cp = C.byref(c) if c is not None else None
+        if stream is None:
+            _lib.check(self._lib.neo_mpc_update_world_scan_layer(self._handle, C.byref(b), cp))
+        else:
+            _lib.check(self._lib.neo_mpc_update_world_scan_layer_device(self._handle, C.byref(b), cp, C.c_void_p(stream)))
+
+    def update_world_scan_layer_from_ranges(self, inscribed_radius, inflation_radius, cost_scaling_factor, ranges, poses,
+                                            scanners, flags=None, clear=None, points_out=None, origins_out=None,
+                                            obstacle_max_range=2.5, obstacle_min_range=0.0, raytrace_max_range=3.0,
+                                            raytrace_min_range=0.0, unknown_value=255):
+        """Projects the ranges as `project_laser` does and updates the fleet's shared layer on the world map from all
+        scanners of all robots (K11 and K12).  Arguments as `update_scan_layer_from_ranges`; `clear` as
+        `update_world_scan_layer`."""
+        b, keep, _, _, stream = self._laser_batch(ranges, poses, scanners, points_out, origins_out, False)
+        b.scan_flags = int(abi.SCAN_CLEAR | abi.SCAN_MARK if flags is None else flags)
+        b.unknown_value = int(unknown_value)
+        b.obstacle_max_range, b.obstacle_min_range = float(obstacle_max_range), float(obstacle_min_range)
+        b.raytrace_max_range, b.raytrace_min_range = float(raytrace_max_range), float(raytrace_min_range)
+        b.inscribed_radius, b.inflation_radius = float(inscribed_radius), float(inflation_radius)
+        b.cost_scaling_factor = float(cost_scaling_factor)
+        c, keep_c = self._fleet_clear(clear, b.count, stream is None)
+        cp = C.byref(c) if c is not None else None
+        if stream is None:
+            _lib.check(self._lib.neo_mpc_update_world_scan_layer_from_ranges(self._handle, C.byref(b), cp))
+        else:
+            _lib.check(self._lib.neo_mpc_update_world_scan_layer_from_ranges_device(self._handle, C.byref(b), cp,
+                                                                                   C.c_void_p(stream)))
+
+    def get_world_scan_layer(self):
+        """(layer, live), uint8 [size_y, size_x] each on the world map's geometry: the fleet's shared layer, values in
+        {255, 0, 254}, and the world map with the layer merged in and inflated, as the last `update_world_scan_layer` left
+        them.  Synchronous; waits for the update in flight."""
+        _lib.check(self._lib.neo_mpc_get_world_scan_layer(self._handle, None, None))
+        sx, sy = C.c_uint32(), C.c_uint32()
+        _lib.check(self._lib.neo_mpc_get_world_map(self._handle, None, C.byref(sx), C.byref(sy), None, None, None))
+        layer = np.zeros((sy.value, sx.value), dtype=np.uint8)
+        live = np.zeros_like(layer)
+        _lib.check(self._lib.neo_mpc_get_world_scan_layer(self._handle, C.c_void_p(layer.ctypes.data),
+                                                         C.c_void_p(live.ctypes.data)))
+        return layer, live
+
+    def reset_world_scan_layer(self):
+        """The next `update_world_scan_layer` starts from a layer of `unknown_value`; until then the roll reads the world
+        map."""
+        _lib.check(self._lib.neo_mpc_reset_world_scan_layer(self._handle))
 
     HOST_PATHS = {"auto": 0, "staged": 1, "zerocopy": 2, "zerocopy_out": 3}
 
