@@ -47,6 +47,8 @@ extern "C" {
  * The laser projection (neo_mpc_scanner, neo_mpc_laser_batch, neo_mpc_laser_beam_table, neo_mpc_project_laser[_device],
  * neo_mpc_update_scan_layer_from_ranges[_device], NEO_MPC_MAX_SCAN_SOURCES, NEO_MPC_LASER_INF_IS_VALID) added two records,
  * five entry points and two constants in the same way: still ABI 2, behaviour 6.
+ * The speckle filter of the world scan layer (neo_mpc_set_world_scan_denoise, neo_mpc_get_world_scan_denoised,
+ * NEO_MPC_MAX_DENOISE_GROUP) added two entry points and a constant and no record: still ABI 2, behaviour 6.
  *
  * Behaviour history (iterates and iteration counts differ between versions, results stay inside the parity protocol of
  * DESIGN.md section 1; neo_mpc_behaviour_version() returns the number of the build that answers):
@@ -546,6 +548,7 @@ typedef struct neo_mpc_scan_batch {
 /* ---- the scan step fed from LaserScan ranges, several scanners per robot (K11) ------------------------- */
 
 #define NEO_MPC_MAX_SCAN_SOURCES 4u
+#define NEO_MPC_MAX_DENOISE_GROUP 16u /* largest minimal_group_size of neo_mpc_set_world_scan_denoise */
 #define NEO_MPC_LASER_INF_IS_VALID 1u   /* neo_mpc_scanner.flags: a range of +inf is a beam that met nothing (nav2's inf_is_valid) */
 
 /* A fleet server receives sensor_msgs/LaserScan messages, not points: float32 ranges, an angle geometry shared by every
@@ -661,6 +664,29 @@ typedef struct neo_mpc_laser_batch {
  *      inflation back.
  * flags == 0 runs steps 3 (if given) and 4 only.  An update repeated with the same inputs changes neither layer nor live.
  * Out of scope: recomposing only the tiles a scan touched; decaying old marks (observation_persistence); a z coordinate.
+ *
+ * Step 3b, Denoise (K13; optional, off by default: neo_mpc_set_world_scan_denoise).  With one layer for the fleet every
+ * robot's false returns land on the same lattice, and each is a 254 seed that step 4 inflates into `live` until some ray
+ * happens to clear it.  Modelled on nav2_costmap_2d::DenoiseLayer, which sits behind the obstacle layer and in front of
+ * inflation -- the contract by transcription, not pinned against it; integers only.  It runs after every clear, mark and
+ * footprint clearing of the update.  With G = minimal_group_size:
+ *   The world cell (i, l), 0 <= i < WSX, 0 <= l < WSY, is OCCUPIED when layer[l][i] == 254 or world[l][i] == 254 -- `layer`
+ *   as step 3 left it, `world` the static world map the handle holds, the array step 4 reads.  Cells outside the world do not
+ *   exist.  Two occupied cells are neighbours when they differ by one in exactly one coordinate (connectivity 4), or by at
+ *   most one in each coordinate and are not the same cell (connectivity 8).  A group is a connected component of occupied
+ *   cells.
+ *   D = layer, except that a cell with layer == 254, world != 254 and a group of fewer than G cells has D = 0: the return
+ *   was real enough to count as an observation of that cell, so it is free, as nav2 sets it.
+ *   Step 4 then reads D wherever it reads the layer, in updateWithMax and as the inflation seeds.
+ *   `layer` itself is NOT changed: a lone mark stays in the layer, and when a later scan marks the cell next to it, both
+ *   appear.
+ * So a mark that touches a wall of the world map belongs to the wall's group and is kept, and two groups of fewer than G
+ * cells each are both dropped however close they lie, unless they are connected.  Stated differences from nav2: the static
+ * map is never altered (nav2 filters the master grid and would drop specks of the static map too), and `live` does not get
+ * the world's own inflation back under a dropped mark, as in step 4.  With the filter off an update is bit for bit, launch
+ * for launch and buffer for buffer what it is without this step.  The device decides a cell's group size without labelling:
+ * the occupied cells within G - 1 neighbour steps of it number at least G exactly when its group does, and they lie within
+ * G - 1 cells of it.
  *
  * The clear record.  Pointers are host pointers for the synchronous calls and device pointers for the _device variants.
  * 64 bytes. */
@@ -1060,6 +1086,20 @@ int neo_mpc_get_world_scan_layer(neo_mpc_handle* handle, uint8_t* layer_out, uin
 /* The next update starts from a layer of unknown_value, and until then the roll reads the world map.  Touches no device
  * memory.  NEO_MPC_ERR_INVALID_ARGUMENT for a null handle. */
 int neo_mpc_reset_world_scan_layer(neo_mpc_handle* handle);
+/* The speckle filter of the shared layer (step 3b of the contract above; K13).  minimal_group_size 0 or 1: off; 2 ..
+ * NEO_MPC_MAX_DENOISE_GROUP: on.  connectivity: 4 or 8, checked when off as well.  Anything else, and a null handle, is
+ * NEO_MPC_ERR_INVALID_ARGUMENT and leaves the previous setting in force.  The call needs no world map, launches nothing and
+ * touches neither layer nor live nor their validity: the setting takes effect with the next update, and an update with
+ * flags == 0 is enough to recompose.  It is handle configuration: it survives neo_mpc_reset_world_scan_layer and
+ * neo_mpc_set_world_map, and a handle on which it was never called behaves as before.  Memory: one more world map's worth
+ * while the filter is on, allocated by the first update behind switching it on and by an update on a larger world -- that
+ * update may synchronise; a later one with the same geometry and setting allocates nothing, so the tick stays capturable
+ * after one eager call.  A captured HIP graph holds the setting it was captured with. */
+int neo_mpc_set_world_scan_denoise(neo_mpc_handle* handle, uint32_t minimal_group_size, uint32_t connectivity);
+/* Reads back D of the last update, cells_out[WSY][WSX]: the layer as step 4 read it -- the layer's own bytes when the filter
+ * was off at that update.  Host pointer, synchronous; waits for the update in flight as neo_mpc_get_world_scan_layer does,
+ * and returns NEO_MPC_ERR_NO_COSTMAP where it does.  A null cells_out only asks whether there is one. */
+int neo_mpc_get_world_scan_denoised(neo_mpc_handle* handle, uint8_t* cells_out);
 
 /* ---- multi-GPU fleets: the one exchange step ------------------------------------------------
  * Instances of one tick shard embarrassingly over the GPUs of a node (one handle per GPU, costmap and parameters

@@ -308,9 +308,14 @@ struct ScanLayers {
 // map with the layer merged in and inflated -- what the roll reads while `live_valid` --, both WSX bytes a row; a cost table of
 // their own at the world's resolution; and what the layer was made for -- an update that meets another geometry or
 // unknown_value resets it.  Ordered by the world map's own event (WorldMap): an update is a rewrite of what the roll reads.
+// K13, the speckle filter: its setting -- configuration, which outlives resets and world maps --, D, the layer as the
+// composition of the last update read it, allocated only while the filter is on, and whether that update filtered.
 struct WorldScanLayer {
   InflationTable table;
   DeviceBuffer layer, live;
+  DeviceBuffer denoised;
+  uint32_t group = 0, connectivity = 8;   // neo_mpc_set_world_scan_denoise: G (0: off) and 4 or 8
+  bool filtered = false;     // the last update wrote D
   bool valid = false;        // the layer holds what the updates since the last reset put there
   bool live_valid = false;   // `live` is the current world map with the layer in it
   int32_t size_x = 0, size_y = 0;
@@ -330,6 +335,8 @@ struct WorldScanLayer {
     if (int rc = layer.reserve(bytes())) return rc;
     return live.reserve(bytes());
   }
+  // D: a no-op from the second update with this geometry and setting on
+  int reserve_denoised() { return group >= 2 ? denoised.reserve(bytes()) : NEO_MPC_OK; }
 };
 
 // K11.  The beam table of one scanner (the contract: neo_mpc_laser_batch, step 4), with libm
@@ -2021,6 +2028,7 @@ static int world_scan(neo_mpc_handle* h, const neo_mpc_scan_batch& d, const neo_
   if (rc) return rc;
   const bool same = l.matches(w, d.unknown_value);
   if (!same && (rc = l.resize(w, d.unknown_value))) return rc;
+  if ((rc = l.reserve_denoised())) return rc;
   hipStream_t st = (hipStream_t)stream;
   // behind the last roll, which reads `live` or the world map, and the previous copy, inflation or update
   if ((rc = w.begin_write(h->fence, on_device, st))) return rc;
@@ -2044,11 +2052,13 @@ static int world_scan(neo_mpc_handle* h, const neo_mpc_scan_batch& d, const neo_
   a.wres = w.resolution; a.wox = w.origin_x; a.woy = w.origin_y;
   a.wsx = w.size_x; a.wsy = w.size_y;
   a.reset = same ? 0u : 1u;
+  if (l.group >= 2) { a.denoised = l.denoised.as<uint8_t>(); a.group = l.group; a.connectivity = l.connectivity; }
   if (laser) launch_laser_project(*laser, stream);
   launch_world_scan(a, stream);
   HIP_TRY(hipGetLastError());
   if ((rc = w.end_write(st))) return rc;   // a roll behind it, on whatever stream, cuts its windows from `live`
   l.valid = true; l.live_valid = true;
+  l.filtered = a.group >= 2;
   return NEO_MPC_OK;
 }
 
@@ -2158,6 +2168,29 @@ int neo_mpc_get_world_scan_layer(neo_mpc_handle* h, uint8_t* layer_out, uint8_t*
   if (int rc = h->world.wait_writer_host()) return rc;   // the update in flight
   if (layer_out) HIP_TRY(hipMemcpy(layer_out, l.layer.ptr, l.bytes(), hipMemcpyDeviceToHost));
   if (live_out) HIP_TRY(hipMemcpy(live_out, l.live.ptr, l.bytes(), hipMemcpyDeviceToHost));
+  return NEO_MPC_OK;
+}
+
+int neo_mpc_set_world_scan_denoise(neo_mpc_handle* h, uint32_t minimal_group_size, uint32_t connectivity) {
+  if (!h) return fail(NEO_MPC_ERR_INVALID_ARGUMENT, "null handle");
+  if (minimal_group_size > NEO_MPC_MAX_DENOISE_GROUP)
+    return fail(NEO_MPC_ERR_INVALID_ARGUMENT, "minimal_group_size %u is more than NEO_MPC_MAX_DENOISE_GROUP %u", minimal_group_size,
+                NEO_MPC_MAX_DENOISE_GROUP);
+  if (connectivity != 4 && connectivity != 8) return fail(NEO_MPC_ERR_INVALID_ARGUMENT, "connectivity %u is neither 4 nor 8", connectivity);
+  h->world_scan.group = minimal_group_size >= 2 ? minimal_group_size : 0u;   // (the next update allocates D and filters)
+  h->world_scan.connectivity = connectivity;
+  return NEO_MPC_OK;
+}
+
+int neo_mpc_get_world_scan_denoised(neo_mpc_handle* h, uint8_t* cells_out) {
+  if (!h) return fail(NEO_MPC_ERR_INVALID_ARGUMENT, "null handle");
+  WorldScanLayer& l = h->world_scan;
+  if (!l.valid)
+    return fail(NEO_MPC_ERR_NO_COSTMAP, "no world scan layer: neo_mpc_update_world_scan_layer has not been called since the last reset");
+  if (!cells_out) return NEO_MPC_OK;
+  HIP_TRY(hipSetDevice(h->device));
+  if (int rc = h->world.wait_writer_host()) return rc;   // the update in flight
+  HIP_TRY(hipMemcpy(cells_out, l.filtered ? l.denoised.ptr : l.layer.ptr, l.bytes(), hipMemcpyDeviceToHost));
   return NEO_MPC_OK;
 }
 

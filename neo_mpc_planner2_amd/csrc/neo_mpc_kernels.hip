@@ -22,6 +22,7 @@
 //   K10 k_scan_shift, k_scan_rays, k_scan_apply  scan_layer.h: the obstacle layer of every window, fed from sensor points.
 //   K11 k_laser_project  laser_projection.h: LaserScan ranges of every scanner of every robot -> those points, HBM-streaming.
 //   K12 k_world_scan_rays, k_world_scan_footprints, k_world_scan_compose  world_scan_layer.h: one obstacle layer for the fleet on the world map.
+//   K13 k_world_scan_denoise  world_scan_denoise.h: that layer's speckle filter, groups of fewer than G occupied cells, in front of K12's composition.
 #include "k1_solve.h"
 #include "costmap_ingest.h"
 #include "footprint_gate.h"
@@ -31,6 +32,7 @@
 #include "scan_layer.h"
 #include "laser_projection.h"
 #include "world_scan_layer.h"
+#include "world_scan_denoise.h"
 
 namespace neo_mpc {
 namespace {
@@ -378,7 +380,9 @@ void launch_laser_project(const LaserArgs& a, void* stream) {
   hipLaunchKernelGGL(k_laser_project, dim3(a.count, a.sources), dim3(kLaserThreads), 0, (hipStream_t)stream, a);
 }
 // K12: the reset (a fill), every clear of every robot, every mark, the footprints, then the composition -- each behind the one
-// before on one stream: every mark lies behind every clear, the footprints behind every mark, the seeds are final when read
+// before on one stream: every mark lies behind every clear, the footprints behind every mark, the seeds are final when read.
+// With the speckle filter on (K13), one more launch in front of the composition, which then reads D where it reads the layer;
+// the window compiled in is the smallest of 3, 7, 15 and 31 rows that holds G - 1 steps either way.
 void launch_world_scan(const WorldScanArgs& a, void* stream) {
   if (a.wsx <= 0 || a.wsy <= 0) return;
   hipStream_t st = (hipStream_t)stream;
@@ -388,8 +392,15 @@ void launch_world_scan(const WorldScanArgs& a, void* stream) {
   if (any && (a.s.flags & NEO_MPC_SCAN_CLEAR)) hipLaunchKernelGGL(k_world_scan_rays<false>, rays, dim3(kScanRayThreads), 0, st, a);
   if (any && (a.s.flags & NEO_MPC_SCAN_MARK)) hipLaunchKernelGGL(k_world_scan_rays<true>, rays, dim3(kScanRayThreads), 0, st, a);
   if (a.clear && a.s.count > 0) hipLaunchKernelGGL(k_world_scan_footprints, dim3(a.s.count), dim3(kLanes), 0, st, a);
-  hipLaunchKernelGGL(k_world_scan_compose, dim3((a.wsx + kInflateTile - 1) / kInflateTile, (a.wsy + kInflateTile - 1) / kInflateTile),
-                     dim3(kLanes * kInflateWaves), 0, st, a);
+  const dim3 tiles((a.wsx + kInflateTile - 1) / kInflateTile, (a.wsy + kInflateTile - 1) / kInflateTile), tile(kLanes * kInflateWaves);
+  if (a.group < 2u) { hipLaunchKernelGGL(k_world_scan_compose, tiles, tile, 0, st, a); return; }
+  if (a.group <= 2u) hipLaunchKernelGGL(k_world_scan_denoise<1>, tiles, tile, 0, st, a);
+  else if (a.group <= 4u) hipLaunchKernelGGL(k_world_scan_denoise<3>, tiles, tile, 0, st, a);
+  else if (a.group <= 8u) hipLaunchKernelGGL(k_world_scan_denoise<7>, tiles, tile, 0, st, a);
+  else hipLaunchKernelGGL(k_world_scan_denoise<15>, tiles, tile, 0, st, a);
+  WorldScanArgs filtered = a;
+  filtered.layer = a.denoised;
+  hipLaunchKernelGGL(k_world_scan_compose, tiles, tile, 0, st, filtered);
 }
 void launch_ingest(const IngestArgs& a, const LaunchTuning& tuning, void* stream) {
   hipLaunchKernelGGL(k_ingest, padded_map_grid(a.rows, a.pitch, kIngestUnroll, a.maps > 0 ? a.maps : 1), dim3(256), 0,

@@ -563,6 +563,25 @@ class BatchSolver:
         map."""
         _lib.check(self._lib.neo_mpc_reset_world_scan_layer(self._handle))
 
+    def set_world_scan_denoise(self, minimal_group_size, connectivity=8):
+        """The speckle filter of the fleet's shared layer (K13; the contract: step 3b of neo_mpc_fleet_clear's text in
+        include/neo_mpc.h): from the next `update_world_scan_layer` on, a mark whose group of occupied cells -- marks and
+        the world map's own 254 cells, connected over 4 or 8 neighbours -- has fewer than `minimal_group_size` members
+        reaches `live` as a free cell; the layer keeps it.  0 or 1 switches the filter off; at most `abi.MAX_DENOISE_GROUP`.
+        Handle configuration: it survives `reset_world_scan_layer` and `set_world_map`."""
+        _lib.check(self._lib.neo_mpc_set_world_scan_denoise(self._handle, int(minimal_group_size), int(connectivity)))
+
+    def get_world_scan_denoised(self):
+        """uint8 [size_y, size_x] on the world map's geometry: the layer as the composition of the last
+        `update_world_scan_layer` read it -- the layer itself when the filter was off.  Synchronous; waits for the update in
+        flight."""
+        _lib.check(self._lib.neo_mpc_get_world_scan_denoised(self._handle, None))
+        sx, sy = C.c_uint32(), C.c_uint32()
+        _lib.check(self._lib.neo_mpc_get_world_map(self._handle, None, C.byref(sx), C.byref(sy), None, None, None))
+        cells = np.zeros((sy.value, sx.value), dtype=np.uint8)
+        _lib.check(self._lib.neo_mpc_get_world_scan_denoised(self._handle, C.c_void_p(cells.ctypes.data)))
+        return cells
+
     HOST_PATHS = {"auto": 0, "staged": 1, "zerocopy": 2, "zerocopy_out": 3}
 
     def set_host_path(self, mode):

@@ -9,8 +9,11 @@ marks: the composition then inflates nothing, so flags 0 is timed on both kinds 
 footprints.  Beside it, for windows of 200 x 200 cells: K7's roll behind an update, and -- unless --alone is given -- the
 per-window updates of K10 and K11 from tools/bench_scan_layer.py and tools/bench_laser_scan.py, run as child processes one
 after the other on the same card, their JSON taken over as it is.
+With --denoise G (may be given more than once), at the end and on the layer of a full scan again: K13's launch
+(k_world_scan_denoise, 8-connectivity) as the difference of flags-0 updates with the filter on and off, and how many marks it
+dropped.  Without the option the filter is never set and nothing of it runs.
 Every figure is median [min, max] of event pairs around back-to-back calls.
-usage: bench_world_scan_layer.py [--alone] [robots]"""
+usage: bench_world_scan_layer.py [--alone] [--denoise G]... [robots]"""
 import json
 import math
 import os
@@ -29,6 +32,8 @@ from neo_mpc_planner2_amd.solver import BatchSolver  # noqa: E402
 
 args = [a for a in sys.argv[1:] if a != "--alone"]
 alone = "--alone" in sys.argv[1:]
+denoise = [int(args[k + 1]) for k, a in enumerate(args) if a == "--denoise"]
+args = [a for k, a in enumerate(args) if a != "--denoise" and (k == 0 or args[k - 1] != "--denoise")]
 count = int(args[0]) if args else 4096
 dev = "cuda:0"
 RES, WORLD, SIZE, POINTS, SOURCES, BEAMS = synthetic.RESOLUTION, 2000, 200, 360, 2, 1081
@@ -137,6 +142,19 @@ with BatchSolver(params) as s:
     o_out = torch.zeros((count, SOURCES, 2), dtype=torch.float64, device=dev)
     out["project_ms"] = timed(lambda: s.project_laser(ranges, poses, SCANNERS, points_out=p_out, origins_out=o_out))
     torch.cuda.synchronize()
+    for group in denoise:
+        # the filter, on the layer of a full scan of points: flags 0 with it against flags 0 without, the same layer
+        update(abi.SCAN_CLEAR | abi.SCAN_MARK)
+        off = timed(lambda: update(0))
+        s.set_world_scan_denoise(group, 8)
+        update(0)                                   # (allocates D)
+        on = timed(lambda: update(0))
+        torch.cuda.synchronize()
+        layer, kept = s.get_world_scan_layer()[0], s.get_world_scan_denoised()
+        s.set_world_scan_denoise(0)
+        out["denoise_%d" % group] = {"minimal_group_size": group, "connectivity": 8, "marks": int((layer == 254).sum()),
+                                     "marks_dropped": int(((layer == 254) & (kept == 0)).sum()),
+                                     "compose_with_filter_ms": on, "denoise_ms": minus(on, off)}
 del world, points, ranges
 torch.cuda.empty_cache()
 if not alone:
