@@ -10,9 +10,12 @@
 // world map's copy, geometry and ordering); the refusals of inflation parameters and InflationTable (K8's, K9's and K10's cached
 // cost table); the handle; parameters and the term table; the shared checks; the device map (geometry, adoption, K3
 // ingest); the staging of host batches by range; then the entry points -- costmaps, the solve paths of K1, K2 and the hooks,
-// K4 carrots, K6 footprint gate, K7 rolling windows, K8 fleet stamp, K9 world inflation, K10 scan layer,
-// K11 laser projection, K12 world scan layer.  A new entry point checks with the
-// shared checks, stages with upload(), and launches through fence.read() or between fence.begin_write() and end_write().
+// K4 carrots, K6 footprint gate, K7 rolling windows; a fleet's outlines (K8's and K12's one view, shape check and host
+// staging), K8 fleet stamp, K9 world inflation; the scan layers -- their checks, K10's and K12 / K13's updates, the staging of an
+// observation and the entry points from points, then K11: the projection, the staging of ranges and the entry points from
+// ranges --; the layers read back, reset, K13's setting.  A new entry point checks with the shared checks, stages with upload()
+// -- an observation, ranges or outlines with the routine there is --, and launches through fence.read() or between
+// fence.begin_write() and end_write(); a new kind of update is a switch of update_from_points() and from_ranges(), not a copy.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -321,7 +324,9 @@ struct WorldScanLayer {
   int32_t size_x = 0, size_y = 0;
   double resolution = 0.0, origin_x = 0.0, origin_y = 0.0;
   uint32_t unknown = 0;
-  DeviceBuffer verts, poses, problems;   // (the host variants' staging of the clear record)
+  // (the host variants' staging of the clear record, stage_outlines().  Apart from the handle's verts / poses / problems, which
+  // K6 and K8 stage into: K12's host variant from ranges has the handle's `poses` in use for the laser poses)
+  DeviceBuffer verts, poses, problems;
   size_t bytes() const { return (size_t)size_x * (size_t)size_y; }
   bool matches(const WorldMap& w, uint32_t u) const {
     return valid && size_x == w.size_x && size_y == w.size_y && resolution == w.resolution && origin_x == w.origin_x &&
@@ -1624,40 +1629,89 @@ static int check_pool_batch(const neo_mpc_handle* h, size_t count, double ins, d
   return inflation_reach(h->map.resolution, ins, infl, csf, "", nullptr);
 }
 
-// The end of a synchronous variant of K8, K9 or K10: the null stream is waited for whether or not the enqueue failed (`rc`) -> the first error
+// The end of a synchronous variant of K8 to K12: the null stream is waited for whether or not the enqueue failed (`rc`) -> the first error
 static int finish_on_null_stream(int rc) {
   if (rc) { (void)hipStreamSynchronize(nullptr); return rc; }
   HIP_TRY(hipStreamSynchronize(nullptr));
   return NEO_MPC_OK;
 }
 
+// ---------------------------------------------------------------------------------------------- a fleet's outlines
+// K8, K12.  What neo_mpc_stamp_batch and neo_mpc_fleet_clear say of the robots' outlines, in one form: polygons in the global
+// frame, or a footprint with poses or problems (`padding`: the clear record's, K8 has none).
+struct Outlines {
+  size_t count;
+  const double* polygons;
+  const double* footprint;
+  uint32_t footprint_points, per_robot;
+  const double* poses;
+  const neo_mpc_problem* problems;
+  double padding;
+};
+static Outlines outlines_of(const neo_mpc_stamp_batch& b) {
+  return {b.count, b.polygons, b.footprint, b.footprint_points, b.per_robot_footprints, b.poses, b.problems, 0.0};
+}
+static Outlines outlines_of(const neo_mpc_fleet_clear& c) {
+  return {c.count, c.polygons, c.footprint, c.footprint_points, c.per_robot_footprints, c.poses, c.problems, c.padding};
+}
+
+// Their shape: check_footprint_shape(), and behind each record's own refusals in between, this one
+static int check_outline_pointers(const Outlines& o) {
+  if (o.count > 0 && !o.polygons && (!o.footprint || (!o.poses && !o.problems)))
+    return fail(NEO_MPC_ERR_INVALID_ARGUMENT, "neither polygons nor a footprint with poses or problems");
+  return NEO_MPC_OK;
+}
+
+// The host variants' staging, for o.count > 0: the values the device variants take as they come are looked at, then the
+// host arrays go into the three buffers and `o` gets the device pointers -- of what the kernels read alone
+static int stage_outlines(neo_mpc_handle* h, Outlines& o, DeviceBuffer& verts, DeviceBuffer& poses, DeviceBuffer& problems) {
+  const size_t n = o.count, np = o.footprint_points;
+  const double* v = o.polygons ? o.polygons : o.footprint;
+  const size_t polygons = o.polygons || o.per_robot ? n : 1;
+  if (int rc = check_vertices_finite(v, polygons, np, "vertex", "polygon")) return rc;
+  if (!o.polygons) if (int rc = check_poses_finite(o.poses, o.problems, n)) return rc;
+  HIP_TRY(hipSetDevice(h->device));
+  const Outlines host = o;
+  o.polygons = nullptr; o.footprint = nullptr; o.poses = nullptr; o.problems = nullptr;
+  const double* d_verts = verts.upload(v, polygons * np * 16);
+  if (!d_verts) return NEO_MPC_ERR_DEVICE;
+  if (host.polygons) o.polygons = d_verts;
+  else {
+    o.footprint = d_verts;
+    if (host.poses) o.poses = poses.upload(host.poses, n * 24);
+    else o.problems = problems.upload(host.problems, n * sizeof(neo_mpc_problem));
+    if (!o.poses && !o.problems) return NEO_MPC_ERR_DEVICE;
+  }
+  return NEO_MPC_OK;
+}
+
+// ---------------------------------------------------------------------------------------------- K8: the fleet stamp
 // What both stamp entry points check: the record's shape and the handle's pool, never a value behind a pointer.
 static int check_stamp_batch(const neo_mpc_handle* h, const neo_mpc_stamp_batch* b) {
   if (!h || !b) return fail(NEO_MPC_ERR_INVALID_ARGUMENT, "null argument");
   if (b->reserved != 0) return fail(NEO_MPC_ERR_INVALID_ARGUMENT, "neo_mpc_stamp_batch.reserved must be zero");
   if (int rc = check_footprint_shape(b->footprint_points, b->per_robot_footprints)) return rc;
   if (int rc = check_inflation_radii(b->inscribed_radius, b->inflation_radius, b->cost_scaling_factor)) return rc;
-  if (b->count > 0 && !b->polygons && (!b->footprint || (!b->poses && !b->problems)))
-    return fail(NEO_MPC_ERR_INVALID_ARGUMENT, "neither polygons nor a footprint with poses or problems");
+  if (int rc = check_outline_pointers(outlines_of(*b))) return rc;
   return check_pool_batch(h, b->count, b->inscribed_radius, b->inflation_radius, b->cost_scaling_factor);
 }
 
-// `d`: the record with device pointers.  Orders itself like roll(): it rewrites the device maps in place.
-static int stamp(neo_mpc_handle* h, const neo_mpc_stamp_batch& d, void* stream) {
-  const size_t n = d.count, np = d.footprint_points;
+// `o`: the outlines with device pointers, `b`: the radii.  Orders itself like roll(): it rewrites the device maps in place.
+static int stamp(neo_mpc_handle* h, const neo_mpc_stamp_batch& b, const Outlines& o, void* stream) {
+  const size_t n = o.count, np = o.footprint_points;
   // (every stamp ends a write of the fence)
-  int rc = h->stamp_table.build(h->map.resolution, d.inscribed_radius, d.inflation_radius, d.cost_scaling_factor, h->fence);
+  int rc = h->stamp_table.build(h->map.resolution, b.inscribed_radius, b.inflation_radius, b.cost_scaling_factor, h->fence);
   if (rc) return rc;
   // (no-ops from the second call with this count and footprint_points on)
   if ((rc = h->stamp_boxes.reserve(n * 32))) return rc;
-  if (!d.polygons && (rc = h->stamp_polys.reserve(n * np * 16))) return rc;
+  if (!o.polygons && (rc = h->stamp_polys.reserve(n * np * 16))) return rc;
   hipStream_t st = (hipStream_t)stream;
   // behind the ingest, roll or stamp that wrote the maps and every launch still reading them
   if ((rc = h->fence.begin_write(st))) return rc;
   StampArgs a;
   std::memset(&a, 0, sizeof(a));
-  a.polygons = d.polygons;
-  if (!d.polygons) { a.footprint = d.footprint; a.poses = d.poses; a.problems = d.poses ? nullptr : d.problems; }
+  a.polygons = o.polygons;
+  if (!o.polygons) { a.footprint = o.footprint; a.poses = o.poses; a.problems = o.poses ? nullptr : o.problems; }
   a.polys = h->stamp_polys.as<double>(); a.boxes = h->stamp_boxes.as<double>();
   a.table = h->stamp_table.buf.as<const uint8_t>();
   a.cells = const_cast<uint8_t*>(h->map.cells);   // (cell (0, 0) of the first map of map_buf, the handle's own)
@@ -1666,46 +1720,30 @@ static int stamp(neo_mpc_handle* h, const neo_mpc_stamp_batch& d, void* stream) 
   a.stride = h->map.pool_stride;
   a.size_x = h->map.size_x; a.size_y = h->map.size_y; a.pitch = h->map.pitch;
   a.reach = h->stamp_table.reach;
-  a.count = (uint32_t)n; a.points = d.footprint_points; a.per_robot = d.per_robot_footprints;
+  a.count = (uint32_t)n; a.points = o.footprint_points; a.per_robot = o.per_robot;
   launch_stamp(a, stream);
   HIP_TRY(hipGetLastError());
   return h->fence.end_write(st);   // a gate or solve behind it sees the stamped pool
 }
 
-int neo_mpc_stamp_fleet_device(neo_mpc_handle* h, const neo_mpc_stamp_batch* b, void* stream) {
+// Both entry points: on `stream` with the record's device pointers, or from host arrays, synchronous
+static int stamp_fleet(neo_mpc_handle* h, const neo_mpc_stamp_batch* b, bool on_device, void* stream) {
   int rc = check_stamp_batch(h, b);
   if (rc) return rc;
   if (b->count == 0) return NEO_MPC_OK;
-  HIP_TRY(hipSetDevice(h->device));
-  return stamp(h, *b, stream);
+  Outlines o = outlines_of(*b);
+  if (on_device) HIP_TRY(hipSetDevice(h->device));
+  else if ((rc = stage_outlines(h, o, h->verts, h->poses, h->problems))) return rc;
+  rc = stamp(h, *b, o, stream);
+  return on_device ? rc : finish_on_null_stream(rc);
 }
 
-int neo_mpc_stamp_fleet(neo_mpc_handle* h, const neo_mpc_stamp_batch* b) {
-  int rc = check_stamp_batch(h, b);
-  if (rc) return rc;
-  if (b->count == 0) return NEO_MPC_OK;
-  const size_t n = b->count, np = b->footprint_points;
-  // the values the device variant takes as they come are looked at here
-  const double* verts = b->polygons ? b->polygons : b->footprint;
-  const size_t polygons = b->polygons || b->per_robot_footprints ? n : 1;
-  if ((rc = check_vertices_finite(verts, polygons, np, "vertex", "polygon"))) return rc;
-  if (!b->polygons && (rc = check_poses_finite(b->poses, b->problems, n))) return rc;
-  HIP_TRY(hipSetDevice(h->device));
-  neo_mpc_stamp_batch d = *b;
-  d.polygons = nullptr; d.footprint = nullptr; d.poses = nullptr; d.problems = nullptr;
-  const double* d_verts = h->verts.upload(verts, polygons * np * 16);
-  if (!d_verts) return NEO_MPC_ERR_DEVICE;
-  if (b->polygons) d.polygons = d_verts;
-  else {
-    d.footprint = d_verts;
-    if (b->poses) d.poses = h->poses.upload(b->poses, n * 24);
-    else d.problems = h->problems.upload(b->problems, n * sizeof(neo_mpc_problem));
-    if (!d.poses && !d.problems) return NEO_MPC_ERR_DEVICE;
-  }
-  return finish_on_null_stream(stamp(h, d, nullptr));
-}
+int neo_mpc_stamp_fleet_device(neo_mpc_handle* h, const neo_mpc_stamp_batch* b, void* stream) { return stamp_fleet(h, b, true, stream); }
 
-// K9.  What both inflation entry points refuse, before any HIP call
+int neo_mpc_stamp_fleet(neo_mpc_handle* h, const neo_mpc_stamp_batch* b) { return stamp_fleet(h, b, false, nullptr); }
+
+// ---------------------------------------------------------------------------------------------- K9: the world inflation
+// What both inflation entry points refuse, before any HIP call
 static int check_inflate_world_map(const neo_mpc_handle* h, double ins, double infl, double csf) {
   if (!h) return fail(NEO_MPC_ERR_INVALID_ARGUMENT, "null handle");
   if (int rc = check_inflation_radii(ins, infl, csf)) return rc;
@@ -1742,6 +1780,10 @@ int neo_mpc_inflate_world_map(neo_mpc_handle* h, double ins, double infl, double
   return finish_on_null_stream(inflate_world_map(h, ins, infl, csf, false, nullptr));
 }
 
+// ---------------------------------------------------------------------------------------------- K10 to K13: the scan layers
+// What the layer an update goes to is: the projection alone has none
+enum Layer { kNoLayer, kPoolLayer, kWorldLayer };
+
 // K12.  What a world-scan update refuses behind the record's own refusals, in place of check_pool_batch: the world map, the
 // number of robots (free of the pool's), the reach at the world's resolution
 static int check_world_scan(const neo_mpc_handle* h, size_t count, double ins, double infl, double csf) {
@@ -1750,30 +1792,64 @@ static int check_world_scan(const neo_mpc_handle* h, size_t count, double ins, d
   return inflation_reach(h->world.resolution, ins, infl, csf, "the world map's ", nullptr);
 }
 
-// K10, K12 (`world`).  What the update entry points check: the record's shape and the handle's pool -- or its world map --,
+static int check_unknown_value(uint32_t u) {
+  return u == 0 || u == 255 ? NEO_MPC_OK : fail(NEO_MPC_ERR_INVALID_ARGUMENT, "unknown_value %u is neither 0 nor 255", u);
+}
+
+// What an update refuses of its settings and its target, behind the refusals of the record it came in: the four ranges, the
+// radii, then the pool's refusals or the world's.  `s`: the update's record, of points (K10, K12) or made of a laser record's
+// fields (scan_batch_of)
+static int check_update_target(const neo_mpc_handle* h, const neo_mpc_scan_batch& s, Layer layer) {
+  for (const double r : {s.obstacle_max_range, s.obstacle_min_range, s.raytrace_max_range, s.raytrace_min_range})
+    if (!std::isfinite(r) || r < 0.0) return fail(NEO_MPC_ERR_INVALID_ARGUMENT, "range %g must be finite and not negative", r);
+  if (int rc = check_inflation_radii(s.inscribed_radius, s.inflation_radius, s.cost_scaling_factor)) return rc;
+  if (layer == kWorldLayer) return check_world_scan(h, s.count, s.inscribed_radius, s.inflation_radius, s.cost_scaling_factor);
+  return check_pool_batch(h, s.count, s.inscribed_radius, s.inflation_radius, s.cost_scaling_factor);
+}
+
+// K10, K12.  What the update entry points check: the record's shape and the handle's pool -- or its world map --,
 // never a value behind a pointer.
-static int check_scan_batch(const neo_mpc_handle* h, const neo_mpc_scan_batch* b, bool world = false) {
+static int check_scan_batch(const neo_mpc_handle* h, const neo_mpc_scan_batch* b, Layer layer) {
   if (!h || !b) return fail(NEO_MPC_ERR_INVALID_ARGUMENT, "null argument");
   if (b->reserved != 0) return fail(NEO_MPC_ERR_INVALID_ARGUMENT, "neo_mpc_scan_batch.reserved must be zero");
   if (b->flags & ~(NEO_MPC_SCAN_CLEAR | NEO_MPC_SCAN_MARK)) return fail(NEO_MPC_ERR_INVALID_ARGUMENT, "unknown flags 0x%x", b->flags);
-  if (b->unknown_value != 0 && b->unknown_value != 255)
-    return fail(NEO_MPC_ERR_INVALID_ARGUMENT, "unknown_value %u is neither 0 nor 255", b->unknown_value);
+  if (int rc = check_unknown_value(b->unknown_value)) return rc;
   if (b->max_points > NEO_MPC_MAX_SCAN_POINTS)
     return fail(NEO_MPC_ERR_INVALID_ARGUMENT, "max_points %u: at most %u", b->max_points, NEO_MPC_MAX_SCAN_POINTS);
   if (b->flags != 0 && b->count > 0 && (!b->points || !b->sensor_origins))
     return fail(NEO_MPC_ERR_INVALID_ARGUMENT, "points and sensor_origins must not be null with flags 0x%x", b->flags);
-  for (const double r : {b->obstacle_max_range, b->obstacle_min_range, b->raytrace_max_range, b->raytrace_min_range})
-    if (!std::isfinite(r) || r < 0.0) return fail(NEO_MPC_ERR_INVALID_ARGUMENT, "range %g must be finite and not negative", r);
-  if (int rc = check_inflation_radii(b->inscribed_radius, b->inflation_radius, b->cost_scaling_factor)) return rc;
-  if (world) return check_world_scan(h, b->count, b->inscribed_radius, b->inflation_radius, b->cost_scaling_factor);
-  return check_pool_batch(h, b->count, b->inscribed_radius, b->inflation_radius, b->cost_scaling_factor);
+  return check_update_target(h, *b, layer);
 }
 
-// `d`: the record with device pointers.  Orders itself like stamp(): it rewrites the device maps in place, and the layer
-// buffers inside the same write.
-// `laser`: K11's projection of `sources` scanners a robot into d.points and d.sensor_origins, enqueued inside the same write,
-// in front of the layers' launches (the rays of the previous update, which read the handle's own points, lie behind the
-// previous write's end).
+// K12.  What the update entry points check of the clear record (null: none): its shape, never a value behind a pointer
+static int check_fleet_clear(const neo_mpc_fleet_clear* c, size_t count) {
+  if (!c) return NEO_MPC_OK;
+  if (c->reserved != 0) return fail(NEO_MPC_ERR_INVALID_ARGUMENT, "neo_mpc_fleet_clear.reserved must be zero");
+  if (int rc = check_footprint_shape(c->footprint_points, c->per_robot_footprints)) return rc;
+  if (!std::isfinite(c->padding) || c->padding < 0.0)
+    return fail(NEO_MPC_ERR_INVALID_ARGUMENT, "padding %g must be finite and not negative", c->padding);
+  if (c->count != count)
+    return fail(NEO_MPC_ERR_INVALID_ARGUMENT, "%zu outlines for %zu robots: they are one to one", c->count, count);
+  return check_outline_pointers(outlines_of(*c));
+}
+
+// The rays of an update as K10's and K12's kernels take them.  `d`: the record with device pointers; `laser`: K11's
+// projection of `sources` scanners a robot into d.points and d.sensor_origins
+static void fill_rays(ScanArgs& s, const neo_mpc_scan_batch& d, const InflationTable& table, const LaserArgs* laser) {
+  if (d.flags != 0) { s.points = d.points; s.point_counts = d.point_counts; s.sensor_origins = d.sensor_origins; }
+  s.table = table.buf.as<const uint8_t>();
+  s.obstacle_max = d.obstacle_max_range; s.obstacle_min = d.obstacle_min_range;
+  s.raytrace_max = d.raytrace_max_range; s.raytrace_min = d.raytrace_min_range;
+  s.reach = table.reach;
+  s.count = (uint32_t)d.count; s.max_points = d.max_points; s.flags = d.flags; s.unknown = d.unknown_value;
+  // (without K11 every point of a robot is its one source's: the address arithmetic of one observation per robot)
+  s.sources = laser ? laser->sources : 1u;
+  s.points_per_source = laser ? laser->beams : (d.max_points > 0 ? d.max_points : 1u);
+}
+
+// K10.  `d`: the record with device pointers.  Orders itself like stamp(): it rewrites the device maps in place, and the layer
+// buffers inside the same write.  `laser`: K11's projection, enqueued inside the same write, in front of the layers' launches
+// (the rays of the previous update, which read the handle's own points, lie behind the previous write's end).
 static int scan(neo_mpc_handle* h, const neo_mpc_scan_batch& d, void* stream, const LaserArgs* laser = nullptr) {
   const DevMap& m = h->map;
   ScanLayers& l = h->scan;
@@ -1786,21 +1862,13 @@ static int scan(neo_mpc_handle* h, const neo_mpc_scan_batch& d, void* stream, co
   if ((rc = h->fence.begin_write(st))) return rc;
   ScanArgs a;
   std::memset(&a, 0, sizeof(a));
-  if (d.flags != 0) { a.points = d.points; a.point_counts = d.point_counts; a.sensor_origins = d.sensor_origins; }
-  a.table = l.table.buf.as<const uint8_t>();
+  fill_rays(a, d, l.table, laser);
   a.layer = l.layer.as<uint8_t>(); a.work = l.work.as<uint8_t>(); a.layer_origins = l.origins.as<double>();
   a.cells = const_cast<uint8_t*>(m.cells);   // (cell (0, 0) of the first map of map_buf, the handle's own)
   a.origins = m.pool_origins;
   a.res = m.resolution;
-  a.obstacle_max = d.obstacle_max_range; a.obstacle_min = d.obstacle_min_range;
-  a.raytrace_max = d.raytrace_max_range; a.raytrace_min = d.raytrace_min_range;
   a.stride = m.pool_stride; a.layer_stride = (int64_t)l.stride();
   a.size_x = m.size_x; a.size_y = m.size_y; a.pitch = m.pitch; a.layer_pitch = l.pitch();
-  a.reach = l.table.reach;
-  a.count = (uint32_t)d.count; a.max_points = d.max_points; a.flags = d.flags; a.unknown = d.unknown_value;
-  // (without K11 every point of a robot is its one source's: the address arithmetic of one observation per robot)
-  a.sources = laser ? laser->sources : 1u;
-  a.points_per_source = laser ? laser->beams : (d.max_points > 0 ? d.max_points : 1u);
   a.reset = same ? 0u : 1u;
   if (laser) launch_laser_project(*laser, stream);
   launch_scan_layer(a, stream);
@@ -1810,23 +1878,50 @@ static int scan(neo_mpc_handle* h, const neo_mpc_scan_batch& d, void* stream, co
   return NEO_MPC_OK;
 }
 
-int neo_mpc_update_scan_layer_device(neo_mpc_handle* h, const neo_mpc_scan_batch* b, void* stream) {
-  int rc = check_scan_batch(h, b);
+// K12, K13.  `d`, `c`: the record and the outlines to clear with device pointers (`c` may be null).  Orders itself like
+// inflate_world_map(): it reads the world map and rewrites what the roll reads -- on `stream`, or on the host and the null
+// stream.  `laser`: as scan()'s, in front of the rays.
+static int world_scan(neo_mpc_handle* h, const neo_mpc_scan_batch& d, const Outlines* c, bool on_device, void* stream,
+                      const LaserArgs* laser = nullptr) {
+  WorldMap& w = h->world;
+  WorldScanLayer& l = h->world_scan;
+  int rc = l.table.build(w.resolution, d.inscribed_radius, d.inflation_radius, d.cost_scaling_factor, w);   // (every update records the world's event)
   if (rc) return rc;
-  if (b->count == 0) return NEO_MPC_OK;
-  HIP_TRY(hipSetDevice(h->device));
-  return scan(h, *b, stream);
+  const bool same = l.matches(w, d.unknown_value);
+  if (!same && (rc = l.resize(w, d.unknown_value))) return rc;
+  if ((rc = l.reserve_denoised())) return rc;
+  hipStream_t st = (hipStream_t)stream;
+  // behind the last roll, which reads `live` or the world map, and the previous copy, inflation or update
+  if ((rc = w.begin_write(h->fence, on_device, st))) return rc;
+  WorldScanArgs a;
+  std::memset(&a, 0, sizeof(a));
+  fill_rays(a.s, d, l.table, laser);
+  a.s.res = w.resolution;
+  a.layer = l.layer.as<uint8_t>(); a.world = w.buf.as<const uint8_t>(); a.live = l.live.as<uint8_t>();
+  if (c && c->count > 0) {
+    a.polygons = c->polygons;
+    if (!c->polygons) { a.footprint = c->footprint; a.poses = c->poses; a.problems = c->poses ? nullptr : c->problems; }
+    a.padding = c->padding; a.points = c->footprint_points; a.per_robot = c->per_robot; a.clear = 1u;
+  }
+  a.wres = w.resolution; a.wox = w.origin_x; a.woy = w.origin_y;
+  a.wsx = w.size_x; a.wsy = w.size_y;
+  a.reset = same ? 0u : 1u;
+  if (l.group >= 2) { a.denoised = l.denoised.as<uint8_t>(); a.group = l.group; a.connectivity = l.connectivity; }
+  if (laser) launch_laser_project(*laser, stream);
+  launch_world_scan(a, stream);
+  HIP_TRY(hipGetLastError());
+  if ((rc = w.end_write(st))) return rc;   // a roll behind it, on whatever stream, cuts its windows from `live`
+  l.valid = true; l.live_valid = true;
+  l.filtered = a.group >= 2;
+  return NEO_MPC_OK;
 }
 
-int neo_mpc_update_scan_layer(neo_mpc_handle* h, const neo_mpc_scan_batch* b) {
-  int rc = check_scan_batch(h, b);
-  if (rc) return rc;
-  if (b->count == 0) return NEO_MPC_OK;
+// The host variants' staging of an observation (K10, K12): the values the device variants take as they come are looked at,
+// then the arrays go into ScanLayers' staging and `d` gets the device pointers
+static int stage_observation(neo_mpc_handle* h, const neo_mpc_scan_batch* b, neo_mpc_scan_batch& d) {
   const size_t n = b->count;
-  neo_mpc_scan_batch d = *b;
   d.points = nullptr; d.point_counts = nullptr; d.sensor_origins = nullptr;
   if (b->flags != 0) {
-    // the values the device variant takes as they come are looked at here
     for (size_t k = 0; k < n; ++k) {
       if (b->point_counts && b->point_counts[k] > b->max_points)
         return fail(NEO_MPC_ERR_INVALID_ARGUMENT, "point_counts[%zu] = %u is more than max_points %u", k, b->point_counts[k], b->max_points);
@@ -1840,10 +1935,45 @@ int neo_mpc_update_scan_layer(neo_mpc_handle* h, const neo_mpc_scan_batch* b) {
     if (b->max_points > 0 && !(d.points = h->scan.points.upload(b->points, n * b->max_points * 16))) return NEO_MPC_ERR_DEVICE;
     if (b->point_counts && !(d.point_counts = h->scan.point_counts.upload(b->point_counts, n * 4))) return NEO_MPC_ERR_DEVICE;
   }
-  return finish_on_null_stream(scan(h, d, nullptr));
+  return NEO_MPC_OK;
 }
 
-// K11.  What the projection refuses of one scanner
+// The update entry points from points: K10 (`layer` the pool's, `c` null) and K12, on `stream` with the records' device
+// pointers, or from host arrays, synchronous.  The refusals in this order: the record's shape, the clear record's, then --
+// behind `count == 0`, which is no work -- the observation's values and the clear record's.
+static int update_from_points(neo_mpc_handle* h, const neo_mpc_scan_batch* b, const neo_mpc_fleet_clear* c, Layer layer,
+                              bool on_device, void* stream) {
+  int rc = check_scan_batch(h, b, layer);
+  if (rc || (rc = check_fleet_clear(c, b->count))) return rc;
+  if (b->count == 0) return NEO_MPC_OK;
+  neo_mpc_scan_batch d = *b;
+  Outlines clear{};
+  if (c) clear = outlines_of(*c);
+  if (on_device) HIP_TRY(hipSetDevice(h->device));
+  else {
+    WorldScanLayer& l = h->world_scan;
+    if ((rc = stage_observation(h, b, d))) return rc;
+    if (clear.count > 0 && (rc = stage_outlines(h, clear, l.verts, l.poses, l.problems))) return rc;
+  }
+  rc = layer == kWorldLayer ? world_scan(h, d, &clear, on_device, stream) : scan(h, d, stream);
+  return on_device ? rc : finish_on_null_stream(rc);
+}
+
+int neo_mpc_update_scan_layer_device(neo_mpc_handle* h, const neo_mpc_scan_batch* b, void* stream) {
+  return update_from_points(h, b, nullptr, kPoolLayer, true, stream);
+}
+int neo_mpc_update_scan_layer(neo_mpc_handle* h, const neo_mpc_scan_batch* b) {
+  return update_from_points(h, b, nullptr, kPoolLayer, false, nullptr);
+}
+int neo_mpc_update_world_scan_layer_device(neo_mpc_handle* h, const neo_mpc_scan_batch* b, const neo_mpc_fleet_clear* c, void* stream) {
+  return update_from_points(h, b, c, kWorldLayer, true, stream);
+}
+int neo_mpc_update_world_scan_layer(neo_mpc_handle* h, const neo_mpc_scan_batch* b, const neo_mpc_fleet_clear* c) {
+  return update_from_points(h, b, c, kWorldLayer, false, nullptr);
+}
+
+// ---------------------------------------------------------------------------------------------- K11: from LaserScan ranges
+// What the projection refuses of one scanner
 static int check_scanner(const neo_mpc_scanner& sc, uint32_t s) {
   if (sc.reserved != 0) return fail(NEO_MPC_ERR_INVALID_ARGUMENT, "neo_mpc_scanner.reserved of scanner %u must be zero", s);
   if (sc.flags & ~NEO_MPC_LASER_INF_IS_VALID) return fail(NEO_MPC_ERR_INVALID_ARGUMENT, "unknown flags 0x%x of scanner %u", sc.flags, s);
@@ -1854,9 +1984,23 @@ static int check_scanner(const neo_mpc_scanner& sc, uint32_t s) {
   return NEO_MPC_OK;
 }
 
-// K11.  What the four entry points check: the record's shape, the scanners (host configuration) and, for an update, what
-// check_scan_batch checks of the handle's pool -- never a value behind ranges, poses or the out pointers.
-static int check_laser_batch(const neo_mpc_handle* h, const neo_mpc_laser_batch* b, bool update, bool device, bool world = false) {
+// The update's record for a laser record's settings and the points projected from it
+static neo_mpc_scan_batch scan_batch_of(const neo_mpc_laser_batch& d, const double* points = nullptr, const double* origins = nullptr) {
+  neo_mpc_scan_batch sb;
+  std::memset(&sb, 0, sizeof(sb));
+  sb.count = d.count; sb.points = points; sb.sensor_origins = origins;
+  sb.max_points = d.sources * d.beams; sb.flags = d.scan_flags;
+  sb.obstacle_max_range = d.obstacle_max_range; sb.obstacle_min_range = d.obstacle_min_range;
+  sb.raytrace_max_range = d.raytrace_max_range; sb.raytrace_min_range = d.raytrace_min_range;
+  sb.inscribed_radius = d.inscribed_radius; sb.inflation_radius = d.inflation_radius; sb.cost_scaling_factor = d.cost_scaling_factor;
+  sb.unknown_value = d.unknown_value;
+  return sb;
+}
+
+// What the six entry points check: the record's shape, the scanners (host configuration) and, for an update, what
+// check_scan_batch checks of the handle's pool or world map -- never a value behind ranges, poses or the out pointers.
+static int check_laser_batch(const neo_mpc_handle* h, const neo_mpc_laser_batch* b, Layer layer, bool device) {
+  const bool update = layer != kNoLayer;
   if (!h || !b) return fail(NEO_MPC_ERR_INVALID_ARGUMENT, "null argument");
   if (b->reserved != 0) return fail(NEO_MPC_ERR_INVALID_ARGUMENT, "neo_mpc_laser_batch.reserved must be zero");
   if (b->sources < 1 || b->sources > NEO_MPC_MAX_SCAN_SOURCES)
@@ -1871,17 +2015,11 @@ static int check_laser_batch(const neo_mpc_handle* h, const neo_mpc_laser_batch*
   if (update) {
     if (b->scan_flags == 0 || (b->scan_flags & ~(NEO_MPC_SCAN_CLEAR | NEO_MPC_SCAN_MARK)))
       return fail(NEO_MPC_ERR_INVALID_ARGUMENT, "scan_flags 0x%x: NEO_MPC_SCAN_CLEAR, NEO_MPC_SCAN_MARK or both", b->scan_flags);
-    if (b->unknown_value != 0 && b->unknown_value != 255)
-      return fail(NEO_MPC_ERR_INVALID_ARGUMENT, "unknown_value %u is neither 0 nor 255", b->unknown_value);
+    if (int rc = check_unknown_value(b->unknown_value)) return rc;
   }
   for (uint32_t s = 0; s < b->sources; ++s)
     if (int rc = check_scanner(b->scanners[s], s)) return rc;
-  if (!update) return NEO_MPC_OK;
-  for (const double r : {b->obstacle_max_range, b->obstacle_min_range, b->raytrace_max_range, b->raytrace_min_range})
-    if (!std::isfinite(r) || r < 0.0) return fail(NEO_MPC_ERR_INVALID_ARGUMENT, "range %g must be finite and not negative", r);
-  if (int rc = check_inflation_radii(b->inscribed_radius, b->inflation_radius, b->cost_scaling_factor)) return rc;
-  if (world) return check_world_scan(h, b->count, b->inscribed_radius, b->inflation_radius, b->cost_scaling_factor);
-  return check_pool_batch(h, b->count, b->inscribed_radius, b->inflation_radius, b->cost_scaling_factor);
+  return update ? check_update_target(h, scan_batch_of(*b), layer) : NEO_MPC_OK;
 }
 
 // `d`: the record with device pointers (points_out / origins_out null: the handle's own) -> the kernel's arguments, the beam
@@ -1906,33 +2044,58 @@ static int laser_args(neo_mpc_handle* h, const neo_mpc_laser_batch& d, LaserArgs
   return NEO_MPC_OK;
 }
 
-// The projection alone: it touches neither maps nor layers, so it is in order on its stream and nothing else
-static int project_laser(neo_mpc_handle* h, const neo_mpc_laser_batch& d, void* stream) {
+// The projection -- alone it touches neither maps nor layers, so it is in order on its stream and nothing else -- or the
+// projection and the layer's update over all sources, in one write of what the update rewrites
+static int project(neo_mpc_handle* h, const neo_mpc_laser_batch& d, const Outlines* c, Layer layer, bool on_device, void* stream) {
   LaserArgs a;
   if (int rc = laser_args(h, d, a)) return rc;
-  launch_laser_project(a, stream);
-  HIP_TRY(hipGetLastError());
+  if (layer == kNoLayer) {
+    launch_laser_project(a, stream);
+    HIP_TRY(hipGetLastError());
+    return NEO_MPC_OK;
+  }
+  const neo_mpc_scan_batch sb = scan_batch_of(d, a.points, a.origins);
+  return layer == kWorldLayer ? world_scan(h, sb, c, on_device, stream, &a) : scan(h, sb, stream, &a);
+}
+
+// The host variants' staging of ranges: the poses are looked at, ranges and poses go into the handle's staging, and the
+// projection goes into the handle's own buffers ...
+static int stage_ranges(neo_mpc_handle* h, const neo_mpc_laser_batch* b, neo_mpc_laser_batch& d) {
+  const size_t n = b->count;
+  if (int rc = check_poses_finite(b->poses, nullptr, n)) return rc;
+  HIP_TRY(hipSetDevice(h->device));
+  d.points_out = nullptr; d.origins_out = nullptr;
+  if (!(d.ranges = h->laser.ranges.upload(b->ranges, n * b->sources * b->beams * 4))) return NEO_MPC_ERR_DEVICE;
+  if (!(d.poses = h->poses.upload(b->poses, n * 24))) return NEO_MPC_ERR_DEVICE;
+  return NEO_MPC_OK;
+}
+// ... which are read back where asked for, behind the wait for the null stream
+static int read_back_projection(neo_mpc_handle* h, const neo_mpc_laser_batch* b) {
+  const size_t scans = b->count * b->sources;
+  if (b->points_out) HIP_TRY(hipMemcpy(b->points_out, h->laser.points.ptr, scans * b->beams * 16, hipMemcpyDeviceToHost));
+  if (b->origins_out) HIP_TRY(hipMemcpy(b->origins_out, h->laser.origins.ptr, scans * 16, hipMemcpyDeviceToHost));
   return NEO_MPC_OK;
 }
 
-// The update's record for the points `a` projects
-static neo_mpc_scan_batch scan_batch_of(const neo_mpc_laser_batch& d, const LaserArgs& a) {
-  neo_mpc_scan_batch sb;
-  std::memset(&sb, 0, sizeof(sb));
-  sb.count = d.count; sb.points = a.points; sb.sensor_origins = a.origins;
-  sb.max_points = d.sources * d.beams; sb.flags = d.scan_flags;
-  sb.obstacle_max_range = d.obstacle_max_range; sb.obstacle_min_range = d.obstacle_min_range;
-  sb.raytrace_max_range = d.raytrace_max_range; sb.raytrace_min_range = d.raytrace_min_range;
-  sb.inscribed_radius = d.inscribed_radius; sb.inflation_radius = d.inflation_radius; sb.cost_scaling_factor = d.cost_scaling_factor;
-  sb.unknown_value = d.unknown_value;
-  return sb;
-}
-
-// The projection and the update over all sources, one write of the device maps
-static int scan_from_ranges(neo_mpc_handle* h, const neo_mpc_laser_batch& d, void* stream) {
-  LaserArgs a;
-  if (int rc = laser_args(h, d, a)) return rc;
-  return scan(h, scan_batch_of(d, a), stream, &a);
+// The entry points from ranges: the projection alone (kNoLayer), K10's update and K12's (`c`: its clear record), on `stream`
+// with the records' device pointers, or from host arrays, synchronous.  The refusals in update_from_points' order.
+static int from_ranges(neo_mpc_handle* h, const neo_mpc_laser_batch* b, const neo_mpc_fleet_clear* c, Layer layer, bool on_device,
+                       void* stream) {
+  int rc = check_laser_batch(h, b, layer, on_device);
+  if (rc || (rc = check_fleet_clear(c, b->count))) return rc;
+  if (b->count == 0) return NEO_MPC_OK;
+  neo_mpc_laser_batch d = *b;
+  Outlines clear{};
+  if (c) clear = outlines_of(*c);
+  if (on_device) {
+    HIP_TRY(hipSetDevice(h->device));
+    return project(h, d, &clear, layer, true, stream);
+  }
+  WorldScanLayer& l = h->world_scan;
+  if ((rc = stage_ranges(h, b, d))) return rc;
+  if (clear.count > 0 && (rc = stage_outlines(h, clear, l.verts, l.poses, l.problems))) return rc;
+  if ((rc = finish_on_null_stream(project(h, d, &clear, layer, false, nullptr)))) return rc;
+  return read_back_projection(h, b);
 }
 
 int neo_mpc_laser_beam_table(const neo_mpc_scanner* scanner, uint32_t beams, double* table_out) {
@@ -1944,41 +2107,24 @@ int neo_mpc_laser_beam_table(const neo_mpc_scanner* scanner, uint32_t beams, dou
 }
 
 int neo_mpc_project_laser_device(neo_mpc_handle* h, const neo_mpc_laser_batch* b, void* stream) {
-  if (int rc = check_laser_batch(h, b, false, true)) return rc;
-  if (b->count == 0) return NEO_MPC_OK;
-  HIP_TRY(hipSetDevice(h->device));
-  return project_laser(h, *b, stream);
+  return from_ranges(h, b, nullptr, kNoLayer, true, stream);
 }
-
+int neo_mpc_project_laser(neo_mpc_handle* h, const neo_mpc_laser_batch* b) { return from_ranges(h, b, nullptr, kNoLayer, false, nullptr); }
 int neo_mpc_update_scan_layer_from_ranges_device(neo_mpc_handle* h, const neo_mpc_laser_batch* b, void* stream) {
-  if (int rc = check_laser_batch(h, b, true, true)) return rc;
-  if (b->count == 0) return NEO_MPC_OK;
-  HIP_TRY(hipSetDevice(h->device));
-  return scan_from_ranges(h, *b, stream);
+  return from_ranges(h, b, nullptr, kPoolLayer, true, stream);
+}
+int neo_mpc_update_scan_layer_from_ranges(neo_mpc_handle* h, const neo_mpc_laser_batch* b) {
+  return from_ranges(h, b, nullptr, kPoolLayer, false, nullptr);
+}
+int neo_mpc_update_world_scan_layer_from_ranges_device(neo_mpc_handle* h, const neo_mpc_laser_batch* b, const neo_mpc_fleet_clear* c,
+                                                       void* stream) {
+  return from_ranges(h, b, c, kWorldLayer, true, stream);
+}
+int neo_mpc_update_world_scan_layer_from_ranges(neo_mpc_handle* h, const neo_mpc_laser_batch* b, const neo_mpc_fleet_clear* c) {
+  return from_ranges(h, b, c, kWorldLayer, false, nullptr);
 }
 
-// The host variants: ranges and poses staged, projected into the handle's own buffers, and those read back where asked for
-static int laser_from_host(neo_mpc_handle* h, const neo_mpc_laser_batch* b, bool update) {
-  if (int rc = check_laser_batch(h, b, update, false)) return rc;
-  if (b->count == 0) return NEO_MPC_OK;
-  const size_t n = b->count, scans = n * b->sources;
-  // the values the device variants take as they come are looked at here
-  if (int rc = check_poses_finite(b->poses, nullptr, n)) return rc;
-  HIP_TRY(hipSetDevice(h->device));
-  neo_mpc_laser_batch d = *b;
-  d.points_out = nullptr; d.origins_out = nullptr;
-  if (!(d.ranges = h->laser.ranges.upload(b->ranges, scans * b->beams * 4))) return NEO_MPC_ERR_DEVICE;
-  if (!(d.poses = h->poses.upload(b->poses, n * 24))) return NEO_MPC_ERR_DEVICE;
-  if (int rc = finish_on_null_stream(update ? scan_from_ranges(h, d, nullptr) : project_laser(h, d, nullptr))) return rc;
-  if (b->points_out) HIP_TRY(hipMemcpy(b->points_out, h->laser.points.ptr, scans * b->beams * 16, hipMemcpyDeviceToHost));
-  if (b->origins_out) HIP_TRY(hipMemcpy(b->origins_out, h->laser.origins.ptr, scans * 16, hipMemcpyDeviceToHost));
-  return NEO_MPC_OK;
-}
-
-int neo_mpc_project_laser(neo_mpc_handle* h, const neo_mpc_laser_batch* b) { return laser_from_host(h, b, false); }
-
-int neo_mpc_update_scan_layer_from_ranges(neo_mpc_handle* h, const neo_mpc_laser_batch* b) { return laser_from_host(h, b, true); }
-
+// ---------------------------------------------------------------------------------------------- the layers read back, reset, K13's setting
 int neo_mpc_get_scan_layer(neo_mpc_handle* h, uint32_t first, uint32_t count, uint8_t* cells_out, double* origins_out) {
   if (!h) return fail(NEO_MPC_ERR_INVALID_ARGUMENT, "null handle");
   const ScanLayers& l = h->scan;
@@ -1999,162 +2145,6 @@ int neo_mpc_get_scan_layer(neo_mpc_handle* h, uint32_t first, uint32_t count, ui
 int neo_mpc_reset_scan_layer(neo_mpc_handle* h) {
   if (!h) return fail(NEO_MPC_ERR_INVALID_ARGUMENT, "null handle");
   h->scan.valid = false;
-  return NEO_MPC_OK;
-}
-
-// ---------------------------------------------------------------------------------------------- K12: the world scan layer
-// What the update entry points check of the clear record: its shape, never a value behind a pointer
-static int check_fleet_clear(const neo_mpc_fleet_clear* c, size_t count) {
-  if (!c) return NEO_MPC_OK;
-  if (c->reserved != 0) return fail(NEO_MPC_ERR_INVALID_ARGUMENT, "neo_mpc_fleet_clear.reserved must be zero");
-  if (int rc = check_footprint_shape(c->footprint_points, c->per_robot_footprints)) return rc;
-  if (!std::isfinite(c->padding) || c->padding < 0.0)
-    return fail(NEO_MPC_ERR_INVALID_ARGUMENT, "padding %g must be finite and not negative", c->padding);
-  if (c->count != count)
-    return fail(NEO_MPC_ERR_INVALID_ARGUMENT, "%zu outlines for %zu robots: they are one to one", c->count, count);
-  if (c->count > 0 && !c->polygons && (!c->footprint || (!c->poses && !c->problems)))
-    return fail(NEO_MPC_ERR_INVALID_ARGUMENT, "neither polygons nor a footprint with poses or problems");
-  return NEO_MPC_OK;
-}
-
-// `d`, `c`: the records with device pointers (`c` may be null).  Orders itself like inflate_world_map(): it reads the world map
-// and rewrites what the roll reads -- on `stream`, or on the host and the null stream.  `laser`: K11's projection into d.points
-// and d.sensor_origins, enqueued inside the same write, in front of the rays.
-static int world_scan(neo_mpc_handle* h, const neo_mpc_scan_batch& d, const neo_mpc_fleet_clear* c, bool on_device, void* stream,
-                      const LaserArgs* laser = nullptr) {
-  WorldMap& w = h->world;
-  WorldScanLayer& l = h->world_scan;
-  int rc = l.table.build(w.resolution, d.inscribed_radius, d.inflation_radius, d.cost_scaling_factor, w);   // (every update records the world's event)
-  if (rc) return rc;
-  const bool same = l.matches(w, d.unknown_value);
-  if (!same && (rc = l.resize(w, d.unknown_value))) return rc;
-  if ((rc = l.reserve_denoised())) return rc;
-  hipStream_t st = (hipStream_t)stream;
-  // behind the last roll, which reads `live` or the world map, and the previous copy, inflation or update
-  if ((rc = w.begin_write(h->fence, on_device, st))) return rc;
-  WorldScanArgs a;
-  std::memset(&a, 0, sizeof(a));
-  if (d.flags != 0) { a.s.points = d.points; a.s.point_counts = d.point_counts; a.s.sensor_origins = d.sensor_origins; }
-  a.s.table = l.table.buf.as<const uint8_t>();
-  a.s.res = w.resolution;
-  a.s.obstacle_max = d.obstacle_max_range; a.s.obstacle_min = d.obstacle_min_range;
-  a.s.raytrace_max = d.raytrace_max_range; a.s.raytrace_min = d.raytrace_min_range;
-  a.s.reach = l.table.reach;
-  a.s.count = (uint32_t)d.count; a.s.max_points = d.flags != 0 ? d.max_points : 0u; a.s.flags = d.flags; a.s.unknown = d.unknown_value;
-  a.s.sources = laser ? laser->sources : 1u;
-  a.s.points_per_source = laser ? laser->beams : (d.max_points > 0 ? d.max_points : 1u);
-  a.layer = l.layer.as<uint8_t>(); a.world = w.buf.as<const uint8_t>(); a.live = l.live.as<uint8_t>();
-  if (c && c->count > 0) {
-    a.polygons = c->polygons;
-    if (!c->polygons) { a.footprint = c->footprint; a.poses = c->poses; a.problems = c->poses ? nullptr : c->problems; }
-    a.padding = c->padding; a.points = c->footprint_points; a.per_robot = c->per_robot_footprints; a.clear = 1u;
-  }
-  a.wres = w.resolution; a.wox = w.origin_x; a.woy = w.origin_y;
-  a.wsx = w.size_x; a.wsy = w.size_y;
-  a.reset = same ? 0u : 1u;
-  if (l.group >= 2) { a.denoised = l.denoised.as<uint8_t>(); a.group = l.group; a.connectivity = l.connectivity; }
-  if (laser) launch_laser_project(*laser, stream);
-  launch_world_scan(a, stream);
-  HIP_TRY(hipGetLastError());
-  if ((rc = w.end_write(st))) return rc;   // a roll behind it, on whatever stream, cuts its windows from `live`
-  l.valid = true; l.live_valid = true;
-  l.filtered = a.group >= 2;
-  return NEO_MPC_OK;
-}
-
-// The clear record's host arrays staged -> `d` with device pointers (the values the device variants take as they come are
-// looked at here)
-static int stage_fleet_clear(neo_mpc_handle* h, const neo_mpc_fleet_clear* c, neo_mpc_fleet_clear& d) {
-  const size_t n = c->count, np = c->footprint_points;
-  const double* verts = c->polygons ? c->polygons : c->footprint;
-  const size_t polygons = c->polygons || c->per_robot_footprints ? n : 1;
-  if (int rc = check_vertices_finite(verts, polygons, np, "vertex", "polygon")) return rc;
-  if (!c->polygons) if (int rc = check_poses_finite(c->poses, c->problems, n)) return rc;
-  HIP_TRY(hipSetDevice(h->device));
-  WorldScanLayer& l = h->world_scan;
-  d = *c;
-  d.polygons = nullptr; d.footprint = nullptr; d.poses = nullptr; d.problems = nullptr;
-  const double* d_verts = l.verts.upload(verts, polygons * np * 16);
-  if (!d_verts) return NEO_MPC_ERR_DEVICE;
-  if (c->polygons) d.polygons = d_verts;
-  else {
-    d.footprint = d_verts;
-    if (c->poses) d.poses = l.poses.upload(c->poses, n * 24);
-    else d.problems = l.problems.upload(c->problems, n * sizeof(neo_mpc_problem));
-    if (!d.poses && !d.problems) return NEO_MPC_ERR_DEVICE;
-  }
-  return NEO_MPC_OK;
-}
-
-int neo_mpc_update_world_scan_layer_device(neo_mpc_handle* h, const neo_mpc_scan_batch* b, const neo_mpc_fleet_clear* c, void* stream) {
-  int rc = check_scan_batch(h, b, true);
-  if (rc || (rc = check_fleet_clear(c, b->count))) return rc;
-  if (b->count == 0) return NEO_MPC_OK;
-  HIP_TRY(hipSetDevice(h->device));
-  return world_scan(h, *b, c, true, stream);
-}
-
-int neo_mpc_update_world_scan_layer(neo_mpc_handle* h, const neo_mpc_scan_batch* b, const neo_mpc_fleet_clear* c) {
-  int rc = check_scan_batch(h, b, true);
-  if (rc || (rc = check_fleet_clear(c, b->count))) return rc;
-  if (b->count == 0) return NEO_MPC_OK;
-  const size_t n = b->count;
-  neo_mpc_scan_batch d = *b;
-  d.points = nullptr; d.point_counts = nullptr; d.sensor_origins = nullptr;
-  if (b->flags != 0) {
-    // the values the device variant takes as they come are looked at here
-    for (size_t k = 0; k < n; ++k) {
-      if (b->point_counts && b->point_counts[k] > b->max_points)
-        return fail(NEO_MPC_ERR_INVALID_ARGUMENT, "point_counts[%zu] = %u is more than max_points %u", k, b->point_counts[k], b->max_points);
-      if (!std::isfinite(b->sensor_origins[2 * k]) || !std::isfinite(b->sensor_origins[2 * k + 1]))
-        return fail(NEO_MPC_ERR_INVALID_ARGUMENT, "the sensor origin of robot %zu is not finite", k);
-    }
-  }
-  neo_mpc_fleet_clear dc;
-  if (c && c->count > 0 && (rc = stage_fleet_clear(h, c, dc))) return rc;
-  HIP_TRY(hipSetDevice(h->device));
-  if (b->flags != 0) {
-    if (!(d.sensor_origins = h->scan.sensors.upload(b->sensor_origins, n * 16))) return NEO_MPC_ERR_DEVICE;
-    if (b->max_points > 0 && !(d.points = h->scan.points.upload(b->points, n * b->max_points * 16))) return NEO_MPC_ERR_DEVICE;
-    if (b->point_counts && !(d.point_counts = h->scan.point_counts.upload(b->point_counts, n * 4))) return NEO_MPC_ERR_DEVICE;
-  }
-  return finish_on_null_stream(world_scan(h, d, c && c->count > 0 ? &dc : nullptr, false, nullptr));
-}
-
-// The projection and the world's update over all sources, one write of what the roll reads
-static int world_scan_from_ranges(neo_mpc_handle* h, const neo_mpc_laser_batch& d, const neo_mpc_fleet_clear* c, bool on_device,
-                                  void* stream) {
-  LaserArgs a;
-  if (int rc = laser_args(h, d, a)) return rc;
-  return world_scan(h, scan_batch_of(d, a), c, on_device, stream, &a);
-}
-
-int neo_mpc_update_world_scan_layer_from_ranges_device(neo_mpc_handle* h, const neo_mpc_laser_batch* b, const neo_mpc_fleet_clear* c,
-                                                       void* stream) {
-  int rc = check_laser_batch(h, b, true, true, true);
-  if (rc || (rc = check_fleet_clear(c, b->count))) return rc;
-  if (b->count == 0) return NEO_MPC_OK;
-  HIP_TRY(hipSetDevice(h->device));
-  return world_scan_from_ranges(h, *b, c, true, stream);
-}
-
-int neo_mpc_update_world_scan_layer_from_ranges(neo_mpc_handle* h, const neo_mpc_laser_batch* b, const neo_mpc_fleet_clear* c) {
-  int rc = check_laser_batch(h, b, true, false, true);
-  if (rc || (rc = check_fleet_clear(c, b->count))) return rc;
-  if (b->count == 0) return NEO_MPC_OK;
-  const size_t n = b->count, scans = n * b->sources;
-  // the values the device variants take as they come are looked at here
-  if ((rc = check_poses_finite(b->poses, nullptr, n))) return rc;
-  neo_mpc_fleet_clear dc;
-  if (c && c->count > 0 && (rc = stage_fleet_clear(h, c, dc))) return rc;
-  HIP_TRY(hipSetDevice(h->device));
-  neo_mpc_laser_batch d = *b;
-  d.points_out = nullptr; d.origins_out = nullptr;
-  if (!(d.ranges = h->laser.ranges.upload(b->ranges, scans * b->beams * 4))) return NEO_MPC_ERR_DEVICE;
-  if (!(d.poses = h->poses.upload(b->poses, n * 24))) return NEO_MPC_ERR_DEVICE;
-  if ((rc = finish_on_null_stream(world_scan_from_ranges(h, d, c && c->count > 0 ? &dc : nullptr, false, nullptr)))) return rc;
-  if (b->points_out) HIP_TRY(hipMemcpy(b->points_out, h->laser.points.ptr, scans * b->beams * 16, hipMemcpyDeviceToHost));
-  if (b->origins_out) HIP_TRY(hipMemcpy(b->origins_out, h->laser.origins.ptr, scans * 16, hipMemcpyDeviceToHost));
   return NEO_MPC_OK;
 }
 

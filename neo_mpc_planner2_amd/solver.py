@@ -252,55 +252,62 @@ class BatchSolver:
         assert shape is not None, "polygons or footprint"
         on_host = isinstance(shape, np.ndarray) or not hasattr(shape, "data_ptr")
         if on_host:
-            keep = []
-
-            def ptr(a, dtype=np.float64):
-                a = np.ascontiguousarray(a, dtype=dtype)
-                keep.append(a)
-                return a, a.ctypes.data
-
-            if polygons is not None:
-                polygons, b.polygons = ptr(polygons)
-                assert polygons.ndim == 3 and polygons.shape[2] == 2
-                b.count, b.footprint_points = polygons.shape[0], polygons.shape[1]
-            else:
-                footprint, b.footprint = ptr(footprint)
-                assert footprint.ndim in (2, 3) and footprint.shape[-1] == 2
-                b.footprint_points = footprint.shape[-2]
-                b.per_robot_footprints = 1 if footprint.ndim == 3 else 0
-                if poses is not None:
-                    poses, b.poses = ptr(poses)
-                    poses = poses.reshape(-1, 3)
-                    b.count = poses.shape[0]
-                elif problems is not None:
-                    assert problems.dtype == abi.PROBLEM_DTYPE and problems.flags.c_contiguous
-                    b.problems = problems.ctypes.data
-                    b.count = problems.shape[0]
-                assert footprint.ndim == 2 or footprint.shape[0] == b.count
+            if polygons is None and poses is not None:
+                poses = np.asarray(poses, dtype=np.float64).reshape(-1, 3)
+            assert polygons is not None or poses is not None or problems is None or problems.dtype == abi.PROBLEM_DTYPE
+        else:
+            for a in (polygons, footprint, poses, problems):
+                assert a is None or (a.is_cuda and a.is_contiguous())
+        b.count, keep = self._outlines(b, on_host, polygons, footprint, poses, problems)
+        if on_host:
             _lib.check(self._lib.neo_mpc_stamp_fleet(self._handle, C.byref(b)))
         else:
             import torch
-            for a in (polygons, footprint, poses, problems):
-                assert a is None or (a.is_cuda and a.is_contiguous())
-            if polygons is not None:
-                assert polygons.dtype == torch.float64 and polygons.dim() == 3 and polygons.shape[2] == 2
-                b.polygons = polygons.data_ptr()
-                b.count, b.footprint_points = polygons.shape[0], polygons.shape[1]
-            else:
-                assert footprint.dtype == torch.float64 and footprint.dim() in (2, 3) and footprint.shape[-1] == 2
-                b.footprint = footprint.data_ptr()
-                b.footprint_points = footprint.shape[-2]
-                b.per_robot_footprints = 1 if footprint.dim() == 3 else 0
-                if poses is not None:
-                    assert poses.dtype == torch.float64 and poses.dim() == 2 and poses.shape[1] == 3
-                    b.poses = poses.data_ptr()
-                    b.count = poses.shape[0]
-                elif problems is not None:
-                    b.problems = problems.data_ptr()
-                    b.count = problems.shape[0]
-                assert footprint.dim() == 2 or footprint.shape[0] == b.count
             stream = torch.cuda.current_stream(shape.device).cuda_stream
             _lib.check(self._lib.neo_mpc_stamp_fleet_device(self._handle, C.byref(b), C.c_void_p(stream)))
+
+    @staticmethod
+    def _outlines(rec, on_host, polygons=None, footprint=None, poses=None, problems=None, count=None):
+        """Marshals a fleet's outlines -- `polygons` [count, points, 2], or `footprint` ([points, 2] or [count, points, 2])
+        with `poses` [count, 3] or `problems` -- into the fields of those names of `rec` (neo_mpc_stamp_batch,
+        neo_mpc_fleet_clear), with footprint_points and per_robot_footprints: from NumPy arrays (`on_host`) or CUDA tensors
+        (float64; `problems` the request records).  `count`: what the arrays must agree with, or None: what they give (0
+        without any) -> (count, what must stay alive)."""
+        keep = []
+
+        def ptr(a, dims):   # (dims None: records, taken as they are)
+            if on_host:
+                a = a if dims is None else np.ascontiguousarray(a, dtype=np.float64)
+                assert a.flags.c_contiguous and (dims is None or a.ndim in dims)
+                keep.append(a)
+                return a, a.ctypes.data
+            import torch
+            assert a.is_cuda and a.is_contiguous() and (dims is None or (a.dtype == torch.float64 and a.dim() in dims))
+            keep.append(a)
+            return a, a.data_ptr()
+
+        given = None
+        if polygons is not None:
+            polygons, rec.polygons = ptr(polygons, (3,))
+            assert polygons.shape[2] == 2
+            given, rec.footprint_points = polygons.shape[0], polygons.shape[1]
+        else:
+            footprint, rec.footprint = ptr(footprint, (2, 3))
+            assert footprint.shape[-1] == 2
+            rec.footprint_points = footprint.shape[-2]
+            rec.per_robot_footprints = 1 if len(footprint.shape) == 3 else 0
+            if poses is not None:
+                poses, rec.poses = ptr(poses, (2,))
+                assert poses.shape[1] == 3
+                given = poses.shape[0]
+            elif problems is not None:
+                problems, rec.problems = ptr(problems, None)
+                given = problems.shape[0]
+        if count is None:
+            count = given or 0
+        assert given is None or given == count
+        assert polygons is not None or len(footprint.shape) == 2 or footprint.shape[0] == count
+        return int(count), keep
 
     # -- scan obstacle layer (the step between the roll and the stamp) --------------------
     def update_scan_layer(self, inscribed_radius, inflation_radius, cost_scaling_factor, points=None, sensor_origins=None,
@@ -406,6 +413,19 @@ class BatchSolver:
         b.count, b.beams = count, beams
         return b, (sc, ranges, poses), points_out, origins_out, stream
 
+    def _laser_update(self, ranges, poses, scanners, points_out, origins_out, flags, unknown_value, obstacle_max_range,
+                      obstacle_min_range, raytrace_max_range, raytrace_min_range, inscribed_radius, inflation_radius,
+                      cost_scaling_factor):
+        """-> (`_laser_batch`'s record with the update's fields filled, what must stay alive, the stream or None)."""
+        b, keep, _, _, stream = self._laser_batch(ranges, poses, scanners, points_out, origins_out, False)
+        b.scan_flags = int(abi.SCAN_CLEAR | abi.SCAN_MARK if flags is None else flags)
+        b.unknown_value = int(unknown_value)
+        b.obstacle_max_range, b.obstacle_min_range = float(obstacle_max_range), float(obstacle_min_range)
+        b.raytrace_max_range, b.raytrace_min_range = float(raytrace_max_range), float(raytrace_min_range)
+        b.inscribed_radius, b.inflation_radius = float(inscribed_radius), float(inflation_radius)
+        b.cost_scaling_factor = float(cost_scaling_factor)
+        return b, keep, stream
+
     def project_laser(self, ranges, poses, scanners, points_out=None, origins_out=None):
         """Projects LaserScan `ranges` (float32 [count, sources, beams], as on the wire) of robots at `poses` (float64
         [count, 3]: x, y, yaw) into global-frame hit points [count, sources, beams, 2] -- (NaN, NaN) for a beam that is not
@@ -428,13 +448,9 @@ class BatchSolver:
         abi.SCAN_CLEAR | abi.SCAN_MARK (the default) or one of them; a tick without a new scan is `update_scan_layer`
         without points.  `points_out` / `origins_out` receive what was projected when given.  NumPy arrays go through the
         synchronous host call; CUDA tensors through the device call on torch's current stream."""
-        b, keep, _, _, stream = self._laser_batch(ranges, poses, scanners, points_out, origins_out, False)
-        b.scan_flags = int(abi.SCAN_CLEAR | abi.SCAN_MARK if flags is None else flags)
-        b.unknown_value = int(unknown_value)
-        b.obstacle_max_range, b.obstacle_min_range = float(obstacle_max_range), float(obstacle_min_range)
-        b.raytrace_max_range, b.raytrace_min_range = float(raytrace_max_range), float(raytrace_min_range)
-        b.inscribed_radius, b.inflation_radius = float(inscribed_radius), float(inflation_radius)
-        b.cost_scaling_factor = float(cost_scaling_factor)
+        b, keep, stream = self._laser_update(ranges, poses, scanners, points_out, origins_out, flags, unknown_value,
+                                             obstacle_max_range, obstacle_min_range, raytrace_max_range, raytrace_min_range,
+                                             inscribed_radius, inflation_radius, cost_scaling_factor)
         if stream is None:
             _lib.check(self._lib.neo_mpc_update_scan_layer_from_ranges(self._handle, C.byref(b)))
         else:
@@ -466,35 +482,9 @@ class BatchSolver:
             return None, None
         assert set(clear) <= {"padding", "polygons", "footprint", "poses", "problems"}, sorted(clear)
         c = abi.NeoMpcFleetClear()
-        c.count, c.padding = int(count), float(clear.get("padding", 0.0))
-        keep = []
-
-        def ptr(a, dim, records=False):
-            if on_host:
-                a = a if records else np.ascontiguousarray(a, dtype=np.float64)
-                assert a.flags.c_contiguous and (records or a.ndim in dim)
-                keep.append(a)
-                return a, a.ctypes.data
-            import torch
-            assert a.is_cuda and a.is_contiguous() and (records or (a.dtype == torch.float64 and a.dim() in dim))
-            keep.append(a)
-            return a, a.data_ptr()
-
-        if clear.get("polygons") is not None:
-            polygons, c.polygons = ptr(clear["polygons"], (3,))
-            assert polygons.shape[0] == count and polygons.shape[2] == 2
-            c.footprint_points = polygons.shape[1]
-        else:
-            footprint, c.footprint = ptr(clear["footprint"], (2, 3))
-            assert footprint.shape[-1] == 2 and (len(footprint.shape) == 2 or footprint.shape[0] == count)
-            c.footprint_points = footprint.shape[-2]
-            c.per_robot_footprints = 1 if len(footprint.shape) == 3 else 0
-            if clear.get("poses") is not None:
-                poses, c.poses = ptr(clear["poses"], (2,))
-                assert tuple(poses.shape) == (count, 3)
-            elif clear.get("problems") is not None:
-                problems, c.problems = ptr(clear["problems"], (), records=True)
-                assert problems.shape[0] == count
+        c.padding = float(clear.get("padding", 0.0))
+        c.count, keep = BatchSolver._outlines(c, on_host, clear.get("polygons"), clear.get("footprint"), clear.get("poses"),
+                                              clear.get("problems"), count=int(count))
         return c, keep
 
     def update_world_scan_layer(self, inscribed_radius, inflation_radius, cost_scaling_factor, points=None, sensor_origins=None,
@@ -530,13 +520,9 @@ class BatchSolver:
         """Projects the ranges as `project_laser` does and updates the fleet's shared layer on the world map from all
         scanners of all robots (K11 and K12).  Arguments as `update_scan_layer_from_ranges`; `clear` as
         `update_world_scan_layer`."""
-        b, keep, _, _, stream = self._laser_batch(ranges, poses, scanners, points_out, origins_out, False)
-        b.scan_flags = int(abi.SCAN_CLEAR | abi.SCAN_MARK if flags is None else flags)
-        b.unknown_value = int(unknown_value)
-        b.obstacle_max_range, b.obstacle_min_range = float(obstacle_max_range), float(obstacle_min_range)
-        b.raytrace_max_range, b.raytrace_min_range = float(raytrace_max_range), float(raytrace_min_range)
-        b.inscribed_radius, b.inflation_radius = float(inscribed_radius), float(inflation_radius)
-        b.cost_scaling_factor = float(cost_scaling_factor)
+        b, keep, stream = self._laser_update(ranges, poses, scanners, points_out, origins_out, flags, unknown_value,
+                                             obstacle_max_range, obstacle_min_range, raytrace_max_range, raytrace_min_range,
+                                             inscribed_radius, inflation_radius, cost_scaling_factor)
         c, keep_c = self._fleet_clear(clear, b.count, stream is None)
         cp = C.byref(c) if c is not None else None
         if stream is None:
