@@ -145,6 +145,7 @@ __global__ __launch_bounds__(kLanes) void k_carrot(const CarrotArgs a) {
     return;
   }
   // closest pose, first minimum (min_by, cpp:83-88)
+  const double fx = poses[0] - rx, fy = poses[1] - ry;   // (the first pose: loaded ahead of the stream, looked at behind it)
   double best = INFINITY;
   uint32_t besti = 0xffffffffu;
   uint32_t k = lane;
@@ -167,7 +168,12 @@ __global__ __launch_bounds__(kLanes) void k_carrot(const CarrotArgs a) {
     if (d < best) { best = d; besti = k; }
   }
   const double gmin = wave_min(best);
-  const uint32_t begin = (uint32_t)wave_min((best == gmin) ? (double)besti : 4.0e9);
+  uint32_t begin = (uint32_t)wave_min((best == gmin) ? (double)besti : 4.0e9);
+  // min_by starts at the first pose and moves on a strict `<` alone: nothing is below a first distance of NaN, and where no
+  // distance is below infinity no lane holds an index
+  // (a NaN component alone does not make the first distance NaN: hypot(NaN, inf) is inf, and the search moves on from it;
+  // the component test only keeps hypot off the common path)
+  if (!(gmin < INFINITY) || ((fx != fx || fy != fy) && isnan(hypot(fx, fy)))) begin = 0;
   out.closer_to_goal = hypot(poses[3 * (np - 1)] - rx, poses[3 * (np - 1) + 1] - ry) <=
                        a.lp.lookahead_dist_close_to_goal ? 1 : 0;       // cpp:95-100
   double la = a.lp.lookahead_dist_min;                                  // cpp:161-169

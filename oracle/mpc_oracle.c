@@ -1692,8 +1692,8 @@ static void orc_select_carrot(const neo_mpc_lookahead_params* lp, const double* 
   if (np == 0) { out->status = 1; return; }                             /* cpp:69-71 */
   const double rx = robot[0], ry = robot[1], rth = robot[2];
   uint32_t begin = 0;
-  double best = INFINITY;
-  for (uint32_t k = 0; k < np; ++k) {                                   /* min_by, cpp:83-88 */
+  double best = hypot(poses[0] - rx, poses[1] - ry);                    /* min_by starts at the first pose: a NaN there stays */
+  for (uint32_t k = 1; k < np; ++k) {                                   /* min_by, cpp:83-88 */
     double d = hypot(poses[3 * k] - rx, poses[3 * k + 1] - ry);
     if (d < best) { best = d; begin = k; }
   }

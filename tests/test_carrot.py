@@ -2,7 +2,8 @@
 (src/NeoMpcPlanner.cpp:83-104 plan pruning, 157-171 look-ahead distance, 173-189 look-ahead
 point, 221-232 slow_down_ state machine).  The C++ plugin cannot be built here (nav2/tf2 absent),
 so the oracle restatement (oracle/mpc_oracle.c part 3) is checked against an independent,
-literal NumPy transcription of those lines, and the HIP kernel against the oracle."""
+literal NumPy transcription of those lines (tests/carrot_reference.py), and the HIP kernel against the oracle and,
+on the constructed edge cases further down, against the transcription itself."""
 import math
 
 import numpy as np
@@ -10,43 +11,11 @@ import pytest
 
 from neo_mpc_planner2_amd import abi, synthetic
 from oracle import c_oracle
+from tests import carrot_reference as cref
+from tests.carrot_reference import transcription
 
 LP = dict(lookahead_dist_min=0.4, lookahead_dist_max=0.8, lookahead_dist_close_to_goal=0.3,
           max_transform_dist=5.0)
-
-
-def transcription(poses, robot, slow, fcost, lp):
-    """cpp:66-135, 157-189, 221-232 line by line for one robot (planar transform)."""
-    if len(poses) == 0:
-        return dict(status=1)
-    d = np.hypot(poses[:, 0] - robot[0], poses[:, 1] - robot[1])
-    begin = int(np.argmin(d))                                   # min_by: first minimum
-    closer = bool(d[-1] <= lp["lookahead_dist_close_to_goal"])
-    far = np.nonzero(d[begin:] > lp["max_transform_dist"])[0]
-    end = begin + int(far[0]) if len(far) else len(poses)
-    if end == begin:
-        return dict(status=2, begin=begin, end=end, closer=closer)
-    la = lp["lookahead_dist_min"]
-    if (not slow) or closer:
-        la = lp["lookahead_dist_max"]
-        if closer:
-            la = lp["lookahead_dist_close_to_goal"]
-    c, s = math.cos(robot[2]), math.sin(robot[2])
-    dx, dy = poses[begin:end, 0] - robot[0], poses[begin:end, 1] - robot[1]
-    lx, ly = c * dx + s * dy, -s * dx + c * dy
-    hit = np.nonzero(np.hypot(lx, ly) >= la)[0]
-    k = int(hit[0]) if len(hit) else end - begin - 1
-    yaw = poses[begin + k, 2] - robot[2]
-    yaw_w = math.atan2(math.sin(yaw), math.cos(yaw))            # what getRPY of the quaternion returns
-    if abs(yaw_w) < 1.0:
-        new_slow = 0
-    elif abs(yaw_w) >= 1.0 and fcost > 200:
-        new_slow = 1
-    else:
-        new_slow = 0
-    # cpp:234-236: `if (footprint_cost == 255) throw ...` -- after the slow_down_ update, before the optimizer request
-    return dict(status=3 if fcost == 255 else 0, begin=begin, end=end, closer=closer, la=la, xy=(lx[k], ly[k]), yaw=yaw_w,
-                slow=new_slow)
 
 
 def _inputs(count, seed):
@@ -254,3 +223,407 @@ def test_skip_fields_other_than_0_or_1_are_refused_on_host_batches():
         torch.cuda.synchronize()
         got = db.commands_host()
         assert (got["flags"] & abi.FLAG_SKIPPED == 0).all() and got.tobytes() == ref.tobytes()
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# K4 at its edges: constructed batches with exact arithmetic (tests/carrot_reference.py), non-finite inputs, the largest
+# shapes and a wide random batch -- the transcription is the reference, the oracle has to agree with it on the CPU and
+# the kernel on the GPU, through both entry points.
+INT_FIELDS = ("begin", "end", "closer_to_goal", "slow_down", "status", "reserved")
+PROBLEM_WRITES = ("carrot_xy", "carrot_q", "switch_opt", "skip")
+Q_ATOL = 1e-12          # the project's tolerance for what goes through sincos
+
+
+def _bits(got, want):
+    """Bit for bit; a NaN matches a NaN (its sign and payload are nobody's contract)."""
+    got, want = np.ascontiguousarray(got, dtype=np.float64), np.ascontiguousarray(want, dtype=np.float64)
+    return bool(((got.view(np.uint64) == want.view(np.uint64)) | (np.isnan(got) & np.isnan(want))).all())
+
+
+def _close(got, want, atol):
+    """|got - want| <= atol where `want` is finite, the same NaN / infinity pattern elsewhere."""
+    got, want = np.asarray(got, dtype=np.float64), np.asarray(want, dtype=np.float64)
+    fin = np.isfinite(want)
+    return bool((np.abs(got[fin] - want[fin]) <= atol).all()) and _bits(got[~fin], want[~fin])
+
+
+def _assert_carrots(got, want, exact):
+    for f in INT_FIELDS:
+        bad = np.nonzero(got[f] != want[f])[0]
+        assert len(bad) == 0, (f, bad[:5], got[f][bad[:5]], want[f][bad[:5]])
+    assert _bits(got["lookahead_dist"], want["lookahead_dist"])
+    assert _bits(got["xy"], want["xy"]) if exact else _close(got["xy"], want["xy"], 1e-12)
+    assert _close(got["q"], want["q"], Q_ATOL) and _bits(got["q"][:, :2], want["q"][:, :2])
+
+
+def _assert_problems(got, want, status, exact):
+    """The request records: the four fields K4 owns against the reference's, every other byte unchanged (the reference
+    started from the same byte pattern), rows that make no carrot (status 1, 2) unchanged apart from `skip`."""
+    assert (got["skip"] == want["skip"]).all() and (got["switch_opt"] == want["switch_opt"]).all()
+    assert _bits(got["carrot_xy"], want["carrot_xy"]) if exact else _close(got["carrot_xy"], want["carrot_xy"], 1e-12)
+    assert _close(got["carrot_q"], want["carrot_q"], Q_ATOL)
+    made = (status == 0) | (status == 3)
+    assert (got["carrot_q"][made, :2] == 0.0).all() and not np.signbit(got["carrot_q"][made, :2]).any()
+    assert got[~made].tobytes() == want[~made].tobytes()
+    rest = got.copy()
+    for f in PROBLEM_WRITES:
+        rest[f] = want[f]
+    assert rest.tobytes() == want.tobytes()
+
+
+_REFERENCES = {}
+
+
+def _reference(key, batch, fcost=True, problems=True):
+    """(carrots, picks, slow_down after, problems after) of the transcription: computed once, never written again."""
+    key = (key, fcost, problems)
+    if key not in _REFERENCES:
+        slow = batch["slow"].copy()
+        probs = cref.fill_problems(len(slow)) if problems else None
+        car, picks = cref.select_carrots(batch["poses"], batch["offsets"], batch["robots"], slow,
+                                         batch["fcost"] if fcost else None, probs, batch["lp"])
+        for a in (car, picks, slow, probs):
+            if a is not None:
+                a.flags.writeable = False
+        _REFERENCES[key] = (car, picks, slow, probs)
+    return _REFERENCES[key]
+
+
+def _check(run, key, batch, exact, fcost=True, problems=True):
+    """`run(batch, fcost, problems)` -> (carrots, slow_down, problems) against the reference."""
+    want, _, want_slow, want_probs = _reference(key, batch, fcost, problems)
+    got, slow, probs = run(batch, fcost, problems)
+    _assert_carrots(got, want, exact)
+    assert (slow == want_slow).all()
+    if problems:
+        _assert_problems(probs, want_probs, want["status"], exact)
+    return got
+
+
+def _run_oracle(batch, fcost=True, problems=True):
+    slow = batch["slow"].copy()
+    probs = cref.fill_problems(len(slow)) if problems else None
+    got = c_oracle.select_carrots(batch["poses"], batch["offsets"], batch["robots"], slow,
+                                  batch["fcost"] if fcost else None, problems=probs, **batch["lp"])
+    return got, slow, probs
+
+
+def _lengths(batch):
+    return np.diff(batch["offsets"].astype(np.int64))
+
+
+def _front(batch):
+    """Distance of every pose of a constructed batch from its robot, exact: |x - ROBOT_X| on the line."""
+    return np.abs(batch["poses"][:, 0] - cref.ROBOT_X)
+
+
+CONSTRUCTED = ("lengths", "ties", "scan_wide", "scan_tight", "equality", "slow", "empty", "all_empty", "one")
+
+
+def test_constructed_batches_names():
+    assert tuple(cref.constructed()) == CONSTRUCTED
+
+
+@pytest.mark.parametrize("name", CONSTRUCTED)
+def test_oracle_matches_transcription_on_constructed_cases(name):
+    _check(_run_oracle, name, cref.constructed()[name], exact=True)
+    if name in ("slow", "empty"):
+        for fcost, problems in ((True, False), (False, True), (False, False)):
+            _check(_run_oracle, name, cref.constructed()[name], exact=True, fcost=fcost, problems=problems)
+
+
+def test_constructed_lengths_cover_every_loop_of_the_search():
+    """Every listed plan length crossed with every listed closest index inside it, pick offset 1, no cut -- counted on the
+    reference's output."""
+    batch = cref.constructed()["lengths"]
+    car, picks, _, _ = _reference("lengths", batch)
+    n = _lengths(batch)
+    have = set(zip(n.tolist(), car["begin"].tolist()))
+    need = {(L, b) for L in cref.LENGTHS for b in cref.BEGINS + (L - 2, L - 1) if 0 <= b < L}
+    assert have == need and len(car) == len(need) and set(n.tolist()) == set(cref.LENGTHS)
+    assert (car["status"] == 0).all() and (car["end"] == n).all()
+    assert (picks == np.minimum(car["begin"] + 1, n - 1)).all()
+    # the minimum in each of the four unrolled candidates of the first and of the second trip, and in the remainder loop
+    unrolled = lambda L, b: (b // 256) * 256 + 192 + b % 64 < L
+    for trip in (0, 1):
+        assert {(b % 256) // 64 for L, b in have if b // 256 == trip and unrolled(L, b)} == {0, 1, 2, 3}
+    assert sum(1 for L, b in have if not unrolled(L, b)) >= 50
+
+
+def test_constructed_ties_repeat_the_closest_pose():
+    batch = cref.constructed()["ties"]
+    car, _, _, _ = _reference("ties", batch)
+    gaps, copies = set(), set()
+    for i, (length, ties) in enumerate(cref.TIES):
+        plan = batch["poses"][batch["offsets"][i]:batch["offsets"][i + 1]]
+        same = np.nonzero((plan == plan[car["begin"][i]]).all(axis=1))[0]
+        d = _front(batch)[batch["offsets"][i]:batch["offsets"][i + 1]]
+        assert len(plan) == length and same.tolist() == list(ties)
+        assert len(same) == length or d[same].max() < np.delete(d, same).min()
+        assert car["begin"][i] == same[0] == ties[0] and car["status"][i] == 0
+        gaps.update((int(b - a), int(a % 64 < b % 64)) for a, b in zip(same[:-1], same[1:]))
+        copies.add(len(same) if len(same) < length else "all")
+    # one lane 64 apart, one lane two trips apart, neighbouring lanes, the later copy in a lower lane
+    assert {(64, 0), (256, 0), (1, 1)} <= gaps and any(up == 0 and g % 64 for g, up in gaps)
+    assert {2, 3, "all"} <= copies and max(c for c in copies if c != "all") >= 50
+    assert sum(1 for length, ties in cref.TIES if len(ties) == length and length > 1) >= 4
+
+
+@pytest.mark.parametrize("name", ("scan_wide", "scan_tight"))
+def test_constructed_scans_place_pick_and_end_where_their_tags_say(name):
+    """Tag (b, p, e): pose b+p is the first at least a look-ahead away, pose b+e the first beyond the cut-off -- checked
+    on the inputs with the reference's look-ahead distance, and the reference's begin / pick / end follow from them."""
+    batch = cref.constructed()[name]
+    car, picks, _, _ = _reference(name, batch)
+    d, n, lp = _front(batch), _lengths(batch), batch["lp"]
+    for i, (b, p, e) in enumerate(batch["tags"]):
+        o = int(batch["offsets"][i])
+        assert car["begin"][i] == b
+        far = np.nonzero(d[o + b:o + n[i]] > lp["max_transform_dist"])[0]
+        assert (far[0] == e) if e is not None else len(far) == 0
+        end = b + e if e is not None else n[i]
+        assert car["end"][i] == end
+        if e == 0:
+            assert car["status"][i] == 2 and car["lookahead_dist"][i] == 0.0 and picks[i] == -1
+            assert car["closer_to_goal"][i] == (name == "scan_tight")
+            continue
+        hit = np.nonzero(d[o + b:o + n[i]] >= car["lookahead_dist"][i])[0]
+        assert (hit[0] == p) if p is not None else len(hit) == 0
+        assert car["status"][i] == 0 and picks[i] == (b + p if p is not None and b + p < end else end - 1)
+    tags = set(batch["tags"])
+    if name == "scan_wide":
+        assert tags == {(b, p, e) for b in cref.SCAN_BEGINS for p, e in cref.SCAN_WIDE + [(None, 0)]}
+        same = lambda p, e: p // 64 == e // 64
+        pe = [(p, e) for p, e in cref.SCAN_WIDE if p is not None and e is not None]
+        assert {p for p, e in cref.SCAN_WIDE if e is None} == {0, 1, 63, 64, 65, 130, None}
+        assert any(p < e and same(p, e) for p, e in pe) and any(p < e - 1 and not same(p, e) for p, e in pe)
+        assert sum(p == e for p, e in pe) >= 3 and any(e == p + 1 and not same(p, e) for p, e in pe)
+        assert (1, 1) in cref.SCAN_WIDE and (0, 1) in cref.SCAN_WIDE
+    else:
+        assert tags == {(b, p, e) for b in cref.SCAN_BEGINS for e, p in cref.SCAN_TIGHT + [(0, None)]}
+        ep = [(e, p) for e, p in cref.SCAN_TIGHT if p is not None]
+        assert any(e // 64 == p // 64 and e < p for e, p in ep) and any(e // 64 + 1 == p // 64 for e, p in ep)
+        assert sum(p is None for e, p in cref.SCAN_TIGHT) >= 2
+
+
+def test_constructed_equalities_and_lookahead_table():
+    batch = cref.constructed()["equality"]
+    car, picks, _, _ = _reference("equality", batch)
+    d, lp = _front(batch), batch["lp"]
+    table = set()
+    for i, (_, sd, closer) in enumerate(batch["tags"]):
+        assert batch["slow"][i] == sd and car["closer_to_goal"][i] == closer and car["status"][i] == 0
+        table.add((sd, closer, float(car["lookahead_dist"][i])))
+    assert table == {(0, 0, lp["lookahead_dist_max"]), (1, 0, lp["lookahead_dist_min"]),
+                     (0, 1, lp["lookahead_dist_close_to_goal"]), (1, 1, lp["lookahead_dist_close_to_goal"])}
+    assert len({lp["lookahead_dist_max"], lp["lookahead_dist_min"], lp["lookahead_dist_close_to_goal"]}) == 3
+    for g in (0, 3):
+        o = batch["offsets"][g:g + 3].astype(np.int64)
+        # the picked pose is exactly a look-ahead away, the one before it is not; the last kept pose exactly at the cut-off
+        assert d[o[0] + picks[g]] == car["lookahead_dist"][g] and d[o[0] + picks[g] - 1] < car["lookahead_dist"][g]
+        assert d[o[0] + car["end"][g] - 1] == lp["max_transform_dist"] and car["end"][g] < _lengths(batch)[g]
+        # the goal one grid step beyond close_to_goal: not closer; exactly at it: closer, whatever slow_down was
+        assert d[o[2] - 1] == lp["lookahead_dist_close_to_goal"] + cref.EPS and not car["closer_to_goal"][g + 1]
+        assert d[o[2] + _lengths(batch)[g + 2] - 1] == lp["lookahead_dist_close_to_goal"] and car["closer_to_goal"][g + 2]
+        assert d[o[2] + picks[g + 2]] == lp["lookahead_dist_close_to_goal"] and picks[g + 2] < _lengths(batch)[g + 2] - 1
+
+
+def test_constructed_slow_down_and_throw():
+    batch = cref.constructed()["slow"]
+    car, _, slow, _ = _reference("slow", batch)
+    cost = np.array([t[0] for t in batch["tags"]])
+    yaw = np.array([t[1] for t in batch["tags"]])
+    wrapped = np.abs(np.arctan2(np.sin(yaw), np.cos(yaw)))
+    assert (np.abs(wrapped - 1.0) >= 1e-6).all() and set(cost.tolist()) == set(cref.COSTS) and 200.0 < cref.COSTS[2] < 200.1
+    assert {2.0 * math.pi - 0.5, -(2.0 * math.pi - 0.5), math.pi + 0.2, -(math.pi + 0.2)} <= set(yaw.tolist())
+    assert ((wrapped < 1.0) & (np.abs(yaw) > 1.0)).any() and ((wrapped > 1.0) & (np.abs(yaw) > math.pi)).any()
+    want = ((wrapped >= 1.0) & (cost > 200.0)).astype(np.int32)
+    assert (car["slow_down"] == want).all() and (slow == want).all()
+    assert ((car["status"] == 3) == (cost == 255.0)).all() and set(car["status"].tolist()) == {0, 3}
+    thrown = car["status"] == 3
+    assert ((slow != batch["slow"]) & thrown & (slow == 1)).any() and ((slow != batch["slow"]) & thrown & (slow == 0)).any()
+    # without footprint costs: no slow-down, no throw
+    car0, _, slow0, _ = _reference("slow", batch, fcost=False)
+    assert (car0["status"] == 0).all() and (slow0 == 0).all()
+
+
+def test_constructed_empty_plans():
+    batch = cref.constructed()["empty"]
+    car, _, slow, probs = _reference("empty", batch)
+    assert car["status"].tolist() == [1, 0, 1, 3, 1] and (_lengths(batch) == 0).tolist() == [True, False, True, False, True]
+    none = cref.constructed()["all_empty"]
+    car, _, slow, probs = _reference("all_empty", none)
+    assert none["offsets"][-1] == 0 and len(none["poses"]) == 0 and (car["status"] == 1).all()
+    assert (slow == none["slow"]).all() and (probs["skip"] == 1).all()
+    assert none["poses"].ctypes.data != 0      # (an empty array still has an address: the entry points refuse a null one)
+    assert len(cref.constructed()["one"]["robots"]) == 1
+
+
+def test_problem_pattern_marks_skip_on_robots_that_make_a_request():
+    """Record hygiene needs robots that come in with skip = 1 and go out with status 0."""
+    for name in ("lengths", "scan_wide", "slow"):
+        car, _, _, probs = _reference(name, cref.constructed()[name])
+        before = cref.fill_problems(len(car))
+        assert ((before["skip"] == 1) & (car["status"] == 0)).sum() >= 10 and (probs["skip"] == (car["status"] != 0)).all()
+        assert np.isfinite(before["carrot_xy"]).all() and (before["carrot_xy"] != 0.0).all()
+
+
+def test_oracle_matches_transcription_on_non_finite_inputs():
+    with_bad, without, bad, keep = cref.nonfinite()
+    got = _check(_run_oracle, "nonfinite", with_bad, exact=True)
+    clean = _check(_run_oracle, "nonfinite_without", without, exact=True)
+    want = _reference("nonfinite", with_bad)[0]
+    by = dict(zip(cref.NONFINITE, bad))
+    # min_by keeps the first pose where no distance compares `<`; a NaN pose further on is passed over
+    for kind in ("robot_nan", "robot_inf_x", "plan_all_nan", "plan_first_nan"):
+        assert want["begin"][by[kind]] == 0, kind
+    assert want["begin"][by["plan_one_nan"]] == 70 and want["begin"][by["robot_nan_yaw"]] == 70
+    assert want["begin"][by["plan_first_inf_nan"]] == 70          # hypot(inf, NaN) is inf: the search moves on from it
+    assert want["status"][by["robot_inf_x"]] == 2 and np.isnan(want["xy"][by["robot_nan"]]).all()
+    assert np.isnan(want["q"][by["robot_nan_yaw"]][2:]).all() and want["slow_down"][by["robot_nan_yaw"]] == 0
+    assert (np.diff(bad) == 2).all() and bad[0] == 1 and bad[-1] == len(want) - 2      # each between two ordinary robots
+    assert got[keep].tobytes() == clean.tobytes() and np.isfinite(clean["xy"]).all()
+
+
+def test_oracle_matches_transcription_at_the_largest_shapes():
+    long_, many = cref.sizes()
+    _check(_run_oracle, "long", long_, exact=True)
+    _check(_run_oracle, "many", many, exact=True)
+    car = _reference("long", long_)[0]
+    assert _lengths(long_).tolist() == [100000, 100000] and car["begin"].tolist() == [99997, 70001]
+    car = _reference("many", many)[0]
+    assert len(car) == 70000 and (_lengths(many) == 2).all() and set(car["begin"].tolist()) == {0, 1}
+    assert set(car["status"].tolist()) == {0, 3}
+
+
+def _made_request(car):
+    return (car["status"] == 0) | (car["status"] == 3)
+
+
+def _random_checks(batch, car):
+    for status in (0, 1, 2, 3):
+        assert (car["status"] == status).sum() >= 100, status
+    made = _made_request(car)
+    cut = car["end"][made] < _lengths(batch)[made]
+    assert cut.mean() >= 0.25 and (~cut).mean() >= 0.25, cut.mean()
+    assert (car["closer_to_goal"] == 1).sum() >= 100 and len(car) == cref.RANDOM_COUNT
+
+
+def test_oracle_matches_transcription_on_the_wide_random_batch():
+    batch = cref.random_batch()
+    _check(_run_oracle, "random", batch, exact=False)
+    car = _reference("random", batch)[0]
+    _random_checks(batch, car)
+    n = _lengths(batch)
+    assert n.min() == 0 and n[n > 0].min() == 1 and n.max() > 1200 and (n > 448).sum() > 1000
+    tags = np.array(batch["tags"])
+    doubled = np.isin(tags, (2, 3)) & _made_request(car)
+    assert doubled.sum() >= 200
+
+
+# ---- on the GPU
+@pytest.fixture(scope="module")
+def k4():
+    """One solver handle for the module and the two ways into K4: `run(batch, fcost, problems)` -> (carrots, slow_down,
+    problems) through neo_mpc_select_carrots, and through neo_mpc_select_carrots_device on a stream of its own."""
+    import torch
+    from neo_mpc_planner2_amd.solver import BatchSolver
+
+    with BatchSolver({}) as s:
+        def host(batch, fcost=True, problems=True):
+            slow = batch["slow"].copy()
+            probs = cref.fill_problems(len(slow)) if problems else None
+            got = s.select_carrots(batch["poses"], batch["offsets"], batch["robots"], slow,
+                                   batch["fcost"] if fcost else None, problems=probs, **batch["lp"])
+            return got, slow, probs
+
+        def device(batch, fcost=True, problems=True):
+            dev = "cuda:0"
+            count = len(batch["slow"])
+            t = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)
+            poses = batch["poses"] if len(batch["poses"]) else np.zeros((1, 3))   # (a null plan_poses is refused)
+            d_poses, d_off, d_rob, d_slow = t(poses), t(batch["offsets"].view(np.int32)), t(batch["robots"]), t(batch["slow"])
+            d_fc = t(batch["fcost"]) if fcost and batch["fcost"] is not None else None
+            d_probs = t(cref.fill_problems(count).view(np.uint8).reshape(count, -1)) if problems else None
+            d_car = torch.full((count, abi.CARROT_DTYPE.itemsize), 0xEE, dtype=torch.uint8, device=dev)
+            lp = abi.NeoMpcLookaheadParams(*(batch["lp"][k] for k in ("lookahead_dist_min", "lookahead_dist_max",
+                                                                     "lookahead_dist_close_to_goal", "max_transform_dist")))
+            stream = torch.cuda.Stream(device=dev)
+            stream.wait_stream(torch.cuda.current_stream(dev))
+            s.select_carrots_device(lp, d_poses, d_off, d_rob, d_slow, d_car, d_fc, problems=d_probs,
+                                    stream=stream.cuda_stream)
+            stream.synchronize()
+            got = d_car.cpu().numpy().reshape(-1).view(abi.CARROT_DTYPE).copy()
+            probs = d_probs.cpu().numpy().reshape(-1).view(abi.PROBLEM_DTYPE).copy() if problems else None
+            return got, d_slow.cpu().numpy(), probs
+
+        yield dict(host=host, device=device, solver=s)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("entry", ("host", "device"))
+@pytest.mark.parametrize("name", CONSTRUCTED)
+def test_carrot_kernel_matches_transcription_on_constructed_cases(k4, name, entry):
+    """Integer fields, lookahead_dist and xy bit for bit, q within 1e-12, the whole record for every status, the caller's
+    slow_down, and the request records byte for byte outside the four fields K4 owns."""
+    _check(k4[entry], name, cref.constructed()[name], exact=True)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("entry", ("host", "device"))
+@pytest.mark.parametrize("fcost,problems", ((True, False), (False, True), (False, False)))
+def test_carrot_kernel_without_footprint_costs_or_problems(k4, entry, fcost, problems):
+    """footprint_costs == NULL: no slow-down and no throw; problems == NULL: nothing but carrots and slow_down."""
+    for name in ("slow", "empty"):
+        _check(k4[entry], name, cref.constructed()[name], exact=True, fcost=fcost, problems=problems)
+
+
+@pytest.mark.gpu
+def test_carrot_entry_points_with_no_robot(k4):
+    """count = 0 with every pointer null: both entry points answer NEO_MPC_OK (the return code is all that is observed
+    here: with no pointer there is nothing a launch could have written to)."""
+    import ctypes as C
+    import torch
+    from neo_mpc_planner2_amd import _lib
+    lib = _lib.load()
+    lp = abi.NeoMpcLookaheadParams(0.5, 1.0, 0.25, 4.0)
+    b = abi.NeoMpcPlanBatch()          # count 0, every pointer null
+    handle = k4["solver"]._handle
+    assert lib.neo_mpc_select_carrots(handle, C.byref(lp), C.byref(b)) == 0
+    stream = torch.cuda.Stream(device="cuda:0")
+    assert lib.neo_mpc_select_carrots_device(handle, C.byref(lp), C.byref(b), C.c_void_p(stream.cuda_stream)) == 0
+    stream.synchronize()
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("entry", ("host", "device"))
+def test_carrot_kernel_on_non_finite_inputs(k4, entry):
+    """A robot pose of NaN, +inf in x, a NaN yaw; a plan of NaN poses, one NaN pose among good ones, a NaN first pose, a
+    first pose of (inf, NaN) whose distance is infinite and not NaN: the reference's record (`begin` = 0 where no distance compares `<`: the plugin erases the plan's head with it), and the
+    robots on either side come out bit for bit as in a call without the offenders."""
+    with_bad, without, bad, keep = cref.nonfinite()
+    got = _check(k4[entry], "nonfinite", with_bad, exact=True)
+    clean = _check(k4[entry], "nonfinite_without", without, exact=True)
+    assert got[keep].tobytes() == clean.tobytes()
+
+
+@pytest.mark.gpu
+def test_carrot_kernel_at_the_largest_shapes(k4):
+    """100 000 poses in one plan (391 trips of the unrolled search, the closest pose third from the end, and a copy of it
+    earlier in the plan), and 70 000 robots (check_count allows them: its limit is 2^31 - 1)."""
+    long_, many = cref.sizes()
+    _check(k4["host"], "long", long_, exact=True)
+    _check(k4["device"], "long", long_, exact=True)
+    _check(k4["host"], "many", many, exact=True)
+    _check(k4["device"], "many", many, exact=True)
+
+
+@pytest.mark.gpu
+def test_carrot_kernel_matches_transcription_on_the_wide_random_batch(k4):
+    """Plans of 0 to 2400 poses, robots far from everything and at the goal, plans doubled back over themselves (every
+    pose twice: the first of equal minima), about half of the plans cut: integer fields and lookahead_dist equal, xy and
+    q within 1e-12."""
+    batch = cref.random_batch()
+    _random_checks(batch, _reference("random", batch)[0])
+    _check(k4["host"], "random", batch, exact=False)
+    _check(k4["device"], "random", batch, exact=False)
