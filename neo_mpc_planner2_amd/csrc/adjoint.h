@@ -22,9 +22,12 @@ namespace {
 // exact_step: the stage records carry the position costates (second-order terms of the rollout step, riccati.h).
 // free_path: every stage of the rollout at u sits in a free cell; nhops: hop candidates in the tolerance block's table.
 // kFew > 0: control_steps == kFew at compile time (at most 16): the prefix sums stop after the DPP steps that reach the stages
-template <bool kTame, bool kRiccati, int kFew = 0>
+// kCovered: the reach tile covers every lookup of the wall model (costmap.h edge_stickiness: its reads issued together)
+// carry (kFew kernels, or null): lane = stage fetches its block of u and of the smooth gradient for the tangent-cone pass
+// (solver_context.h StageCarry) at its own end, under the hop table and the barrier
+template <bool kTame, bool kRiccati, int kFew = 0, bool kCovered = false>
 __device__ __forceinline__ void adjoint_by_scans(const SolveArgs& a, const Ctx& c, double* L, bool exact_step, int lane, int n,
-                                                 bool& free_path, int& nhops) {
+                                                 bool& free_path, int& nhops, StageCarry* carry = nullptr) {
   auto scan = [](double v) { if constexpr (kFew > 0) return wave_scan_few<kFew>(v); else return wave_scan(v); };
   constexpr int kLast = kFew > 0 ? kFew - 1 : 63;   // (the lane that holds a prefix sum's total)
   const DevParams& p = a.p;
@@ -63,7 +66,7 @@ __device__ __forceinline__ void adjoint_by_scans(const SolveArgs& a, const Ctx& 
       float* rs = RS + kRicStage * lane;
       rs[RS_CS] = (float)cs; rs[RS_SN] = (float)sn; rs[RS_PX] = (float)ddx; rs[RS_PY] = (float)ddy;
       double wxx, wxy, wyy, wlx, wly;
-      raw_here = edge_stickiness(a, c, L, x, y, cs, sn, wxx, wxy, wyy, wlx, wly, has_hop, hop_x, hop_y);
+      raw_here = edge_stickiness<kCovered>(a, c, L, x, y, cs, sn, wxx, wxy, wyy, wlx, wly, has_hop, hop_x, hop_y);
       rs[RS_WXX] = (float)wxx; rs[RS_WXY] = (float)wxy; rs[RS_WYY] = (float)wyy;
       rs[RS_WLX] = (float)wlx; rs[RS_WLY] = (float)wly;
       // position costates of this stage, for the second-order terms of the rollout step (riccati.h): only behind an
@@ -71,6 +74,16 @@ __device__ __forceinline__ void adjoint_by_scans(const SolveArgs& a, const Ctx& 
       // indefinite and the Gauss-Newton direction is the safer one
       rs[RS_SY] = exact_step ? (float)SY : 0.0f;
       ARTF[2 * lane + 1] = exact_step ? (float)SX : 0.0f;
+    }
+    if (kFew > 0 && carry) {
+      // (the lane's block of u and of gs once more, behind the wall model -- the kernel's register peak, across which six
+      // more doubles do not fit -- through an offset the compiler cannot see through, or it keeps the first copies instead:
+      // the loads are on their way under the hop table and the barrier below, and the cone pass starts without a round
+      // trip of its own)
+      int off = 3 * lane;
+      asm volatile("" : "+v"(off));
+      carry->u0 = u[off]; carry->u1 = u[off + 1]; carry->u2 = u[off + 2];
+      carry->g0 = gs[off]; carry->g1 = gs[off + 1]; carry->g2 = gs[off + 2];
     }
   }
   if (kRiccati) {

@@ -110,21 +110,48 @@ __device__ __forceinline__ int edge_stickiness(const SolveArgs& a, const Ctx& c,
   // (position inside the cell, in cells: by the reciprocal -- distances to an edge are compared with 0.01 ... 0.25)
   const double fx = (X - a.map.origin_x) * a.map.inv_resolution - (double)mx;
   const double fy = (Y - a.map.origin_y) * a.map.inv_resolution - (double)my;
-  const int raw_here = cell_raw<kCovered>(a, c, L, mx, my);
-  const double here = L[a.lds.term + raw_here];
+  // The chain of LDS reads.  Serial form: hop range, own cell byte, its table word, then behind each axis' divergent branch the
+  // neighbour's byte and its table word -- five or six dependent round trips, and a lone wave pays each in full.  Which
+  // neighbour an axis wants (mx - 1 or mx + 1) follows from fx and the zone alone, and `xlo ? mx - 1 : mx + 1` names the high
+  // neighbour where neither side is in the zone: a cell the tile of a kCovered kernel holds all the same (it covers every
+  // reachable cell AND its neighbours), read and not used.  kCovered: the two tolerance words first, under the cell
+  // arithmetic; the three bytes with one wait; the three table words with one wait; the branches consume the copies.  The
+  // empty asm holds the loads where they are (left alone they sink back into the arms).  The other kernels keep the
+  // serial form: a neighbour's byte may have to come from the global map.
+  double hop_range, drop;   // (drop: the best drop so far)
+  if (kCovered) { hop_range = L[a.lds.tol + T_HOP_RANGE]; drop = L[a.lds.tol + T_HOP_DROP]; }
+  int raw_here, raw_nx = 0, raw_ny = 0;
+  double here, there_x = 0.0, there_y = 0.0;
+  if (kCovered) {
+    // (tile coordinates in unsigned arithmetic: a saturated cell index wraps without overflow; LDS reads beyond the
+    // allocation return zero, and `far` below discards them)
+    const double zone0 = fmax(kWallDist, hop_range);
+    const unsigned tx = (unsigned)mx - (unsigned)c.tile_x0, ty = (unsigned)my - (unsigned)c.tile_y0;
+    const unsigned ntx = fx < zone0 ? tx - 1u : tx + 1u, nty = fy < zone0 ? ty - 1u : ty + 1u;
+    const int lg = c.tile_geom & 31;
+    const uint8_t* tile = reinterpret_cast<const uint8_t*>(L + a.lds.tile);
+    raw_here = tile[(ty << lg) + tx]; raw_nx = tile[(ty << lg) + ntx]; raw_ny = tile[(nty << lg) + tx];
+    asm volatile("" : "+v"(raw_here), "+v"(raw_nx), "+v"(raw_ny));
+    here = L[a.lds.term + raw_here]; there_x = L[a.lds.term + raw_nx]; there_y = L[a.lds.term + raw_ny];
+    asm volatile("" : "+v"(here), "+v"(there_x), "+v"(there_y));
+  } else {
+    raw_here = cell_raw<false>(a, c, L, mx, my);
+    here = L[a.lds.term + raw_here];
+  }
   // (saturated cell indices -- positions far outside every map -- wrap in mx +- 1; such cells read lethal
   // on both sides, so no edge is sticky there)
   const bool far = mx <= -2147483647 || mx >= 2147483646 || my <= -2147483647 || my >= 2147483646;
   if (far) return raw_here;
   // at most one edge per axis can be within the (wider) wall / hop zone: the low side (push back along +axis) or the high side
-  const double hop_range = L[a.lds.tol + T_HOP_RANGE];
+  if (!kCovered) hop_range = L[a.lds.tol + T_HOP_RANGE];
   const double zone = fmax(kWallDist, hop_range);
   const bool xlo = fx < zone, xhi = 1.0 - fx < zone, ylo = fy < zone, yhi = 1.0 - fy < zone;
   double rx = 0.0, ry = 0.0, pbx = 0.0, pby = 0.0;
-  double drop = L[a.lds.tol + T_HOP_DROP], hwx = 0.0, hwy = 0.0;   // best drop so far, hop in world axes (metres)
+  if (!kCovered) drop = L[a.lds.tol + T_HOP_DROP];
+  double hwx = 0.0, hwy = 0.0;   // hop in world axes (metres)
   if (xlo || xhi) {
-    const int raw_n = cell_raw<kCovered>(a, c, L, xlo ? mx - 1 : mx + 1, my);
-    const double dist = xlo ? fx : 1.0 - fx, there = L[a.lds.term + raw_n];
+    const int raw_n = kCovered ? raw_nx : cell_raw<false>(a, c, L, xlo ? mx - 1 : mx + 1, my);
+    const double dist = xlo ? fx : 1.0 - fx, there = kCovered ? there_x : L[a.lds.term + raw_n];
     const bool wall = raw_n == 254 && raw_here != 254;
     if (wall) { if (dist < kWallDist) { rx = kWall * 2.0 * wt_n; pbx = (xlo ? kWallDist - dist : dist - kWallDist) * a.map.resolution; } }
     else if (dist < kStickyDist && there > here) rx = kSticky * 2.0 * wt_n;
@@ -134,8 +161,8 @@ __device__ __forceinline__ int edge_stickiness(const SolveArgs& a, const Ctx& c,
     }
   }
   if (ylo || yhi) {
-    const int raw_n = cell_raw<kCovered>(a, c, L, mx, ylo ? my - 1 : my + 1);
-    const double dist = ylo ? fy : 1.0 - fy, there = L[a.lds.term + raw_n];
+    const int raw_n = kCovered ? raw_ny : cell_raw<false>(a, c, L, mx, ylo ? my - 1 : my + 1);
+    const double dist = ylo ? fy : 1.0 - fy, there = kCovered ? there_y : L[a.lds.term + raw_n];
     const bool wall = raw_n == 254 && raw_here != 254;
     if (wall) { if (dist < kWallDist) { ry = kWall * 2.0 * wt_n; pby = (ylo ? kWallDist - dist : dist - kWallDist) * a.map.resolution; } }
     else if (dist < kStickyDist && there > here) ry = kSticky * 2.0 * wt_n;

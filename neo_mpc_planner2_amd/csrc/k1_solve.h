@@ -270,6 +270,9 @@ __device__ __forceinline__ bool solve_search(double* L, uint32_t b, SolveCarry& 
   // know each stage's case as a scalar before the sweep starts
   constexpr bool kHandOff = kFew > 0;
   constexpr bool kScalarCase = kFew > 0 && kTame;
+  // ... and lane = stage fetches what the tangent-cone pass reads of its block at the END of the adjoint pass (adjoint.h)
+  constexpr bool kStageCarry = kFew > 0 && kTame;
+  constexpr bool kAcceptFetch = kFew > 0 && kTame;
   // Newton: control_steps == kSteps, or (kSteps == 0) any control_steps <= kNewtonMaxSteps -- the
   // system's arrays are sized for the bound and every loop over them is guarded by the run-time size
   constexpr int kNwSteps = !kNewton ? 1 : kSteps ? kSteps : kNewtonMaxSteps;
@@ -385,6 +388,7 @@ __device__ __forceinline__ bool solve_search(double* L, uint32_t b, SolveCarry& 
     float newton_sol = 0.0f;  // Newton: entry `lane` of the direction
     float dm_reg = 0.0f;                // kHandOff: the step test's maximum over this lane's three entries of d (riccati_finish)
     int near_reg = 0;                   // ... and the near word of the lane's stage
+    StageCarry carry = {};              // kStageCarry: the cone pass' operands, fetched at the adjoint pass' end
     if (kNewton) {
       double hcol[kSteps ? kVars : 1];  // control_steps specialisation: gradient of this lane's perturbed copy
       // Every lane runs the rollout + adjoint sweep on its own copy of u: lane k < 3N perturbs
@@ -448,12 +452,12 @@ __device__ __forceinline__ bool solve_search(double* L, uint32_t b, SolveCarry& 
       }
       WAVE_SYNC();
     }
-    else if (!kSteps || kRiccati) adjoint_by_scans<kTame, kRiccati, kFew>(a, c, L, exact_step, lane, n, free_path, nhops);
+    else if (!kSteps || kRiccati) adjoint_by_scans<kTame, kRiccati, kFew, kCovered>(a, c, L, exact_step, lane, n, free_path, nhops, kStageCarry ? &carry : nullptr);
     else adjoint_short_sweep<kSteps, kTame>(a, c, L, have_trig, lane, n);
     NEO_PHASE(1);
     // ---- total gradient (control norm: minimal-norm subgradient at the kink), tangent-cone reduction at active bounds,
     //      face records of the second-order directions (tangent_cone.h)
-    const bool my_corner = tangent_cone_pass<kTame, kNewton, kRiccati>(a, c, L, TOL[T_KINK], lane, n);
+    const bool my_corner = tangent_cone_pass<kTame, kNewton, kRiccati>(a, c, L, TOL[T_KINK], lane, n, kStageCarry ? &carry : nullptr);
     WAVE_SYNC();
     // (in free space only -- no costmap term under the iterate's rollout: next to a cost step the Newton model is off either
     // way; the dense kernel knows that sum from the previous iteration's winner)
@@ -642,12 +646,24 @@ __device__ __forceinline__ bool solve_search(double* L, uint32_t b, SolveCarry& 
     // stage-wise: under the rollout the iteration started from)
     const bool free_rollout = kBlockedRule ? lane_value(cterm, best) == 0.0 : false;
     const bool free_now = kRiccati ? free_path : (kNewton ? free_rollout : false);
+    // (three tame stages: the rule book's seven tolerance words are launch parameters -- the set-up copied them into the
+    // tolerance block word for word -- and this phase reads them where they came from: one scalar fetch through the
+    // kernel-argument pointer, one wait, and scalar operands, instead of an LDS round trip behind each of the rule book's
+    // conditions; nothing of it is held across the loop)
+    double tolk[NEO_TOL_COUNT] = {};
+    if (kAcceptFetch) {
+      auto kp = (const __attribute__((address_space(4))) char*)__builtin_amdgcn_kernarg_segment_ptr();
+      asm volatile("" : "+s"(kp));
+      const DevParams& q = ((const SolveArgs*)kp)->p;
+      tolk[NEO_TOL_XTOL] = q.xtol; tolk[NEO_TOL_FTOL] = q.ftol; tolk[NEO_TOL_STALL] = q.stall_step; tolk[NEO_TOL_WTOL] = q.wtol;
+      tolk[NEO_TOL_WTOL_LATE] = q.wtol_late; tolk[NEO_TOL_BTOL_MAP] = q.btol_map; tolk[NEO_TOL_BTOL_FREE] = q.btol_free;
+    }
     if (kFew) { run.gain1 = TOL[T_GAIN1]; run.gain2 = TOL[T_GAIN2]; }
     // (the gain is wave-uniform but comes out of the vector ALU.  Dense direction: it goes on as a scalar -- the two gains the
     // rules carry are four vector registers held across the Hessian pass, and the run-time-sized kernel at four waves per SIMD
     // parked two more registers in scratch with the rules called than with their text in place)
     const double gain = kNewton ? lane_value(f - fb, 0) : f - fb;
-    const bool ends = neo_rules_iteration_ends(kRiccati, kRouted, kBlockedRule, TOL, &run, it, best >= 32, lane_value(step, best), hop_won,
+    const bool ends = neo_rules_iteration_ends(kRiccati, kRouted, kBlockedRule, kAcceptFetch ? tolk : TOL, &run, it, best >= 32, lane_value(step, best), hop_won,
                                                gain, fb, (double)stepmax, free_now, free_rollout);
     double* TOLW = L + tol_off;
     if (kFew) { if (lane == 0) { TOLW[T_GAIN2] = run.gain2; TOLW[T_GAIN1] = run.gain1; } }

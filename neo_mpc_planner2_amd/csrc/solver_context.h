@@ -54,5 +54,9 @@ struct Ctx {
   int tile_geom;  // reach tile in LDS: rows << 8 | kTileFree | kTileWall | log2(row stride in bytes); 0: no tile
 };
 
+// what lane = stage fetches at the end of the adjoint pass for the tangent-cone pass (three-stage kernels): its block of u
+// and of the smooth gradient
+struct StageCarry { double u0, u1, u2, g0, g1, g2; };
+
 }  // namespace
 }  // namespace neo_mpc

@@ -21,8 +21,12 @@ namespace {
 
 constexpr int kNewtonRecord = 13;   // float32 record per control block of the dense Newton system: P00 P01 P11 PW, C (3 x 3)
 
+// carry (or null): lane = block i already holds u_i and the smooth gradient of block i in registers (fetched at the end of
+// adjoint.h adjoint_by_scans; control_steps known at compile time: every block has a lane of its own) -- the bits the two
+// reads below would return
 template <bool kTame, bool kNewton, bool kRiccati>
-__device__ __forceinline__ bool tangent_cone_pass(const SolveArgs& a, const Ctx& c, double* L, double kink_radius, int lane, int n) {
+__device__ __forceinline__ bool tangent_cone_pass(const SolveArgs& a, const Ctx& c, double* L, double kink_radius, int lane, int n,
+                                                  const StageCarry* carry = nullptr) {
   constexpr bool kSecond = kNewton || kRiccati;
   const DevParams& p = a.p;
   const double* u = L + a.lds.u;
@@ -36,8 +40,13 @@ __device__ __forceinline__ bool tangent_cone_pass(const SolveArgs& a, const Ctx&
   float* ARTF = reinterpret_cast<float*>(L + a.lds.rt);  // (stage-wise: [2 i] disc curvature lambda / r of block i)
   bool my_corner = false;   // a block of this lane slides along one constraint in a corner of the feasible set
   for (int i = lane; i < n; i += kLanes) {
-    const double u0 = u[3 * i], u1 = u[3 * i + 1], u2 = u[3 * i + 2];
-    const double g0 = gs[3 * i], g1 = gs[3 * i + 1], g2 = gs[3 * i + 2];
+    double u0, u1, u2, g0, g1, g2;
+    if (carry) {
+      u0 = carry->u0; u1 = carry->u1; u2 = carry->u2; g0 = carry->g0; g1 = carry->g1; g2 = carry->g2;
+    } else {
+      u0 = u[3 * i]; u1 = u[3 * i + 1]; u2 = u[3 * i + 2];
+      g0 = gs[3 * i]; g1 = gs[3 * i + 1]; g2 = gs[3 * i + 2];
+    }
     const double e0 = u0 - c.v0, e1 = u1 - c.v1, e2 = u2 - c.v2;
     // |e| and 1/|e| from one reciprocal square root (a shorter dependent chain than sqrt, then rcp)
     const double ne2 = e0 * e0 + e1 * e1 + e2 * e2;
