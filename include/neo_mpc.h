@@ -49,6 +49,8 @@ extern "C" {
  * five entry points and two constants in the same way: still ABI 2, behaviour 6.
  * The speckle filter of the world scan layer (neo_mpc_set_world_scan_denoise, neo_mpc_get_world_scan_denoised,
  * NEO_MPC_MAX_DENOISE_GROUP) added two entry points and a constant and no record: still ABI 2, behaviour 6.
+ * The decay of the world scan layer's old marks (neo_mpc_set_world_scan_decay, neo_mpc_get_world_scan_ages, NEO_MPC_NO_AGE)
+ * added two entry points and a constant and no record: still ABI 2, behaviour 6.
  *
  * Behaviour history (iterates and iteration counts differ between versions, results stay inside the parity protocol of
  * DESIGN.md section 1; neo_mpc_behaviour_version() returns the number of the build that answers):
@@ -460,8 +462,9 @@ typedef struct neo_mpc_stamp_batch {
  * in the costmap's global frame; the projection of a LaserScan and the tf transform happen in front of it (laser_geometry,
  * ObservationBuffer).  The record takes the same thing, one observation per robot and tick; LaserScan ranges and several
  * scanners per robot go through neo_mpc_laser_batch (K11, below), which projects them and runs this update over all of
- * them.  Out of scope: a z coordinate (min / max_obstacle_height); observation_persistence; footprint_clearing_enabled -- obstacle_min_range is the stand-in for a scanner that sees its own
- * robot.
+ * them.  Out of scope: a z coordinate (min / max_obstacle_height); observation_persistence (the shared layer's decay, K14, is
+ * another thing: step 2b below); footprint_clearing_enabled -- obstacle_min_range is the stand-in for a scanner that sees its
+ * own robot.
  *
  * Like neo_mpc_stamp_batch's, the contract is one by transcription: nav2 cannot be built next to this library, so the text
  * below is the contract (tests/scan_layer_reference.py is its executable form).  Neither is pinned against nav2 itself: nav2's
@@ -549,6 +552,7 @@ typedef struct neo_mpc_scan_batch {
 
 #define NEO_MPC_MAX_SCAN_SOURCES 4u
 #define NEO_MPC_MAX_DENOISE_GROUP 16u /* largest minimal_group_size of neo_mpc_set_world_scan_denoise */
+#define NEO_MPC_NO_AGE 0xFFFFFFFFu   /* neo_mpc_get_world_scan_ages: the cell holds no mark */
 #define NEO_MPC_LASER_INF_IS_VALID 1u   /* neo_mpc_scanner.flags: a range of +inf is a beam that met nothing (nav2's inf_is_valid) */
 
 /* A fleet server receives sensor_msgs/LaserScan messages, not points: float32 ranges, an angle geometry shared by every
@@ -662,8 +666,34 @@ typedef struct neo_mpc_laser_batch {
  *      R = ceil(inflation_radius / wres) <= NEO_MPC_MAX_INFLATION_CELLS and T from neo_mpc_inflation_costs at wres.  The
  *      stated difference from nav2 carries over: a cell the layer turns from unknown to free does not get the world's own
  *      inflation back.
- * flags == 0 runs steps 3 (if given) and 4 only.  An update repeated with the same inputs changes neither layer nor live.
- * Out of scope: recomposing only the tiles a scan touched; decaying old marks (observation_persistence); a z coordinate.
+ * flags == 0 runs steps 3 (if given) and 4 only.  An update repeated with the same inputs changes neither layer nor live --
+ * with one exception: with decay on (step 2b), a repeated update with NEO_MPC_SCAN_MARK advances the clock and may expire
+ * marks; a repeated flags == 0 update still changes nothing.
+ * Out of scope: recomposing only the tiles a scan touched; a z coordinate.
+ *
+ * Step 2b, Decay (K14; optional, off by default: neo_mpc_set_world_scan_decay).  The lattice is fixed, so a mark stays until a
+ * later ray happens to pass through it: a person or a pallet jack marked where no robot looks again, or beyond every
+ * raytrace_max_range, is a lethal seed for as long as the handle lives.  With decay on, a mark that no scan has made again for
+ * a while goes away -- what nav2 users get from the spatio-temporal voxel layer.  It is NOT nav2's observation_persistence,
+ * which keeps observations in a buffer and applies them again.  The library's own rule, by contract and transcription, as
+ * step 3 is; integers only.  It runs behind every mark and in front of the footprint clearing.
+ *   The unit.  The library has no clock and the records no spare field: age is counted in SCAN UPDATES.  A scan update is an
+ *   update, from points or from ranges, with NEO_MPC_SCAN_MARK in its flags and count > 0; flags == 0 and CLEAR-only updates
+ *   are none.  A server whose scanners run at 10 Hz and that wants five seconds sets 50.
+ *   The state, kept only while decay is on: `stamp`, a uint32_t per world cell, read only under a cell that is 254, and
+ *   `clock`, one uint32_t in device memory, the number of scan updates so far -- advanced by device code on the caller's
+ *   stream, so that a captured update that is replayed advances it.  Every difference is an unsigned 32-bit subtraction:
+ *   wrap-around is harmless.
+ *   With A = max_age: a scan update first advances `clock` by one.  Its step 2 writes stamp[cell] = clock wherever it writes
+ *   254.  Then, in EVERY update while decay is on -- a flags == 0 update too, so that a lowered max_age acts at once --, a cell
+ *   with layer == 254 and clock - stamp >= A becomes unknown_value, in the layer itself: the layer has forgotten the cell, in
+ *   `live` the world map shows through and the ring is gone.
+ *   So a mark made by scan update n is in the layer after scan updates n .. n + A - 1 and gone after scan update n + A; a
+ *   mark that is made again is young again.  A mark that is in the layer when decay comes on -- made with decay off, or
+ *   before an off -> on -> off -> on sequence -- counts as made by the last scan update before that: the first update with
+ *   decay on fills `stamp` with the clock as it stands.  A layer reset needs nothing: no cell is 254.
+ *   Steps 3, 3b and 4 read the layer as decay left it: the survivor of a pair whose partner expired is a lone mark to step 3b.
+ * With decay off an update is bit for bit, launch for launch and buffer for buffer what it is without this step.
  *
  * Step 3b, Denoise (K13; optional, off by default: neo_mpc_set_world_scan_denoise).  With one layer for the fleet every
  * robot's false returns land on the same lattice, and each is a 254 seed that step 4 inflates into `live` until some ray
@@ -1058,8 +1088,8 @@ int neo_mpc_update_world_scan_layer(neo_mpc_handle* handle, const neo_mpc_scan_b
 /* Same with every pointer of both records in device memory; enqueued on `stream`, returns without waiting; no value behind a
  * pointer is looked at on the host.  Ordering: an update reads the world map and rewrites what the roll reads, so it is fenced
  * exactly like neo_mpc_inflate_world_map_device -- it waits on its stream for the last roll and the previous copy, inflation
- * or update, and a roll on another stream waits for it.  Memory: two more world maps' worth, allocated on the first update
- * and on a larger world.  The cost table is kept in the handle, apart from K8's, K9's and K10's, and rebuilt synchronously
+ * or update, and a roll on another stream waits for it.  Memory: two more world maps' worth (with decay on, four more bytes a
+ * cell), allocated on the first update and on a larger world.  The cost table is kept in the handle, apart from K8's, K9's and K10's, and rebuilt synchronously
  * when (wres, inscribed_radius, inflation_radius, cost_scaling_factor) differ from the previous update's.  A device update
  * with the shapes and inflation parameters of the previous one allocates nothing, copies nothing and does not synchronise, so
  * world scan -> roll -> stamp -> gate -> carrots -> solve can be captured on one stream in one HIP graph and replayed with
@@ -1100,6 +1130,22 @@ int neo_mpc_set_world_scan_denoise(neo_mpc_handle* handle, uint32_t minimal_grou
  * was off at that update.  Host pointer, synchronous; waits for the update in flight as neo_mpc_get_world_scan_layer does,
  * and returns NEO_MPC_ERR_NO_COSTMAP where it does.  A null cells_out only asks whether there is one. */
 int neo_mpc_get_world_scan_denoised(neo_mpc_handle* handle, uint8_t* cells_out);
+/* The decay of the shared layer's old marks (step 2b of the contract above; K14).  max_age 0: off; every other value: on, a
+ * mark expires max_age scan updates after the last one that made it.  NEO_MPC_ERR_INVALID_ARGUMENT for a null handle.  The
+ * call needs no world map, launches nothing and touches neither layer nor live nor their validity: the setting takes effect
+ * with the next update, and an update with flags == 0 is enough to let a lowered max_age act.  It is handle configuration: it
+ * survives neo_mpc_reset_world_scan_layer and neo_mpc_set_world_map, and a handle on which it was never called behaves as
+ * before.  Memory: four bytes per world cell and a word while decay is on (16 MB on a 2000 x 2000 map), allocated by the
+ * first update behind switching it on and by an update on a larger world -- that update may synchronise, and fills the
+ * stamps; a later one with the same geometry allocates and copies nothing, so the tick stays capturable after one eager
+ * call.  A captured HIP graph holds the max_age it was captured with; the clock is the device's and goes on counting. */
+int neo_mpc_set_world_scan_decay(neo_mpc_handle* handle, uint32_t max_age);
+/* The marks' ages as the last update left them, ages_out[WSY][WSX]: clock - stamp under a cell of the layer that is 254 -- 0
+ * for a mark the last scan update made --, NEO_MPC_NO_AGE under every other cell.  For displays that fade marks, and for logs.
+ * Host pointer, synchronous; waits for the update in flight as neo_mpc_get_world_scan_layer does, and returns
+ * NEO_MPC_ERR_NO_COSTMAP where it does; NEO_MPC_ERR_UNSUPPORTED when the last update ran without decay.  A null ages_out only
+ * asks whether there are any. */
+int neo_mpc_get_world_scan_ages(neo_mpc_handle* handle, uint32_t* ages_out);
 
 /* ---- multi-GPU fleets: the one exchange step ------------------------------------------------
  * Instances of one tick shard embarrassingly over the GPUs of a node (one handle per GPU, costmap and parameters

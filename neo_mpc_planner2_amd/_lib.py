@@ -35,6 +35,7 @@ EXPORTS = (
     "neo_mpc_update_world_scan_layer_from_ranges", "neo_mpc_update_world_scan_layer_from_ranges_device",
     "neo_mpc_get_world_scan_layer", "neo_mpc_reset_world_scan_layer",
     "neo_mpc_set_world_scan_denoise", "neo_mpc_get_world_scan_denoised",
+    "neo_mpc_set_world_scan_decay", "neo_mpc_get_world_scan_ages",
     "neo_mpc_rccl_available", "neo_mpc_comm_init_all", "neo_mpc_comm_destroy", "neo_mpc_group_start",
     "neo_mpc_group_end", "neo_mpc_allgather_velocities", "neo_mpc_broadcast_costmap",
 )
@@ -148,6 +149,8 @@ def load():
         lib.neo_mpc_reset_world_scan_layer.argtypes = [C.c_void_p]
         lib.neo_mpc_set_world_scan_denoise.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32]
         lib.neo_mpc_get_world_scan_denoised.argtypes = [C.c_void_p, C.c_void_p]
+        lib.neo_mpc_set_world_scan_decay.argtypes = [C.c_void_p, C.c_uint32]
+        lib.neo_mpc_get_world_scan_ages.argtypes = [C.c_void_p, C.c_void_p]
     _lib = lib
     return lib
 

@@ -222,6 +222,7 @@ assert LASER_BATCH_DTYPE.itemsize == 128 == _C.sizeof(NeoMpcLaserBatch)
 
 MAX_SCAN_SOURCES = 4
 MAX_DENOISE_GROUP = 16   # NEO_MPC_MAX_DENOISE_GROUP
+NO_AGE = 0xFFFFFFFF       # NEO_MPC_NO_AGE
 LASER_INF_IS_VALID = 1   # NEO_MPC_LASER_INF_IS_VALID: a range of +inf is a beam that met nothing, at range_max - 1e-4
 
 

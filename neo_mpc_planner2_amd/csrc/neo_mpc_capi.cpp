@@ -13,7 +13,7 @@
 // K4 carrots, K6 footprint gate, K7 rolling windows; a fleet's outlines (K8's and K12's one view, shape check and host
 // staging), K8 fleet stamp, K9 world inflation; the scan layers -- their checks, K10's and K12 / K13's updates, the staging of an
 // observation and the entry points from points, then K11: the projection, the staging of ranges and the entry points from
-// ranges --; the layers read back, reset, K13's setting.  A new entry point checks with the shared checks, stages with upload()
+// ranges --; the layers read back, reset, K13's and K14's settings.  A new entry point checks with the shared checks, stages with upload()
 // -- an observation, ranges or outlines with the routine there is --, and launches through fence.read() or between
 // fence.begin_write() and end_write(); a new kind of update is a switch of update_from_points() and from_ranges(), not a copy.
 #include <hip/hip_runtime.h>
@@ -313,12 +313,17 @@ struct ScanLayers {
 // unknown_value resets it.  Ordered by the world map's own event (WorldMap): an update is a rewrite of what the roll reads.
 // K13, the speckle filter: its setting -- configuration, which outlives resets and world maps --, D, the layer as the
 // composition of the last update read it, allocated only while the filter is on, and whether that update filtered.
+// K14, decay: its setting -- configuration too --, `stamp`, a word per cell, and `clock`, one word, both allocated by the first
+// update with decay on, and whether the last update ran with it: the stamps then go with the layer's marks.
 struct WorldScanLayer {
   InflationTable table;
   DeviceBuffer layer, live;
   DeviceBuffer denoised;
+  DeviceBuffer stamp, clock;
   uint32_t group = 0, connectivity = 8;   // neo_mpc_set_world_scan_denoise: G (0: off) and 4 or 8
+  uint32_t max_age = 0;      // neo_mpc_set_world_scan_decay: A, scan updates (0: off)
   bool filtered = false;     // the last update wrote D
+  bool decaying = false;     // the last update ran with decay on
   bool valid = false;        // the layer holds what the updates since the last reset put there
   bool live_valid = false;   // `live` is the current world map with the layer in it
   int32_t size_x = 0, size_y = 0;
@@ -342,6 +347,16 @@ struct WorldScanLayer {
   }
   // D: a no-op from the second update with this geometry and setting on
   int reserve_denoised() { return group >= 2 ? denoised.reserve(bytes()) : NEO_MPC_OK; }
+  // `stamp` and `clock`: no-ops from the second update with this geometry and decay on.  The clock starts at 0 (a blocking
+  // fill); a stamp is read only under a mark, and a layer that has just been made or reset holds none
+  int reserve_decay() {
+    if (max_age == 0) return NEO_MPC_OK;
+    if (int rc = stamp.reserve(bytes() * sizeof(uint32_t))) return rc;
+    if (clock.ptr) return NEO_MPC_OK;
+    if (int rc = clock.reserve(sizeof(uint32_t))) return rc;
+    HIP_TRY(hipMemset(clock.ptr, 0, sizeof(uint32_t)));
+    return NEO_MPC_OK;
+  }
 };
 
 // K11.  The beam table of one scanner (the contract: neo_mpc_laser_batch, step 4), with libm
@@ -1780,7 +1795,7 @@ int neo_mpc_inflate_world_map(neo_mpc_handle* h, double ins, double infl, double
   return finish_on_null_stream(inflate_world_map(h, ins, infl, csf, false, nullptr));
 }
 
-// ---------------------------------------------------------------------------------------------- K10 to K13: the scan layers
+// ---------------------------------------------------------------------------------------------- K10 to K14: the scan layers
 // What the layer an update goes to is: the projection alone has none
 enum Layer { kNoLayer, kPoolLayer, kWorldLayer };
 
@@ -1878,7 +1893,7 @@ static int scan(neo_mpc_handle* h, const neo_mpc_scan_batch& d, void* stream, co
   return NEO_MPC_OK;
 }
 
-// K12, K13.  `d`, `c`: the record and the outlines to clear with device pointers (`c` may be null).  Orders itself like
+// K12 to K14.  `d`, `c`: the record and the outlines to clear with device pointers (`c` may be null).  Orders itself like
 // inflate_world_map(): it reads the world map and rewrites what the roll reads -- on `stream`, or on the host and the null
 // stream.  `laser`: as scan()'s, in front of the rays.
 static int world_scan(neo_mpc_handle* h, const neo_mpc_scan_batch& d, const Outlines* c, bool on_device, void* stream,
@@ -1889,7 +1904,7 @@ static int world_scan(neo_mpc_handle* h, const neo_mpc_scan_batch& d, const Outl
   if (rc) return rc;
   const bool same = l.matches(w, d.unknown_value);
   if (!same && (rc = l.resize(w, d.unknown_value))) return rc;
-  if ((rc = l.reserve_denoised())) return rc;
+  if ((rc = l.reserve_denoised()) || (rc = l.reserve_decay())) return rc;
   hipStream_t st = (hipStream_t)stream;
   // behind the last roll, which reads `live` or the world map, and the previous copy, inflation or update
   if ((rc = w.begin_write(h->fence, on_device, st))) return rc;
@@ -1907,12 +1922,17 @@ static int world_scan(neo_mpc_handle* h, const neo_mpc_scan_batch& d, const Outl
   a.wsx = w.size_x; a.wsy = w.size_y;
   a.reset = same ? 0u : 1u;
   if (l.group >= 2) { a.denoised = l.denoised.as<uint8_t>(); a.group = l.group; a.connectivity = l.connectivity; }
+  if (l.max_age != 0) {
+    a.stamp = l.stamp.as<uint32_t>(); a.clock = l.clock.as<uint32_t>(); a.max_age = l.max_age;
+    a.stamp_fresh = l.decaying ? 0u : 1u;   // (the marks that are there count as made by the last scan update before this one)
+  }
   if (laser) launch_laser_project(*laser, stream);
   launch_world_scan(a, stream);
   HIP_TRY(hipGetLastError());
   if ((rc = w.end_write(st))) return rc;   // a roll behind it, on whatever stream, cuts its windows from `live`
   l.valid = true; l.live_valid = true;
   l.filtered = a.group >= 2;
+  l.decaying = a.max_age != 0;
   return NEO_MPC_OK;
 }
 
@@ -2124,7 +2144,7 @@ int neo_mpc_update_world_scan_layer_from_ranges(neo_mpc_handle* h, const neo_mpc
   return from_ranges(h, b, c, kWorldLayer, false, nullptr);
 }
 
-// ---------------------------------------------------------------------------------------------- the layers read back, reset, K13's setting
+// ---------------------------------------------------------------------------------------------- the layers read back, reset, K13's and K14's settings
 int neo_mpc_get_scan_layer(neo_mpc_handle* h, uint32_t first, uint32_t count, uint8_t* cells_out, double* origins_out) {
   if (!h) return fail(NEO_MPC_ERR_INVALID_ARGUMENT, "null handle");
   const ScanLayers& l = h->scan;
@@ -2181,6 +2201,32 @@ int neo_mpc_get_world_scan_denoised(neo_mpc_handle* h, uint8_t* cells_out) {
   HIP_TRY(hipSetDevice(h->device));
   if (int rc = h->world.wait_writer_host()) return rc;   // the update in flight
   HIP_TRY(hipMemcpy(cells_out, l.filtered ? l.denoised.ptr : l.layer.ptr, l.bytes(), hipMemcpyDeviceToHost));
+  return NEO_MPC_OK;
+}
+
+int neo_mpc_set_world_scan_decay(neo_mpc_handle* h, uint32_t max_age) {
+  if (!h) return fail(NEO_MPC_ERR_INVALID_ARGUMENT, "null handle");
+  h->world_scan.max_age = max_age;   // (the next update allocates the stamps and the clock, and lets marks expire)
+  return NEO_MPC_OK;
+}
+
+int neo_mpc_get_world_scan_ages(neo_mpc_handle* h, uint32_t* ages_out) {
+  if (!h) return fail(NEO_MPC_ERR_INVALID_ARGUMENT, "null handle");
+  WorldScanLayer& l = h->world_scan;
+  if (!l.valid)
+    return fail(NEO_MPC_ERR_NO_COSTMAP, "no world scan layer: neo_mpc_update_world_scan_layer has not been called since the last reset");
+  if (!l.decaying)
+    return fail(NEO_MPC_ERR_UNSUPPORTED, "no ages: the last update ran without decay (neo_mpc_set_world_scan_decay)");
+  if (!ages_out) return NEO_MPC_OK;
+  HIP_TRY(hipSetDevice(h->device));
+  if (int rc = h->world.wait_writer_host()) return rc;   // the update in flight
+  // the stamps go where the ages will be, and become ages under the layer's marks
+  std::vector<uint8_t> layer(l.bytes());
+  uint32_t now = 0;
+  HIP_TRY(hipMemcpy(ages_out, l.stamp.ptr, l.bytes() * sizeof(uint32_t), hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(layer.data(), l.layer.ptr, l.bytes(), hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(&now, l.clock.ptr, sizeof(now), hipMemcpyDeviceToHost));
+  for (size_t at = 0; at < layer.size(); ++at) ages_out[at] = layer[at] == 254 ? now - ages_out[at] : NEO_MPC_NO_AGE;
   return NEO_MPC_OK;
 }
 

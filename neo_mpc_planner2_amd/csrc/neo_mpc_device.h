@@ -289,6 +289,8 @@ struct WorldScanArgs {
   const uint8_t* world;             // the static world map
   uint8_t* live;                    // handle-owned: the world map with the layer merged in and inflated
   uint8_t* denoised;                // K13, handle-owned: D, the layer as the composition reads it (null with group < 2)
+  uint32_t* stamp;                  // K14, handle-owned: [wsy][wsx] the clock when the cell was last marked (null with max_age == 0)
+  uint32_t* clock;                  // K14, handle-owned: the scan updates so far, advanced on the device (null with max_age == 0)
   const double* polygons;           // fleet footprint clearing (neo_mpc_fleet_clear): as StampArgs; all null with clear == 0
   const double* footprint;
   const double* poses;
@@ -302,6 +304,8 @@ struct WorldScanArgs {
   uint32_t reset;                   // 1: the layer starts from s.unknown
   uint32_t group;                   // K13: G, 2 .. NEO_MPC_MAX_DENOISE_GROUP; 0: the filter is off and step 3b is not launched
   uint32_t connectivity;            // K13: 4 or 8
+  uint32_t max_age;                 // K14: A, scan updates; 0: decay is off and nothing of step 2b is launched
+  uint32_t stamp_fresh;             // K14: 1: the first update with decay on, `stamp` is filled with the clock first
 };
 
 // K11: LaserScan ranges projected into global-frame points and sensor origins (neo_mpc_laser_batch, device pointers)
@@ -341,7 +345,7 @@ void launch_stamp(const StampArgs& a, void* stream); // K8: k_stamp_boxes, then 
 void launch_inflate_world(const InflateArgs& a, void* stream);   // K9: k_inflate_world
 void launch_scan_layer(const ScanArgs& a, void* stream);         // K10: k_scan_shift, k_scan_rays (clear, mark), k_scan_apply
 void launch_laser_project(const LaserArgs& a, void* stream);     // K11: k_laser_project
-void launch_world_scan(const WorldScanArgs& a, void* stream);    // K12: k_world_scan_rays (clear, mark), k_world_scan_footprints, [K13: k_world_scan_denoise,] k_world_scan_compose
+void launch_world_scan(const WorldScanArgs& a, void* stream);    // K12: k_world_scan_rays (clear, mark), [K14: k_world_scan_decay,] k_world_scan_footprints, [K13: k_world_scan_denoise,] k_world_scan_compose
 // K5: dispatch order of the next launch from the iteration counts of the previous one (neo_mpc_balance_dispatch_device)
 void launch_dispatch_order(const neo_mpc_command* commands, float* load, uint32_t* order, uint32_t count, bool fresh, void* stream);
 constexpr uint32_t kDispatchSimds = 1024;   // a 4096-instance launch is one residency round: workgroups w, w + 1024, w + 2048, w + 3072 share a SIMD

@@ -23,6 +23,7 @@
 //   K11 k_laser_project  laser_projection.h: LaserScan ranges of every scanner of every robot -> those points, HBM-streaming.
 //   K12 k_world_scan_rays, k_world_scan_footprints, k_world_scan_compose  world_scan_layer.h: one obstacle layer for the fleet on the world map.
 //   K13 k_world_scan_denoise  world_scan_denoise.h: that layer's speckle filter, groups of fewer than G occupied cells, in front of K12's composition.
+//   K14 k_world_scan_tick, k_world_scan_stamp_fill, k_world_scan_marks_stamped, k_world_scan_decay  world_scan_decay.h: that layer's old marks expire, counted in scan updates.
 #include "k1_solve.h"
 #include "costmap_ingest.h"
 #include "footprint_gate.h"
@@ -33,6 +34,7 @@
 #include "laser_projection.h"
 #include "world_scan_layer.h"
 #include "world_scan_denoise.h"
+#include "world_scan_decay.h"
 
 namespace neo_mpc {
 namespace {
@@ -389,6 +391,9 @@ void launch_laser_project(const LaserArgs& a, void* stream) {
 // before on one stream: every mark lies behind every clear, the footprints behind every mark, the seeds are final when read.
 // With the speckle filter on (K13), one more launch in front of the composition, which then reads D where it reads the layer;
 // the window compiled in is the smallest of 3, 7, 15 and 31 rows that holds G - 1 steps either way.
+// With decay on (K14): on the first such update the fill of `stamp`, in front of everything; in a scan update -- MARK in the
+// flags, count > 0 -- the tick in front of the marks, which then stamp what they mark; and in every update the sweep between the
+// marks and the footprints.  With decay off none of the four is enqueued and the marking launch is K12a's.
 void launch_world_scan(const WorldScanArgs& a, void* stream) {
   if (a.wsx <= 0 || a.wsy <= 0) return;
   hipStream_t st = (hipStream_t)stream;
@@ -396,7 +401,18 @@ void launch_world_scan(const WorldScanArgs& a, void* stream) {
   const dim3 rays((a.s.max_points + kScanRayThreads - 1) / kScanRayThreads, a.s.count);
   const bool any = a.s.count > 0 && a.s.max_points > 0;
   if (any && (a.s.flags & NEO_MPC_SCAN_CLEAR)) hipLaunchKernelGGL(k_world_scan_rays<false>, rays, dim3(kScanRayThreads), 0, st, a);
-  if (any && (a.s.flags & NEO_MPC_SCAN_MARK)) hipLaunchKernelGGL(k_world_scan_rays<true>, rays, dim3(kScanRayThreads), 0, st, a);
+  if (a.max_age == 0u) {
+    if (any && (a.s.flags & NEO_MPC_SCAN_MARK)) hipLaunchKernelGGL(k_world_scan_rays<true>, rays, dim3(kScanRayThreads), 0, st, a);
+  } else {
+    const int64_t cells = (int64_t)a.wsx * a.wsy;
+    const int64_t fill = (cells >> 2) + (cells & 3), sweep = cells / kDecayCells + cells % kDecayCells;   // lanes: < 2^31 * 256
+    if (a.stamp_fresh) hipLaunchKernelGGL(k_world_scan_stamp_fill, dim3((uint32_t)((fill + kDecayThreads - 1) / kDecayThreads)), dim3(kDecayThreads), 0, st, a);
+    if (a.s.count > 0 && (a.s.flags & NEO_MPC_SCAN_MARK)) {
+      hipLaunchKernelGGL(k_world_scan_tick, dim3(1), dim3(kLanes), 0, st, a);
+      if (any) hipLaunchKernelGGL(k_world_scan_marks_stamped, rays, dim3(kScanRayThreads), 0, st, a);
+    }
+    hipLaunchKernelGGL(k_world_scan_decay, dim3((uint32_t)((sweep + kDecayThreads - 1) / kDecayThreads)), dim3(kDecayThreads), 0, st, a);
+  }
   if (a.clear && a.s.count > 0) hipLaunchKernelGGL(k_world_scan_footprints, dim3(a.s.count), dim3(kLanes), 0, st, a);
   const dim3 tiles((a.wsx + kInflateTile - 1) / kInflateTile, (a.wsy + kInflateTile - 1) / kInflateTile), tile(kLanes * kInflateWaves);
   if (a.group < 2u) { hipLaunchKernelGGL(k_world_scan_compose, tiles, tile, 0, st, a); return; }

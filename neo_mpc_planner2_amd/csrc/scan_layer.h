@@ -76,9 +76,11 @@ __device__ __forceinline__ uint32_t scan_cell_distance(double d, double res) {
 // One ray of steps 2 and 3 of the contract: point p of robot k of the batch `a`, on a grid of sx x sy cells of `res` at (ox, oy)
 // whose cell (0, 0) is at `layer`, rows lp bytes apart (kMark false: the clearing walk; true: the mark).  The one copy of the
 // clips, raytraceLine and the mark test: K10b runs it on a window's geometry and layer, K12a (world_scan_layer.h) on the world's.
-template <bool kMark>
+// kStamp (K14c alone, world_scan_decay.h): the mark also writes `now` into `stamp`, a word per cell with rows lp words apart;
+// without it the two arguments are dead and every kernel comes out as it did before they were there.
+template <bool kMark, bool kStamp = false>
 __device__ __forceinline__ void scan_ray(const ScanArgs& a, uint32_t k, uint32_t p, double ox, double oy, double res, int sx,
-                                         int sy, int lp, uint8_t* layer) {
+                                         int sy, int lp, uint8_t* layer, uint32_t* stamp = nullptr, uint32_t now = 0u) {
 #pragma clang fp contract(off)
   uint32_t np = a.max_points;
   if (a.point_counts) { const uint32_t c = a.point_counts[k]; np = c < np ? c : np; }
@@ -94,6 +96,7 @@ __device__ __forceinline__ void scan_ray(const ScanArgs& a, uint32_t k, uint32_t
     int mx, my;
     if (!scan_world_to_map(wx, wy, ox, oy, res, sx, sy, mx, my)) return;
     layer[(int64_t)my * lp + mx] = 254;   // 0 <= mx < sx, 0 <= my < sy by worldToMap
+    if (kStamp) stamp[(int64_t)my * lp + mx] = now;
     return;
   }
   int x0, y0, x1, y1;

@@ -568,6 +568,24 @@ class BatchSolver:
         _lib.check(self._lib.neo_mpc_get_world_scan_denoised(self._handle, C.c_void_p(cells.ctypes.data)))
         return cells
 
+    def set_world_scan_decay(self, max_age):
+        """The decay of the fleet's shared layer (K14; the contract: step 2b of neo_mpc_fleet_clear's text in
+        include/neo_mpc.h): from the next `update_world_scan_layer` on, a mark that no scan update -- an update with
+        abi.SCAN_MARK in its flags -- has made again for `max_age` scan updates becomes `unknown_value` in the layer itself.
+        0 switches it off.  Handle configuration: it survives `reset_world_scan_layer` and `set_world_map`."""
+        _lib.check(self._lib.neo_mpc_set_world_scan_decay(self._handle, int(max_age)))
+
+    def get_world_scan_ages(self):
+        """uint32 [size_y, size_x] on the world map's geometry: under a mark of the layer the number of scan updates since it
+        was last made (0: by the last one), `abi.NO_AGE` elsewhere, as the last `update_world_scan_layer` left them.  Refused
+        when that update ran without decay.  Synchronous; waits for the update in flight."""
+        _lib.check(self._lib.neo_mpc_get_world_scan_ages(self._handle, None))
+        sx, sy = C.c_uint32(), C.c_uint32()
+        _lib.check(self._lib.neo_mpc_get_world_map(self._handle, None, C.byref(sx), C.byref(sy), None, None, None))
+        ages = np.zeros((sy.value, sx.value), dtype=np.uint32)
+        _lib.check(self._lib.neo_mpc_get_world_scan_ages(self._handle, C.c_void_p(ages.ctypes.data)))
+        return ages
+
     HOST_PATHS = {"auto": 0, "staged": 1, "zerocopy": 2, "zerocopy_out": 3}
 
     def set_host_path(self, mode):

@@ -12,8 +12,14 @@ after the other on the same card, their JSON taken over as it is.
 With --denoise G (may be given more than once), at the end and on the layer of a full scan again: K13's launch
 (k_world_scan_denoise, 8-connectivity) as the difference of flags-0 updates with the filter on and off, and how many marks it
 dropped.  Without the option the filter is never set and nothing of it runs.
+With --decay A (may be given more than once), behind that and on the layer of a full scan again: what K14 adds to an update
+without a scan -- its sweep, k_world_scan_decay, as the difference of flags-0 updates with decay on and off -- and to a full
+scan update -- k_world_scan_tick, the stamped marking launch in place of the plain one, and the sweep --, both beside the
+composition alone measured in the same run; and how many marks the timed scan updates left.  Every robot's scan marks its
+cells again in every update, so nothing expires while it is timed: the sweep fetches a stamp under every mark and stores
+nothing, which is what it does in a fleet whose scanners run.  Without the option decay is never set and nothing of it runs.
 Every figure is median [min, max] of event pairs around back-to-back calls.
-usage: bench_world_scan_layer.py [--alone] [--denoise G]... [robots]"""
+usage: bench_world_scan_layer.py [--alone] [--denoise G]... [--decay A]... [robots]"""
 import json
 import math
 import os
@@ -33,7 +39,8 @@ from neo_mpc_planner2_amd.solver import BatchSolver  # noqa: E402
 args = [a for a in sys.argv[1:] if a != "--alone"]
 alone = "--alone" in sys.argv[1:]
 denoise = [int(args[k + 1]) for k, a in enumerate(args) if a == "--denoise"]
-args = [a for k, a in enumerate(args) if a != "--denoise" and (k == 0 or args[k - 1] != "--denoise")]
+decay = [int(args[k + 1]) for k, a in enumerate(args) if a == "--decay"]
+args = [a for k, a in enumerate(args) if a not in ("--denoise", "--decay") and (k == 0 or args[k - 1] not in ("--denoise", "--decay"))]
 count = int(args[0]) if args else 4096
 dev = "cuda:0"
 RES, WORLD, SIZE, POINTS, SOURCES, BEAMS = synthetic.RESOLUTION, 2000, 200, 360, 2, 1081
@@ -155,6 +162,22 @@ with BatchSolver(params) as s:
         out["denoise_%d" % group] = {"minimal_group_size": group, "connectivity": 8, "marks": int((layer == 254).sum()),
                                      "marks_dropped": int(((layer == 254) & (kept == 0)).sum()),
                                      "compose_with_filter_ms": on, "denoise_ms": minus(on, off)}
+    for max_age in decay:
+        # decay, on the layer of a full scan of points: updates with it against the same updates without, the same layer
+        update(abi.SCAN_CLEAR | abi.SCAN_MARK)
+        off, full_off = timed(lambda: update(0)), timed(lambda: update(abi.SCAN_CLEAR | abi.SCAN_MARK))
+        s.set_world_scan_decay(max_age)
+        update(0)                                   # (allocates the stamps and the clock, and fills the stamps)
+        on, full_on = timed(lambda: update(0)), timed(lambda: update(abi.SCAN_CLEAR | abi.SCAN_MARK))
+        torch.cuda.synchronize()
+        layer, ages = s.get_world_scan_layer()[0], s.get_world_scan_ages()
+        s.set_world_scan_decay(0)
+        update(0)
+        out["decay_%d" % max_age] = {"max_age": max_age, "marks": int((layer == 254).sum()),
+                                     "oldest_mark": int(ages[layer == 254].max()), "stamp_bytes": int(ages.nbytes),
+                                     "compose_ms": off, "compose_with_decay_ms": on, "decay_sweep_ms": minus(on, off),
+                                     "update_full_ms": full_off, "update_full_with_decay_ms": full_on,
+                                     "decay_in_a_scan_update_ms": minus(full_on, full_off)}
 del world, points, ranges
 torch.cuda.empty_cache()
 if not alone:
