@@ -13,6 +13,7 @@ from neo_mpc_planner2_amd import abi, synthetic
 from oracle import c_oracle
 from tests import carrot_reference as cref
 from tests.carrot_reference import transcription
+from tests.fleet_kit import gpu
 
 LP = dict(lookahead_dist_min=0.4, lookahead_dist_max=0.8, lookahead_dist_close_to_goal=0.3,
           max_transform_dist=5.0)
@@ -127,8 +128,7 @@ def test_carrots_feed_the_solver_on_device():
         want, _ = s.solve(pc, st.copy(), warm.copy())
         dev = "cuda:0"
         db = DeviceBatch(probs, st, warm, dev)
-        t = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)
-        d_poses, d_off, d_rob, d_slow, d_fc = t(poses), t(offsets.view(np.int32)), t(robots), t(slow), t(fcost)
+        d_poses, d_off, d_rob, d_slow, d_fc = gpu(poses), gpu(offsets.view(np.int32)), gpu(robots), gpu(slow), gpu(fcost)
         d_car = torch.zeros((count, abi.CARROT_DTYPE.itemsize), dtype=torch.uint8, device=dev)
         lp = abi.NeoMpcLookaheadParams(LP["lookahead_dist_min"], LP["lookahead_dist_max"],
                                        LP["lookahead_dist_close_to_goal"], LP["max_transform_dist"])
@@ -540,11 +540,10 @@ def k4():
         def device(batch, fcost=True, problems=True):
             dev = "cuda:0"
             count = len(batch["slow"])
-            t = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)
             poses = batch["poses"] if len(batch["poses"]) else np.zeros((1, 3))   # (a null plan_poses is refused)
-            d_poses, d_off, d_rob, d_slow = t(poses), t(batch["offsets"].view(np.int32)), t(batch["robots"]), t(batch["slow"])
-            d_fc = t(batch["fcost"]) if fcost and batch["fcost"] is not None else None
-            d_probs = t(cref.fill_problems(count).view(np.uint8).reshape(count, -1)) if problems else None
+            d_poses, d_off, d_rob, d_slow = gpu(poses), gpu(batch["offsets"].view(np.int32)), gpu(batch["robots"]), gpu(batch["slow"])
+            d_fc = gpu(batch["fcost"]) if fcost and batch["fcost"] is not None else None
+            d_probs = gpu(cref.fill_problems(count).view(np.uint8).reshape(count, -1)) if problems else None
             d_car = torch.full((count, abi.CARROT_DTYPE.itemsize), 0xEE, dtype=torch.uint8, device=dev)
             lp = abi.NeoMpcLookaheadParams(*(batch["lp"][k] for k in ("lookahead_dist_min", "lookahead_dist_max",
                                                                      "lookahead_dist_close_to_goal", "max_transform_dist")))

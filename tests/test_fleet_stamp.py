@@ -20,6 +20,7 @@ from tests import fleet_stamp_reference as ref
 from tests import footprint_gate_reference as gate_ref
 from tests import rolling_window_reference as roll_ref
 from tests.c_probe import HEADER, run_c_probe
+from tests.fleet_kit import RECT, Side, capture_fleet, gpu, replay_against_direct, standing_fleet
 
 ENTRY_POINTS = ("neo_mpc_stamp_fleet", "neo_mpc_stamp_fleet_device", "neo_mpc_inflation_costs")
 WRES, WOX, WOY, WSIZE = synthetic.RESOLUTION, -1.5, -1.5, 300         # the world: 15 m around a 12 m yard
@@ -27,7 +28,6 @@ PARAMS = (0.45, 0.9, 3.0)           # inscribed_radius, inflation_radius, cost_s
 STAMPS_ONLY = (0.3, 0.0, 1.0)       # R = 0: no ring
 SIZES = {"13x11": (13, 11), "36x20": (36, 20), "200x200": (200, 200)}
 RESOLUTIONS = {"5cm": 0.05, "2.5cm": 0.025}
-RECT = tuple(synthetic.RECT_FOOTPRINT)
 BIG = ((1.0, 0.8), (-1.0, 0.8), (-1.0, -0.8), (1.0, -0.8))            # 80 x 64 cells at 2.5 cm: more than one 64 x 64 tile
 TRIANGLE = ((0.4, 0.0), (-0.3, 0.3), (-0.3, -0.3))
 GON16 = tuple((0.4 * math.cos(2 * math.pi * k / 16), 0.4 * math.sin(2 * math.pi * k / 16)) for k in range(16))
@@ -257,11 +257,8 @@ STAMP_CASES = [(size, resolution, PARAMS) for size in sorted(SIZES) for resoluti
 @pytest.mark.parametrize("size,resolution,params", STAMP_CASES,
                          ids=["%s-%s-%s" % (a, b, "ring" if c is PARAMS else "stamps-only") for a, b, c in STAMP_CASES])
 def test_stamp_equals_the_transcription(size, resolution, params):
-    import torch
     poses, footprints, _ = fleet(size, resolution)
     res = RESOLUTIONS[resolution]
-    dev = "cuda:0"
-    t = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)
     with solver_with_world() as s:
         origins, old, polygons = rolled(s, size, resolution)
         want = ref.stamp_pool(old, origins, res, polygons, *params)
@@ -272,8 +269,8 @@ def test_stamp_equals_the_transcription(size, resolution, params):
         variants = (("host polygons", lambda: s.stamp_fleet(*params, polygons=polygons)),
                     ("host polygons, other winding", lambda: s.stamp_fleet(*params, polygons=reversed_polygons)),
                     ("host footprint + poses", lambda: s.stamp_fleet(*params, footprint=footprints, poses=poses)),
-                    ("device polygons", lambda: s.stamp_fleet(*params, polygons=t(polygons))),
-                    ("device footprint + poses", lambda: s.stamp_fleet(*params, footprint=t(footprints), poses=t(poses))))
+                    ("device polygons", lambda: s.stamp_fleet(*params, polygons=gpu(polygons))),
+                    ("device footprint + poses", lambda: s.stamp_fleet(*params, footprint=gpu(footprints), poses=gpu(poses))))
         for k, (name, call) in enumerate(variants):
             if k:
                 refill(s, size, resolution, origins)
@@ -369,14 +366,12 @@ def test_a_solve_and_a_gate_cannot_tell_a_stamped_pool_from_an_ingested_one():
     # "robot" k stands next to the centre of window k + 1: every window holds one stamped neighbour, none its own
     robots = np.concatenate([np.roll(offsets, -1, axis=0) + (1.1, 0.6), rng.uniform(-3, 3, size=(m, 1))], 1)
     polygons = np.array([gate_ref.oriented(p, RECT) for p in robots])
-    dev = "cuda:0"
-    t = lambda a: torch.from_numpy(np.array(a)).to(dev)
-    fp = t(np.asarray(RECT, dtype=np.float64))
+    fp = gpu(np.asarray(RECT, dtype=np.float64))
     results = []
     with BatchSolver(orc.make_params()) as s:
-        s.set_world_map(t(world), res, wox, woy)
-        d_orig = t(start)
-        s.roll_costmap_pool(size, size, res, d_orig, poses=t(np.concatenate([offsets, np.zeros((m, 1))], 1)))
+        s.set_world_map(gpu(world), res, wox, woy)
+        d_orig = gpu(start)
+        s.roll_costmap_pool(size, size, res, d_orig, poses=gpu(np.concatenate([offsets, np.zeros((m, 1))], 1)))
         torch.cuda.synchronize()
         raw, want_o = s.get_costmap_pool()
         stamped = ref.stamp_pool(raw, want_o, res, polygons, *PARAMS)
@@ -384,15 +379,15 @@ def test_a_solve_and_a_gate_cannot_tell_a_stamped_pool_from_an_ingested_one():
     for how in ("stamped", "ingested"):
         with BatchSolver(orc.make_params()) as s:
             if how == "stamped":
-                s.set_world_map(t(world), res, wox, woy)
-                d_orig = t(start)
-                s.roll_costmap_pool(size, size, res, d_orig, poses=t(np.concatenate([offsets, np.zeros((m, 1))], 1)))
-                s.stamp_fleet(*PARAMS, polygons=t(polygons))
+                s.set_world_map(gpu(world), res, wox, woy)
+                d_orig = gpu(start)
+                s.roll_costmap_pool(size, size, res, d_orig, poses=gpu(np.concatenate([offsets, np.zeros((m, 1))], 1)))
+                s.stamp_fleet(*PARAMS, polygons=gpu(polygons))
             else:
-                d_orig = t(want_o)
-                s.set_costmap_pool(t(stamped), res, d_orig)
-            b = DeviceBatch(probs, st, warm, dev)
-            costs = torch.zeros(count, dtype=torch.float64, device=dev)
+                d_orig = gpu(want_o)
+                s.set_costmap_pool(gpu(stamped), res, d_orig)
+            b = DeviceBatch(probs, st, warm, "cuda:0")
+            costs = torch.zeros(count, dtype=torch.float64, device="cuda:0")
             s.footprint_gate_device(fp, costs, problems=b.problems)
             s.solve_device(b.problems, b.states, b.warm, b.commands, solution=b.solution)
             torch.cuda.synchronize()
@@ -433,16 +428,7 @@ def test_the_tick_sees_the_neighbour():
         b_xy = np.array([rear + 0.35, a_xy[1]])
         c_xy = b_xy + (0.0, 0.25 + 0.2 + 0.25)              # 0.2 m between the outlines: inside the 0.45 m inscribed ring
         poses = np.array([(a_xy[0], a_xy[1], 0.0), (b_xy[0], b_xy[1], 0.0), (c_xy[0], c_xy[1], 0.0)])
-        probs = synthetic.make_problems(3, 200, seed=5)
-        probs["cur_xy"] = poses[:, :2]
-        probs["cur_q"] = (0.0, 0.0, 0.0, 1.0)
-        probs["carrot_xy"] = (0.4, 0.0)
-        probs["carrot_q"] = (0.0, 0.0, 0.0, 1.0)
-        probs["goal_xyz"][:, :2] = poses[:, :2] + (5.0, 0.0)
-        probs["goal_q"] = (0.0, 0.0, 0.0, 1.0)
-        probs["cur_vel"] = 0.0
-        probs["map_index"] = np.arange(3, dtype=np.int32)
-        st, warm = synthetic.make_states(probs, 3)
+        probs, st, warm = standing_fleet(3, poses[:, :2], poses[:, :2] + (5.0, 0.0), seed=5)
         base = torch.from_numpy(np.asarray(RECT, dtype=np.float64)).to(dev)
         d_poses = torch.from_numpy(poses).to(dev)
         out = {}
@@ -538,78 +524,31 @@ def test_roll_stamp_gate_solve_can_be_captured_in_a_hip_graph():
     stream, a linear chain, and replayed with the poses rewritten in between; pool, gate costs and commands equal the
     same calls made directly on a second handle."""
     import torch
-    from neo_mpc_planner2_amd.solver import BatchSolver, DeviceBatch
-    from oracle import mpc_oracle as orc
-    count, sx, sy = 64, 48, 44
-    world, res, wox, woy = synthetic.make_costmap(300, seed=91)
-    probs = synthetic.make_problems(count, 120, seed=92)          # 64 robots within 4 m x 4 m: windows full of neighbours
-    probs["map_index"] = np.arange(count, dtype=np.int32)
-    st, warm = synthetic.make_states(probs, 3)
-    dev = "cuda:0"
-    t = lambda a: torch.from_numpy(np.array(a)).to(dev)
+    f = capture_fleet(120)                                        # 64 robots within 4 m x 4 m: windows full of neighbours
     rng = np.random.default_rng(93)
-    ticks = [np.concatenate([probs["cur_xy"] + rng.uniform(-0.4, 0.4, size=(count, 2)) * k,
-                             rng.uniform(-3, 3, size=(count, 1))], 1) for k in range(3)]
-    start = probs["cur_xy"] - 1.0
-    fp = t(np.asarray(RECT, dtype=np.float64))
+    ticks = [(np.concatenate([f.probs["cur_xy"] + rng.uniform(-0.4, 0.4, size=(f.count, 2)) * k,
+                              rng.uniform(-3, 3, size=(f.count, 1))], 1),) for k in range(3)]
+    fp = gpu(np.asarray(RECT, dtype=np.float64))
 
-    class Side:
-        def __init__(self):
-            self.s = BatchSolver(orc.make_params())
-            self.s.set_world_map(t(world), res, wox, woy)
-            self.b = DeviceBatch(probs, st, warm, dev)
-            self.origins, self.poses = t(start), t(ticks[0])
-            self.costs = torch.zeros(count, dtype=torch.float64, device=dev)
-            self.xy = self.b.problems.view(torch.float64).reshape(count, -1)[:, 0:2]
-
-        def set_poses(self, p):
-            self.poses.copy_(t(p))
-            self.xy.copy_(self.poses[:, :2])
-
+    class StampSide(Side):
         def tick(self):
-            self.s.roll_costmap_pool(sx, sy, res, self.origins, poses=self.poses)
+            self.s.roll_costmap_pool(f.sx, f.sy, f.res, self.origins, poses=self.poses)
             self.s.stamp_fleet(*PARAMS, footprint=fp, poses=self.poses)
             self.s.footprint_gate_device(fp, self.costs, poses=self.poses, problems=self.b.problems)
             self.s.solve_device(self.b.problems, self.b.states, self.b.warm, self.b.commands, solution=self.b.solution)
 
         def result(self):
-            torch.cuda.synchronize()
-            return (self.b.commands_host().tobytes(), self.b.states_host().tobytes(), self.costs.cpu().numpy().tolist(),
-                    self.origins.cpu().numpy().tolist(), self.s.get_costmap_pool()[0].tobytes())
+            return super().result() + (self.s.get_costmap_pool()[0].tobytes(),)
 
-    direct, graphed = Side(), Side()
-    try:
-        side = torch.cuda.Stream()
-        side.wait_stream(torch.cuda.current_stream())
-        with torch.cuda.stream(side):          # the eager call, on the capture stream
-            graphed.tick()
-        torch.cuda.synchronize()
-        direct.tick()
-        first = direct.result()
-        assert first == graphed.result()
-        g = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(g, stream=side):
-            graphed.tick()
-        for k in (1, 2):
-            for x in (direct, graphed):
-                x.set_poses(ticks[k])
-            torch.cuda.synchronize()
-            g.replay()
-            direct.tick()
-            a, b = graphed.result(), direct.result()
-            assert a == b, k
-            assert a[4] != first[4]                # the pool changed
+    with replay_against_direct(lambda: StampSide(f, ticks[0]), ticks, changed=(4,)) as (direct, a, _):   # the pool changed
         # ... and the pool is the stamped one: the transcription on the rolled windows, K6's polygons
         s = direct.s
-        s.roll_costmap_pool(sx, sy, res, direct.origins, poses=direct.poses)
+        s.roll_costmap_pool(f.sx, f.sy, f.res, direct.origins, poses=direct.poses)
         torch.cuda.synchronize()
         raw, origins = s.get_costmap_pool()
-        _, polygons = s.footprint_gate(np.asarray(RECT), poses=ticks[2], map_indices=probs["map_index"], want_polygons=True)
-        want = ref.stamp_pool(raw, origins, res, polygons, *PARAMS)
+        _, polygons = s.footprint_gate(np.asarray(RECT), poses=ticks[2][0], map_indices=f.probs["map_index"], want_polygons=True)
+        want = ref.stamp_pool(raw, origins, f.res, polygons, *PARAMS)
         assert np.frombuffer(a[4], dtype=np.uint8).tolist() == want.reshape(-1).tolist() and (want != raw).any()
-    finally:
-        direct.s.close()
-        graphed.s.close()
 
 
 # ------------------------------------------------------------------------------------------ 11: the closed loop
@@ -625,16 +564,7 @@ def test_closed_loop_two_robots_head_on():
     from oracle import mpc_oracle as orc
     size, res, ticks = 100, 0.05, 150
     world = np.zeros((400, 400), dtype=np.uint8)
-    probs = synthetic.make_problems(2, 200, seed=7)
-    probs["cur_xy"] = ((-2.0, 0.011), (2.0, 0.011))
-    probs["cur_q"] = synthetic.yaw_quat(np.array([0.0, math.pi]))
-    probs["carrot_xy"] = (0.4, 0.0)
-    probs["carrot_q"] = (0.0, 0.0, 0.0, 1.0)
-    probs["goal_xyz"][:, :2] = ((6.0, 0.011), (-6.0, 0.011))
-    probs["goal_q"] = probs["cur_q"]
-    probs["cur_vel"] = 0.0
-    probs["map_index"] = np.arange(2, dtype=np.int32)
-    st, warm = synthetic.make_states(probs, 3)
+    probs, st, warm = standing_fleet(2, ((-2.0, 0.011), (2.0, 0.011)), ((6.0, 0.011), (-6.0, 0.011)), yaw=np.array([0.0, math.pi]))
     runs = {}
     with BatchSolver(orc.make_params()) as s:
         s.set_world_map(world, res, -10.0, -10.0)

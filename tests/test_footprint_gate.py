@@ -19,9 +19,9 @@ import pytest
 from neo_mpc_planner2_amd import _lib, abi, synthetic
 from tests import footprint_gate_reference as ref
 from tests.c_probe import HEADER, run_c_probe
+from tests.fleet_kit import RECT, gpu
 
 RES = synthetic.RESOLUTION
-RECT = synthetic.RECT_FOOTPRINT
 TRIANGLE = ((0.4, 0.0), (-0.3, 0.3), (-0.3, -0.3))
 GON16 = tuple((0.4 * math.cos(2 * math.pi * k / 16), 0.4 * math.sin(2 * math.pi * k / 16)) for k in range(16))
 POLYGONS = {"rect": RECT, "triangle": TRIANGLE, "gon16": GON16}
@@ -224,14 +224,13 @@ def test_pool_map_indices_problem_indices_and_rewritten_origins():
     want2 = ref.gate(cells, RES, origins + shift, poses, RECT, idx)
     assert want2.tolist() != want.tolist()
     dev = "cuda:0"
-    t = lambda a: torch.from_numpy(np.array(a)).to(dev)
     with BatchSolver({}) as s:
-        d_origins = t(origins)
-        s.set_costmap_pool(t(cells), RES, d_origins)
-        d_fp, d_poses, d_idx = t(np.asarray(RECT, dtype=np.float64)), t(poses), t(idx)
+        d_origins = gpu(origins)
+        s.set_costmap_pool(gpu(cells), RES, d_origins)
+        d_fp, d_poses, d_idx = gpu(np.asarray(RECT, dtype=np.float64)), gpu(poses), gpu(idx)
         c1, c2 = torch.zeros(len(poses), dtype=torch.float64, device=dev), torch.zeros(len(poses), dtype=torch.float64, device=dev)
         s.footprint_gate_device(d_fp, c1, poses=d_poses, map_indices=d_idx)
-        d_origins += t(shift)
+        d_origins += gpu(shift)
         s.footprint_gate_device(d_fp, c2, poses=d_poses, map_indices=d_idx)
         torch.cuda.synchronize()
         assert c1.cpu().numpy().tolist() == want.tolist() and c2.cpu().numpy().tolist() == want2.tolist()
@@ -313,21 +312,20 @@ def test_gate_carrots_solve_chain_on_the_device():
     slow = np.ones(count, dtype=np.int32)
     lp = abi.NeoMpcLookaheadParams(0.4, 0.8, 0.3, 1e9)
     dev = "cuda:0"
-    t = lambda a: torch.from_numpy(np.array(a)).to(dev)
     results = []
     with solver_on(random_map(), orc.make_params()) as s:
-        d_plans, d_off, d_rob = t(plan_poses), t(offsets.view(np.int32)), t(poses)
+        d_plans, d_off, d_rob = gpu(plan_poses), gpu(offsets.view(np.int32)), gpu(poses)
         for chain in ("device", "host-fed"):
             db = DeviceBatch(probs, st, warm, dev)
-            d_slow = t(slow)
+            d_slow = gpu(slow)
             d_car = torch.zeros((count, abi.CARROT_DTYPE.itemsize), dtype=torch.uint8, device=dev)
             if chain == "device":
                 d_costs = torch.zeros(count, dtype=torch.float64, device=dev)
                 d_polys = torch.zeros((count, 4, 2), dtype=torch.float64, device=dev)
-                s.footprint_gate_device(t(np.asarray(RECT, dtype=np.float64)), d_costs, problems=db.problems,
+                s.footprint_gate_device(gpu(np.asarray(RECT, dtype=np.float64)), d_costs, problems=db.problems,
                                         footprints_out=d_polys)
             else:
-                d_costs, d_polys = t(want), t(world)
+                d_costs, d_polys = gpu(want), gpu(world)
             s.select_carrots_device(lp, d_plans, d_off, d_rob, d_slow, d_car, d_costs, problems=db.problems)
             s.solve_device(db.problems, db.states, db.warm, db.commands, footprints=d_polys)
             torch.cuda.synchronize()
@@ -353,10 +351,9 @@ def test_gates_are_ordered_against_costmap_ingests():
     want_b = ref.gate(other, res, (ox, oy), poses, RECT)
     assert want_a.tolist() != want_b.tolist()
     dev = "cuda:0"
-    t = lambda a: torch.from_numpy(np.array(a)).to(dev)
     from neo_mpc_planner2_amd.solver import BatchSolver
     with BatchSolver({}) as s:
-        d_fp, d_poses = t(np.asarray(RECT, dtype=np.float64)), t(poses)
+        d_fp, d_poses = gpu(np.asarray(RECT, dtype=np.float64)), gpu(poses)
         ca, cb = torch.zeros(len(poses), dtype=torch.float64, device=dev), torch.zeros(len(poses), dtype=torch.float64, device=dev)
         torch.cuda.synchronize()
         stream = torch.cuda.Stream()

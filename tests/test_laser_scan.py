@@ -15,25 +15,19 @@ import re
 import numpy as np
 import pytest
 
-from neo_mpc_planner2_amd import _lib, abi, synthetic
+from neo_mpc_planner2_amd import _lib, abi
 from tests import laser_scan_reference as ref
 from tests import scan_layer_reference as scan_ref
 from tests.c_probe import HEADER, run_c_probe
+from tests.fleet_kit import F32, RECT, Side, capture_fleet, gpu, inflation_for, replay_against_direct, same, scanner, standing_fleet, window_state
 
 ENTRY_POINTS = ("neo_mpc_laser_beam_table", "neo_mpc_project_laser", "neo_mpc_project_laser_device",
                 "neo_mpc_update_scan_layer_from_ranges", "neo_mpc_update_scan_layer_from_ranges_device")
-RECT = tuple(synthetic.RECT_FOOTPRINT)
-F32 = np.float32
 
 
 def f32(v):
     """A LaserScan field as the caller hands it over: float32 on the wire, widened."""
     return float(F32(v))
-
-
-def scanner(mount, angle_min, angle_increment, range_min, range_max, flags=0):
-    return dict(mount_x=mount[0], mount_y=mount[1], mount_yaw=mount[2], angle_min=angle_min, angle_increment=angle_increment,
-                range_min=range_min, range_max=range_max, flags=flags)
 
 
 # ------------------------------------------------------------------------------------------ 1: the hand-worked projection
@@ -145,25 +139,7 @@ def test_every_clear_runs_before_every_mark_in_the_transcription():
     assert pool[0, 16, 20] == 254 and pool[0, 16, 24] == 254 and (pool == 254).sum() == 2
 
 
-# ------------------------------------------------------------------------------------------ shared GPU helpers
-def gpu(a, dtype=None):
-    import torch
-    a = np.ascontiguousarray(a) if dtype is None else np.ascontiguousarray(a).astype(dtype)
-    return torch.from_numpy(a.copy()).to("cuda:0")
-
-
-def state_of(s):
-    import torch
-    torch.cuda.synchronize()
-    layers, layer_origins = s.get_scan_layer()
-    pool, origins = s.get_costmap_pool()
-    return layers, layer_origins, pool, origins
-
-
-def same_state(a, b):
-    return all(x.tobytes() == y.tobytes() for x, y in zip(a, b))
-
-
+# ------------------------------------------------------------------------------------------ ranges for the GPU tests
 def special_ranges(rng, shape, sc_min=0.05, sc_max=10.0, high=12.0):
     """float32 ranges [count, sources, beams] from `rng`, most of them valid, with every special value of the contract in
     every scan that has room for them: in the first chunk of 256 beams and, where there is one, in the tail behind it."""
@@ -239,11 +215,6 @@ UPDATE_MOVES = (np.zeros((UPDATE_WINDOWS, 2)), np.array([(3.0, -2.7), (-2.7, 3.0
                 np.array([(5.0, -2.7), (-2.7, 1.0), (0.0, 0.0), (141.0, 1.0)]))
 
 
-def inflation_for(reach, res):
-    radius = 0.0 if reach == 0 else (reach - 0.5) * res
-    return min(radius, 1.5 * res), radius, 3.0 / (res * max(reach, 1))
-
-
 @functools.lru_cache(maxsize=None)
 def update_world():
     world = np.random.default_rng(77).choice(np.array([0, 0, 0, 0, 90, 254, 255, 255], dtype=np.uint8), size=(400, 400))
@@ -290,7 +261,7 @@ def test_update_from_ranges_equals_projection_then_the_multi_source_transcriptio
             points, sensors = points.cpu().numpy(), sensors.cpu().numpy()
             want = model.update_sources(rolled, origins, UPDATE_RES, *params, points, sensors, unknown_value=unknown, **UPDATE_KW)
             s.update_scan_layer_from_ranges(*params, d_ranges, d_poses, UPDATE_SCANNERS, unknown_value=unknown, **UPDATE_KW)
-            got = state_of(s)
+            got = window_state(s)
             print("tick %d: %d marks, %d free layer cells, %d window cells changed" %
                   (k, int((model.layers == 254).sum()), int((model.layers == 0).sum()), int((want != rolled).sum())))
             assert (model.layers == 254).any() and (want != rolled).any(), k
@@ -305,7 +276,7 @@ def test_update_from_ranges_equals_projection_then_the_multi_source_transcriptio
                                         origins_out=out_o, **UPDATE_KW)
         assert out_p.tobytes() == points.tobytes() and out_o.tobytes() == sensors.tobytes()
         again = model.update_sources(rolled, origins, UPDATE_RES, *params, points, sensors, unknown_value=unknown, **UPDATE_KW)
-        got = state_of(s)
+        got = window_state(s)
         assert np.array_equal(got[0], model.layers) and np.array_equal(got[2], again)
 
 
@@ -331,9 +302,9 @@ def test_one_source_equals_the_update_from_points():
             points, sensors = b.project_laser(d_ranges, d_poses, UPDATE_SCANNERS[:1])
             b.update_scan_layer(*params, points=points.reshape(UPDATE_WINDOWS, UPDATE_BEAMS, 2),
                                 sensor_origins=sensors.reshape(UPDATE_WINDOWS, 2), **UPDATE_KW)
-            got, want = state_of(a), state_of(b)
+            got, want = window_state(a), window_state(b)
             assert (want[0] == 254).any() and (want[0] == 0).any(), k
-            assert same_state(got, want), k
+            assert same(got, want), k
 
 
 # ------------------------------------------------------------------------------------------ 8: the two scanners on the device
@@ -346,12 +317,12 @@ def test_every_clear_runs_before_every_mark_on_the_device():
             s.set_costmap_pool(cells, TWO_RES, origins)
             s.reset_scan_layer()
             s.update_scan_layer_from_ranges(*TWO_INFLATION, put(TWO_RANGES), put(TWO_POSE), [TWO_A, TWO_B], **TWO_KW)
-            together, pool = state_of(s)[0][0], state_of(s)[2][0]
+            together, pool = window_state(s)[0][0], window_state(s)[2][0]
             s.set_costmap_pool(cells, TWO_RES, origins)
             s.reset_scan_layer()
             for k, sc in enumerate((TWO_A, TWO_B)):
                 s.update_scan_layer_from_ranges(*TWO_INFLATION, put(TWO_RANGES[:, k:k + 1]), put(TWO_POSE), [sc], **TWO_KW)
-            check_two_scanners(together, state_of(s)[0][0])
+            check_two_scanners(together, window_state(s)[0][0])
             assert pool[16, 20] == 254 and pool[16, 24] == 254 and (pool == 254).sum() == 2
 
 
@@ -404,7 +375,7 @@ def test_refusals_leave_pool_layers_and_points_alone():
         assert call() == -5 and call(device=True) == -5 and untouched()       # a single costmap: NEO_MPC_ERR_UNSUPPORTED
         s.set_costmap_pool(cells, UPDATE_RES, start)
         s.update_scan_layer_from_ranges(*params, ranges, poses, UPDATE_SCANNERS, **UPDATE_KW)   # what the refusals must leave alone
-        held = state_of(s)
+        held = window_state(s)
         assert (held[0] == 254).any() and (held[0] == 0).any()
         nan, inf = float("nan"), float("inf")
         shape_errors = [dict(reserved=1), dict(sources=0), dict(sources=5), dict(beams=0), dict(beams=4097), dict(scanners=None),
@@ -427,16 +398,16 @@ def test_refusals_leave_pool_layers_and_points_alone():
                     errors.append(dict(points_out=dev[2].data_ptr() + 8))     # ... the device variants at the alignment
                 for over in errors:
                     assert call(entry, device, **over) == -1, (entry, device, over)
-                    assert lib.neo_mpc_last_error_code() == -1 and untouched() and same_state(state_of(s), held), (entry, device, over)
-                assert call(entry, device, count=0) == 0 and untouched() and same_state(state_of(s), held)
+                    assert lib.neo_mpc_last_error_code() == -1 and untouched() and same(window_state(s), held), (entry, device, over)
+                assert call(entry, device, count=0) == 0 and untouched() and same(window_state(s), held)
             assert call("update", device, inflation_radius=66 * UPDATE_RES) == -5 and untouched()       # 66 cells
-            assert same_state(state_of(s), held)
+            assert same(window_state(s), held)
             for entry in ("update", "project"):
                 fn = getattr(lib, "neo_mpc_update_scan_layer_from_ranges" if entry == "update" else "neo_mpc_project_laser")
                 assert fn(h, None) == -1 and fn(None, C.byref(abi.NeoMpcLaserBatch())) == -1
         # the projection alone ignores the update's fields and the pool's count, and writes the out buffers
         assert call("project", True, scan_flags=0, unknown_value=9, inflation_radius=nan, count=UPDATE_WINDOWS - 1) == 0
-        assert not untouched() and same_state(state_of(s), held)
+        assert not untouched() and same(window_state(s), held)
 
 
 # ------------------------------------------------------------------------------------------ 10: graph capture
@@ -445,37 +416,26 @@ def test_roll_scan_from_ranges_stamp_gate_solve_can_be_captured_in_a_hip_graph()
     """After one eager call -- it builds the tables and allocates -- roll -> update from ranges -> stamp -> gate -> solve is
     captured on one stream, a linear chain, and replayed twice with ranges and poses rewritten in between; layers, pool,
     gate costs and commands equal the same calls made directly on a second handle."""
-    import torch
-    from neo_mpc_planner2_amd.solver import BatchSolver, DeviceBatch
-    from oracle import mpc_oracle as orc
-    count, sx, sy, beams = 64, 48, 44, 40
+    beams = 40
     stamp, scan = (0.45, 0.9, 3.0), (0.1, 0.3, 3.0)
     scanners = [scanner((0.3, 0.0, 0.0), -1.5, 3.0 / 39, 0.05, 5.0, ref.INF_IS_VALID), scanner((-0.3, 0.0, math.pi), -1.5, 3.0 / 39, 0.05, 5.0)]
-    world, res, wox, woy = synthetic.make_costmap(300, seed=91)
-    probs = synthetic.make_problems(count, 120, seed=92)
-    probs["map_index"] = np.arange(count, dtype=np.int32)
-    st, warm = synthetic.make_states(probs, 3)
+    f = capture_fleet(120)
+    count, sx, sy, res = f.count, f.sx, f.sy, f.res
     rng = np.random.default_rng(94)
     ticks = []
     for k in range(3):
-        poses = np.concatenate([probs["cur_xy"] + rng.uniform(-0.4, 0.4, size=(count, 2)) * k, rng.uniform(-3, 3, size=(count, 1))], 1)
+        poses = np.concatenate([f.probs["cur_xy"] + rng.uniform(-0.4, 0.4, size=(count, 2)) * k, rng.uniform(-3, 3, size=(count, 1))], 1)
         ticks.append((poses, special_ranges(rng, (count, 2, beams), 0.05, 5.0, 1.8)))
-    start = probs["cur_xy"] - 1.0
     fp = gpu(np.asarray(RECT, dtype=np.float64))
 
-    class Side:
-        def __init__(self):
-            self.s = BatchSolver(orc.make_params())
-            self.s.set_world_map(gpu(world), res, wox, woy)
-            self.b = DeviceBatch(probs, st, warm, "cuda:0")
-            self.origins, self.poses, self.ranges = gpu(start), gpu(ticks[0][0]), gpu(ticks[0][1])
-            self.costs = torch.zeros(count, dtype=torch.float64, device="cuda:0")
-            self.xy = self.b.problems.view(torch.float64).reshape(count, -1)[:, 0:2]
+    class LaserSide(Side):
+        def __init__(self, fleet, tick):
+            super().__init__(fleet, tick)
+            self.ranges = gpu(tick[1])
 
         def set_inputs(self, tick):
-            self.poses.copy_(gpu(tick[0]))
+            super().set_inputs(tick)
             self.ranges.copy_(gpu(tick[1]))
-            self.xy.copy_(self.poses[:, :2])
 
         def tick(self):
             self.s.roll_costmap_pool(sx, sy, res, self.origins, poses=self.poses)
@@ -486,39 +446,13 @@ def test_roll_scan_from_ranges_stamp_gate_solve_can_be_captured_in_a_hip_graph()
             self.s.solve_device(self.b.problems, self.b.states, self.b.warm, self.b.commands, solution=self.b.solution)
 
         def result(self):
-            torch.cuda.synchronize()
+            common = super().result()
             layers, layer_origins = self.s.get_scan_layer()
-            return (self.b.commands_host().tobytes(), self.b.states_host().tobytes(), self.costs.cpu().numpy().tolist(),
-                    self.origins.cpu().numpy().tolist(), self.s.get_costmap_pool()[0].tobytes(), layers.tobytes(),
-                    layer_origins.tolist())
+            return common + (self.s.get_costmap_pool()[0].tobytes(), layers.tobytes(), layer_origins.tolist())
 
-    direct, graphed = Side(), Side()
-    try:
-        side = torch.cuda.Stream()
-        side.wait_stream(torch.cuda.current_stream())
-        with torch.cuda.stream(side):          # the eager call, on the capture stream
-            graphed.tick()
-        torch.cuda.synchronize()
-        direct.tick()
-        first = direct.result()
-        assert first == graphed.result()
-        g = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(g, stream=side):
-            graphed.tick()
-        for k in (1, 2):
-            for x in (direct, graphed):
-                x.set_inputs(ticks[k])
-            torch.cuda.synchronize()
-            g.replay()
-            direct.tick()
-            a, b = graphed.result(), direct.result()
-            assert a == b, k
-            assert a[4] != first[4] and a[5] != first[5]       # pool and layers changed
+    with replay_against_direct(lambda: LaserSide(f, ticks[0]), ticks, changed=(4, 5)) as (_, a, _):   # pool and layers changed
         layers = np.frombuffer(a[5], dtype=np.uint8).reshape(count, sy, sx)
         assert (layers == 254).any() and (layers == 0).any()
-    finally:
-        direct.s.close()
-        graphed.s.close()
 
 
 # ------------------------------------------------------------------------------------------ 11: the closed loop
@@ -533,17 +467,9 @@ def test_closed_loop_with_laser_ranges_and_without():
     from oracle import mpc_oracle as orc
     count, size, res, ticks, beams = 64, 60, 0.05, 4, 61
     world = np.zeros((400, 400), dtype=np.uint8)
-    probs = synthetic.make_problems(count, 200, seed=7)
     grid = np.stack(np.meshgrid(np.arange(8), np.arange(8)), -1).reshape(-1, 2)
-    probs["cur_xy"] = -7.0 + 2.0 * grid + 0.011
-    probs["cur_q"] = (0.0, 0.0, 0.0, 1.0)
-    probs["carrot_xy"] = (0.4, 0.0)
-    probs["carrot_q"] = (0.0, 0.0, 0.0, 1.0)
-    probs["goal_xyz"][:, :2] = probs["cur_xy"] + (5.0, 0.0)
-    probs["goal_q"] = probs["cur_q"]
-    probs["cur_vel"] = 0.0
-    probs["map_index"] = np.arange(count, dtype=np.int32)
-    st, warm = synthetic.make_states(probs, 3)
+    xy = -7.0 + 2.0 * grid + 0.011
+    probs, st, warm = standing_fleet(count, xy, xy + (5.0, 0.0))
     front = scanner((0.1, 0.0, 0.0), -1.2, 2.4 / (beams - 1), 0.05, 8.0)
     rear = scanner((-0.1, 0.0, math.pi), -1.2, 2.4 / (beams - 1), 0.05, 8.0, ref.INF_IS_VALID)
     angle = front["angle_min"] + np.arange(beams) * front["angle_increment"]

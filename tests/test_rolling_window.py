@@ -14,6 +14,7 @@ import pytest
 from neo_mpc_planner2_amd import _lib, abi, synthetic
 from tests import rolling_window_reference as ref
 from tests.c_probe import HEADER, run_c_probe
+from tests.fleet_kit import RECT, Side, capture_fleet, gpu, replay_against_direct
 
 WRES = synthetic.RESOLUTION
 WOX, WOY = -1.0, -1.5
@@ -252,21 +253,19 @@ def test_a_solve_and_a_gate_cannot_tell_a_rolled_pool_from_an_ingested_one():
     st, warm = synthetic.make_states(probs, 3)
     start = offsets - 4.3                                   # anywhere: the roll moves the windows to their centres
     want_o, raw = ref.roll(world, res, wox, woy, start, size, size, res, poses=offsets, outside_value=255)
-    dev = "cuda:0"
-    t = lambda a: torch.from_numpy(np.array(a)).to(dev)
-    fp = t(np.asarray(synthetic.RECT_FOOTPRINT, dtype=np.float64))
+    fp = gpu(np.asarray(RECT, dtype=np.float64))
     results = []
     for how in ("rolled", "ingested"):
         with BatchSolver(orc.make_params()) as s:
             if how == "rolled":
-                s.set_world_map(t(world), res, wox, woy)
-                d_orig = t(start)
-                s.roll_costmap_pool(size, size, res, d_orig, poses=t(np.concatenate([offsets, np.zeros((m, 1))], 1)))
+                s.set_world_map(gpu(world), res, wox, woy)
+                d_orig = gpu(start)
+                s.roll_costmap_pool(size, size, res, d_orig, poses=gpu(np.concatenate([offsets, np.zeros((m, 1))], 1)))
             else:
-                d_orig = t(want_o)
-                s.set_costmap_pool(t(raw), res, d_orig)
-            b = DeviceBatch(probs, st, warm, dev)
-            costs = torch.zeros(count, dtype=torch.float64, device=dev)
+                d_orig = gpu(want_o)
+                s.set_costmap_pool(gpu(raw), res, d_orig)
+            b = DeviceBatch(probs, st, warm, "cuda:0")
+            costs = torch.zeros(count, dtype=torch.float64, device="cuda:0")
             s.footprint_gate_device(fp, costs, problems=b.problems)
             s.solve_device(b.problems, b.states, b.warm, b.commands, solution=b.solution)
             torch.cuda.synchronize()
@@ -375,76 +374,25 @@ def test_roll_gate_solve_can_be_captured_in_a_hip_graph():
     """A roll with the geometry, count and origins of the previous one allocates nothing and does not synchronise: after one
     warm-up call, roll -> gate -> solve is captured on one stream and replayed with the poses rewritten in between; the
     replays equal the same calls made directly (on a second handle: same world, same inputs)."""
-    import torch
-    from neo_mpc_planner2_amd.solver import BatchSolver, DeviceBatch
-    from oracle import mpc_oracle as orc
-    count, sx, sy = 64, 48, 44
-    world, res, wox, woy = synthetic.make_costmap(300, seed=91)
-    probs = synthetic.make_problems(count, 260, seed=92)
-    probs["map_index"] = np.arange(count, dtype=np.int32)
-    st, warm = synthetic.make_states(probs, 3)
-    dev = "cuda:0"
-    t = lambda a: torch.from_numpy(np.array(a)).to(dev)
+    f = capture_fleet(260)
     rng = np.random.default_rng(93)
-    ticks = [np.concatenate([probs["cur_xy"] + rng.uniform(-0.4, 0.4, size=(count, 2)) * k, np.zeros((count, 1))], 1)
+    ticks = [(np.concatenate([f.probs["cur_xy"] + rng.uniform(-0.4, 0.4, size=(f.count, 2)) * k, np.zeros((f.count, 1))], 1),)
              for k in range(3)]
-    start = probs["cur_xy"] - 1.0
-    fp = t(np.asarray(synthetic.RECT_FOOTPRINT, dtype=np.float64))
+    fp = gpu(np.asarray(RECT, dtype=np.float64))
 
-    class Side:
-        def __init__(self):
-            self.s = BatchSolver(orc.make_params())
-            self.s.set_world_map(t(world), res, wox, woy)
-            self.b = DeviceBatch(probs, st, warm, dev)
-            self.origins, self.poses = t(start), t(ticks[0])
-            self.costs = torch.zeros(count, dtype=torch.float64, device=dev)
-            self.xy = self.b.problems.view(torch.float64).reshape(count, -1)[:, 0:2]
-
-        def set_poses(self, p):
-            self.poses.copy_(t(p))
-            self.xy.copy_(self.poses[:, :2])
-
+    class RollSide(Side):
         def tick(self):
-            self.s.roll_costmap_pool(sx, sy, res, self.origins, poses=self.poses)
+            self.s.roll_costmap_pool(f.sx, f.sy, f.res, self.origins, poses=self.poses)
             self.s.footprint_gate_device(fp, self.costs, poses=self.poses, problems=self.b.problems)
             self.s.solve_device(self.b.problems, self.b.states, self.b.warm, self.b.commands, solution=self.b.solution)
 
-        def result(self):
-            torch.cuda.synchronize()
-            return (self.b.commands_host().tobytes(), self.b.states_host().tobytes(), self.costs.cpu().numpy().tolist(),
-                    self.origins.cpu().numpy().tolist())
-
-    direct, graphed = Side(), Side()
-    try:
-        side = torch.cuda.Stream()
-        side.wait_stream(torch.cuda.current_stream())
-        with torch.cuda.stream(side):          # the warm-up call, on the capture stream: it allocates and derives
-            graphed.tick()
-        torch.cuda.synchronize()
-        direct.tick()
-        first = direct.result()
-        assert first == graphed.result()
-        g = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(g, stream=side):
-            graphed.tick()
-        for k in (1, 2):
-            for x in (direct, graphed):
-                x.set_poses(ticks[k])
-            torch.cuda.synchronize()
-            g.replay()
-            direct.tick()
-            a, b = graphed.result(), direct.result()
-            assert a == b, k
-            assert a[3] != first[3]                # the windows moved
-        want_o = start
-        for p in ticks:                                          # the warm-up call, then the two replays
-            want_o, _ = ref.roll(world, res, wox, woy, want_o, sx, sy, res, poses=p, fill=False)
+    with replay_against_direct(lambda: RollSide(f, ticks[0]), ticks, changed=(3,)) as (direct, a, _):     # the windows moved
+        want_o = f.start
+        for poses, in ticks:                                     # the warm-up call, then the two replays
+            want_o, _ = ref.roll(f.world, f.res, f.wox, f.woy, want_o, f.sx, f.sy, f.res, poses=poses, fill=False)
         assert a[3] == want_o.tolist()
-        _, want_c = ref.roll(world, res, wox, woy, want_o, sx, sy, res)
+        _, want_c = ref.roll(f.world, f.res, f.wox, f.woy, want_o, f.sx, f.sy, f.res)
         assert np.array_equal(direct.s.get_costmap_pool()[0], want_c)
-    finally:
-        direct.s.close()
-        graphed.s.close()
 
 
 # ------------------------------------------------------------------------------------------ 9: the closed loop

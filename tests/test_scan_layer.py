@@ -13,13 +13,14 @@ import re
 import numpy as np
 import pytest
 
-from neo_mpc_planner2_amd import _lib, abi, synthetic
+from neo_mpc_planner2_amd import _lib, abi
 from tests import fleet_stamp_reference as stamp_ref
 from tests import footprint_gate_reference as gate_ref
 from tests import rolling_window_reference as roll_ref
 from tests import scan_layer_reference as ref
-from tests import world_inflation_reference as world_ref
 from tests.c_probe import HEADER, run_c_probe
+from tests.fleet_kit import RECT, Side, capture_fleet, gpu, inflation_for, replay_against_direct, same, standing_fleet, window_state
+from tests.world_scan_cases import distance_64_case
 
 ENTRY_POINTS = ("neo_mpc_update_scan_layer", "neo_mpc_update_scan_layer_device", "neo_mpc_get_scan_layer",
                 "neo_mpc_reset_scan_layer")
@@ -28,15 +29,8 @@ SHAPES = {"96x70-5cm": (96, 70, 0.05), "40x40-10cm": (40, 40, 0.1), "130x67-2.5c
 REACHES = (0, 3, 12, 64)
 MAX_POINTS = (1, 64, 130)           # one lane, one full wave, two waves and a tail
 WINDOWS = 5
-RECT = tuple(synthetic.RECT_FOOTPRINT)
 #: shape x R, the three point counts dealt over them
 CASES = [(shape, reach, MAX_POINTS[(a + b) % 3]) for a, shape in enumerate(sorted(SHAPES)) for b, reach in enumerate(REACHES)]
-
-
-def inflation_for(reach, res):
-    """(inscribed_radius, inflation_radius, cost_scaling_factor) with ceil(inflation_radius / res) == reach."""
-    radius = 0.0 if reach == 0 else (reach - 0.5) * res
-    return min(radius, 1.5 * res), radius, 3.0 / (res * max(reach, 1))
 
 
 # ------------------------------------------------------------------------------------------ 1: the hand-worked map
@@ -274,25 +268,6 @@ def test_the_cases_take_every_branch():
     assert marks[0] > 0 and marks[2] < marks[1] <= marks[0]
 
 
-# ------------------------------------------------------------------------------------------ shared GPU helpers
-def gpu(a, dtype=None):
-    import torch
-    a = np.ascontiguousarray(a) if dtype is None else np.ascontiguousarray(a).astype(dtype)
-    return torch.from_numpy(a.copy()).to("cuda:0")
-
-
-def state_of(s):
-    import torch
-    torch.cuda.synchronize()
-    layers, layer_origins = s.get_scan_layer()
-    pool, origins = s.get_costmap_pool()
-    return layers, layer_origins, pool, origins
-
-
-def same_state(a, b):
-    return all(x.tobytes() == y.tobytes() for x, y in zip(a, b))
-
-
 # ------------------------------------------------------------------------------------------ 5: one update
 @pytest.mark.gpu
 @pytest.mark.parametrize("shape,reach,max_points", CASES, ids=["%s-R%d-%dpoints" % c for c in CASES])
@@ -307,7 +282,7 @@ def test_update_equals_the_transcription(shape, reach, max_points):
         s.set_costmap_pool(cells, res, origins)
         d = (gpu(points), gpu(sensors), gpu(counts, np.int32))
         s.update_scan_layer(*params, points=d[0], sensor_origins=d[1], point_counts=d[2], **ranges)
-        first = state_of(s)
+        first = window_state(s)
         print("%s R=%d %d points: %d layer cells set, %d window cells change" %
               (shape, reach, max_points, int((want_layers != 255).sum()), int((want_pool != cells).sum())))
         assert np.array_equal(first[0], want_layers), int((first[0] != want_layers).sum())
@@ -315,12 +290,12 @@ def test_update_equals_the_transcription(shape, reach, max_points):
         assert np.array_equal(first[2], want_pool), int((first[2] != want_pool).sum())
         # idempotence: the same batch again, no roll in between
         s.update_scan_layer(*params, points=d[0], sensor_origins=d[1], point_counts=d[2], **ranges)
-        assert same_state(state_of(s), first)
+        assert same(window_state(s), first)
         # the host variant, from scratch: identical bytes
         s.set_costmap_pool(cells, res, origins)
         s.reset_scan_layer()
         s.update_scan_layer(*params, points=points, sensor_origins=sensors, point_counts=counts, **ranges)
-        assert same_state(state_of(s), first)
+        assert same(window_state(s), first)
 
 
 @pytest.mark.gpu
@@ -339,7 +314,7 @@ def test_a_sensor_origin_that_is_not_finite_clears_nothing_on_the_device():
     with BatchSolver({}) as s:
         s.set_costmap_pool(cells, res, origins)
         s.update_scan_layer(*params, points=gpu(points), sensor_origins=gpu(sensors), point_counts=gpu(big), **ranges)
-        got = state_of(s)
+        got = window_state(s)
         assert np.array_equal(got[0], model.layers) and np.array_equal(got[2], want_pool)
 
 
@@ -359,12 +334,12 @@ def test_three_ticks_roll_the_layer_with_its_window():
             s.roll_costmap_pool(sx, sy, res, d_origins, poses=gpu(poses))
             call = lambda: s.update_scan_layer(*params, points=gpu(points), sensor_origins=gpu(sensors), flags=flags, **ranges)
             call()
-            got = state_of(s)
+            got = window_state(s)
             assert got[3].tolist() == want[k][0].tolist() == got[1].tolist(), k
             assert np.array_equal(got[0], want[k][1]), (k, int((got[0] != want[k][1]).sum()))
             assert np.array_equal(got[2], want[k][2]), (k, int((got[2] != want[k][2]).sum()))
             call()                                                  # repeated: nothing changes
-            assert same_state(state_of(s), got), k
+            assert same(window_state(s), got), k
 
 
 # ------------------------------------------------------------------------------------------ 7: unknown_value
@@ -385,7 +360,7 @@ def test_unknown_value_0_frees_unknown_ground_and_a_change_resets_the_layer():
             s.update_scan_layer(*params, unknown_value=unknown, **kw, **ranges)
             want = model.update(cells, origins, res, *params, unknown_value=unknown, **ranges,
                                 **(dict(points=points, sensor_origins=sensors) if with_points else {}))
-            got = state_of(s)
+            got = window_state(s)
             assert np.array_equal(got[0], model.layers) and np.array_equal(got[2], want), step
             seen[step] = got
         assert (seen[0][0] == 254).any() and (seen[0][2] == 255).any()
@@ -462,7 +437,7 @@ def test_refusals_leave_pool_and_layer_alone():
         assert call() == -5 and call(device=True) == -5                     # a single costmap: NEO_MPC_ERR_UNSUPPORTED
         s.set_costmap_pool(cells, res, origins)
         assert call() == 0                                                  # the layer the refusals must leave alone
-        held = state_of(s)
+        held = window_state(s)
         assert (held[0] == 254).any() and (held[0] == 0).any()
         shape_errors = [dict(reserved=1), dict(flags=4), dict(flags=7), dict(unknown_value=1), dict(unknown_value=254),
                         dict(max_points=8193), dict(points=None), dict(sensor_origins=None), dict(count=4), dict(count=6)]
@@ -472,20 +447,20 @@ def test_refusals_leave_pool_and_layer_alone():
         values = [dict(point_counts=bad_counts.ctypes.data), dict(sensor_origins=bad_sensors.ctypes.data)]
         for over in shape_errors + values:                                  # the host variant looks at the values too
             assert call(**over) == -1, over
-            assert lib.neo_mpc_last_error_code() == -1 and same_state(state_of(s), held), over
+            assert lib.neo_mpc_last_error_code() == -1 and same(window_state(s), held), over
         for over in shape_errors:                                           # the device variant: the record's shape alone
             assert call(device=True, **over) == -1, over
-            assert same_state(state_of(s), held), over
+            assert same(window_state(s), held), over
         assert lib.neo_mpc_update_scan_layer(h, None) == -1 and lib.neo_mpc_update_scan_layer_device(h, None, None) == -1
         assert lib.neo_mpc_update_scan_layer(None, C.byref(abi.NeoMpcScanBatch())) == -1
         assert lib.neo_mpc_reset_scan_layer(None) == -1 and lib.neo_mpc_get_scan_layer(None, 0, 1, None, None) == -1
         assert lib.neo_mpc_get_scan_layer(h, 3, 3, None, None) == -1
         for device in (False, True):
             assert call(device, inflation_radius=6.6) == -5                 # 66 cells at 10 cm
-            assert same_state(state_of(s), held)
-            assert call(device, count=0) == 0 and same_state(state_of(s), held)   # nothing to do
+            assert same(window_state(s), held)
+            assert call(device, count=0) == 0 and same(window_state(s), held)   # nothing to do
         assert call(flags=0, points=None, sensor_origins=None, point_counts=None) == 0    # flags 0 needs no pointers
-        assert same_state(state_of(s), held)                                # ... and is the idempotent repeat here
+        assert same(window_state(s), held)                                # ... and is the idempotent repeat here
 
 
 # ------------------------------------------------------------------------------------------ 10: the tick sees the obstacle
@@ -513,16 +488,7 @@ def test_gate_and_solve_see_the_scanned_wall():
         wall = np.array([(wall_x, o_a[1] + (a_l + j + 0.5) * res) for j in range(-12, 13)])
         poses = np.array([(a_xy[0], a_xy[1], 0.0), (wall_x, a_xy[1], 0.0)])
         points = np.stack([wall, wall])
-        probs = synthetic.make_problems(2, 200, seed=5)
-        probs["cur_xy"] = poses[:, :2]
-        probs["cur_q"] = (0.0, 0.0, 0.0, 1.0)
-        probs["carrot_xy"] = (0.4, 0.0)
-        probs["carrot_q"] = (0.0, 0.0, 0.0, 1.0)
-        probs["goal_xyz"][:, :2] = poses[:, :2] + (5.0, 0.0)
-        probs["goal_q"] = (0.0, 0.0, 0.0, 1.0)
-        probs["cur_vel"] = 0.0
-        probs["map_index"] = np.arange(2, dtype=np.int32)
-        st, warm = synthetic.make_states(probs, 3)
+        probs, st, warm = standing_fleet(2, poses[:, :2], poses[:, :2] + (5.0, 0.0), seed=5)
         base, d_poses = gpu(np.asarray(RECT, dtype=np.float64)), gpu(poses)
         out = {}
         for scan in (False, True):
@@ -556,40 +522,29 @@ def test_roll_scan_stamp_gate_solve_can_be_captured_in_a_hip_graph():
     """After one eager call -- it builds the cost tables and allocates -- roll -> scan -> stamp -> gate -> solve is captured
     on one stream, a linear chain, and replayed with points and poses rewritten in between; layers, pool, gate costs and
     commands equal the same calls made directly on a second handle."""
-    import torch
-    from neo_mpc_planner2_amd.solver import BatchSolver, DeviceBatch
-    from oracle import mpc_oracle as orc
-    count, sx, sy, n_points = 64, 48, 44, 40
+    n_points = 40
     stamp, scan = (0.45, 0.9, 3.0), (0.1, 0.3, 3.0)
-    world, res, wox, woy = synthetic.make_costmap(300, seed=91)
-    probs = synthetic.make_problems(count, 120, seed=92)
-    probs["map_index"] = np.arange(count, dtype=np.int32)
-    st, warm = synthetic.make_states(probs, 3)
+    f = capture_fleet(120)
+    count, sx, sy, res = f.count, f.sx, f.sy, f.res
     rng = np.random.default_rng(94)
     ticks = []
     for k in range(3):
-        poses = np.concatenate([probs["cur_xy"] + rng.uniform(-0.4, 0.4, size=(count, 2)) * k, rng.uniform(-3, 3, size=(count, 1))], 1)
+        poses = np.concatenate([f.probs["cur_xy"] + rng.uniform(-0.4, 0.4, size=(count, 2)) * k, rng.uniform(-3, 3, size=(count, 1))], 1)
         angle = rng.uniform(0, 2 * np.pi, size=(count, n_points))
         points = poses[:, None, :2] + rng.uniform(0.2, 1.6, size=(count, n_points))[..., None] * np.stack([np.cos(angle), np.sin(angle)], -1)
         ticks.append((poses, points))
-    start = probs["cur_xy"] - 1.0
     fp = gpu(np.asarray(RECT, dtype=np.float64))
 
-    class Side:
-        def __init__(self):
-            self.s = BatchSolver(orc.make_params())
-            self.s.set_world_map(gpu(world), res, wox, woy)
-            self.b = DeviceBatch(probs, st, warm, "cuda:0")
-            self.origins, self.poses, self.points = gpu(start), gpu(ticks[0][0]), gpu(ticks[0][1])
+    class ScanSide(Side):
+        def __init__(self, fleet, tick):
+            super().__init__(fleet, tick)
+            self.points = gpu(tick[1])
             self.sensors = self.poses[:, :2].contiguous()
-            self.costs = torch.zeros(count, dtype=torch.float64, device="cuda:0")
-            self.xy = self.b.problems.view(torch.float64).reshape(count, -1)[:, 0:2]
 
         def set_inputs(self, tick):
-            self.poses.copy_(gpu(tick[0]))
+            super().set_inputs(tick)
             self.points.copy_(gpu(tick[1]))
             self.sensors.copy_(self.poses[:, :2])
-            self.xy.copy_(self.poses[:, :2])
 
         def tick(self):
             self.s.roll_costmap_pool(sx, sy, res, self.origins, poses=self.poses)
@@ -600,34 +555,11 @@ def test_roll_scan_stamp_gate_solve_can_be_captured_in_a_hip_graph():
             self.s.solve_device(self.b.problems, self.b.states, self.b.warm, self.b.commands, solution=self.b.solution)
 
         def result(self):
-            torch.cuda.synchronize()
+            common = super().result()
             layers, layer_origins = self.s.get_scan_layer()
-            return (self.b.commands_host().tobytes(), self.b.states_host().tobytes(), self.costs.cpu().numpy().tolist(),
-                    self.origins.cpu().numpy().tolist(), self.s.get_costmap_pool()[0].tobytes(), layers.tobytes(),
-                    layer_origins.tolist())
+            return common + (self.s.get_costmap_pool()[0].tobytes(), layers.tobytes(), layer_origins.tolist())
 
-    direct, graphed = Side(), Side()
-    try:
-        side = torch.cuda.Stream()
-        side.wait_stream(torch.cuda.current_stream())
-        with torch.cuda.stream(side):          # the eager call, on the capture stream
-            graphed.tick()
-        torch.cuda.synchronize()
-        direct.tick()
-        first = direct.result()
-        assert first == graphed.result()
-        g = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(g, stream=side):
-            graphed.tick()
-        for k in (1, 2):
-            for x in (direct, graphed):
-                x.set_inputs(ticks[k])
-            torch.cuda.synchronize()
-            g.replay()
-            direct.tick()
-            a, b = graphed.result(), direct.result()
-            assert a == b, k
-            assert a[4] != first[4] and a[5] != first[5]       # pool and layers changed
+    with replay_against_direct(lambda: ScanSide(f, ticks[0]), ticks, changed=(4, 5)) as (_, a, _):   # pool and layers changed
         # ... and the layers are persistent ones: the last tick's hold marks no point of that tick explains
         layers = np.frombuffer(a[5], dtype=np.uint8).reshape(count, sy, sx)
         alone = ref.ScanLayers()
@@ -635,9 +567,6 @@ def test_roll_scan_stamp_gate_solve_can_be_captured_in_a_hip_graph():
         alone.update(np.zeros((count, sy, sx), dtype=np.uint8), raw_origins, res, *scan, points=ticks[2][1],
                      sensor_origins=ticks[2][0][:, :2], obstacle_max_range=1.5, raytrace_max_range=1.2, raytrace_min_range=0.1)
         assert ((layers == 254) & (alone.layers != 254)).any()
-    finally:
-        direct.s.close()
-        graphed.s.close()
 
 
 # ------------------------------------------------------------------------------------------ 12: the closed loop
@@ -651,16 +580,7 @@ def test_closed_loop_with_a_scan_and_without():
     from oracle import mpc_oracle as orc
     size, res, ticks = 100, 0.05, 100
     world = np.zeros((400, 400), dtype=np.uint8)
-    probs = synthetic.make_problems(2, 200, seed=7)
-    probs["cur_xy"] = ((-2.0, 0.011), (-2.0, 4.011))
-    probs["cur_q"] = (0.0, 0.0, 0.0, 1.0)
-    probs["carrot_xy"] = (0.4, 0.0)
-    probs["carrot_q"] = (0.0, 0.0, 0.0, 1.0)
-    probs["goal_xyz"][:, :2] = ((6.0, 0.011), (6.0, 4.011))
-    probs["goal_q"] = probs["cur_q"]
-    probs["cur_vel"] = 0.0
-    probs["map_index"] = np.arange(2, dtype=np.int32)
-    st, warm = synthetic.make_states(probs, 3)
+    probs, st, warm = standing_fleet(2, ((-2.0, 0.011), (-2.0, 4.011)), ((6.0, 0.011), (6.0, 4.011)))
     wall_x = -1.2
     wall = np.array([[(wall_x, y0 + j * res / 2) for j in range(-40, 41)] for y0 in (0.011, 4.011)])
     d_wall = gpu(wall)
@@ -695,31 +615,6 @@ def test_closed_loop_with_a_scan_and_without():
 
 
 # ------------------------------------------------------------------------------------------ 13: a seed exactly 64 cells away
-@functools.lru_cache(maxsize=None)
-def distance_64_case():
-    """193 x 66 free cells of 1/16 m (a layer pitch of 256), seeds at (64, 1) and (64, 65), R = 64: K9's and K10's shared pass
-    where a seed is exactly 64 columns away across a tile border on either side, and 64 rows.  -> (world, inflated world,
-    parameters, the two scan points [1, 2, 2], sensor origin [1, 2], layers, pool), the cell values asserted by hand."""
-    params = inflation_for(64, 0.0625)
-    table, reach = world_ref.table_for(0.0625, *params)
-    assert reach == 64 and table[4096] >= 1                              # (or the arm could not be seen)
-    world = np.zeros((66, 193), dtype=np.uint8)
-    world[1, 64] = world[65, 64] = 254
-    want = world_ref.inflate_world(world, 0.0625, *params)
-    # the centres of the seeds' cells, seen from the centre of cell (64, 33): 2 m either way, inside the default ranges
-    points, sensor = np.array([[(4.03125, 0.09375), (4.03125, 4.09375)]]), np.array([(4.03125, 2.09375)])
-    model = ref.ScanLayers()
-    pool = model.update(world[None] * 0, np.zeros((1, 2)), 0.0625, *params, points=points, sensor_origins=sensor)
-    assert np.argwhere(model.layers[0] == 254).tolist() == [[1, 64], [65, 64]]
-    for got in (want, pool[0]):
-        # 64 columns to the left and to the right of either seed: T[4096], in those two rows alone; from column 129 on: untouched
-        assert got[1, 0] == got[1, 128] == got[65, 0] == got[65, 128] == table[4096] and not got[:, 129:].any()
-        assert np.flatnonzero(got[:, 0]).tolist() == np.flatnonzero(got[:, 128]).tolist() == [1, 65]
-        # 64 rows from the other seed: each is a seed itself and keeps 254 from there, max(254, T[4096])
-        assert got[1, 64] == got[65, 64] == 254 and (got == 254).sum() == 2
-    return world, want, params, points, sensor, model.layers, pool
-
-
 def test_a_seed_exactly_64_cells_away_in_the_transcriptions():
     assert np.array_equal(distance_64_case()[1], distance_64_case()[6][0])    # unknown layer cells leave a free window alone
 
@@ -735,5 +630,5 @@ def test_a_seed_exactly_64_cells_away_on_the_gpu():
             assert np.array_equal(s.get_world_map()[0], want), put.__name__
             s.set_costmap_pool(world[None] * 0, 0.0625, np.zeros((1, 2)))
             s.update_scan_layer(*params, points=put(points), sensor_origins=put(sensor))
-            got = state_of(s)
+            got = window_state(s)
             assert np.array_equal(got[0], layers) and np.array_equal(got[2], pool), put.__name__

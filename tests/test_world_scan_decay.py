@@ -13,18 +13,17 @@ import re
 import numpy as np
 import pytest
 
-from neo_mpc_planner2_amd import _lib, abi, synthetic
+from neo_mpc_planner2_amd import _lib, abi
 from tests import rolling_window_reference as roll_ref
 from tests import world_decay_reference as ref
 from tests import world_denoise_reference as denoise_ref
 from tests import world_scan_layer_reference as world_ref
 from tests.c_probe import HEADER, kernel_resources, run_c_probe
-from tests.test_world_scan_denoise import FAR, cell_centre, denoised_of
-from tests.test_world_scan_layer import WORLDS, gpu, inflation_for, rectangle, rolled_pool, same, scanner, state_of
+from tests.fleet_kit import (F32, FAR, RECT, capture, cell_centre, denoised_of, eager_on_side_stream, gpu, inflation_for,
+                             pairs_fleet, rectangle, rolled_pool, same, scanner, world_state)
+from tests.world_scan_cases import WORLDS
 
 ENTRY_POINTS = ("neo_mpc_set_world_scan_decay", "neo_mpc_get_world_scan_ages")
-RECT = tuple(synthetic.RECT_FOOTPRINT)
-F32 = np.float32
 CLEAR, MARK = world_ref.CLEAR, world_ref.MARK
 SCAN = CLEAR | MARK
 NO_AGE = ref.NO_AGE
@@ -205,7 +204,7 @@ def expected(world, reach, max_age, robots):
 
 def device_state(s):
     """(layer, live, D, ages) of the handle."""
-    layer, live = state_of(s)
+    layer, live = world_state(s)
     return layer, live, denoised_of(s), s.get_world_scan_ages()
 
 
@@ -360,7 +359,7 @@ class Pair:
             mine.update(clear=clear)
         self.s.update_world_scan_layer(*self.params, **kw)
         live = self.model.update(self.world, 1.0, 0.0, 0.0, *self.params, **mine)
-        layer, got_live = state_of(self.s)
+        layer, got_live = world_state(self.s)
         assert same((layer, got_live, denoised_of(self.s)), (self.model.layer, live, self.model.denoised))
         if self.model.decaying:
             ages = self.s.get_world_scan_ages()
@@ -440,7 +439,7 @@ def test_off_is_the_update_as_it_was_and_the_ages_getter_refuses():
                     else:
                         kw.update(on_device=True)
                     s.update_world_scan_layer(*params, **kw)
-                    got = state_of(s) + (denoised_of(s),)
+                    got = world_state(s) + (denoised_of(s),)
                     assert same(got, want[k]), (group, setting, k, differing(got, want[k]))
                     assert s._lib.neo_mpc_get_world_scan_ages(s._handle, None) == -5   # a layer, and no ages
                     assert s._lib.neo_mpc_last_error_code() == -5
@@ -456,9 +455,9 @@ def test_on_off_on_treats_the_marks_present_as_new_and_the_setting_survives_rese
             p.update(marks_at(X, Y), MARK)
             layer, _, ages = p.update(marks_at(X), MARK)
             assert at(ages, X) == 0 and at(ages, Y) == 1
-            held = state_of(s)
+            held = world_state(s)
             p.set_decay(0)
-            assert same(state_of(s), held)                               # the setter itself changes nothing ...
+            assert same(world_state(s), held)                               # the setter itself changes nothing ...
             assert np.array_equal(s.get_world_scan_ages(), ages)         # ... and the last update still ran with decay
             layer, _, ages = p.update()                                  # off: Pair.update checks that the getter refuses
             assert ages is None and at(layer, Y) == 254
@@ -518,10 +517,10 @@ def test_a_lowered_max_age_acts_with_the_next_update_without_a_scan_and_a_raised
             p.set_decay(2)
             layer, _, ages = p.update()                                  # flags == 0
             assert [at(layer, c) for c in (first, second, third)] == [255, 255, 254] and at(ages, third) == 0
-            held = state_of(s)
+            held = world_state(s)
             p.set_decay(10)
             layer, _, ages = p.update()
-            assert same(state_of(s), held) and at(ages, third) == 0      # nothing comes back, nothing else goes
+            assert same(world_state(s), held) and at(ages, third) == 0      # nothing comes back, nothing else goes
             layer, _, ages = p.update(marks_at(first), MARK)
             assert [at(ages, c) for c in (first, third)] == [0, 1] and at(layer, second) == 255
 
@@ -644,16 +643,11 @@ def test_a_captured_update_that_is_replayed_advances_the_clock():
             layer, live = s.get_world_scan_layer()
             return layer, s.get_world_scan_ages(), s.get_costmap_pool()[0]
 
-        side = torch.cuda.Stream()
-        side.wait_stream(torch.cuda.current_stream())
-        with torch.cuda.stream(side):                                    # the eager call, on the capture stream: it allocates
-            tick()
+        side = eager_on_side_stream(tick)                                # (it allocates)
         layer, ages, pool = seen()
         assert at(layer, cx) == 254 and at(layer, cy) == 254 and at(ages, cx) == 0 and at(ages, cy) == 0
         assert (layer == 254).sum() == 2 and (pool == 254).sum() == 2
-        g = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(g, stream=side):
-            tick()
+        g = capture(tick, side)
         ranges.copy_(gpu(np.array([[[5.0, np.inf]]], dtype=F32)))        # (no INF_IS_VALID: beam 1 is nothing, not even a ray)
         torch.cuda.synchronize()
         for replay in range(1, max_age + 2):
@@ -669,7 +663,7 @@ def test_a_captured_update_that_is_replayed_advances_the_clock():
 # ------------------------------------------------------------------------------------------ 12: the closed loop
 @pytest.mark.gpu
 def test_closed_loop_a_wall_seen_once_lets_the_robots_go_again_and_a_wall_seen_every_tick_does_not():
-    """64 robots in 32 pairs on a free world map, placed as in tests/test_world_scan_layer.py: the even robot of a pair stands
+    """64 robots in 32 pairs on a free world map, fleet_kit.pairs_fleet with 161 beams: the even robot of a pair stands
     1.5 m behind the odd one and its front scanner looks at it.  Its ranges hold a short wall 0.15 m in front of the odd robot's
     centre, from 0.2 m to 0.4 m to its LEFT: it crosses the left edge of that robot's outline, so its footprint gate reads 254
     and the robot is stopped for that tick, and it lies more than the inscribed ring away from the line the robot's own
@@ -683,25 +677,11 @@ def test_closed_loop_a_wall_seen_once_lets_the_robots_go_again_and_a_wall_seen_e
     from neo_mpc_planner2_amd import fleet as fleet_loop
     from neo_mpc_planner2_amd.solver import BatchSolver, DeviceBatch
     from oracle import mpc_oracle as orc
-    count, size, res, ticks, beams = 64, 60, 0.05, 6, 161
+    ticks = 6
     wox = woy = -10.0
     world = np.zeros((400, 400), dtype=np.uint8)
-    probs = synthetic.make_problems(count, 200, seed=7)
-    grid_ = np.stack(np.meshgrid(np.arange(4), np.arange(8)), -1).reshape(-1, 2)
-    seers = np.array([-8.0, -7.0]) + grid_ * (4.0, 2.0) + 0.011
-    xy = np.empty((count, 2))
-    xy[0::2], xy[1::2] = seers, seers + (1.5, 0.0)
-    probs["cur_xy"] = xy
-    probs["cur_q"] = (0.0, 0.0, 0.0, 1.0)
-    probs["carrot_xy"] = (0.4, 0.0)
-    probs["carrot_q"] = (0.0, 0.0, 0.0, 1.0)
-    probs["goal_xyz"][:, :2] = xy + (5.0, 0.0)
-    probs["goal_q"] = probs["cur_q"]
-    probs["cur_vel"] = 0.0
-    probs["map_index"] = np.arange(count, dtype=np.int32)
-    st, warm = synthetic.make_states(probs, 3)
-    front = scanner((0.1, 0.0, 0.0), -0.25, 0.5 / (beams - 1), 0.05, 8.0)
-    angle = front["angle_min"] + np.arange(beams) * front["angle_increment"]
+    p = pairs_fleet(beams=161)
+    count, size, res, beams, probs, st, warm, angle = p.count, p.size, p.res, p.beams, p.probs, p.st, p.warm, p.angle
     # the wall: x = 0.1 + 1.55 in the even robot's base frame, y from 0.2 to 0.4 (the even robots move a few centimetres in these
     # ticks and their wall with them: it goes on crossing the left edge, which reaches from -0.35 to 0.35)
     across = 1.55 * np.tan(angle)
@@ -716,9 +696,9 @@ def test_closed_loop_a_wall_seen_once_lets_the_robots_go_again_and_a_wall_seen_e
     d_first, d_later = gpu(first), gpu(later)
     params = (0.1, 0.3, 3.0)
 
-    def world_scan(t, poses):
+    def world_scan(t, poses):                                            # (fleet_kit.world_scan_callback with two sets of ranges)
         return dict(zip(("inscribed_radius", "inflation_radius", "cost_scaling_factor"), params),
-                    ranges=d_first if t == 0 else d_later, poses=poses, scanners=[front])
+                    ranges=d_first if t == 0 else d_later, poses=poses, scanners=[p.front])
 
     stopped, moving = {}, {}
     for how, max_age in (("never set", None), ("A = 3", 3)):
@@ -727,7 +707,7 @@ def test_closed_loop_a_wall_seen_once_lets_the_robots_go_again_and_a_wall_seen_e
                 s.set_world_scan_decay(max_age)
             s.set_world_map(world, res, wox, woy)
             commands = []
-            d_orig = gpu(xy - size * res / 2 + 0.013)
+            d_orig = gpu(p.origins)
             s.roll_costmap_pool(size, size, res, d_orig)
             b = DeviceBatch(probs, st, warm, "cuda:0")
             fleet_loop.closed_loop(s, b, ticks, after_tick=lambda t, cm: commands.append(cm.copy()), footprint=RECT,

@@ -14,22 +14,21 @@ import re
 import numpy as np
 import pytest
 
-from neo_mpc_planner2_amd import _lib, abi, synthetic
+from neo_mpc_planner2_amd import _lib, abi
 from tests import rolling_window_reference as roll_ref
 from tests import world_denoise_reference as ref
 from tests import world_scan_layer_reference as world_ref
 from tests.c_probe import HEADER, run_c_probe
-from tests.test_world_scan_layer import WORLDS, gpu, inflation_for, rectangle, rolled_pool, same, scanner, state_of
-from tests.test_world_scan_layer import case as world_case
+from tests.fleet_kit import (F32, FAR, RECT, Side, capture_fleet, cell_centre, denoised_of, gpu, inflation_for, pairs_fleet,
+                             rectangle, replay_against_direct, rolled_pool, same, scanner, world_scan_callback, world_state)
+from tests.world_scan_cases import UPDATE_FLAGS, WORLDS, expected, ranges_for
+from tests.world_scan_cases import case as world_case
 
 ENTRY_POINTS = ("neo_mpc_set_world_scan_denoise", "neo_mpc_get_world_scan_denoised")
-RECT = tuple(synthetic.RECT_FOOTPRINT)
-F32 = np.float32
 MARK = world_ref.MARK
 SETTINGS = ((2, 8), (2, 4), (3, 8), (16, 8), (16, 4))
 DENOISE_WORLDS = ("130x67-2.5cm", "40x40-10cm")      # more than one tile each way, a width that is no multiple of 4; less than a tile
 DENOISE_REACHES = (0, 3, 64)
-FAR = dict(obstacle_max_range=100.0, obstacle_min_range=0.0, raytrace_max_range=100.0, raytrace_min_range=0.0)
 
 
 # ------------------------------------------------------------------------------------------ 1: the rule by hand
@@ -188,7 +187,7 @@ def shapes_for(world, group, connectivity):
 @functools.lru_cache(maxsize=None)
 def denoise_case(world, group, connectivity):
     """(cells [sy, sx] of the world map, wox, woy, points [1, n, 2], sensor origin [1, 2], shapes).  The world map is random
-    as in tests/test_world_scan_layer.py, so walls join groups; speckle of density 0.02 everywhere but around the shapes."""
+    as in tests/world_scan_cases.py, so walls join groups; speckle of density 0.02 everywhere but around the shapes."""
     sx, sy, res = WORLDS[world]
     rng = np.random.default_rng(77 * sx + 5 * group + connectivity)
     cells = rng.choice(np.array([0, 0, 0, 0, 60, 150, 253, 254, 255, 255, 255], dtype=np.uint8), size=(sy, sx))
@@ -269,12 +268,6 @@ def test_the_shapes_of_the_cases_come_out_as_designed(world, group, connectivity
 
 
 # ------------------------------------------------------------------------------------------ 4: equality with the transcription
-def denoised_of(s):
-    import torch
-    torch.cuda.synchronize()
-    return s.get_world_scan_denoised()
-
-
 CASES = [(w, r, g, c) for w in DENOISE_WORLDS for r in DENOISE_REACHES for g, c in SETTINGS]
 
 
@@ -295,7 +288,7 @@ def test_filtered_updates_equal_the_transcription(world, reach, group, connectiv
             s.reset_world_scan_layer()
             for repeat in range(2):                                       # repeated with the same inputs: nothing changes
                 s.update_world_scan_layer(*params, points=put(points), sensor_origins=put(sensor), flags=MARK, **FAR)
-                got_layer, got_live = state_of(s)
+                got_layer, got_live = world_state(s)
                 got_d = denoised_of(s)
                 assert np.array_equal(got_layer, layer), (put.__name__, repeat)       # the layer is not changed by the filter
                 assert np.array_equal(got_d, d), (put.__name__, repeat, np.argwhere(got_d != d)[:8].tolist())
@@ -309,7 +302,6 @@ def test_filtered_updates_equal_the_transcription(world, reach, group, connectiv
 @pytest.mark.gpu
 def test_off_is_the_update_as_it_was():
     from neo_mpc_planner2_amd.solver import BatchSolver
-    from tests.test_world_scan_layer import UPDATE_FLAGS, expected, ranges_for
     key = ("96x70-5cm", 3, 3, 64, 255)
     sx, sy, res = WORLDS[key[0]]
     cells, wox, woy, updates, polygons = world_case(key[0], key[2], key[3])
@@ -328,16 +320,12 @@ def test_off_is_the_update_as_it_was():
                 else:
                     kw.update(on_device=True)
                 s.update_world_scan_layer(*params, **kw)
-                got = state_of(s)
+                got = world_state(s)
                 assert np.array_equal(got[0], want[k][0]) and np.array_equal(got[1], want[k][1]), (setting, k)
                 assert np.array_equal(denoised_of(s), want[k][0]), (setting, k)   # the getter returns the layer
 
 
 # ------------------------------------------------------------------------------------------ 6: the layer remembers
-def cell_centre(i, l, res=1.0, ox=0.0, oy=0.0):
-    return (ox + (i + 0.5) * res, oy + (l + 0.5) * res)
-
-
 @pytest.mark.gpu
 def test_the_layer_remembers_a_lone_mark_until_its_neighbour_comes():
     from neo_mpc_planner2_amd.solver import BatchSolver
@@ -356,13 +344,13 @@ def test_the_layer_remembers_a_lone_mark_until_its_neighbour_comes():
             s.set_world_scan_denoise(2, 8)
             # update 1 marks one cell: in the layer, not in live
             s.update_world_scan_layer(*params, points=put(first), sensor_origins=put(sensor), flags=MARK, **FAR)
-            layer, live = state_of(s)
+            layer, live = world_state(s)
             assert layer[20, 63] == 254 and (layer == 254).sum() == 1 and not live.any() and denoised_of(s)[20, 63] == 0
             want = model.update(world, 1.0, 0.0, 0.0, *params, points=first, sensor_origins=sensor, flags=MARK, **FAR)
             assert same((layer, live, denoised_of(s)), (model.layer, want, model.denoised))
             # update 2, marks alone, marks its neighbour: both are in live with their rings
             s.update_world_scan_layer(*params, points=put(second), sensor_origins=put(sensor), flags=MARK, **FAR)
-            layer, live = state_of(s)
+            layer, live = world_state(s)
             want = model.update(world, 1.0, 0.0, 0.0, *params, points=second, sensor_origins=sensor, flags=MARK, **FAR)
             assert layer[20, 63] == 254 and layer[20, 64] == 254 and live[20, 63] == 254 and live[20, 64] == 254
             assert 0 < live[20, 61] < 253 and 0 < live[22, 64] < 253 and live[20, 59] == 0    # (R = 3: the ring ends three cells out)
@@ -372,25 +360,25 @@ def test_the_layer_remembers_a_lone_mark_until_its_neighbour_comes():
         model.reset()
         s.update_world_scan_layer(*params, points=first, sensor_origins=sensor, flags=MARK, **FAR)
         model.update(world, 1.0, 0.0, 0.0, *params, points=first, sensor_origins=sensor, flags=MARK, **FAR)
-        held = state_of(s)
+        held = world_state(s)
         assert not held[1].any()
         s.set_world_scan_denoise(0)
-        assert same(state_of(s), held)                                   # the setter itself changes nothing
+        assert same(world_state(s), held)                                   # the setter itself changes nothing
         s.update_world_scan_layer(*params, flags=0, **FAR)
         model.set_denoise(0)
         want = model.update(world, 1.0, 0.0, 0.0, *params, flags=0, **FAR)
-        layer, live = state_of(s)
+        layer, live = world_state(s)
         assert live[20, 63] == 254 and 0 < live[20, 65] < 253 and same((layer, live), (model.layer, want))
         assert np.array_equal(denoised_of(s), layer)
         s.set_world_scan_denoise(2, 4)
         s.update_world_scan_layer(*params, flags=0, **FAR)
-        layer, live = state_of(s)
+        layer, live = world_state(s)
         assert layer[20, 63] == 254 and not live.any() and denoised_of(s)[20, 63] == 0
         # the setting survives a reset of the layer and a new world map
         s.reset_world_scan_layer()
         s.set_world_map(world, 1.0, 0.0, 0.0)
         s.update_world_scan_layer(*params, points=first, sensor_origins=sensor, flags=MARK, **FAR)
-        layer, live = state_of(s)
+        layer, live = world_state(s)
         assert layer[20, 63] == 254 and not live.any()
 
 
@@ -413,12 +401,12 @@ def test_the_filter_runs_behind_the_footprint_clearing_of_the_same_update():
             s.reset_world_scan_layer()
             model.reset()
             s.update_world_scan_layer(*params, points=put(points), sensor_origins=put(sensor), flags=MARK, **FAR)
-            assert (state_of(s)[1] == 254).sum() == 3                     # without the clearing: a group of three, kept
+            assert (world_state(s)[1] == 254).sum() == 3                     # without the clearing: a group of three, kept
             s.reset_world_scan_layer()
             s.update_world_scan_layer(*params, points=put(points), sensor_origins=put(sensor), flags=MARK,
                                       clear=dict(polygons=put(clear["polygons"]), padding=0.0), **FAR)
             want = model.update(world, 1.0, 0.0, 0.0, *params, points=points, sensor_origins=sensor, flags=MARK, clear=clear, **FAR)
-            layer, live = state_of(s)
+            layer, live = world_state(s)
             assert layer[12, 10] == 254 and layer[12, 11] == 254 and layer[12, 12] == 0 and (layer == 254).sum() == 2
             assert not (live == 254).any() and same((layer, live, denoised_of(s)), (model.layer, want, model.denoised))
 
@@ -449,7 +437,7 @@ def test_the_roll_cuts_its_windows_from_the_filtered_map():
         s.set_world_scan_denoise(2)
         s.set_world_map(gpu(world), res, -5.0, -5.0)
         s.update_world_scan_layer(*params, points=gpu(points), sensor_origins=gpu(poses[:, :2]))
-        assert same(state_of(s), (model.layer, live))
+        assert same(world_state(s), (model.layer, live))
         pool, origins = rolled_pool(s, size, size, res, start.copy(), poses)
         assert origins.tolist() == want_origins.tolist() and np.array_equal(pool, want)
         assert not pool[1][unfiltered[1] != want[1]].any()               # no cell the speck's ring would have raised
@@ -480,7 +468,7 @@ def test_refused_settings_leave_everything_and_the_setting_in_force_alone():
         rolled_pool(s, size, size, res, start.copy(), poses)
 
         def state():
-            return state_of(s) + (denoised_of(s), s.get_costmap_pool()[0])
+            return world_state(s) + (denoised_of(s), s.get_costmap_pool()[0])
 
         held = state()
         assert same(held[:3], (layer, live, d)) and (d != layer).any()
@@ -507,91 +495,60 @@ def test_the_filtered_tick_can_be_captured_in_a_hip_graph():
     """The chain of tests/test_world_scan_layer.py's capture test with the filter on at G = 3: after one eager call, world scan
     from ranges -> roll -> stamp -> gate -> solve is captured on one stream, a linear chain, and replayed twice with ranges
     and poses rewritten in between; layer, D, live, pool, gate costs and commands equal direct calls on a second handle."""
-    import torch
-    from neo_mpc_planner2_amd.solver import BatchSolver, DeviceBatch
-    from oracle import mpc_oracle as orc
-    count, sx, sy, beams = 64, 48, 44, 40
+    beams = 40
     stamp, scan = (0.45, 0.9, 3.0), (0.1, 0.3, 3.0)
     scanners = [scanner((0.3, 0.0, 0.0), -1.5, 3.0 / 39, 0.05, 5.0, abi.LASER_INF_IS_VALID), scanner((-0.3, 0.0, math.pi), -1.5, 3.0 / 39, 0.05, 5.0)]
-    world, res, wox, woy = synthetic.make_costmap(300, seed=91)
-    probs = synthetic.make_problems(count, 120, seed=92)
-    probs["map_index"] = np.arange(count, dtype=np.int32)
-    st, warm = synthetic.make_states(probs, 3)
+    f = capture_fleet(120)
+    count = f.count
     rng = np.random.default_rng(95)
     ticks = []
     for k in range(3):
-        poses = np.concatenate([probs["cur_xy"] + rng.uniform(-0.4, 0.4, size=(count, 2)) * k, rng.uniform(-3, 3, size=(count, 1))], 1)
+        poses = np.concatenate([f.probs["cur_xy"] + rng.uniform(-0.4, 0.4, size=(count, 2)) * k, rng.uniform(-3, 3, size=(count, 1))], 1)
         ranges = rng.uniform(0.0, 1.8, size=(count, 2, beams)).astype(F32)
         ranges[:, :, 3:39:7] = np.array([np.nan, np.inf, -np.inf, 0.05, 5.0, 0.04], dtype=F32)
         ticks.append((poses, ranges))
-    start = probs["cur_xy"] - 1.0
     fp = gpu(np.asarray(RECT, dtype=np.float64))
 
-    class Side:
-        def __init__(self):
-            self.s = BatchSolver(orc.make_params())
-            self.s.set_world_scan_denoise(3)
-            self.s.set_world_map(gpu(world), res, wox, woy)
-            self.b = DeviceBatch(probs, st, warm, "cuda:0")
-            self.origins, self.poses, self.ranges = gpu(start), gpu(ticks[0][0]), gpu(ticks[0][1])
-            self.costs = torch.zeros(count, dtype=torch.float64, device="cuda:0")
-            self.xy = self.b.problems.view(torch.float64).reshape(count, -1)[:, 0:2]
+    class FilteredSide(Side):
+        def __init__(self, fleet, tick):
+            super().__init__(fleet, tick)
+            self.ranges = gpu(tick[1])
+
+        def open_solver(self):
+            s = super().open_solver()
+            s.set_world_scan_denoise(3)
+            return s
 
         def set_inputs(self, tick):
-            self.poses.copy_(gpu(tick[0]))
+            super().set_inputs(tick)
             self.ranges.copy_(gpu(tick[1]))
-            self.xy.copy_(self.poses[:, :2])
 
-        def tick(self):
+        def tick(self):                                                   # (the eager one allocates D)
             self.s.update_world_scan_layer_from_ranges(*scan, self.ranges, self.poses, scanners, obstacle_max_range=1.5,
                                                        raytrace_max_range=1.2, raytrace_min_range=0.1,
                                                        clear=dict(footprint=fp, poses=self.poses, padding=0.1))
-            self.s.roll_costmap_pool(sx, sy, res, self.origins, poses=self.poses)
+            self.s.roll_costmap_pool(f.sx, f.sy, f.res, self.origins, poses=self.poses)
             self.s.stamp_fleet(*stamp, footprint=fp, poses=self.poses)
             self.s.footprint_gate_device(fp, self.costs, poses=self.poses, problems=self.b.problems)
             self.s.solve_device(self.b.problems, self.b.states, self.b.warm, self.b.commands, solution=self.b.solution)
 
         def result(self):
-            torch.cuda.synchronize()
+            common = super().result()
             layer, live = self.s.get_world_scan_layer()
-            return (self.b.commands_host().tobytes(), self.b.states_host().tobytes(), self.costs.cpu().numpy().tolist(),
-                    self.origins.cpu().numpy().tolist(), self.s.get_costmap_pool()[0].tobytes(), layer.tobytes(), live.tobytes(),
-                    self.s.get_world_scan_denoised().tobytes())
+            return common + (self.s.get_costmap_pool()[0].tobytes(), layer.tobytes(), live.tobytes(),
+                             self.s.get_world_scan_denoised().tobytes())
 
-    direct, graphed = Side(), Side()
-    try:
-        side = torch.cuda.Stream()
-        side.wait_stream(torch.cuda.current_stream())
-        with torch.cuda.stream(side):          # the eager call, on the capture stream: it allocates D
-            graphed.tick()
-        torch.cuda.synchronize()
-        direct.tick()
-        first = direct.result()
-        assert first == graphed.result()
-        g = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(g, stream=side):
-            graphed.tick()
-        for k in (1, 2):
-            for x in (direct, graphed):
-                x.set_inputs(ticks[k])
-            torch.cuda.synchronize()
-            g.replay()
-            direct.tick()
-            a, b = graphed.result(), direct.result()
-            assert a == b, k
-            assert a[4] != first[4] and a[5] != first[5] and a[6] != first[6] and a[7] != first[7]
-        shape = world.shape
+    # pool, layer, live and D changed
+    with replay_against_direct(lambda: FilteredSide(f, ticks[0]), ticks, changed=(4, 5, 6, 7)) as (_, a, _):
+        shape = f.world.shape
         layer, live, d = (np.frombuffer(x, dtype=np.uint8).reshape(shape) for x in a[5:8])
-        assert (layer == 254).any() and (d != layer).any() and np.array_equal(d, ref.denoise(layer, world, 3, 8))
-    finally:
-        direct.s.close()
-        graphed.s.close()
+        assert (layer == 254).any() and (d != layer).any() and np.array_equal(d, ref.denoise(layer, f.world, 3, 8))
 
 
 # ------------------------------------------------------------------------------------------ 11: the closed loop
 @pytest.mark.gpu
 def test_closed_loop_a_stray_return_no_longer_stops_a_robot_and_a_wall_still_does():
-    """64 robots in 32 pairs on a free world map, as in tests/test_world_scan_layer.py: the even robot of a pair stands 1.5 m
+    """64 robots in 32 pairs on a free world map, fleet_kit.pairs_fleet: the even robot of a pair stands 1.5 m
     behind the odd one and its front scanner looks at it; the odd robots' own ranges hold nothing.  In a third of the pairs
     ONE beam of the even robot returns, from the odd robot's front edge -- the world cell that the odd robot's window shows in
     the column its gate walks for that edge at tick 0; in the others all beams return a wall 0.3 m in front of the odd robot's
@@ -603,44 +560,24 @@ def test_closed_loop_a_stray_return_no_longer_stops_a_robot_and_a_wall_still_doe
     from neo_mpc_planner2_amd import fleet as fleet_loop
     from neo_mpc_planner2_amd.solver import BatchSolver, DeviceBatch
     from oracle import mpc_oracle as orc
-    count, size, res, ticks, beams = 64, 60, 0.05, 4, 41
+    ticks = 4
     wox = woy = -10.0
     world = np.zeros((400, 400), dtype=np.uint8)
-    probs = synthetic.make_problems(count, 200, seed=7)
-    grid_ = np.stack(np.meshgrid(np.arange(4), np.arange(8)), -1).reshape(-1, 2)
-    seers = np.array([-8.0, -7.0]) + grid_ * (4.0, 2.0) + 0.011
-    xy = np.empty((count, 2))
-    xy[0::2], xy[1::2] = seers, seers + (1.5, 0.0)
-    probs["cur_xy"] = xy
-    probs["cur_q"] = (0.0, 0.0, 0.0, 1.0)
-    probs["carrot_xy"] = (0.4, 0.0)
-    probs["carrot_q"] = (0.0, 0.0, 0.0, 1.0)
-    probs["goal_xyz"][:, :2] = xy + (5.0, 0.0)
-    probs["goal_q"] = probs["cur_q"]
-    probs["cur_vel"] = 0.0
-    probs["map_index"] = np.arange(count, dtype=np.int32)
-    st, warm = synthetic.make_states(probs, 3)
-    front = scanner((0.1, 0.0, 0.0), -0.25, 0.5 / (beams - 1), 0.05, 8.0)
-    angle = front["angle_min"] + np.arange(beams) * front["angle_increment"]
+    p = pairs_fleet()
+    count, size, res, beams, probs, st, warm, xy, origins = p.count, p.size, p.res, p.beams, p.probs, p.st, p.warm, p.xy, p.origins
     stray = np.arange(32) % 3 == 0                                       # pairs 0, 3, 6, ...: a third
-    origins = xy - size * res / 2 + 0.013
     ranges = np.full((count, 1, beams), np.inf, dtype=F32)               # (no INF_IS_VALID: nothing, not even a clearing ray)
     for pair in range(32):
         seer, odd = 2 * pair, 2 * pair + 1
         if not stray[pair]:
-            ranges[seer, 0] = (1.7 / np.cos(angle)).astype(F32)          # x = 0.1 + 1.7 in the even robot's base frame
+            ranges[seer, 0] = (1.7 / np.cos(p.angle)).astype(F32)          # x = 0.1 + 1.7 in the even robot's base frame
             continue
         ox = roll_ref.move_origin(origins[odd], xy[odd], size, size, res)[0]
         column = math.floor((xy[odd, 0] + RECT[0][0] - ox) / res)        # the window column of the front edge
         shown = roll_ref.world_cell(ox + (column + 0.5) * res, wox, res, 400)          # ... and the world column it shows
         ranges[seer, 0, beams // 2] = wox + (shown + 0.5) * res - (xy[seer, 0] + 0.1)
-    assert abs(angle[beams // 2]) < 1e-12 and stray.sum() == 11
-    d_ranges = gpu(ranges)
-    params = (0.1, 0.3, 3.0)
-
-    def world_scan(t, poses):
-        return dict(zip(("inscribed_radius", "inflation_radius", "cost_scaling_factor"), params), ranges=d_ranges, poses=poses,
-                    scanners=[front])
+    assert abs(p.angle[beams // 2]) < 1e-12 and stray.sum() == 11
+    world_scan = world_scan_callback((0.1, 0.3, 3.0), gpu(ranges), p.front)
 
     runs, marks = {}, {}
     for how, group in (("never set", None), ("off", 0), ("G = 2", 2)):

@@ -17,47 +17,26 @@ import re
 import numpy as np
 import pytest
 
-from neo_mpc_planner2_amd import _lib, abi, synthetic
+from neo_mpc_planner2_amd import _lib, abi
 from tests import fleet_stamp_reference as stamp_ref
-from tests import footprint_gate_reference as gate_ref
 from tests import rolling_window_reference as roll_ref
 from tests import scan_layer_reference as scan_ref
 from tests import world_inflation_reference as world_ref
 from tests import world_scan_layer_reference as ref
 from tests.c_probe import HEADER, run_c_probe
+from tests.fleet_kit import (F32, RECT, Side, capture_fleet, gpu, inflation_for, pairs_fleet, rectangle, replay_against_direct,
+                             rolled_pool, same, scanner, world_scan_callback, world_state)
+from tests.world_scan_cases import UPDATE_FLAGS, WORLDS, case, distance_64_case, expected, ranges_for
 
 ENTRY_POINTS = ("neo_mpc_update_world_scan_layer", "neo_mpc_update_world_scan_layer_device",
                 "neo_mpc_update_world_scan_layer_from_ranges", "neo_mpc_update_world_scan_layer_from_ranges_device",
                 "neo_mpc_get_world_scan_layer", "neo_mpc_reset_world_scan_layer")
-RECT = tuple(synthetic.RECT_FOOTPRINT)
-F32 = np.float32
-#: the last: a width that is no multiple of 4, more than one 64-cell tile each way
-WORLDS = {"96x70-5cm": (96, 70, 0.05), "40x40-10cm": (40, 40, 0.1), "130x67-2.5cm": (130, 67, 0.025)}
 REACHES = (0, 3, 12, 64)
 ROBOTS = (1, 3, 7)
 MAX_POINTS = (1, 64, 130)           # one lane, one full wave, two waves and a tail
 #: world x R, with the robots, the point counts and the two unknown values dealt over them
 CASES = [(w, reach, ROBOTS[(a + b) % 3], MAX_POINTS[(2 * a + b) % 3], (255, 0)[(a + b) % 2])
          for a, w in enumerate(sorted(WORLDS)) for b, reach in enumerate(REACHES)]
-UPDATE_FLAGS = (ref.CLEAR | ref.MARK, 0, ref.CLEAR)   # three successive updates: a full scan, none, rays alone
-
-
-def inflation_for(reach, res):
-    """(inscribed_radius, inflation_radius, cost_scaling_factor) with ceil(inflation_radius / res) == reach."""
-    radius = 0.0 if reach == 0 else (reach - 0.5) * res
-    return min(radius, 1.5 * res), radius, 3.0 / (res * max(reach, 1))
-
-
-def ranges_for(world):
-    sx, sy, res = WORLDS[world]
-    span = max(sx, sy) * res
-    return dict(obstacle_max_range=0.45 * span, obstacle_min_range=3 * res, raytrace_max_range=0.4 * span,
-                raytrace_min_range=2 * res)
-
-
-def rectangle(x0, y0, x1, y1, clockwise=False):
-    p = [(x0, y0), (x1, y0), (x1, y1), (x0, y1)]
-    return np.array(p[::-1] if clockwise else p, dtype=np.float64)
 
 
 # ------------------------------------------------------------------------------------------ 1: the rule by hand
@@ -139,56 +118,7 @@ def test_fleet_clear_layout_and_entry_points(tmp_path):
     assert _lib.load().neo_mpc_abi_version() == 2 and _lib.load().neo_mpc_behaviour_version() == 6
 
 
-# ------------------------------------------------------------------------------------------ the generator
-@functools.lru_cache(maxsize=None)
-def case(world, robots, max_points):
-    """(cells [sy, sx], wox, woy, per update (points [robots, max_points, 2], point_counts, sensor origins [robots, 2],
-    polygons [robots, 4, 2])).  Robot 0: the sensor near the middle, points far beyond every edge and corner, one not
-    finite; robot 1: the sensor off the world, its outline partly off it too; the last robot's cloud is ragged.  Everything
-    else at random around the sensors, many points outside the world."""
-    sx, sy, res = WORLDS[world]
-    rng = np.random.default_rng(1000 * sx + 10 * robots + max_points)
-    cells = rng.choice(np.array([0, 0, 0, 0, 60, 150, 253, 254, 255, 255, 255], dtype=np.uint8), size=(sy, sx))
-    wox, woy = (float(v) for v in rng.uniform(-5.0, 5.0, size=2))
-    span = np.array([sx * res, sy * res])
-    sensors = np.array([wox, woy]) + span * rng.uniform(0.25, 0.75, size=(robots, 2))
-    if robots > 1:
-        sensors[1] = np.array([wox, woy]) + span * (-0.05, 0.5)
-    angle = rng.uniform(0.0, 2 * np.pi, size=(robots, max_points))
-    radius = rng.uniform(0.0, 1.2 * span.max(), size=(robots, max_points))
-    points = sensors[:, None, :] + radius[..., None] * np.stack([np.cos(angle), np.sin(angle)], -1)
-    counts = np.full(robots, max_points, dtype=np.uint32)
-    counts[-1] = max_points - max_points // 3
-    if max_points >= 16:
-        for j, (dx, dy) in enumerate(((-3, 0.1), (3, -0.1), (0.1, -3), (-0.1, 3), (-3, -3), (3, 3), (-3, 3), (3, -3))):
-            points[0, j] = sensors[0] + span * (dx, dy)
-        points[0, 8] = (np.nan, sensors[0, 1])
-        points[0, 9] = sensors[0] + (res, 0.0)                  # nearer than obstacle_min_range
-    points[:, 10 if max_points >= 16 else 0] = sensors + span * (0.2, 0.1)   # every robot marks a cell of the world
-    base = np.array(RECT) * (6 * res / 0.35)                    # an outline of about 12 x 8.5 cells
-    yaws = rng.uniform(-3.0, 3.0, size=robots)
-    polygons = np.array([gate_ref.oriented((sensors[k, 0], sensors[k, 1], yaws[k]), base) for k in range(robots)])
-    beyond = sensors[:, None, :] + 1.3 * (points - sensors[:, None, :])   # the third update's rays run through the marks
-    for a in (cells, points, counts, sensors, polygons, beyond):
-        a.setflags(write=False)
-    return cells, wox, woy, ((points, counts, sensors), (None, None, None), (beyond, counts, sensors)), polygons
-
-
-@functools.lru_cache(maxsize=None)
-def expected(world, reach, robots, max_points, unknown, by_definition=False):
-    """The transcription on a case: [(layer, live) per update], and the branches taken -- by definition only."""
-    cells, wox, woy, updates, polygons = case(world, robots, max_points)
-    res = WORLDS[world][2]
-    stats = collections.Counter() if by_definition else None
-    model, out = ref.WorldScanLayer(), []
-    for (points, counts, sensors), flags in zip(updates, UPDATE_FLAGS):
-        live = model.update(cells, res, wox, woy, *inflation_for(reach, res), points=points, sensor_origins=sensors,
-                            point_counts=counts, flags=flags, clear=dict(polygons=polygons, padding=1.5 * res),
-                            unknown_value=unknown, by_definition=by_definition, stats=stats, **ranges_for(world))
-        out.append((model.layer.copy(), live.copy()))
-    return out, stats
-
-
+# ------------------------------------------------------------------------------------------ the generator has teeth
 def test_the_array_transcription_equals_the_definition_on_a_case():
     case_ = ("40x40-10cm", 3, 3, 64, 255)
     for a, b in zip(expected(*case_)[0], expected(*case_, by_definition=True)[0]):
@@ -200,29 +130,6 @@ def test_the_array_transcription_equals_the_definition_on_a_case():
     layers = [x[0] for x in expected(*case_)[0]]
     assert (layers[0] == 254).any() and np.array_equal(layers[0], layers[1])          # flags 0 keeps the layer
     assert (layers[2] == 254).sum() < (layers[0] == 254).sum()                        # rays alone erase marks
-
-
-# ------------------------------------------------------------------------------------------ shared GPU helpers
-def gpu(a, dtype=None):
-    import torch
-    a = np.ascontiguousarray(a) if dtype is None else np.ascontiguousarray(a).astype(dtype)
-    return torch.from_numpy(a.copy()).to("cuda:0")
-
-
-def state_of(s):
-    import torch
-    torch.cuda.synchronize()
-    return s.get_world_scan_layer()
-
-
-def same(a, b):
-    return all(x.tobytes() == y.tobytes() for x, y in zip(a, b))
-
-
-def rolled_pool(s, sx, sy, res, origins, poses):
-    """A roll on the host variant: (pool, origins)."""
-    s.roll_costmap_pool(sx, sy, res, origins, poses=poses)
-    return s.get_costmap_pool()
 
 
 # ------------------------------------------------------------------------------------------ 4: equality with the transcription
@@ -248,11 +155,11 @@ def test_updates_equal_the_transcription(world, reach, robots, max_points, unkno
                 elif put is gpu:
                     kw.update(on_device=True)
                 s.update_world_scan_layer(*params, **kw)
-                got = state_of(s)
+                got = world_state(s)
                 assert np.array_equal(got[0], want[k][0]), (put.__name__, k, int((got[0] != want[k][0]).sum()))
                 assert np.array_equal(got[1], want[k][1]), (put.__name__, k, int((got[1] != want[k][1]).sum()))
                 s.update_world_scan_layer(*params, **kw)                  # repeated with the same inputs: nothing changes
-                assert same(state_of(s), got), (put.__name__, k)
+                assert same(world_state(s), got), (put.__name__, k)
             assert np.array_equal(s.get_world_map()[0], cells)            # the static map is what it was
         print("%s R=%d %d robots %d points: %d marks, %d free layer cells, %d world cells changed" %
               (world, reach, robots, max_points, int((want[0][0] == 254).sum()), int((want[0][0] == 0).sum()),
@@ -261,9 +168,9 @@ def test_updates_equal_the_transcription(world, reach, robots, max_points, unkno
 
 @pytest.mark.gpu
 def test_a_seed_exactly_64_cells_away_on_this_path():
-    """The 193 x 66 case of tests/test_scan_layer.py: seeds at (64, 1) and (64, 65), R = 64, a world width of 193."""
+    """The 193 x 66 case of tests/test_scan_layer.py (world_scan_cases.distance_64_case): seeds at (64, 1) and (64, 65), R = 64,
+    a world width of 193."""
     from neo_mpc_planner2_amd.solver import BatchSolver
-    from tests.test_scan_layer import distance_64_case
     world, want, params, points, sensor, layers, pool = distance_64_case()
     model = ref.WorldScanLayer()
     live = model.update(world * 0, 0.0625, 0.0, 0.0, *params, points=points, sensor_origins=sensor)
@@ -273,7 +180,7 @@ def test_a_seed_exactly_64_cells_away_on_this_path():
             s.set_world_map(put(world * 0), 0.0625, 0.0, 0.0)
             s.reset_world_scan_layer()
             s.update_world_scan_layer(*params, points=put(points), sensor_origins=put(sensor))
-            got = state_of(s)
+            got = world_state(s)
             assert np.array_equal(got[0], model.layer) and np.array_equal(got[1], live), put.__name__
 
 
@@ -295,7 +202,7 @@ def test_a_mark_of_one_robot_survives_the_ray_of_another_in_the_same_update():
             s.set_world_map(put(world), 1.0, 0.0, 0.0)
             s.reset_world_scan_layer()
             s.update_world_scan_layer(*TWO_INFLATION, points=put(TWO_POINTS), sensor_origins=put(TWO_SENSORS), **TWO_KW)
-            layer, live = state_of(s)
+            layer, live = world_state(s)
             row = layer[16]
             assert row[20] == 254 and row[24] == 254                              # both marks stand
             assert (row[21:24] == 0).all() and (row[12:20] == 0).all()            # B's ray: free between the marks and before them
@@ -303,7 +210,7 @@ def test_a_mark_of_one_robot_survives_the_ray_of_another_in_the_same_update():
             assert live[16, 20] == 254 and live[16, 24] == 254 and (live == 254).sum() == 2
             # robot B's scan alone, one robot: its ray frees A's cell
             s.update_world_scan_layer(*TWO_INFLATION, points=put(TWO_POINTS[1:]), sensor_origins=put(TWO_SENSORS[1:]), **TWO_KW)
-            layer, live = state_of(s)
+            layer, live = world_state(s)
             assert layer[16, 20] == 0 and layer[16, 24] == 254 and live[16, 20] == 0 and (live == 254).sum() == 1
 
 
@@ -328,7 +235,7 @@ def test_what_robot_0_sees_reaches_robot_1s_window():
     with BatchSolver({}) as s:
         s.set_world_map(gpu(world), res, -5.0, -5.0)
         s.update_world_scan_layer(*params, points=gpu(points), sensor_origins=gpu(poses[:, :2]))
-        assert same(state_of(s), (model.layer, live))
+        assert same(world_state(s), (model.layer, live))
         pool, origins = rolled_pool(s, size, size, res, start.copy(), poses)
         assert origins.tolist() == want_origins.tolist() and np.array_equal(pool, want)
     with BatchSolver({}) as s:                                            # a handle that never saw a world-scan update
@@ -375,7 +282,7 @@ def test_fleet_footprint_clearing_frees_the_hulls_and_nothing_beyond_the_padding
             else:
                 s.update_world_scan_layer(*params, points=points[:2], sensor_origins=sensors[:2],
                                           clear=dict(footprint=fp, poses=poses[:2], padding=padding))
-            layer, live = state_of(s)
+            layer, live = world_state(s)
             pool, origins = rolled_pool(s, size, size, res, start.copy(), poses[:2])
             costs, polys = s.footprint_gate(fp, poses=poses[:2], map_indices=np.arange(2, dtype=np.int32), want_polygons=True)
             seen[how] = (layer, live, costs)
@@ -434,31 +341,31 @@ def test_live_is_valid_from_an_update_to_the_next_change_of_the_world_map():
         s.update_world_scan_layer(*params, **ranges)
         kept = model.layer.copy()
         live = model.update(other, res, wox, woy, *params, **ranges)
-        assert np.array_equal(model.layer, kept) and same(state_of(s), (kept, live)) and np.array_equal(rolled(), roll_of(live))
+        assert np.array_equal(model.layer, kept) and same(world_state(s), (kept, live)) and np.array_equal(rolled(), roll_of(live))
         # an inflation of the world map: the same
         s.inflate_world_map(*params)
         inflated = world_ref.inflate_world(other, res, *params)
         assert np.array_equal(rolled(), roll_of(inflated))
         s.update_world_scan_layer(*params, **ranges)
         live = model.update(inflated, res, wox, woy, *params, **ranges)
-        assert same(state_of(s), (kept, live)) and np.array_equal(rolled(), roll_of(live))
+        assert same(world_state(s), (kept, live)) and np.array_equal(rolled(), roll_of(live))
         # another origin: the layer is reset
         s.set_world_map(other, res, wox + res, woy)
         s.update_world_scan_layer(*params, **ranges)
-        layer, live = state_of(s)
+        layer, live = world_state(s)
         assert (layer == 255).all() and np.array_equal(live, other)
         # ... and by the reset call, behind which there is no layer and the roll reads the static map
         s.update_world_scan_layer(*params, points=points, sensor_origins=sensors, point_counts=counts, **ranges)
-        assert (state_of(s)[0] != 255).any()
+        assert (world_state(s)[0] != 255).any()
         s.reset_world_scan_layer()
         assert s._lib.neo_mpc_get_world_scan_layer(s._handle, None, None) == -4
         assert np.array_equal(rolled(), roll_ref.roll(other, res, wox + res, woy, start, size, size, res, poses=poses)[1])
         s.update_world_scan_layer(*params, **ranges)
-        assert (state_of(s)[0] == 255).all()
+        assert (world_state(s)[0] == 255).all()
         # another unknown_value resets it too
         s.update_world_scan_layer(*params, points=points, sensor_origins=sensors, point_counts=counts, **ranges)
         s.update_world_scan_layer(*params, unknown_value=0, **ranges)
-        assert (state_of(s)[0] == 0).all()
+        assert (world_state(s)[0] == 0).all()
 
 
 # ------------------------------------------------------------------------------------------ 9: refusals
@@ -529,7 +436,7 @@ def test_refusals_leave_layer_live_pool_and_validity_alone():
         rolled_pool(s, size, size, res, start.copy(), poses)
 
         def state():
-            return state_of(s) + (s.get_costmap_pool()[0],)
+            return world_state(s) + (s.get_costmap_pool()[0],)
 
         held = state()
         assert (held[0] == 254).any() and (held[0] == 0).any() and not np.array_equal(held[1], cells)
@@ -569,15 +476,10 @@ def test_refusals_leave_layer_live_pool_and_validity_alone():
         pool = rolled_pool(s, size, size, res, start.copy(), poses)[0]
         assert np.array_equal(pool, roll_ref.roll(held[1], res, wox, woy, start, size, size, res, poses=poses)[1])
         assert call(flags=0, points=None, sensor_origins=None, point_counts=None, clear=clear_record()) == 0   # flags 0 needs no points
-        assert same(state_of(s), held[:2])                                  # ... and is the idempotent repeat here
+        assert same(world_state(s), held[:2])                                  # ... and is the idempotent repeat here
 
 
 # ------------------------------------------------------------------------------------------ 10: from ranges
-def scanner(mount, angle_min, angle_increment, range_min, range_max, flags=0):
-    return dict(mount_x=mount[0], mount_y=mount[1], mount_yaw=mount[2], angle_min=angle_min, angle_increment=angle_increment,
-                range_min=range_min, range_max=range_max, flags=flags)
-
-
 LASER_SCANNERS = [scanner((0.3, 0.1, 0.2), -1.6, 3.2 / 89, 0.05, 6.0, abi.LASER_INF_IS_VALID), scanner((-0.3, -0.05, 3.0), -1.6, 3.2 / 89, 0.05, 6.0)]
 LASER_KW = dict(obstacle_max_range=2.0, obstacle_min_range=0.15, raytrace_max_range=2.4, raytrace_min_range=0.1)
 
@@ -611,7 +513,7 @@ def test_update_from_ranges_equals_projection_then_the_transcription():
             live = model.update(cells, res, wox, woy, *params, points=points, sensor_origins=sensors, clear=clear, **LASER_KW)
             s.update_world_scan_layer_from_ranges(*params, d_ranges, d_poses, LASER_SCANNERS,
                                                   clear=dict(footprint=gpu(fp), poses=d_poses, padding=0.08), **LASER_KW)
-            got = state_of(s)
+            got = world_state(s)
             print("tick %d: %d marks, %d free layer cells" % (k, int((model.layer == 254).sum()), int((model.layer == 0).sum())))
             assert (model.layer == 254).any() and (model.layer == 0).any()
             assert np.array_equal(got[0], model.layer), (k, int((got[0] != model.layer).sum()))
@@ -624,7 +526,7 @@ def test_update_from_ranges_equals_projection_then_the_transcription():
         s.update_world_scan_layer_from_ranges(*params, ranges, poses, LASER_SCANNERS, points_out=out_p, origins_out=out_o,
                                               clear=dict(footprint=fp, poses=poses, padding=0.08), **LASER_KW)
         assert out_p.tobytes() == points.tobytes() and out_o.tobytes() == sensors.tobytes()
-        assert same(state_of(s), (before.layer, want))
+        assert same(world_state(s), (before.layer, want))
 
 
 # ------------------------------------------------------------------------------------------ 11: both kinds of layer in one tick
@@ -652,7 +554,7 @@ def test_world_layer_and_window_layers_in_one_tick_compose():
         import torch
         torch.cuda.synchronize()
         assert np.array_equal(s.get_costmap_pool()[0], want)
-        assert np.array_equal(s.get_scan_layer()[0], window_model.layers) and same(state_of(s), (world_model.layer, live))
+        assert np.array_equal(s.get_scan_layer()[0], window_model.layers) and same(world_state(s), (world_model.layer, live))
 
 
 # ------------------------------------------------------------------------------------------ 12: graph capture
@@ -661,83 +563,48 @@ def test_world_scan_roll_stamp_gate_solve_can_be_captured_in_a_hip_graph():
     """After one eager call -- it builds the tables and allocates -- world scan from ranges -> roll -> stamp -> gate -> solve
     is captured on one stream, a linear chain, and replayed twice with ranges and poses rewritten in between; layer, live,
     pool, gate costs and commands equal the same calls made directly on a second handle."""
-    import torch
-    from neo_mpc_planner2_amd.solver import BatchSolver, DeviceBatch
-    from oracle import mpc_oracle as orc
-    count, sx, sy, beams = 64, 48, 44, 40
+    beams = 40
     stamp, scan = (0.45, 0.9, 3.0), (0.1, 0.3, 3.0)
     scanners = [scanner((0.3, 0.0, 0.0), -1.5, 3.0 / 39, 0.05, 5.0, abi.LASER_INF_IS_VALID), scanner((-0.3, 0.0, math.pi), -1.5, 3.0 / 39, 0.05, 5.0)]
-    world, res, wox, woy = synthetic.make_costmap(300, seed=91)
-    probs = synthetic.make_problems(count, 120, seed=92)
-    probs["map_index"] = np.arange(count, dtype=np.int32)
-    st, warm = synthetic.make_states(probs, 3)
+    f = capture_fleet(120)
+    count = f.count
     rng = np.random.default_rng(95)
     ticks = []
     for k in range(3):
-        poses = np.concatenate([probs["cur_xy"] + rng.uniform(-0.4, 0.4, size=(count, 2)) * k, rng.uniform(-3, 3, size=(count, 1))], 1)
+        poses = np.concatenate([f.probs["cur_xy"] + rng.uniform(-0.4, 0.4, size=(count, 2)) * k, rng.uniform(-3, 3, size=(count, 1))], 1)
         ranges = rng.uniform(0.0, 1.8, size=(count, 2, beams)).astype(F32)
         ranges[:, :, 3:39:7] = np.array([np.nan, np.inf, -np.inf, 0.05, 5.0, 0.04], dtype=F32)
         ticks.append((poses, ranges))
-    start = probs["cur_xy"] - 1.0
     fp = gpu(np.asarray(RECT, dtype=np.float64))
 
-    class Side:
-        def __init__(self):
-            self.s = BatchSolver(orc.make_params())
-            self.s.set_world_map(gpu(world), res, wox, woy)
-            self.b = DeviceBatch(probs, st, warm, "cuda:0")
-            self.origins, self.poses, self.ranges = gpu(start), gpu(ticks[0][0]), gpu(ticks[0][1])
-            self.costs = torch.zeros(count, dtype=torch.float64, device="cuda:0")
-            self.xy = self.b.problems.view(torch.float64).reshape(count, -1)[:, 0:2]
+    class WorldScanSide(Side):
+        def __init__(self, fleet, tick):
+            super().__init__(fleet, tick)
+            self.ranges = gpu(tick[1])
 
         def set_inputs(self, tick):
-            self.poses.copy_(gpu(tick[0]))
+            super().set_inputs(tick)
             self.ranges.copy_(gpu(tick[1]))
-            self.xy.copy_(self.poses[:, :2])
 
         def tick(self):
             self.s.update_world_scan_layer_from_ranges(*scan, self.ranges, self.poses, scanners, obstacle_max_range=1.5,
                                                        raytrace_max_range=1.2, raytrace_min_range=0.1,
                                                        clear=dict(footprint=fp, poses=self.poses, padding=0.1))
-            self.s.roll_costmap_pool(sx, sy, res, self.origins, poses=self.poses)
+            self.s.roll_costmap_pool(f.sx, f.sy, f.res, self.origins, poses=self.poses)
             self.s.stamp_fleet(*stamp, footprint=fp, poses=self.poses)
             self.s.footprint_gate_device(fp, self.costs, poses=self.poses, problems=self.b.problems)
             self.s.solve_device(self.b.problems, self.b.states, self.b.warm, self.b.commands, solution=self.b.solution)
 
         def result(self):
-            torch.cuda.synchronize()
+            common = super().result()
             layer, live = self.s.get_world_scan_layer()
-            return (self.b.commands_host().tobytes(), self.b.states_host().tobytes(), self.costs.cpu().numpy().tolist(),
-                    self.origins.cpu().numpy().tolist(), self.s.get_costmap_pool()[0].tobytes(), layer.tobytes(), live.tobytes())
+            return common + (self.s.get_costmap_pool()[0].tobytes(), layer.tobytes(), live.tobytes())
 
-    direct, graphed = Side(), Side()
-    try:
-        side = torch.cuda.Stream()
-        side.wait_stream(torch.cuda.current_stream())
-        with torch.cuda.stream(side):          # the eager call, on the capture stream
-            graphed.tick()
-        torch.cuda.synchronize()
-        direct.tick()
-        first = direct.result()
-        assert first == graphed.result()
-        g = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(g, stream=side):
-            graphed.tick()
-        for k in (1, 2):
-            for x in (direct, graphed):
-                x.set_inputs(ticks[k])
-            torch.cuda.synchronize()
-            g.replay()
-            direct.tick()
-            a, b = graphed.result(), direct.result()
-            assert a == b, k
-            assert a[4] != first[4] and a[5] != first[5] and a[6] != first[6]       # pool, layer and live changed
+    # pool, layer and live changed
+    with replay_against_direct(lambda: WorldScanSide(f, ticks[0]), ticks, changed=(4, 5, 6)) as (_, a, _):
         layer = np.frombuffer(a[5], dtype=np.uint8)
         live = np.frombuffer(a[6], dtype=np.uint8)
-        assert (layer == 254).any() and (layer == 0).any() and live.tobytes() != world.tobytes()
-    finally:
-        direct.s.close()
-        graphed.s.close()
+        assert (layer == 254).any() and (layer == 0).any() and live.tobytes() != f.world.tobytes()
 
 
 # ------------------------------------------------------------------------------------------ 13: the closed loop
@@ -751,39 +618,20 @@ def test_closed_loop_a_wall_seen_by_half_the_fleet_stops_the_other_half():
     from neo_mpc_planner2_amd import fleet as fleet_loop
     from neo_mpc_planner2_amd.solver import BatchSolver, DeviceBatch
     from oracle import mpc_oracle as orc
-    count, size, res, ticks, beams = 64, 60, 0.05, 4, 41
+    ticks = 4
     world = np.zeros((400, 400), dtype=np.uint8)
-    probs = synthetic.make_problems(count, 200, seed=7)
-    grid = np.stack(np.meshgrid(np.arange(4), np.arange(8)), -1).reshape(-1, 2)
-    seers = np.array([-8.0, -7.0]) + grid * (4.0, 2.0) + 0.011
-    xy = np.empty((count, 2))
-    xy[0::2], xy[1::2] = seers, seers + (1.5, 0.0)
-    probs["cur_xy"] = xy
-    probs["cur_q"] = (0.0, 0.0, 0.0, 1.0)
-    probs["carrot_xy"] = (0.4, 0.0)
-    probs["carrot_q"] = (0.0, 0.0, 0.0, 1.0)
-    probs["goal_xyz"][:, :2] = xy + (5.0, 0.0)
-    probs["goal_q"] = probs["cur_q"]
-    probs["cur_vel"] = 0.0
-    probs["map_index"] = np.arange(count, dtype=np.int32)
-    st, warm = synthetic.make_states(probs, 3)
-    front = scanner((0.1, 0.0, 0.0), -0.25, 0.5 / (beams - 1), 0.05, 8.0)
-    angle = front["angle_min"] + np.arange(beams) * front["angle_increment"]
-    ranges = np.full((count, 1, beams), np.inf, dtype=F32)               # (no INF_IS_VALID: nothing, not even a clearing ray)
-    ranges[0::2, 0] = (1.7 / np.cos(angle)).astype(F32)                  # x = 0.1 + 1.7 in the even robot's base frame
-    d_ranges = gpu(ranges)
-    params = (0.1, 0.3, 3.0)
-
-    def world_scan(t, poses):
-        return dict(zip(("inscribed_radius", "inflation_radius", "cost_scaling_factor"), params), ranges=d_ranges, poses=poses,
-                    scanners=[front])
+    p = pairs_fleet()
+    count, size, res, probs, st, warm = p.count, p.size, p.res, p.probs, p.st, p.warm
+    ranges = np.full((count, 1, p.beams), np.inf, dtype=F32)             # (no INF_IS_VALID: nothing, not even a clearing ray)
+    ranges[0::2, 0] = (1.7 / np.cos(p.angle)).astype(F32)                # x = 0.1 + 1.7 in the even robot's base frame
+    world_scan = world_scan_callback((0.1, 0.3, 3.0), gpu(ranges), p.front)
 
     runs = {}
     with BatchSolver(orc.make_params()) as s:
         s.set_world_map(world, res, -10.0, -10.0)
         for how, kw in (("default", {}), ("none", dict(world_scan=None)), ("world_scan", dict(world_scan=world_scan))):
             flags = []
-            d_orig = gpu(xy - size * res / 2 + 0.013)
+            d_orig = gpu(p.origins)
             s.reset_world_scan_layer()
             s.roll_costmap_pool(size, size, res, d_orig)
             b = DeviceBatch(probs, st, warm, "cuda:0")

@@ -37,6 +37,29 @@ def oracle_costmap(cells, meta):
     return orc.Costmap(cells, meta[0], meta[1], meta[2])
 
 
+def random_params(rng, steps=(1, 2, 3, 3, 3, 4, 6, 8)):
+    """A random parameter set of the fuzz tests: weights, bounds (disc in box, box cuts disc, box in disc), horizon."""
+    vmax = rng.uniform(0.2, 1.5)
+    p = orc.make_params(
+        control_steps=int(rng.choice(steps)),
+        prediction_horizon=float(rng.uniform(0.3, 1.5)),
+        w_trans=float(rng.uniform(0.1, 2.0)), w_orient=float(rng.uniform(0.05, 1.0)),
+        w_control=float(rng.choice([0.0, 0.02, 0.05, 0.3])), w_terminal=float(rng.uniform(0.0, 0.5)),
+        w_costmap=float(rng.uniform(0.0, 0.5)), w_footprint=float(rng.choice([0, 2000])),
+        max_vel_trans=vmax, low_pass_gain=float(rng.uniform(0.2, 1.0)),
+        acc_x_limit=float(rng.uniform(0.5, 3)), acc_y_limit=float(rng.uniform(0.5, 3)),
+        acc_theta_limit=float(rng.uniform(0.5, 3)), opt_tolerance=float(rng.choice([1e-3, 1e-4, 1e-5])),
+        max_vel_theta=float(rng.uniform(0.3, 1.2)))
+    p["min_vel_theta"] = -p["max_vel_theta"] * float(rng.choice([1.0, 0.5]))
+    kind = rng.integers(0, 3)
+    if kind == 0:      # disc inside the box
+        p.update(max_vel_x=vmax * 1.2, min_vel_x=-vmax * 1.2, max_vel_y=vmax, min_vel_y=-vmax)
+    elif kind == 1:    # box cuts the disc, asymmetric (no reverse driving)
+        p.update(max_vel_x=vmax * 0.8, min_vel_x=-vmax * 0.1, max_vel_y=vmax * 0.6, min_vel_y=-vmax * 0.9)
+    else:              # box inside the disc
+        p.update(max_vel_x=vmax * 0.5, min_vel_x=-vmax * 0.5, max_vel_y=vmax * 0.4, min_vel_y=-vmax * 0.4)
+    return p
+
 
 def load_seam_dump(path):
     """`examples/plugin_seam.cpp --run --dump FILE`: header (tick count, control_steps, map size, parameters, map

@@ -7,7 +7,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from neo_mpc_planner2_amd import synthetic
 from neo_mpc_planner2_amd.solver import BatchSolver
 from oracle import c_oracle, mpc_oracle as orc
-from tests.test_gpu_fuzz import random_params
+from tests.util import random_params
 
 ap = argparse.ArgumentParser()
 ap.add_argument("--seed", type=int, default=0)

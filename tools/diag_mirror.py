@@ -21,7 +21,7 @@ ap.add_argument("--show", type=int, default=0, help="print the iterates of the w
 ap.add_argument("--from-iterate", type=int, default=0, help="k > 0: warm-start both sides from the mirror's iterate after k iterations")
 args = ap.parse_args()
 if args.fuzz_seed is not None:
-    from tests.test_gpu_fuzz import random_params
+    from tests.util import random_params
     rng = np.random.default_rng(1000 + args.fuzz_seed)
     fparams = random_params(rng)
     fres = float(rng.choice([0.025, 0.05, 0.1]))
