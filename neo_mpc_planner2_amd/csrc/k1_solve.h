@@ -270,6 +270,8 @@ __device__ __forceinline__ bool solve_search(double* L, uint32_t b, SolveCarry& 
   // know each stage's case as a scalar before the sweep starts
   constexpr bool kHandOff = kFew > 0;
   constexpr bool kScalarCase = kFew > 0 && kTame;
+  // ... and, sweeping once per iteration, keep the sweep's gains in registers from its backward to its forward half
+  constexpr bool kKeepGains = kFew > 0 && kTame;
   // ... and lane = stage fetches what the tangent-cone pass reads of its block at the END of the adjoint pass (adjoint.h)
   constexpr bool kStageCarry = kFew > 0 && kTame;
   constexpr bool kAcceptFetch = kFew > 0 && kTame;
@@ -487,7 +489,7 @@ __device__ __forceinline__ bool solve_search(double* L, uint32_t b, SolveCarry& 
       if (corner_any) riccati_keep_linear_terms(a, L, n, lane, true);   // (the sweep writes its gains over them)
       auto sweep = [&]() {
         SweepHandOff<float> ho = {};
-        riccati_sweep<float, (kMinWavesPerSimd < 4), kFew, kHandOff, kScalarCase>(a, L, n, lane, &ho, stage_flags);
+        riccati_sweep<float, (kMinWavesPerSimd < 4), kFew, kHandOff, kScalarCase, kKeepGains>(a, L, n, lane, &ho, stage_flags);
         riccati_finish<kHandOff>(a, c, L, n, lane, &ho, &dm_reg);
         near_reg = ho.near;
       };

@@ -190,10 +190,15 @@ struct SweepHandOff {
 };
 // kHandOff (kFew only): the steps leave in `ho`; nothing is written to d and no barrier follows the forward sweep.
 // kScalarCase: the stages' flags words come in `stage_flags` (scalars) instead of from the records.
-template <typename T, bool kPrefetch = true, int kFew = 0, bool kHandOff = false, bool kScalarCase = false>
+// kKeepGains (kHandOff only): the backward sweep is wave-uniform -- every lane computes every stage's gains K, k -- so the
+// forward sweep takes them, and px, py of each stage, from the registers of the backward one: lane 0 stores the tokink word
+// alone, and no drain and no fetch stand between the two sweeps.  The records then keep their linear terms: for the kernels
+// in which nothing but the forward sweep read the gains (the tame ones: no riccati_keep_linear_terms, no second sweep).
+template <typename T, bool kPrefetch = true, int kFew = 0, bool kHandOff = false, bool kScalarCase = false, bool kKeepGains = false>
 __device__ __forceinline__ void riccati_sweep(const SolveArgs& a, double* L, int n, int lane, SweepHandOff<T>* ho = nullptr,
                                               const int* stage_flags = nullptr) {
   static_assert(!(kHandOff || kScalarCase) || kFew > 0, "register hand-offs: the unrolled sweeps");
+  static_assert(!kKeepGains || kHandOff, "gains in registers: the sweeps that hand their steps on in registers");
   const DevParams& p = a.p;
   float* RS = static_cast<float*>(__builtin_assume_aligned(reinterpret_cast<float*>(L + a.lds.ric), 16));
   int* AMODE = reinterpret_cast<int*>(L + a.lds.mode);
@@ -205,6 +210,8 @@ __device__ __forceinline__ void riccati_sweep(const SolveArgs& a, double* L, int
 
   T V00 = (T)0.0, V01 = (T)0.0, V02 = (T)0.0, V11 = (T)0.0, V12 = (T)0.0, V22 = (T)0.0, v0 = (T)0.0, v1 = (T)0.0, v2 = (T)0.0;
   ric_f4 r0, r1, r2, r3, r4, r5, r6;
+  // kKeepGains: per stage K (row-major), k, then px, py -- the order of the record's words the forward sweep reads
+  T held[kKeepGains ? kFew : 1][14];
   if (kPrefetch) {
     const ric_f4* R4 = reinterpret_cast<const ric_f4*>(RS + kRicStage * (n - 1));
     r0 = R4[0]; r1 = R4[1]; r2 = R4[2]; r3 = R4[3]; r4 = R4[4]; r5 = R4[5]; r6 = R4[6];
@@ -374,7 +381,16 @@ __device__ __forceinline__ void riccati_sweep(const SolveArgs& a, double* L, int
         V00 = S00; V01 = S01; V02 = M02; V11 = S11; V12 = M12; V22 = Z22;
         break;
     }
-    if (lane == 0) {   // the gains take the place of the stage's linear terms
+    if (kKeepGains) {
+      const T g[14] = {K00, K01, K02, K10, K11, K12, K20, K21, K22, k0, k1, k2, px, py};
+      for (int j = 0; j < 14; ++j) {
+        held[i][j] = (T)(float)g[j];
+        // (as opaque to the compiler as the LDS reads they replace: the forward sweep's products and sums are formed and
+        // fused as they were around loaded values)
+        asm("" : "+v"(held[i][j]));
+      }
+      if (lane == 0) AMODE[4 * i + 3] = tokink ? 1 : 0;
+    } else if (lane == 0) {   // the gains take the place of the stage's linear terms
       ric_f4* G4 = reinterpret_cast<ric_f4*>(RS + kRicStage * i + RS_GAIN);
       G4[0] = ric_f4{(float)K00, (float)K01, (float)K02, (float)K10};
       G4[1] = ric_f4{(float)K11, (float)K12, (float)K20, (float)K21};
@@ -383,7 +399,7 @@ __device__ __forceinline__ void riccati_sweep(const SolveArgs& a, double* L, int
     }
     if (kHandOff && tokink) ho->tokink |= 1u << i;
   }
-  WAVE_SYNC();
+  if (!kKeepGains) WAVE_SYNC();
   // forward sweep: w_i = k_i + K_i dz_{i-1}, dz_i = A_i (dz_{i-1} + w_i)
   T z0 = (T)0.0, z1 = (T)0.0, z2 = (T)0.0;
   // (kFew: every stage's step and gains are fetched in front of the first stage, one wait for all of them -- read stage by
@@ -391,6 +407,14 @@ __device__ __forceinline__ void riccati_sweep(const SolveArgs& a, double* L, int
   ric_f4 fs[kFew ? kFew : 1][4];
   if (kFew) {
     for (int i = 0; i < kFew; ++i) {
+      if (kKeepGains) {
+        const T* h = held[i];
+        fs[i][0] = ric_f4{(float)h[12], (float)h[13], 0.0f, 0.0f};
+        fs[i][1] = ric_f4{(float)h[0], (float)h[1], (float)h[2], (float)h[3]};
+        fs[i][2] = ric_f4{(float)h[4], (float)h[5], (float)h[6], (float)h[7]};
+        fs[i][3] = ric_f4{(float)h[8], (float)h[9], (float)h[10], (float)h[11]};
+        continue;
+      }
       const ric_f4* R4 = reinterpret_cast<const ric_f4*>(RS + kRicStage * i);
       fs[i][0] = R4[0]; fs[i][1] = R4[4]; fs[i][2] = R4[5]; fs[i][3] = R4[6];
     }
