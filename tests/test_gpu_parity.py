@@ -1309,7 +1309,7 @@ def test_g17_p3_on_warm_starts_at_random_parameter_sets(solver_mod):
         return get(params, cmap).solve(rows, st, wm)
 
     def post(params, cmap, rows, st, wm, x, ok):
-        c_oracle.postprocess_batch(params, cmap, rows, st, wm, x, ok)   # (the reference's next state: P5 pins K2 on it elsewhere)
+        c_oracle.postprocess_batch(params, cmap, rows, st, wm, x, ok)   # (the reference's next state: tests/test_wrapper_edges.py pins K2 on it)
     try:
         rows = util.p3w_random_sets(solve, post)
     finally:
