@@ -51,6 +51,8 @@ extern "C" {
  * NEO_MPC_MAX_DENOISE_GROUP) added two entry points and a constant and no record: still ABI 2, behaviour 6.
  * The decay of the world scan layer's old marks (neo_mpc_set_world_scan_decay, neo_mpc_get_world_scan_ages, NEO_MPC_NO_AGE)
  * added two entry points and a constant and no record: still ABI 2, behaviour 6.
+ * The plan check (neo_mpc_plan_check_batch, neo_mpc_plan_check, neo_mpc_check_plans[_device]) added two records and two
+ * entry points in the same way: still ABI 2, behaviour 6.
  *
  * Behaviour history (iterates and iteration counts differ between versions, results stay inside the parity protocol of
  * DESIGN.md section 1; neo_mpc_behaviour_version() returns the number of the build that answers):
@@ -734,6 +736,69 @@ typedef struct neo_mpc_fleet_clear {
   uint64_t reserved;               /* MUST be zero */
 } neo_mpc_fleet_clear;
 
+/* ---- the fleet's global plans against the live world map: which of them it blocks (K15) ----------------- */
+
+/* The world map -- static map, inflation (K9), the fleet's shared obstacle layer (K12 to K14) -- is the one live picture the
+ * fleet server holds, and the global plans are the one input of a tick that never met it: neo_mpc_select_carrots streams them
+ * and picks a look-ahead pose without knowing whether the plan behind that pose still exists.  nav2 answers this robot by
+ * robot with the planner server's `is_path_valid` service, which the behaviour tree polls to trigger a replan; a server that
+ * holds every plan and the live map answers it for the whole fleet in one launch (neo_mpc_check_plans[_device]).  nav2
+ * cannot be built next to this library, so the text below is the contract (tests/plan_check_reference.py is its executable
+ * form).  Every output is an integer.
+ *
+ * Which map.  The world map the next roll would read: the composition of the last world-scan update while one is current
+ * (see neo_mpc_update_world_scan_layer: `live`), else the handle's copy of the world map; WSX x WSY cells, resolution wres,
+ * origin (wox, woy).  Plan poses are in that map's frame.  The rolling windows and what is stamped into them are not looked
+ * at: the other robots of the fleet are no obstacles to a plan.
+ *
+ * For robot i, with np = plan_offsets[i + 1] - plan_offsets[i] poses (x, y, yaw):
+ *   np == 0           status 2 (nav2 calls an empty path invalid), begin = end = first_blocked = 0, value = 0.
+ *   begin             with `robot_poses`: the plan's closest pose, by neo_mpc_select_carrots' rule to the letter (cpp:83-88:
+ *                     the first minimum of the float64 hypot, nav2's min_by -- pose 0 where the first distance is NaN or no
+ *                     distance is below infinity); without: 0.
+ *   end               max_poses == 0: np; else min(np, begin + max_poses).
+ *   value of pose k, point mode (no footprint)  neo_mpc_footprint_batch's vertex rule against the map's true size: off the
+ *                     map when X < wox, Y < woy or a coordinate is not finite; else mx = trunc((X - wox) / wres), my
+ *                     likewise, off the map unless mx < WSX and my < WSY; off the map the value is `outside_value`, else
+ *                     the raw cell world[my][mx].  (nav2's service ignores worldToMap's refusal and reads a cell from
+ *                     indices it left unset -- a stale cell; this contract deliberately does not: the caller says what the
+ *                     outside of the map is worth.)
+ *   value of pose k, footprint mode  neo_mpc_footprint_batch's outline cost -- oriented polygon, LineIterator's cells,
+ *                     nav2's order-dependent fold, 254 for any vertex off the map -- of `footprint` at (x, y, yaw) of the
+ *                     pose, on the world map.  `outside_value` is not read.
+ *   a value v blocks  when v == 255 ? unknown_blocks : v >= max_cost.  max_cost 253 is nav2's rule (inscribed or lethal).
+ *   first_blocked     the smallest k in [begin, end) whose value blocks, `end` when none does; status 1 when one does,
+ *                     else 0.
+ *   value             blocked: the value of pose first_blocked.  Not blocked: the largest value below 255 met over
+ *                     [begin, end), 0 when there is none -- how tight a still-valid plan has become.
+ * The call writes `results` and nothing else: neo_mpc_problem.skip stays neo_mpc_select_carrots' to set, and what to do about
+ * a blocked plan is the caller's decision.
+ * Out of scope: replanning; the rolling windows; one footprint per robot; the arc length to the blocked pose (the caller has
+ * the index); neo_mpc_select_carrots or this call inside a closed fleet loop that has no plans.
+ * Pointers are host pointers for neo_mpc_check_plans and device pointers for neo_mpc_check_plans_device.  72 bytes. */
+typedef struct neo_mpc_plan_check {   /* 24 bytes */
+  uint32_t begin, end;      /* poses [begin, end) were checked */
+  uint32_t first_blocked;   /* end: none */
+  int32_t status;           /* 0 valid; 1 blocked; 2 plan with zero length */
+  uint32_t value;           /* 0 .. 255, see above */
+  uint32_t reserved;        /* written as 0 */
+} neo_mpc_plan_check;
+
+typedef struct neo_mpc_plan_check_batch {
+  size_t count;
+  const double* plan_poses;      /* [plan_offsets[count]][3]: neo_mpc_plan_batch's ragged layout, so one array serves the */
+  const uint32_t* plan_offsets;  /* [count + 1]                carrots and the check; poses in the world map's frame */
+  const double* robot_poses;     /* optional [count][3]; NULL: every check starts at pose 0 */
+  const double* footprint;       /* optional [footprint_points][2] base frame, shared by the fleet; NULL: point mode */
+  uint32_t footprint_points;     /* 0 with a NULL footprint, else 3 .. NEO_MPC_MAX_FOOTPRINT_POINTS */
+  uint32_t max_cost;             /* 1 .. 254 */
+  uint32_t unknown_blocks;       /* 0 or 1: whether the value 255 blocks */
+  uint32_t outside_value;        /* 0 .. 255 */
+  uint32_t max_poses;            /* 0: to the plan's end */
+  uint32_t reserved;             /* MUST be zero */
+  neo_mpc_plan_check* results;   /* [count] out */
+} neo_mpc_plan_check_batch;
+
 typedef struct neo_mpc_handle neo_mpc_handle;
 
 /* library / ABI */
@@ -1146,6 +1211,23 @@ int neo_mpc_set_world_scan_decay(neo_mpc_handle* handle, uint32_t max_age);
  * NEO_MPC_ERR_NO_COSTMAP where it does; NEO_MPC_ERR_UNSUPPORTED when the last update ran without decay.  A null ages_out only
  * asks whether there are any. */
 int neo_mpc_get_world_scan_ages(neo_mpc_handle* handle, uint32_t* ages_out);
+
+/* The plan check for `count` robots (neo_mpc_plan_check_batch above; K15).  Host pointers, synchronous: the records are in
+ * `results` when it returns.  NEO_MPC_ERR_NO_COSTMAP without a world map; NEO_MPC_ERR_INVALID_ARGUMENT for a null handle or
+ * record, a null plan_poses / plan_offsets / results with count > 0, max_cost outside 1 .. 254, unknown_blocks > 1,
+ * outside_value > 255, reserved != 0, a footprint without footprint_points or the other way round, footprint_points outside
+ * 3 .. 16, a count beyond 2^31 - 1 -- and, looked at on the host by this variant alone, plan_offsets that decrease and a
+ * footprint vertex that is not finite.  Plan and robot poses are taken as they come: a coordinate that is not finite is off
+ * the map, and the closest pose follows nav2's min_by.  count == 0 is NEO_MPC_OK and launches nothing. */
+int neo_mpc_check_plans(neo_mpc_handle* handle, const neo_mpc_plan_check_batch* batch);
+/* Same with every pointer in device memory; enqueued on `stream`, returns without waiting; no value behind a pointer is
+ * looked at on the host.  The check orders itself like a roll, which reads the same map: it waits for the world map's writer
+ * -- the copy, the inflation, the world-scan update that composed `live` -- and a later neo_mpc_set_world_map*,
+ * neo_mpc_inflate_world_map* or world-scan update, on whatever stream, waits for its reads.  (Like a roll it also takes its
+ * place among the launches on the device map, whose ordering carries this.)  Any time between a world-scan update and the
+ * next one sees that update's map.  It allocates nothing, copies nothing and does not synchronise, so it can be captured in
+ * a HIP graph with the rest of the tick. */
+int neo_mpc_check_plans_device(neo_mpc_handle* handle, const neo_mpc_plan_check_batch* batch, void* stream);
 
 /* ---- multi-GPU fleets: the one exchange step ------------------------------------------------
  * Instances of one tick shard embarrassingly over the GPUs of a node (one handle per GPU, costmap and parameters

@@ -36,6 +36,7 @@ EXPORTS = (
     "neo_mpc_get_world_scan_layer", "neo_mpc_reset_world_scan_layer",
     "neo_mpc_set_world_scan_denoise", "neo_mpc_get_world_scan_denoised",
     "neo_mpc_set_world_scan_decay", "neo_mpc_get_world_scan_ages",
+    "neo_mpc_check_plans", "neo_mpc_check_plans_device",
     "neo_mpc_rccl_available", "neo_mpc_comm_init_all", "neo_mpc_comm_destroy", "neo_mpc_group_start",
     "neo_mpc_group_end", "neo_mpc_allgather_velocities", "neo_mpc_broadcast_costmap",
 )
@@ -151,6 +152,8 @@ def load():
         lib.neo_mpc_get_world_scan_denoised.argtypes = [C.c_void_p, C.c_void_p]
         lib.neo_mpc_set_world_scan_decay.argtypes = [C.c_void_p, C.c_uint32]
         lib.neo_mpc_get_world_scan_ages.argtypes = [C.c_void_p, C.c_void_p]
+        lib.neo_mpc_check_plans.argtypes = [C.c_void_p, P(abi.NeoMpcPlanCheckBatch)]
+        lib.neo_mpc_check_plans_device.argtypes = [C.c_void_p, P(abi.NeoMpcPlanCheckBatch), C.c_void_p]
     _lib = lib
     return lib
 

@@ -138,6 +138,27 @@ class NeoMpcFootprintBatch(_C.Structure):
                 ("problems", _C.c_void_p), ("footprint_costs", _C.c_void_p), ("footprints_out", _C.c_void_p)]
 
 
+class NeoMpcPlanCheckBatch(_C.Structure):
+    """`neo_mpc_plan_check_batch` (include/neo_mpc.h): the fleet's plans checked against the live world map (K15)."""
+    _fields_ = [("count", _C.c_size_t), ("plan_poses", _C.c_void_p), ("plan_offsets", _C.c_void_p),
+                ("robot_poses", _C.c_void_p), ("footprint", _C.c_void_p), ("footprint_points", _C.c_uint32),
+                ("max_cost", _C.c_uint32), ("unknown_blocks", _C.c_uint32), ("outside_value", _C.c_uint32),
+                ("max_poses", _C.c_uint32), ("reserved", _C.c_uint32), ("results", _C.c_void_p)]
+
+
+class NeoMpcPlanCheck(_C.Structure):
+    """`neo_mpc_plan_check` (include/neo_mpc.h): one robot's result of the plan check."""
+    _fields_ = [("begin", _C.c_uint32), ("end", _C.c_uint32), ("first_blocked", _C.c_uint32), ("status", _C.c_int32),
+                ("value", _C.c_uint32), ("reserved", _C.c_uint32)]
+
+
+#: `neo_mpc_plan_check` (24 bytes) as a NumPy dtype
+PLAN_CHECK_DTYPE = np.dtype([
+    ("begin", "<u4"), ("end", "<u4"), ("first_blocked", "<u4"), ("status", "<i4"), ("value", "<u4"), ("reserved", "<u4"),
+], align=False)
+assert PLAN_CHECK_DTYPE.itemsize == 24 == _C.sizeof(NeoMpcPlanCheck) and _C.sizeof(NeoMpcPlanCheckBatch) == 72
+
+
 class NeoMpcWindowBatch(_C.Structure):
     """`neo_mpc_window_batch` (include/neo_mpc.h): one roll of a fleet's costmap windows over the world map."""
     _fields_ = [("count", _C.c_size_t), ("size_x", _C.c_uint32), ("size_y", _C.c_uint32), ("resolution", _C.c_double),

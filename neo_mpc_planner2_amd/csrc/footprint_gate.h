@@ -49,6 +49,30 @@ __device__ __forceinline__ void orient_vertex(double x, double y, double sn, dou
   X = ox; Y = oy;
 }
 
+// Costmap2D::worldToMap's rule for a point (X, Y) against a map of sx x sy cells (its TRUE size) -> whether the point is off the
+// map, and its cell.  cell_of equals the exact division wherever the result is >= 0; NaN fails both >= tests, +inf saturates
+// beyond every size.  K6's vertices and K15's vertices and plan poses (plan_check.h) all go through it.
+__device__ __forceinline__ bool off_map_cell(double X, double Y, double ox, double oy, double res, double inv, int sx, int sy,
+                                             int& mx, int& my) {
+  mx = cell_of(X, ox, res, inv);
+  my = cell_of(Y, oy, res, inv);
+  return !(X >= ox) || !(Y >= oy) || mx >= sx || my >= sy;
+}
+
+// nav2_util::LineIterator's walk from cell (x0, y0) to (x1, y1) in closed form: cell k of the edge, k = 0 .. max(dx, dy), as a
+// function of k alone (K6 deals the cells of a whole outline over the lanes, K15 walks one outline per lane).
+__device__ __forceinline__ void line_cell(int x0, int y0, int x1, int y1, int k, int& cx, int& cy) {
+  const int dx = x1 >= x0 ? x1 - x0 : x0 - x1, dy = y1 >= y0 ? y1 - y0 : y0 - y1;
+  const int sx = x1 >= x0 ? 1 : -1, sy = y1 >= y0 ? 1 : -1;
+  const int major = dx >= dy ? dx : dy, minor = dx >= dy ? dy : dx;
+  // (major / 2 + k * minor) / major in integers: the numerator stays below 2^41 for maps of up to 2^20 cells a side
+  // and the quotient below 2^21, so the float64 division, truncated, is the integer division (a quotient that is not
+  // whole is 1 / major >= 2^-20 from the next integer, the division's rounding error below 2^-31)
+  const int q = major ? (int)((double)((long)(major >> 1) + (long)k * minor) / (double)major) : 0;
+  cx = dx >= dy ? x0 + sx * k : x0 + sx * q;
+  cy = dx >= dy ? y0 + sy * q : y0 + sy * k;
+}
+
 // K6: nav2's FootprintCollisionChecker::footprintCostAtPose on raw cell values (the contract: include/neo_mpc.h,
 // neo_mpc_footprint_batch), one wavefront per robot.  Vertices go one per lane (<= 16: one DPP row): oriented in float64,
 // turned into cells by worldToMap's rule against the map's TRUE size.  LineIterator's walk has a closed form -- cell k of an
@@ -84,11 +108,8 @@ __global__ __launch_bounds__(kLanes * kGateWaves) void k_footprint_gate(const Fo
     double* out = a.footprints_out + (b * (size_t)n + lane) * 2;
     out[0] = X; out[1] = Y;
   }
-  // worldToMap: cell_of equals the exact division wherever the result is >= 0; NaN fails both >= tests, +inf saturates
-  // beyond every size
-  const int mx = cell_of(X, m.origin_x, m.resolution, m.inv_resolution);
-  const int my = cell_of(Y, m.origin_y, m.resolution, m.inv_resolution);
-  const bool off = !(X >= m.origin_x) || !(Y >= m.origin_y) || mx >= m.size_x || my >= m.size_y;
+  int mx, my;
+  const bool off = off_map_cell(X, Y, m.origin_x, m.origin_y, m.resolution, m.inv_resolution, m.size_x, m.size_y, mx, my);
   int cost = 254;   // a vertex off the map: nav2's fold returns LETHAL_OBSTACLE at that vertex, or did so before it
   if (__ballot(has && off) == 0ull) {
     // edge `lane` runs from vertex `lane` to the next one (the last edge closes the polygon); every vertex is on the map,
@@ -106,14 +127,8 @@ __global__ __launch_bounds__(kLanes * kGateWaves) void k_footprint_gate(const Fo
       for (int j = 0; j < n - 1; ++j) e += t >= __builtin_amdgcn_readlane(incl, j) ? 1 : 0;
       const int x0 = __shfl(mx, e), y0 = __shfl(my, e), x1 = __shfl(nx, e), y1 = __shfl(ny, e);
       const int k = t - __shfl(incl - len, e);
-      const int dx = x1 >= x0 ? x1 - x0 : x0 - x1, dy = y1 >= y0 ? y1 - y0 : y0 - y1;
-      const int sx = x1 >= x0 ? 1 : -1, sy = y1 >= y0 ? 1 : -1;
-      const int major = dx >= dy ? dx : dy, minor = dx >= dy ? dy : dx;
-      // (major / 2 + k * minor) / major in integers: the numerator stays below 2^41 for maps of up to 2^20 cells a side
-      // and the quotient below 2^21, so the float64 division, truncated, is the integer division (a quotient that is not
-      // whole is 1 / major >= 2^-20 from the next integer, the division's rounding error below 2^-31)
-      const int q = major ? (int)((double)((long)(major >> 1) + (long)k * minor) / (double)major) : 0;
-      const int cx = dx >= dy ? x0 + sx * k : x0 + sx * q, cy = dx >= dy ? y0 + sy * q : y0 + sy * k;
+      int cx, cy;
+      line_cell(x0, y0, x1, y1, k, cx, cy);
       if (t < total) {
         // (the bounds test cannot fail -- see above; it keeps a wrong index from ever becoming a read outside the map)
         const bool inside = (unsigned)cx < (unsigned)m.size_x && (unsigned)cy < (unsigned)m.size_y;

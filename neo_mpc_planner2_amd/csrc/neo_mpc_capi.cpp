@@ -13,7 +13,7 @@
 // K4 carrots, K6 footprint gate, K7 rolling windows; a fleet's outlines (K8's and K12's one view, shape check and host
 // staging), K8 fleet stamp, K9 world inflation; the scan layers -- their checks, K10's and K12 / K13's updates, the staging of an
 // observation and the entry points from points, then K11: the projection, the staging of ranges and the entry points from
-// ranges --; the layers read back, reset, K13's and K14's settings.  A new entry point checks with the shared checks, stages with upload()
+// ranges --; the layers read back, reset, K13's and K14's settings; K15 plan check.  A new entry point checks with the shared checks, stages with upload()
 // -- an observation, ranges or outlines with the routine there is --, and launches through fence.read() or between
 // fence.begin_write() and end_write(); a new kind of update is a switch of update_from_points() and from_ranges(), not a copy.
 #include <hip/hip_runtime.h>
@@ -454,6 +454,7 @@ struct __attribute__((visibility("hidden"))) neo_mpc_handle {
   ScanLayers scan;   // K10 neo_mpc_update_scan_layer
   LaserProjection laser;   // K11 neo_mpc_project_laser, neo_mpc_update_scan_layer_from_ranges
   WorldScanLayer world_scan;   // K12 neo_mpc_update_world_scan_layer
+  DeviceBuffer plan_checks;    // K15 neo_mpc_check_plans: its results (its plans: K4's plan_poses / plan_offsets; poses, verts)
 };
 constexpr size_t kLatencyPathMaxCount = 64;
 constexpr size_t kChunkedMinCount = 65536;   // staged host batches from here on go through in kChunks pieces on two streams
@@ -2234,6 +2235,83 @@ int neo_mpc_reset_world_scan_layer(neo_mpc_handle* h) {
   if (!h) return fail(NEO_MPC_ERR_INVALID_ARGUMENT, "null handle");
   h->world_scan.valid = false;
   h->world_scan.live_valid = false;
+  return NEO_MPC_OK;
+}
+
+// ---------------------------------------------------------------------------------------------- K15: the plan check
+// What both entry points check: the record's shape, never a value behind a pointer.
+static int check_plan_check_batch(const neo_mpc_handle* h, const neo_mpc_plan_check_batch* b) {
+  if (!h || !b) return fail(NEO_MPC_ERR_INVALID_ARGUMENT, "null argument");
+  if (!h->world.has) return fail(NEO_MPC_ERR_NO_COSTMAP, "neo_mpc_set_world_map has not been called");
+  if (b->reserved != 0) return fail(NEO_MPC_ERR_INVALID_ARGUMENT, "neo_mpc_plan_check_batch.reserved must be zero (got %u)", b->reserved);
+  if (b->max_cost < 1 || b->max_cost > 254) return fail(NEO_MPC_ERR_INVALID_ARGUMENT, "max_cost %u outside [1, 254]", b->max_cost);
+  if (b->unknown_blocks > 1) return fail(NEO_MPC_ERR_INVALID_ARGUMENT, "unknown_blocks must be 0 or 1 (got %u)", b->unknown_blocks);
+  if (b->outside_value > 255) return fail(NEO_MPC_ERR_INVALID_ARGUMENT, "outside_value %u is no cell value (0 .. 255)", b->outside_value);
+  if ((b->footprint == nullptr) != (b->footprint_points == 0))
+    return fail(NEO_MPC_ERR_INVALID_ARGUMENT, "footprint and footprint_points (%u) must be given together", b->footprint_points);
+  if (b->footprint)
+    if (int rc = check_footprint_shape(b->footprint_points, 0)) return rc;
+  if (b->count > 0 && (!b->plan_poses || !b->plan_offsets || !b->results))
+    return fail(NEO_MPC_ERR_INVALID_ARGUMENT, "plan_poses/plan_offsets/results must not be null");
+  return check_count(b->count);
+}
+
+// `d`: the record with device pointers.  Orders itself like roll(), whose reads it shares -- the map the next roll would cut
+// its windows from, behind that map's writer -- and like a roll it runs between the fence's begin_write and end_write: every
+// rewrite of the world map waits for the fence's last write (WorldMap::begin_write), and that is how it waits for this read.
+static int plan_check(neo_mpc_handle* h, const neo_mpc_plan_check_batch& d, void* stream) {
+  hipStream_t st = (hipStream_t)stream;
+  int rc;
+  if ((rc = h->fence.begin_write(st))) return rc;
+  if ((rc = h->world.wait_writer(st))) return rc;
+  const WorldMap& w = h->world;
+  PlanCheckArgs a;
+  std::memset(&a, 0, sizeof(a));
+  a.plan_poses = d.plan_poses; a.plan_offsets = d.plan_offsets; a.robot_poses = d.robot_poses; a.footprint = d.footprint;
+  a.results = d.results;
+  // (K12: while an update's composition is current it is the map -- roll()'s choice, same geometry, same event)
+  a.world = h->world_scan.live_valid ? h->world_scan.live.as<const uint8_t>() : w.buf.as<const uint8_t>();
+  a.wres = w.resolution; a.winv = 1.0 / w.resolution; a.wox = w.origin_x; a.woy = w.origin_y;
+  a.wsx = w.size_x; a.wsy = w.size_y;
+  a.count = (uint32_t)d.count; a.footprint_points = d.footprint_points;
+  a.max_cost = d.max_cost; a.unknown_blocks = d.unknown_blocks; a.outside = d.outside_value; a.max_poses = d.max_poses;
+  launch_plan_check(a, stream);
+  HIP_TRY(hipGetLastError());
+  return h->fence.end_write(st);
+}
+
+int neo_mpc_check_plans_device(neo_mpc_handle* h, const neo_mpc_plan_check_batch* b, void* stream) {
+  int rc = check_plan_check_batch(h, b);
+  if (rc) return rc;
+  if (b->count == 0) return NEO_MPC_OK;
+  HIP_TRY(hipSetDevice(h->device));
+  return plan_check(h, *b, stream);
+}
+
+int neo_mpc_check_plans(neo_mpc_handle* h, const neo_mpc_plan_check_batch* b) {
+  int rc = check_plan_check_batch(h, b);
+  if (rc) return rc;
+  if (b->count == 0) return NEO_MPC_OK;
+  const size_t n = b->count, np = b->footprint_points;
+  // the values the device variant takes as they come are looked at here
+  for (size_t i = 0; i < n; ++i)
+    if (b->plan_offsets[i + 1] < b->plan_offsets[i])
+      return fail(NEO_MPC_ERR_INVALID_ARGUMENT, "plan_offsets[%zu] = %u is below plan_offsets[%zu] = %u", i + 1, b->plan_offsets[i + 1],
+                  i, b->plan_offsets[i]);
+  if (b->footprint && (rc = check_vertices_finite(b->footprint, 1, np, "footprint vertex", "polygon"))) return rc;
+  HIP_TRY(hipSetDevice(h->device));
+  const size_t total = b->plan_offsets[n];
+  if ((rc = h->plan_poses.reserve(total * 24 + 8))) return rc;   // (never empty: a fleet without a plan pose stages nothing)
+  if ((rc = h->plan_checks.reserve(n * sizeof(neo_mpc_plan_check)))) return rc;
+  neo_mpc_plan_check_batch d = *b;
+  d.results = h->plan_checks.as<neo_mpc_plan_check>();
+  if (!(d.plan_poses = h->plan_poses.upload(b->plan_poses, total * 24))) return NEO_MPC_ERR_DEVICE;
+  if (!(d.plan_offsets = h->plan_offsets.upload(b->plan_offsets, (n + 1) * 4))) return NEO_MPC_ERR_DEVICE;
+  if (b->robot_poses && !(d.robot_poses = h->poses.upload(b->robot_poses, n * 24))) return NEO_MPC_ERR_DEVICE;
+  if (b->footprint && !(d.footprint = h->verts.upload(b->footprint, np * 16))) return NEO_MPC_ERR_DEVICE;
+  if ((rc = plan_check(h, d, nullptr))) return finish_on_null_stream(rc);
+  // (a blocking copy on the null stream, behind the kernel)
+  HIP_TRY(hipMemcpy(b->results, h->plan_checks.ptr, n * sizeof(neo_mpc_plan_check), hipMemcpyDeviceToHost));
   return NEO_MPC_OK;
 }
 

@@ -326,6 +326,21 @@ struct LaserArgs {
   uint32_t count, sources, beams;
 };
 
+// K15: the plan check (neo_mpc_plan_check_batch, device pointers) on the world map the next roll would read
+struct PlanCheckArgs {
+  const double* plan_poses;         // [plan_offsets[count]][3]
+  const uint32_t* plan_offsets;     // [count + 1]
+  const double* robot_poses;        // optional [count][3]; null: every check starts at pose 0
+  const double* footprint;          // [footprint_points][2] base frame, shared; null: point mode
+  neo_mpc_plan_check* results;      // [count]
+  const uint8_t* world;             // the world map or K12's composition, row-major wsx * wsy
+  double wres, winv, wox, woy;      // winv = 1 / wres (cell_of redoes the division where it matters)
+  int32_t wsx, wsy;
+  uint32_t count;
+  uint32_t footprint_points;        // 0: point mode
+  uint32_t max_cost, unknown_blocks, outside, max_poses;
+};
+
 // A/B switches of the measurement tools: read from the environment ONCE, by neo_mpc_create (include/neo_mpc.h), kept in
 // the handle -- nothing on the solve path looks at the environment.
 struct LaunchTuning {
@@ -346,6 +361,7 @@ void launch_inflate_world(const InflateArgs& a, void* stream);   // K9: k_inflat
 void launch_scan_layer(const ScanArgs& a, void* stream);         // K10: k_scan_shift, k_scan_rays (clear, mark), k_scan_apply
 void launch_laser_project(const LaserArgs& a, void* stream);     // K11: k_laser_project
 void launch_world_scan(const WorldScanArgs& a, void* stream);    // K12: k_world_scan_rays (clear, mark), [K14: k_world_scan_decay,] k_world_scan_footprints, [K13: k_world_scan_denoise,] k_world_scan_compose
+void launch_plan_check(const PlanCheckArgs& a, void* stream);    // K15: k_plan_check (point or footprint mode)
 // K5: dispatch order of the next launch from the iteration counts of the previous one (neo_mpc_balance_dispatch_device)
 void launch_dispatch_order(const neo_mpc_command* commands, float* load, uint32_t* order, uint32_t count, bool fresh, void* stream);
 constexpr uint32_t kDispatchSimds = 1024;   // a 4096-instance launch is one residency round: workgroups w, w + 1024, w + 2048, w + 3072 share a SIMD

@@ -24,6 +24,8 @@
 //   K12 k_world_scan_rays, k_world_scan_footprints, k_world_scan_compose  world_scan_layer.h: one obstacle layer for the fleet on the world map.
 //   K13 k_world_scan_denoise  world_scan_denoise.h: that layer's speckle filter, groups of fewer than G occupied cells, in front of K12's composition.
 //   K14 k_world_scan_tick, k_world_scan_stamp_fill, k_world_scan_marks_stamped, k_world_scan_decay  world_scan_decay.h: that layer's old marks expire, counted in scan updates.
+//   K15 k_plan_check  plan_check.h: which of the fleet's global plans the live world map blocks, one wave per plan, HBM-streaming;
+//                     K4's closest-pose stream lives there too.
 #include "k1_solve.h"
 #include "costmap_ingest.h"
 #include "footprint_gate.h"
@@ -35,6 +37,7 @@
 #include "world_scan_layer.h"
 #include "world_scan_denoise.h"
 #include "world_scan_decay.h"
+#include "plan_check.h"
 
 namespace neo_mpc {
 namespace {
@@ -146,36 +149,8 @@ __global__ __launch_bounds__(kLanes) void k_carrot(const CarrotArgs a) {
     if (lane == 0) { a.b.carrots[b] = out; if (a.b.problems) a.b.problems[b].skip = 1; }   // (a throw: no request this tick)
     return;
   }
-  // closest pose, first minimum (min_by, cpp:83-88)
-  const double fx = poses[0] - rx, fy = poses[1] - ry;   // (the first pose: loaded ahead of the stream, looked at behind it)
-  double best = INFINITY;
-  uint32_t besti = 0xffffffffu;
-  uint32_t k = lane;
-  for (; k + 3 * kLanes < np; k += 4 * kLanes) {  // four independent pose loads in flight per lane
-#define NT(p) __builtin_nontemporal_load(p)
-    const double x0 = NT(poses + 3 * k), y0 = NT(poses + 3 * k + 1);
-    const double x1 = NT(poses + 3 * (k + kLanes)), y1 = NT(poses + 3 * (k + kLanes) + 1);
-    const double x2 = NT(poses + 3 * (k + 2 * kLanes)), y2 = NT(poses + 3 * (k + 2 * kLanes) + 1);
-    const double x3 = NT(poses + 3 * (k + 3 * kLanes)), y3 = NT(poses + 3 * (k + 3 * kLanes) + 1);
-#undef NT
-    const double d0 = hypot(x0 - rx, y0 - ry), d1 = hypot(x1 - rx, y1 - ry);
-    const double d2 = hypot(x2 - rx, y2 - ry), d3 = hypot(x3 - rx, y3 - ry);
-    if (d0 < best) { best = d0; besti = k; }
-    if (d1 < best) { best = d1; besti = k + kLanes; }
-    if (d2 < best) { best = d2; besti = k + 2 * kLanes; }
-    if (d3 < best) { best = d3; besti = k + 3 * kLanes; }
-  }
-  for (; k < np; k += kLanes) {
-    const double d = hypot(poses[3 * k] - rx, poses[3 * k + 1] - ry);
-    if (d < best) { best = d; besti = k; }
-  }
-  const double gmin = wave_min(best);
-  uint32_t begin = (uint32_t)wave_min((best == gmin) ? (double)besti : 4.0e9);
-  // min_by starts at the first pose and moves on a strict `<` alone: nothing is below a first distance of NaN, and where no
-  // distance is below infinity no lane holds an index
-  // (a NaN component alone does not make the first distance NaN: hypot(NaN, inf) is inf, and the search moves on from it;
-  // the component test only keeps hypot off the common path)
-  if (!(gmin < INFINITY) || ((fx != fx || fy != fy) && isnan(hypot(fx, fy)))) begin = 0;
+  // closest pose, first minimum (min_by, cpp:83-88): the stream K15 shares (plan_check.h)
+  const uint32_t begin = closest_pose(poses, np, rx, ry, lane);
   out.closer_to_goal = hypot(poses[3 * (np - 1)] - rx, poses[3 * (np - 1) + 1] - ry) <=
                        a.lp.lookahead_dist_close_to_goal ? 1 : 0;       // cpp:95-100
   double la = a.lp.lookahead_dist_min;                                  // cpp:161-169
@@ -423,6 +398,12 @@ void launch_world_scan(const WorldScanArgs& a, void* stream) {
   WorldScanArgs filtered = a;
   filtered.layer = a.denoised;
   hipLaunchKernelGGL(k_world_scan_compose, tiles, tile, 0, st, filtered);
+}
+// K15: one wave per plan; the mode is the kernel's (a polygon or none: uniform over the launch)
+void launch_plan_check(const PlanCheckArgs& a, void* stream) {
+  if (a.count == 0) return;
+  if (a.footprint_points != 0) hipLaunchKernelGGL(k_plan_check<true>, dim3(a.count), dim3(kLanes), 0, (hipStream_t)stream, a);
+  else hipLaunchKernelGGL(k_plan_check<false>, dim3(a.count), dim3(kLanes), 0, (hipStream_t)stream, a);
 }
 void launch_ingest(const IngestArgs& a, const LaunchTuning& tuning, void* stream) {
   hipLaunchKernelGGL(k_ingest, padded_map_grid(a.rows, a.pitch, kIngestUnroll, a.maps > 0 ? a.maps : 1), dim3(256), 0,

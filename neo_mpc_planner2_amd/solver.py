@@ -751,6 +751,59 @@ class BatchSolver:
             stream = torch.cuda.current_stream(robot_poses.device).cuda_stream
         _lib.check(self._lib.neo_mpc_select_carrots_device(self._handle, C.byref(lp), C.byref(b), C.c_void_p(stream)))
 
+    # -- plan check (the fleet's plans against the live world map) -------------------------
+    @staticmethod
+    def _plan_check_batch(count, footprint_points, max_cost, unknown_blocks, outside_value, max_poses):
+        b = abi.NeoMpcPlanCheckBatch()
+        b.count = count
+        b.footprint_points = footprint_points
+        b.max_cost, b.unknown_blocks, b.outside_value, b.max_poses = int(max_cost), int(unknown_blocks), int(outside_value), int(max_poses)
+        return b
+
+    def check_plans(self, plan_poses, plan_offsets, robot_poses=None, footprint=None, max_cost=253, unknown_blocks=False,
+                    outside_value=255, max_poses=0):
+        """Which plans of a ragged batch (`select_carrots`' arrays, poses in the world map's frame) the world map the
+        next roll would read blocks (K15; the contract: include/neo_mpc.h, neo_mpc_plan_check_batch).  With `robot_poses`
+        [count, 3] the check starts at each plan's closest pose, else at pose 0; `footprint` [points, 2] (base frame,
+        shared) selects footprint mode, None point mode.  Returns the records (abi.PLAN_CHECK_DTYPE [count])."""
+        plan_poses = np.ascontiguousarray(plan_poses, dtype=np.float64).reshape(-1, 3)
+        plan_offsets = np.ascontiguousarray(plan_offsets, dtype=np.uint32)
+        count = plan_offsets.shape[0] - 1
+        results = np.zeros(count, dtype=abi.PLAN_CHECK_DTYPE)
+        points = 0
+        if footprint is not None:
+            footprint = np.ascontiguousarray(footprint, dtype=np.float64)
+            assert footprint.ndim == 2 and footprint.shape[1] == 2
+            points = footprint.shape[0]
+        b = self._plan_check_batch(count, points, max_cost, unknown_blocks, outside_value, max_poses)
+        b.plan_poses = plan_poses.ctypes.data
+        b.plan_offsets = plan_offsets.ctypes.data
+        if robot_poses is not None:
+            robot_poses = np.ascontiguousarray(robot_poses, dtype=np.float64).reshape(-1, 3)
+            assert robot_poses.shape[0] == count
+            b.robot_poses = robot_poses.ctypes.data
+        b.footprint = footprint.ctypes.data if footprint is not None else None
+        b.results = results.ctypes.data
+        _lib.check(self._lib.neo_mpc_check_plans(self._handle, C.byref(b)))
+        return results
+
+    def check_plans_device(self, plan_poses, plan_offsets, results, robot_poses=None, footprint=None, max_cost=253,
+                           unknown_blocks=False, outside_value=255, max_poses=0, stream=None):
+        """Device-resident variant: contiguous torch CUDA tensors (float64; `plan_offsets` [count + 1] as int32 or uint32
+        bits; `results` the records as bytes, 24 a robot); enqueues K15 on `stream` (default: torch's current) and
+        returns without waiting.  Capturable in a HIP graph behind one call of the same shape."""
+        import torch
+        b = self._plan_check_batch(plan_offsets.shape[0] - 1, footprint.shape[0] if footprint is not None else 0,
+                                   max_cost, unknown_blocks, outside_value, max_poses)
+        b.plan_poses = plan_poses.data_ptr()
+        b.plan_offsets = plan_offsets.data_ptr()
+        b.robot_poses = robot_poses.data_ptr() if robot_poses is not None else None
+        b.footprint = footprint.data_ptr() if footprint is not None else None
+        b.results = results.data_ptr()
+        if stream is None:
+            stream = torch.cuda.current_stream(results.device).cuda_stream
+        _lib.check(self._lib.neo_mpc_check_plans_device(self._handle, C.byref(b), C.c_void_p(stream)))
+
     # -- footprint gate (the step before the carrot) --------------------------------------
     def footprint_gate(self, footprint, poses=None, problems=None, map_indices=None, want_polygons=False):
         """`footprintCostAtPose` (NeoMpcPlanner.cpp:218-219; nav2's FootprintCollisionChecker on raw cell values) for a
