@@ -14,32 +14,77 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 #: call: box-to-box variance is ~5 %, so two builds are only comparable on the same box)
 LIB_PATH = os.environ.get("NEO_MPC_LIB") or os.path.join(HERE, "libneo_mpc.so")
 
-#: every symbol include/neo_mpc.h declares
-EXPORTS = (
-    "neo_mpc_abi_version", "neo_mpc_behaviour_version", "neo_mpc_effective_method", "neo_mpc_balance_dispatch_device", "neo_mpc_last_error", "neo_mpc_last_error_code", "neo_mpc_default_params", "neo_mpc_create",
-    "neo_mpc_destroy", "neo_mpc_set_params", "neo_mpc_get_params", "neo_mpc_set_costmap",
-    "neo_mpc_set_costmap_device", "neo_mpc_set_costmap_pool", "neo_mpc_set_costmap_pool_device", "neo_mpc_solve_batch", "neo_mpc_solve_batch_device",
-    "neo_mpc_solve_batch_device_timed", "neo_mpc_solve_batch_begin", "neo_mpc_solve_batch_wait",
-    "neo_mpc_postprocess_batch", "neo_mpc_objective_batch", "neo_mpc_gradient_batch", "neo_mpc_direction_batch",
-    "neo_mpc_kernel_info", "neo_mpc_pin_host_memory", "neo_mpc_unpin_host_memory", "neo_mpc_set_host_path",
-    "neo_mpc_select_carrots", "neo_mpc_select_carrots_device",
-    "neo_mpc_footprint_gate", "neo_mpc_footprint_gate_device",
-    "neo_mpc_set_world_map", "neo_mpc_set_world_map_device", "neo_mpc_roll_costmap_pool",
-    "neo_mpc_roll_costmap_pool_device", "neo_mpc_get_costmap_pool",
-    "neo_mpc_stamp_fleet", "neo_mpc_stamp_fleet_device", "neo_mpc_inflation_costs",
-    "neo_mpc_inflate_world_map", "neo_mpc_inflate_world_map_device", "neo_mpc_get_world_map",
-    "neo_mpc_update_scan_layer", "neo_mpc_update_scan_layer_device", "neo_mpc_get_scan_layer", "neo_mpc_reset_scan_layer",
-    "neo_mpc_laser_beam_table", "neo_mpc_project_laser", "neo_mpc_project_laser_device",
-    "neo_mpc_update_scan_layer_from_ranges", "neo_mpc_update_scan_layer_from_ranges_device",
-    "neo_mpc_update_world_scan_layer", "neo_mpc_update_world_scan_layer_device",
-    "neo_mpc_update_world_scan_layer_from_ranges", "neo_mpc_update_world_scan_layer_from_ranges_device",
-    "neo_mpc_get_world_scan_layer", "neo_mpc_reset_world_scan_layer",
-    "neo_mpc_set_world_scan_denoise", "neo_mpc_get_world_scan_denoised",
-    "neo_mpc_set_world_scan_decay", "neo_mpc_get_world_scan_ages",
-    "neo_mpc_check_plans", "neo_mpc_check_plans_device",
-    "neo_mpc_rccl_available", "neo_mpc_comm_init_all", "neo_mpc_comm_destroy", "neo_mpc_group_start",
-    "neo_mpc_group_end", "neo_mpc_allgather_velocities", "neo_mpc_broadcast_costmap",
-)
+_P = C.POINTER
+_H = _V = C.c_void_p     # the handle; any other address: an array, a stream, an event
+_U32, _F64, _SIZE = C.c_uint32, C.c_double, C.c_size_t
+_COSTMAP = [_H, _V, _U32, _U32, _F64, _F64, _F64]
+_CELLS = [_H, _U32, _U32, _V, _V]
+
+
+def _pair(name, *args):
+    """The prototypes of a step's host entry point and of its `_device` twin, which takes a stream behind the same arguments."""
+    return {name: (C.c_int, [_H, *args]), name + "_device": (C.c_int, [_H, *args, _V])}
+
+
+#: every symbol include/neo_mpc.h declares -> (restype, argtypes), or None where this package declares no prototype
+PROTOTYPES = {
+    "neo_mpc_abi_version": (C.c_int, None),
+    "neo_mpc_behaviour_version": (C.c_int, None),
+    "neo_mpc_effective_method": (C.c_int, [_H]),
+    "neo_mpc_balance_dispatch_device": (C.c_int, [_H, _V, _SIZE, _V]),
+    "neo_mpc_last_error": (C.c_char_p, None),
+    "neo_mpc_last_error_code": None,
+    "neo_mpc_default_params": (C.c_int, [_P(abi.NeoMpcParams)]),
+    "neo_mpc_create": (C.c_void_p, [_P(abi.NeoMpcParams), C.c_int]),
+    "neo_mpc_destroy": (None, [_H]),
+    "neo_mpc_set_params": (C.c_int, [_H, _P(abi.NeoMpcParams)]),
+    "neo_mpc_get_params": (C.c_int, [_H, _P(abi.NeoMpcParams)]),
+    "neo_mpc_set_costmap": (C.c_int, _COSTMAP),
+    "neo_mpc_set_costmap_device": (C.c_int, _COSTMAP + [_V]),
+    "neo_mpc_set_costmap_pool": (C.c_int, [_H, _V, _U32, _U32, _U32, _F64, _V]),
+    "neo_mpc_set_costmap_pool_device": (C.c_int, [_H, _V, _U32, _U32, _U32, _F64, _V, _V]),
+    **_pair("neo_mpc_solve_batch", _P(abi.NeoMpcBatch)),
+    "neo_mpc_solve_batch_device_timed": (C.c_int, [_H, _P(abi.NeoMpcBatch), _V, _V, _V]),
+    "neo_mpc_solve_batch_begin": (C.c_int, [_H, _P(abi.NeoMpcBatch), _P(_U32)]),
+    "neo_mpc_solve_batch_wait": (C.c_int, [_H, _U32]),
+    "neo_mpc_postprocess_batch": (C.c_int, [_H, _P(abi.NeoMpcBatch), _V]),
+    "neo_mpc_objective_batch": (C.c_int, [_H, _V, _V, _V, _SIZE]),
+    "neo_mpc_gradient_batch": (C.c_int, [_H, _V, _V, _V, _SIZE]),
+    "neo_mpc_direction_batch": (C.c_int, [_H, _V, _V, _V, _SIZE, C.c_int]),
+    "neo_mpc_kernel_info": (C.c_int, [_H, _P(_U32), _P(_U32), _P(_U32)]),
+    "neo_mpc_pin_host_memory": (C.c_int, [_V, _SIZE]),
+    "neo_mpc_unpin_host_memory": (C.c_int, [_V]),
+    "neo_mpc_set_host_path": (C.c_int, [_H, C.c_int]),
+    **_pair("neo_mpc_select_carrots", _P(abi.NeoMpcLookaheadParams), _P(abi.NeoMpcPlanBatch)),
+    **_pair("neo_mpc_footprint_gate", _P(abi.NeoMpcFootprintBatch)),
+    "neo_mpc_set_world_map": (C.c_int, _COSTMAP),
+    "neo_mpc_set_world_map_device": (C.c_int, _COSTMAP + [_V]),
+    **_pair("neo_mpc_roll_costmap_pool", _P(abi.NeoMpcWindowBatch)),
+    "neo_mpc_get_costmap_pool": (C.c_int, _CELLS),
+    **_pair("neo_mpc_stamp_fleet", _P(abi.NeoMpcStampBatch)),
+    "neo_mpc_inflation_costs": (C.c_int, [_F64, _F64, _F64, _F64, _V, _SIZE, _P(_U32)]),
+    **_pair("neo_mpc_inflate_world_map", _F64, _F64, _F64),
+    "neo_mpc_get_world_map": (C.c_int, [_H, _V, _P(_U32), _P(_U32), _P(_F64), _P(_F64), _P(_F64)]),
+    **_pair("neo_mpc_update_scan_layer", _P(abi.NeoMpcScanBatch)),
+    "neo_mpc_get_scan_layer": (C.c_int, _CELLS),
+    "neo_mpc_reset_scan_layer": (C.c_int, [_H]),
+    "neo_mpc_laser_beam_table": (C.c_int, [_P(abi.NeoMpcScanner), _U32, _V]),
+    **_pair("neo_mpc_project_laser", _P(abi.NeoMpcLaserBatch)),
+    **_pair("neo_mpc_update_scan_layer_from_ranges", _P(abi.NeoMpcLaserBatch)),
+    **_pair("neo_mpc_update_world_scan_layer", _P(abi.NeoMpcScanBatch), _P(abi.NeoMpcFleetClear)),
+    **_pair("neo_mpc_update_world_scan_layer_from_ranges", _P(abi.NeoMpcLaserBatch), _P(abi.NeoMpcFleetClear)),
+    "neo_mpc_get_world_scan_layer": (C.c_int, [_H, _V, _V]),
+    "neo_mpc_reset_world_scan_layer": (C.c_int, [_H]),
+    "neo_mpc_set_world_scan_denoise": (C.c_int, [_H, _U32, _U32]),
+    "neo_mpc_get_world_scan_denoised": (C.c_int, [_H, _V]),
+    "neo_mpc_set_world_scan_decay": (C.c_int, [_H, _U32]),
+    "neo_mpc_get_world_scan_ages": (C.c_int, [_H, _V]),
+    **_pair("neo_mpc_check_plans", _P(abi.NeoMpcPlanCheckBatch)),
+    "neo_mpc_rccl_available": None, "neo_mpc_comm_init_all": None, "neo_mpc_comm_destroy": None,
+    "neo_mpc_group_start": None, "neo_mpc_group_end": None,
+    "neo_mpc_allgather_velocities": None, "neo_mpc_broadcast_costmap": None,
+}
+EXPORTS = tuple(PROTOTYPES)
 
 _lib = None
 
@@ -67,93 +112,23 @@ def load():
     except ImportError:
         pass
     lib = C.CDLL(LIB_PATH)
-    P = C.POINTER
-    lib.neo_mpc_abi_version.restype = C.c_int
-    lib.neo_mpc_last_error.restype = C.c_char_p
-    lib.neo_mpc_default_params.argtypes = [P(abi.NeoMpcParams)]
-    lib.neo_mpc_create.restype = C.c_void_p
-    lib.neo_mpc_create.argtypes = [P(abi.NeoMpcParams), C.c_int]
-    lib.neo_mpc_destroy.restype = None
-    lib.neo_mpc_destroy.argtypes = [C.c_void_p]
-    lib.neo_mpc_set_params.argtypes = [C.c_void_p, P(abi.NeoMpcParams)]
-    lib.neo_mpc_get_params.argtypes = [C.c_void_p, P(abi.NeoMpcParams)]
-    lib.neo_mpc_set_costmap.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32,
-                                        C.c_double, C.c_double, C.c_double]
-    lib.neo_mpc_set_costmap_device.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32,
-                                               C.c_double, C.c_double, C.c_double, C.c_void_p]
-    lib.neo_mpc_set_costmap_pool.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32,
-                                             C.c_double, C.c_void_p]
-    lib.neo_mpc_set_costmap_pool_device.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32,
-                                                    C.c_double, C.c_void_p, C.c_void_p]
-    lib.neo_mpc_solve_batch.argtypes = [C.c_void_p, P(abi.NeoMpcBatch)]
-    lib.neo_mpc_solve_batch_device.argtypes = [C.c_void_p, P(abi.NeoMpcBatch), C.c_void_p]
-    lib.neo_mpc_solve_batch_device_timed.argtypes = [C.c_void_p, P(abi.NeoMpcBatch), C.c_void_p, C.c_void_p, C.c_void_p]
-    lib.neo_mpc_postprocess_batch.argtypes = [C.c_void_p, P(abi.NeoMpcBatch), C.c_void_p]
-    lib.neo_mpc_objective_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t]
-    lib.neo_mpc_gradient_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t]
-    lib.neo_mpc_direction_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_int]
-    lib.neo_mpc_select_carrots.argtypes = [C.c_void_p, P(abi.NeoMpcLookaheadParams), P(abi.NeoMpcPlanBatch)]
-    lib.neo_mpc_select_carrots_device.argtypes = [C.c_void_p, P(abi.NeoMpcLookaheadParams),
-                                                  P(abi.NeoMpcPlanBatch), C.c_void_p]
-    lib.neo_mpc_solve_batch_begin.argtypes = [C.c_void_p, P(abi.NeoMpcBatch), P(C.c_uint32)]
-    lib.neo_mpc_solve_batch_wait.argtypes = [C.c_void_p, C.c_uint32]
-    lib.neo_mpc_pin_host_memory.argtypes = [C.c_void_p, C.c_size_t]
-    lib.neo_mpc_unpin_host_memory.argtypes = [C.c_void_p]
-    lib.neo_mpc_set_host_path.argtypes = [C.c_void_p, C.c_int]
-    lib.neo_mpc_kernel_info.argtypes = [C.c_void_p, P(C.c_uint32), P(C.c_uint32), P(C.c_uint32)]
-    if os.environ.get("NEO_MPC_LIB"):
-        # development A/B against an older build of the same library (tools/ab_many.sh): the record layouts have not
-        # changed since ABI 1, so only the entry points a tool actually calls have to exist
-        if lib.neo_mpc_abi_version() not in (1, abi.ABI_VERSION):
-            raise ImportError("%s: ABI version %d" % (LIB_PATH, lib.neo_mpc_abi_version()))
-    else:
-        for name in EXPORTS:
-            getattr(lib, name)     # AttributeError here = the .so is older than include/neo_mpc.h
-        if lib.neo_mpc_abi_version() != abi.ABI_VERSION:
-            raise ImportError("libneo_mpc.so ABI version %d, this package binds %d" % (lib.neo_mpc_abi_version(), abi.ABI_VERSION))
-        lib.neo_mpc_behaviour_version.restype = C.c_int
-        lib.neo_mpc_effective_method.restype = C.c_int
-        lib.neo_mpc_effective_method.argtypes = [C.c_void_p]
-        lib.neo_mpc_balance_dispatch_device.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
-        lib.neo_mpc_footprint_gate.argtypes = [C.c_void_p, P(abi.NeoMpcFootprintBatch)]
-        lib.neo_mpc_footprint_gate_device.argtypes = [C.c_void_p, P(abi.NeoMpcFootprintBatch), C.c_void_p]
-        lib.neo_mpc_set_world_map.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_double, C.c_double,
-                                              C.c_double]
-        lib.neo_mpc_set_world_map_device.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_double,
-                                                     C.c_double, C.c_double, C.c_void_p]
-        lib.neo_mpc_roll_costmap_pool.argtypes = [C.c_void_p, P(abi.NeoMpcWindowBatch)]
-        lib.neo_mpc_roll_costmap_pool_device.argtypes = [C.c_void_p, P(abi.NeoMpcWindowBatch), C.c_void_p]
-        lib.neo_mpc_get_costmap_pool.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p]
-        lib.neo_mpc_stamp_fleet.argtypes = [C.c_void_p, P(abi.NeoMpcStampBatch)]
-        lib.neo_mpc_stamp_fleet_device.argtypes = [C.c_void_p, P(abi.NeoMpcStampBatch), C.c_void_p]
-        lib.neo_mpc_inflation_costs.argtypes = [C.c_double, C.c_double, C.c_double, C.c_double, C.c_void_p, C.c_size_t,
-                                                P(C.c_uint32)]
-        lib.neo_mpc_inflate_world_map.argtypes = [C.c_void_p, C.c_double, C.c_double, C.c_double]
-        lib.neo_mpc_inflate_world_map_device.argtypes = [C.c_void_p, C.c_double, C.c_double, C.c_double, C.c_void_p]
-        lib.neo_mpc_get_world_map.argtypes = [C.c_void_p, C.c_void_p, P(C.c_uint32), P(C.c_uint32), P(C.c_double),
-                                              P(C.c_double), P(C.c_double)]
-        lib.neo_mpc_update_scan_layer.argtypes = [C.c_void_p, P(abi.NeoMpcScanBatch)]
-        lib.neo_mpc_update_scan_layer_device.argtypes = [C.c_void_p, P(abi.NeoMpcScanBatch), C.c_void_p]
-        lib.neo_mpc_get_scan_layer.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p]
-        lib.neo_mpc_reset_scan_layer.argtypes = [C.c_void_p]
-        lib.neo_mpc_laser_beam_table.argtypes = [P(abi.NeoMpcScanner), C.c_uint32, C.c_void_p]
-        lib.neo_mpc_project_laser.argtypes = [C.c_void_p, P(abi.NeoMpcLaserBatch)]
-        lib.neo_mpc_project_laser_device.argtypes = [C.c_void_p, P(abi.NeoMpcLaserBatch), C.c_void_p]
-        lib.neo_mpc_update_scan_layer_from_ranges.argtypes = [C.c_void_p, P(abi.NeoMpcLaserBatch)]
-        lib.neo_mpc_update_scan_layer_from_ranges_device.argtypes = [C.c_void_p, P(abi.NeoMpcLaserBatch), C.c_void_p]
-        lib.neo_mpc_update_world_scan_layer.argtypes = [C.c_void_p, P(abi.NeoMpcScanBatch), P(abi.NeoMpcFleetClear)]
-        lib.neo_mpc_update_world_scan_layer_device.argtypes = [C.c_void_p, P(abi.NeoMpcScanBatch), P(abi.NeoMpcFleetClear), C.c_void_p]
-        lib.neo_mpc_update_world_scan_layer_from_ranges.argtypes = [C.c_void_p, P(abi.NeoMpcLaserBatch), P(abi.NeoMpcFleetClear)]
-        lib.neo_mpc_update_world_scan_layer_from_ranges_device.argtypes = [C.c_void_p, P(abi.NeoMpcLaserBatch),
-                                                                          P(abi.NeoMpcFleetClear), C.c_void_p]
-        lib.neo_mpc_get_world_scan_layer.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
-        lib.neo_mpc_reset_world_scan_layer.argtypes = [C.c_void_p]
-        lib.neo_mpc_set_world_scan_denoise.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32]
-        lib.neo_mpc_get_world_scan_denoised.argtypes = [C.c_void_p, C.c_void_p]
-        lib.neo_mpc_set_world_scan_decay.argtypes = [C.c_void_p, C.c_uint32]
-        lib.neo_mpc_get_world_scan_ages.argtypes = [C.c_void_p, C.c_void_p]
-        lib.neo_mpc_check_plans.argtypes = [C.c_void_p, P(abi.NeoMpcPlanCheckBatch)]
-        lib.neo_mpc_check_plans_device.argtypes = [C.c_void_p, P(abi.NeoMpcPlanCheckBatch), C.c_void_p]
+    # development A/B against an older build of the same library (NEO_MPC_LIB, tools/ab_many.sh): the record layouts have not
+    # changed since ABI 1, so only the entry points a tool actually calls have to exist.  Otherwise a missing symbol is an
+    # AttributeError here: the .so is older than include/neo_mpc.h
+    older = bool(os.environ.get("NEO_MPC_LIB"))
+    for name, prototype in PROTOTYPES.items():
+        if older and not hasattr(lib, name):
+            continue
+        entry = getattr(lib, name)
+        if prototype is not None:
+            entry.restype = prototype[0]
+            if prototype[1] is not None:
+                entry.argtypes = prototype[1]
+    version = lib.neo_mpc_abi_version()
+    if older and version not in (1, abi.ABI_VERSION):
+        raise ImportError("%s: ABI version %d" % (LIB_PATH, version))
+    if not older and version != abi.ABI_VERSION:
+        raise ImportError("libneo_mpc.so ABI version %d, this package binds %d" % (version, abi.ABI_VERSION))
     _lib = lib
     return lib
 

@@ -69,6 +69,52 @@ class BatchSolver:
     def __exit__(self, *exc):
         self.close()
 
+    # -- marshalling: one path for NumPy arrays and CUDA tensors -----------------------
+    @staticmethod
+    def _array(a, on_host, dtype, shape=None, coerce=True):
+        """One argument -> (array, address), by the same rule on both sides.  `on_host`: NumPy data, made contiguous and of
+        `dtype` -- or, without `coerce`, asserted to be an array that is so already; else a torch tensor, asserted to be CUDA,
+        contiguous and of `dtype` (uint32 as its int32 bits).  `dtype` None or a record dtype: the records as they are -- a
+        tensor holds them as bytes, so only its leading dimension is compared.  `shape`: what the array's must be; None in it
+        is any length."""
+        records = dtype is None or np.dtype(dtype).names is not None
+        if on_host:
+            if coerce and dtype is not None:
+                a = np.ascontiguousarray(a, dtype=dtype)
+            assert isinstance(a, np.ndarray) and a.flags.c_contiguous and (dtype is None or a.dtype == dtype)
+            address = a.ctypes.data
+        else:
+            import torch
+            assert a.is_cuda and a.is_contiguous()
+            assert records or a.dtype == getattr(torch, np.dtype(dtype).name.replace("uint32", "int32"))
+            address = a.data_ptr()
+        if shape is not None:
+            got = tuple(a.shape)
+            if records and not on_host:
+                got, shape = got[:1], shape[:1]
+            assert len(got) == len(shape) and all(w is None or w == g for w, g in zip(shape, got)), (got, shape)
+        return a, address
+
+    @staticmethod
+    def _addresses(on_host, *arrays):
+        """The addresses of NumPy arrays (`on_host`) or of torch tensors, taken as they are; None (a NULL pointer) stays None."""
+        return [None if a is None else a.ctypes.data if on_host else a.data_ptr() for a in arrays]
+
+    @staticmethod
+    def _stream(on_host, where):
+        """torch's current stream on the device of `where` (a tensor or a torch device); None for the host variant."""
+        if on_host:
+            return None
+        import torch
+        return torch.cuda.current_stream(getattr(where, "device", where)).cuda_stream
+
+    def _call(self, name, stream, *args):
+        """The entry point `name` without a stream, `name`_device on `stream` with one (0 is a stream: torch's default)."""
+        if stream is None:
+            _lib.check(getattr(self._lib, name)(self._handle, *args))
+        else:
+            _lib.check(getattr(self._lib, name + "_device")(self._handle, *args, C.c_void_p(stream)))
+
     # -- configuration --------------------------------------------------------------
     def set_params(self, **changes):
         """Dynamic reconfigure (reference: cb_params, mpc_optimization_server.py:405-439)."""
@@ -82,19 +128,11 @@ class BatchSolver:
 
     def set_costmap(self, cells, resolution, origin_x, origin_y):
         """cells: uint8 [size_y, size_x] raw nav2 costs (NumPy) or a CUDA uint8 torch tensor."""
-        if isinstance(cells, np.ndarray):
-            cells = np.ascontiguousarray(cells, dtype=np.uint8)
-            sy, sx = cells.shape
-            _lib.check(self._lib.neo_mpc_set_costmap(self._handle, C.c_void_p(cells.ctypes.data), sx, sy,
-                                                    float(resolution), float(origin_x), float(origin_y)))
-        else:
-            import torch
-            assert cells.is_cuda and cells.dtype == torch.uint8 and cells.is_contiguous()
-            sy, sx = cells.shape
-            stream = torch.cuda.current_stream(cells.device).cuda_stream
-            _lib.check(self._lib.neo_mpc_set_costmap_device(
-                self._handle, C.c_void_p(cells.data_ptr()), sx, sy, float(resolution), float(origin_x),
-                float(origin_y), C.c_void_p(stream)))
+        on_host = isinstance(cells, np.ndarray)
+        cells, address = self._array(cells, on_host, np.uint8)
+        sy, sx = cells.shape
+        self._call("neo_mpc_set_costmap", self._stream(on_host, cells), C.c_void_p(address), sx, sy, float(resolution),
+                   float(origin_x), float(origin_y))
         self._map_shape = (1, int(sy), int(sx))
 
     def set_costmap_pool(self, cells, resolution, origins):
@@ -102,24 +140,15 @@ class BatchSolver:
         float64 [count, 2]; instances pick their map with `problems["map_index"]`.  With device
         tensors `origins` is read by every later solve and must stay alive (it may be updated in
         place between ticks, as rolling windows move)."""
-        if isinstance(cells, np.ndarray):
-            cells = np.ascontiguousarray(cells, dtype=np.uint8)
-            origins = np.ascontiguousarray(origins, dtype=np.float64)
-            m, sy, sx = cells.shape
-            assert origins.shape == (m, 2)
-            _lib.check(self._lib.neo_mpc_set_costmap_pool(self._handle, C.c_void_p(cells.ctypes.data), m, sx, sy,
-                                                         float(resolution), C.c_void_p(origins.ctypes.data)))
-        else:
-            import torch
-            assert cells.is_cuda and cells.dtype == torch.uint8 and cells.is_contiguous()
-            assert origins.is_cuda and origins.dtype == torch.float64 and origins.is_contiguous()
-            m, sy, sx = cells.shape
-            assert tuple(origins.shape) == (m, 2)
+        on_host = isinstance(cells, np.ndarray)
+        cells, cells_at = self._array(cells, on_host, np.uint8)
+        origins, origins_at = self._array(origins, on_host, np.float64)
+        m, sy, sx = cells.shape
+        assert tuple(origins.shape) == (m, 2)
+        if not on_host:
             self._pool_origins = origins   # keep it alive
-            stream = torch.cuda.current_stream(cells.device).cuda_stream
-            _lib.check(self._lib.neo_mpc_set_costmap_pool_device(
-                self._handle, C.c_void_p(cells.data_ptr()), m, sx, sy, float(resolution),
-                C.c_void_p(origins.data_ptr()), C.c_void_p(stream)))
+        self._call("neo_mpc_set_costmap_pool", self._stream(on_host, cells), C.c_void_p(cells_at), m, sx, sy, float(resolution),
+                   C.c_void_p(origins_at))
         self._map_shape = (int(m), int(sy), int(sx))
 
     # -- rolling windows (the step before the gate) ----------------------------------------
@@ -127,34 +156,20 @@ class BatchSolver:
         """The one world map a fleet's rolling windows are cut from (`roll_costmap_pool`): uint8 [size_y, size_x] raw
         nav2 costs, NumPy or a CUDA torch tensor.  The handle keeps its own device copy; the costmap(s) it holds are
         not touched."""
-        if isinstance(cells, np.ndarray):
-            cells = np.ascontiguousarray(cells, dtype=np.uint8)
-            sy, sx = cells.shape
-            _lib.check(self._lib.neo_mpc_set_world_map(self._handle, C.c_void_p(cells.ctypes.data), sx, sy,
-                                                      float(resolution), float(origin_x), float(origin_y)))
-            self._world_device = None
-        else:
-            import torch
-            assert cells.is_cuda and cells.dtype == torch.uint8 and cells.is_contiguous()
-            sy, sx = cells.shape
-            stream = torch.cuda.current_stream(cells.device).cuda_stream
-            _lib.check(self._lib.neo_mpc_set_world_map_device(
-                self._handle, C.c_void_p(cells.data_ptr()), sx, sy, float(resolution), float(origin_x),
-                float(origin_y), C.c_void_p(stream)))
-            self._world_device = cells.device
+        on_host = isinstance(cells, np.ndarray)
+        cells, address = self._array(cells, on_host, np.uint8)
+        sy, sx = cells.shape
+        self._call("neo_mpc_set_world_map", self._stream(on_host, cells), C.c_void_p(address), sx, sy, float(resolution),
+                   float(origin_x), float(origin_y))
+        self._world_device = None if on_host else cells.device
 
     def inflate_world_map(self, inscribed_radius, inflation_radius, cost_scaling_factor):
         """nav2's inflation layer on the handle's copy of the world map, in place (K9; the contract:
         neo_mpc_inflate_world_map in include/neo_mpc.h): set_world_map(raw) -> inflate_world_map -> rolls.  Like
         `set_world_map`: when the world map was set from a CUDA tensor the device call on torch's current stream,
         otherwise the synchronous host call."""
-        args = (float(inscribed_radius), float(inflation_radius), float(cost_scaling_factor))
-        if self._world_device is None:
-            _lib.check(self._lib.neo_mpc_inflate_world_map(self._handle, *args))
-        else:
-            import torch
-            stream = torch.cuda.current_stream(self._world_device).cuda_stream
-            _lib.check(self._lib.neo_mpc_inflate_world_map_device(self._handle, *args, C.c_void_p(stream)))
+        self._call("neo_mpc_inflate_world_map", self._stream(self._world_device is None, self._world_device),
+                   float(inscribed_radius), float(inflation_radius), float(cost_scaling_factor))
 
     def get_world_map(self):
         """The handle's copy of the world map as the last `set_world_map` or `inflate_world_map` left it: (cells uint8
@@ -178,34 +193,18 @@ class BatchSolver:
         b = abi.NeoMpcWindowBatch()
         b.size_x, b.size_y, b.resolution = int(size_x), int(size_y), float(resolution)
         b.outside_value = int(outside_value)
-        if isinstance(origins, np.ndarray):
-            assert origins.dtype == np.float64 and origins.ndim == 2 and origins.shape[1] == 2 and origins.flags.c_contiguous
-            count = origins.shape[0]
-            if poses is not None:
-                poses = np.ascontiguousarray(poses, dtype=np.float64).reshape(-1, 3)
-                assert poses.shape[0] == count
-                b.poses = poses.ctypes.data
-            if problems is not None:
-                assert problems.dtype == abi.PROBLEM_DTYPE and problems.shape == (count,) and problems.flags.c_contiguous
-                b.problems = problems.ctypes.data
-            b.count = count
-            b.origins = origins.ctypes.data
-            _lib.check(self._lib.neo_mpc_roll_costmap_pool(self._handle, C.byref(b)))
-        else:
-            import torch
-            assert origins.is_cuda and origins.dtype == torch.float64 and origins.is_contiguous() and origins.shape[1] == 2
-            count = origins.shape[0]
-            if poses is not None:
-                assert poses.is_cuda and poses.dtype == torch.float64 and poses.is_contiguous() and tuple(poses.shape) == (count, 3)
-                b.poses = poses.data_ptr()
-            if problems is not None:
-                assert problems.is_cuda and problems.is_contiguous() and problems.shape[0] == count
-                b.problems = problems.data_ptr()
-            b.count = count
-            b.origins = origins.data_ptr()
+        on_host = isinstance(origins, np.ndarray)
+        origins, b.origins = self._array(origins, on_host, np.float64, (None, 2), coerce=False)
+        b.count = count = origins.shape[0]
+        if poses is not None:
+            if on_host:
+                poses = np.reshape(poses, (-1, 3))
+            poses, b.poses = self._array(poses, on_host, np.float64, (count, 3))
+        if problems is not None:
+            problems, b.problems = self._array(problems, on_host, abi.PROBLEM_DTYPE, (count,), coerce=False)
+        if not on_host:
             self._pool_origins = origins   # keep it alive
-            stream = torch.cuda.current_stream(origins.device).cuda_stream
-            _lib.check(self._lib.neo_mpc_roll_costmap_pool_device(self._handle, C.byref(b), C.c_void_p(stream)))
+        self._call("neo_mpc_roll_costmap_pool", self._stream(on_host, origins), C.byref(b))
         if count:
             self._map_shape = (int(count), int(size_y), int(size_x))
 
@@ -213,14 +212,17 @@ class BatchSolver:
         """The raw cells of maps [first, first + count) of the pool (or of the single map: a pool of one) the handle
         holds, uint8 [count, size_y, size_x] without border and pitch, and their origins, float64 [count, 2].
         Synchronous; waits for the ingest or roll in flight."""
+        return self._pool_cells(self._lib.neo_mpc_get_costmap_pool, first, count)
+
+    def _pool_cells(self, getter, first, count):
+        """Cells of the pool's shape read back through `getter`, maps [first, first + count) -> (cells, origins)."""
         assert self._map_shape is not None, "no costmap has been set through this BatchSolver"
         maps, sy, sx = self._map_shape
         if count is None:
             count = maps - first
         cells = np.zeros((count, sy, sx), dtype=np.uint8)
         origins = np.zeros((count, 2), dtype=np.float64)
-        _lib.check(self._lib.neo_mpc_get_costmap_pool(self._handle, int(first), int(count), C.c_void_p(cells.ctypes.data),
-                                                     C.c_void_p(origins.ctypes.data)))
+        _lib.check(getter(self._handle, int(first), int(count), C.c_void_p(cells.ctypes.data), C.c_void_p(origins.ctypes.data)))
         return cells, origins
 
     # -- fleet stamp (the step behind the roll) -------------------------------------------
@@ -259,12 +261,7 @@ class BatchSolver:
             for a in (polygons, footprint, poses, problems):
                 assert a is None or (a.is_cuda and a.is_contiguous())
         b.count, keep = self._outlines(b, on_host, polygons, footprint, poses, problems)
-        if on_host:
-            _lib.check(self._lib.neo_mpc_stamp_fleet(self._handle, C.byref(b)))
-        else:
-            import torch
-            stream = torch.cuda.current_stream(shape.device).cuda_stream
-            _lib.check(self._lib.neo_mpc_stamp_fleet_device(self._handle, C.byref(b), C.c_void_p(stream)))
+        self._call("neo_mpc_stamp_fleet", self._stream(on_host, shape), C.byref(b))
 
     @staticmethod
     def _outlines(rec, on_host, polygons=None, footprint=None, poses=None, problems=None, count=None):
@@ -276,15 +273,10 @@ class BatchSolver:
         keep = []
 
         def ptr(a, dims):   # (dims None: records, taken as they are)
-            if on_host:
-                a = a if dims is None else np.ascontiguousarray(a, dtype=np.float64)
-                assert a.flags.c_contiguous and (dims is None or a.ndim in dims)
-                keep.append(a)
-                return a, a.ctypes.data
-            import torch
-            assert a.is_cuda and a.is_contiguous() and (dims is None or (a.dtype == torch.float64 and a.dim() in dims))
+            a, address = BatchSolver._array(a, on_host, None if dims is None else np.float64)
+            assert dims is None or len(a.shape) in dims
             keep.append(a)
-            return a, a.data_ptr()
+            return a, address
 
         given = None
         if polygons is not None:
@@ -324,10 +316,7 @@ class BatchSolver:
         b, stream, _ = self._scan_batch(self._map_shape[0], inscribed_radius, inflation_radius, cost_scaling_factor, points,
                                         sensor_origins, point_counts, flags, obstacle_max_range, obstacle_min_range,
                                         raytrace_max_range, raytrace_min_range, unknown_value, on_device)
-        if stream is None:
-            _lib.check(self._lib.neo_mpc_update_scan_layer(self._handle, C.byref(b)))
-        else:
-            _lib.check(self._lib.neo_mpc_update_scan_layer_device(self._handle, C.byref(b), C.c_void_p(stream)))
+        self._call("neo_mpc_update_scan_layer", stream, C.byref(b))
 
     def _scan_batch(self, count, inscribed_radius, inflation_radius, cost_scaling_factor, points, sensor_origins, point_counts,
                     flags, obstacle_max_range, obstacle_min_range, raytrace_max_range, raytrace_min_range, unknown_value,
@@ -348,29 +337,14 @@ class BatchSolver:
         elif points is None and on_device is not None and on_device is not False:
             import torch
             device = torch.device("cuda", self.device) if on_device is True else torch.device(on_device)
-        if device is None:
-            if points is not None:
-                points = np.ascontiguousarray(points, dtype=np.float64)
-                sensor_origins = np.ascontiguousarray(sensor_origins, dtype=np.float64)
-                assert points.ndim == 3 and points.shape[0] == b.count and points.shape[2] == 2
-                assert sensor_origins.shape == (b.count, 2)
-                b.points, b.sensor_origins, b.max_points = points.ctypes.data, sensor_origins.ctypes.data, points.shape[1]
-                if point_counts is not None:
-                    point_counts = np.ascontiguousarray(point_counts, dtype=np.uint32)
-                    assert point_counts.shape == (b.count,)
-                    b.point_counts = point_counts.ctypes.data
-            return b, None, (points, sensor_origins, point_counts)
-        import torch
+        on_host = device is None
         if points is not None:
-            for a in (points, sensor_origins, point_counts):
-                assert a is None or (a.is_cuda and a.is_contiguous())
-            assert points.dtype == torch.float64 and points.dim() == 3 and points.shape[0] == b.count and points.shape[2] == 2
-            assert sensor_origins.dtype == torch.float64 and tuple(sensor_origins.shape) == (b.count, 2)
-            b.points, b.sensor_origins, b.max_points = points.data_ptr(), sensor_origins.data_ptr(), points.shape[1]
+            points, b.points = self._array(points, on_host, np.float64, (b.count, None, 2))
+            sensor_origins, b.sensor_origins = self._array(sensor_origins, on_host, np.float64, (b.count, 2))
+            b.max_points = points.shape[1]
             if point_counts is not None:
-                assert point_counts.dtype == torch.int32 and tuple(point_counts.shape) == (b.count,)
-                b.point_counts = point_counts.data_ptr()
-        return b, torch.cuda.current_stream(device).cuda_stream, (points, sensor_origins, point_counts)
+                point_counts, b.point_counts = self._array(point_counts, on_host, np.uint32, (b.count,))
+        return b, self._stream(on_host, device), (points, sensor_origins, point_counts)
 
     # -- the scan step fed from LaserScan ranges -----------------------------------------
     def _laser_batch(self, ranges, poses, scanners, points_out, origins_out, need_out):
@@ -379,39 +353,24 @@ class BatchSolver:
         b = abi.NeoMpcLaserBatch()
         sc = abi.scanner_array(scanners)
         b.scanners, b.sources = sc.ctypes.data, sc.shape[0]
-        if not hasattr(ranges, "data_ptr"):
-            ranges = np.ascontiguousarray(ranges, dtype=np.float32)
-            poses = np.ascontiguousarray(poses, dtype=np.float64)
-            assert ranges.ndim == 3 and ranges.shape[1] == b.sources and poses.shape == (ranges.shape[0], 3)
-            count, _, beams = ranges.shape
-            if points_out is None and need_out:
-                points_out = np.zeros((count, b.sources, beams, 2), dtype=np.float64)
-            if origins_out is None and need_out:
-                origins_out = np.zeros((count, b.sources, 2), dtype=np.float64)
-            for a, shape in ((points_out, (count, b.sources, beams, 2)), (origins_out, (count, b.sources, 2))):
-                assert a is None or (isinstance(a, np.ndarray) and a.dtype == np.float64 and a.flags.c_contiguous and a.shape == shape)
-            b.ranges, b.poses = ranges.ctypes.data, poses.ctypes.data
-            b.points_out = points_out.ctypes.data if points_out is not None else None
-            b.origins_out = origins_out.ctypes.data if origins_out is not None else None
-            stream = None
-        else:
-            import torch
-            assert ranges.is_cuda and ranges.is_contiguous() and ranges.dtype == torch.float32 and ranges.dim() == 3
-            assert ranges.shape[1] == b.sources
-            count, _, beams = ranges.shape
-            assert poses.is_cuda and poses.is_contiguous() and poses.dtype == torch.float64 and tuple(poses.shape) == (count, 3)
-            if points_out is None and need_out:
-                points_out = torch.zeros((count, b.sources, beams, 2), dtype=torch.float64, device=ranges.device)
-            if origins_out is None and need_out:
-                origins_out = torch.zeros((count, b.sources, 2), dtype=torch.float64, device=ranges.device)
-            for a, shape in ((points_out, (count, b.sources, beams, 2)), (origins_out, (count, b.sources, 2))):
-                assert a is None or (a.is_cuda and a.is_contiguous() and a.dtype == torch.float64 and tuple(a.shape) == shape)
-            b.ranges, b.poses = ranges.data_ptr(), poses.data_ptr()
-            b.points_out = points_out.data_ptr() if points_out is not None else None
-            b.origins_out = origins_out.data_ptr() if origins_out is not None else None
-            stream = torch.cuda.current_stream(ranges.device).cuda_stream
+        on_host = not hasattr(ranges, "data_ptr")
+        ranges, b.ranges = self._array(ranges, on_host, np.float32, (None, b.sources, None))
+        count, _, beams = ranges.shape
         b.count, b.beams = count, beams
-        return b, (sc, ranges, poses), points_out, origins_out, stream
+        poses, b.poses = self._array(poses, on_host, np.float64, (count, 3))
+
+        def out(a, shape):   # an output: the caller's, taken as it is, or -- where the call needs one -- a fresh one
+            if a is None and need_out:
+                if on_host:
+                    a = np.zeros(shape, dtype=np.float64)
+                else:
+                    import torch
+                    a = torch.zeros(shape, dtype=torch.float64, device=ranges.device)
+            return (None, None) if a is None else self._array(a, on_host, np.float64, shape, coerce=False)
+
+        points_out, b.points_out = out(points_out, (count, b.sources, beams, 2))
+        origins_out, b.origins_out = out(origins_out, (count, b.sources, 2))
+        return b, (sc, ranges, poses), points_out, origins_out, self._stream(on_host, ranges)
 
     def _laser_update(self, ranges, poses, scanners, points_out, origins_out, flags, unknown_value, obstacle_max_range,
                       obstacle_min_range, raytrace_max_range, raytrace_min_range, inscribed_radius, inflation_radius,
@@ -433,10 +392,7 @@ class BatchSolver:
         include/neo_mpc.h).  `scanners`: what abi.scanner_array takes, host configuration.  NumPy arrays go through the
         synchronous host call; CUDA tensors through the device call on torch's current stream.  Needs no costmap."""
         b, keep, points_out, origins_out, stream = self._laser_batch(ranges, poses, scanners, points_out, origins_out, True)
-        if stream is None:
-            _lib.check(self._lib.neo_mpc_project_laser(self._handle, C.byref(b)))
-        else:
-            _lib.check(self._lib.neo_mpc_project_laser_device(self._handle, C.byref(b), C.c_void_p(stream)))
+        self._call("neo_mpc_project_laser", stream, C.byref(b))
         return points_out, origins_out
 
     def update_scan_layer_from_ranges(self, inscribed_radius, inflation_radius, cost_scaling_factor, ranges, poses, scanners,
@@ -451,23 +407,12 @@ class BatchSolver:
         b, keep, stream = self._laser_update(ranges, poses, scanners, points_out, origins_out, flags, unknown_value,
                                              obstacle_max_range, obstacle_min_range, raytrace_max_range, raytrace_min_range,
                                              inscribed_radius, inflation_radius, cost_scaling_factor)
-        if stream is None:
-            _lib.check(self._lib.neo_mpc_update_scan_layer_from_ranges(self._handle, C.byref(b)))
-        else:
-            _lib.check(self._lib.neo_mpc_update_scan_layer_from_ranges_device(self._handle, C.byref(b), C.c_void_p(stream)))
+        self._call("neo_mpc_update_scan_layer_from_ranges", stream, C.byref(b))
 
     def get_scan_layer(self, first=0, count=None):
         """Layers [first, first + count) as the last `update_scan_layer` left them: uint8 [count, size_y, size_x] with
         values in {255, 0, 254}, and their origins, float64 [count, 2].  Synchronous; waits for the update in flight."""
-        assert self._map_shape is not None, "no costmap has been set through this BatchSolver"
-        maps, sy, sx = self._map_shape
-        if count is None:
-            count = maps - first
-        cells = np.zeros((count, sy, sx), dtype=np.uint8)
-        origins = np.zeros((count, 2), dtype=np.float64)
-        _lib.check(self._lib.neo_mpc_get_scan_layer(self._handle, int(first), int(count), C.c_void_p(cells.ctypes.data),
-                                                   C.c_void_p(origins.ctypes.data)))
-        return cells, origins
+        return self._pool_cells(self._lib.neo_mpc_get_scan_layer, first, count)
 
     def reset_scan_layer(self):
         """The next `update_scan_layer` starts from a layer of `unknown_value`."""
@@ -507,11 +452,7 @@ class BatchSolver:
                                            sensor_origins, point_counts, flags, obstacle_max_range, obstacle_min_range,
                                            raytrace_max_range, raytrace_min_range, unknown_value, on_device)
         c, keep_c = self._fleet_clear(clear, count, stream is None)
-        cp = C.byref(c) if c is not None else None
-        if stream is None:
-            _lib.check(self._lib.neo_mpc_update_world_scan_layer(self._handle, C.byref(b), cp))
-        else:
-            _lib.check(self._lib.neo_mpc_update_world_scan_layer_device(self._handle, C.byref(b), cp, C.c_void_p(stream)))
+        self._call("neo_mpc_update_world_scan_layer", stream, C.byref(b), C.byref(c) if c is not None else None)
 
     def update_world_scan_layer_from_ranges(self, inscribed_radius, inflation_radius, cost_scaling_factor, ranges, poses,
                                             scanners, flags=None, clear=None, points_out=None, origins_out=None,
@@ -524,25 +465,23 @@ class BatchSolver:
                                              obstacle_max_range, obstacle_min_range, raytrace_max_range, raytrace_min_range,
                                              inscribed_radius, inflation_radius, cost_scaling_factor)
         c, keep_c = self._fleet_clear(clear, b.count, stream is None)
-        cp = C.byref(c) if c is not None else None
-        if stream is None:
-            _lib.check(self._lib.neo_mpc_update_world_scan_layer_from_ranges(self._handle, C.byref(b), cp))
-        else:
-            _lib.check(self._lib.neo_mpc_update_world_scan_layer_from_ranges_device(self._handle, C.byref(b), cp,
-                                                                                   C.c_void_p(stream)))
+        self._call("neo_mpc_update_world_scan_layer_from_ranges", stream, C.byref(b), C.byref(c) if c is not None else None)
 
     def get_world_scan_layer(self):
         """(layer, live), uint8 [size_y, size_x] each on the world map's geometry: the fleet's shared layer, values in
         {255, 0, 254}, and the world map with the layer merged in and inflated, as the last `update_world_scan_layer` left
         them.  Synchronous; waits for the update in flight."""
-        _lib.check(self._lib.neo_mpc_get_world_scan_layer(self._handle, None, None))
+        return self._world_cells(self._lib.neo_mpc_get_world_scan_layer, np.uint8, np.uint8)
+
+    def _world_cells(self, getter, *dtypes):
+        """Cells of the world's shape read back through `getter`, one array per dtype: asks `getter` without arrays first, so
+        that what it refuses is refused before anything is made, then the world map for its size -> the arrays."""
+        _lib.check(getter(self._handle, *[None] * len(dtypes)))
         sx, sy = C.c_uint32(), C.c_uint32()
         _lib.check(self._lib.neo_mpc_get_world_map(self._handle, None, C.byref(sx), C.byref(sy), None, None, None))
-        layer = np.zeros((sy.value, sx.value), dtype=np.uint8)
-        live = np.zeros_like(layer)
-        _lib.check(self._lib.neo_mpc_get_world_scan_layer(self._handle, C.c_void_p(layer.ctypes.data),
-                                                         C.c_void_p(live.ctypes.data)))
-        return layer, live
+        cells = tuple(np.zeros((sy.value, sx.value), dtype=dtype) for dtype in dtypes)
+        _lib.check(getter(self._handle, *[C.c_void_p(a.ctypes.data) for a in cells]))
+        return cells
 
     def reset_world_scan_layer(self):
         """The next `update_world_scan_layer` starts from a layer of `unknown_value`; until then the roll reads the world
@@ -561,12 +500,7 @@ class BatchSolver:
         """uint8 [size_y, size_x] on the world map's geometry: the layer as the composition of the last
         `update_world_scan_layer` read it -- the layer itself when the filter was off.  Synchronous; waits for the update in
         flight."""
-        _lib.check(self._lib.neo_mpc_get_world_scan_denoised(self._handle, None))
-        sx, sy = C.c_uint32(), C.c_uint32()
-        _lib.check(self._lib.neo_mpc_get_world_map(self._handle, None, C.byref(sx), C.byref(sy), None, None, None))
-        cells = np.zeros((sy.value, sx.value), dtype=np.uint8)
-        _lib.check(self._lib.neo_mpc_get_world_scan_denoised(self._handle, C.c_void_p(cells.ctypes.data)))
-        return cells
+        return self._world_cells(self._lib.neo_mpc_get_world_scan_denoised, np.uint8)[0]
 
     def set_world_scan_decay(self, max_age):
         """The decay of the fleet's shared layer (K14; the contract: step 2b of neo_mpc_fleet_clear's text in
@@ -579,12 +513,7 @@ class BatchSolver:
         """uint32 [size_y, size_x] on the world map's geometry: under a mark of the layer the number of scan updates since it
         was last made (0: by the last one), `abi.NO_AGE` elsewhere, as the last `update_world_scan_layer` left them.  Refused
         when that update ran without decay.  Synchronous; waits for the update in flight."""
-        _lib.check(self._lib.neo_mpc_get_world_scan_ages(self._handle, None))
-        sx, sy = C.c_uint32(), C.c_uint32()
-        _lib.check(self._lib.neo_mpc_get_world_map(self._handle, None, C.byref(sx), C.byref(sy), None, None, None))
-        ages = np.zeros((sy.value, sx.value), dtype=np.uint32)
-        _lib.check(self._lib.neo_mpc_get_world_scan_ages(self._handle, C.c_void_p(ages.ctypes.data)))
-        return ages
+        return self._world_cells(self._lib.neo_mpc_get_world_scan_ages, np.uint32)[0]
 
     HOST_PATHS = {"auto": 0, "staged": 1, "zerocopy": 2, "zerocopy_out": 3}
 
@@ -718,46 +647,40 @@ class BatchSolver:
         carrots = np.zeros(count, dtype=abi.CARROT_DTYPE)
         lp = abi.NeoMpcLookaheadParams(lookahead_dist_min, lookahead_dist_max, lookahead_dist_close_to_goal,
                                        max_transform_dist)
-        b = abi.NeoMpcPlanBatch()
-        b.count = count
-        b.plan_poses = plan_poses.ctypes.data
-        b.plan_offsets = plan_offsets.ctypes.data
-        b.robot_poses = robot_poses.ctypes.data
         if footprint_costs is not None:
             footprint_costs = np.ascontiguousarray(footprint_costs, dtype=np.float64)
-            b.footprint_costs = footprint_costs.ctypes.data
-        b.slow_down = slow_down.ctypes.data
-        b.carrots = carrots.ctypes.data
         if problems is not None:
             assert problems.dtype == abi.PROBLEM_DTYPE and problems.flags.c_contiguous
-            b.problems = problems.ctypes.data
+        b = self._plan_batch(True, count, plan_poses, plan_offsets, robot_poses, slow_down, carrots, footprint_costs, problems)
         _lib.check(self._lib.neo_mpc_select_carrots(self._handle, C.byref(lp), C.byref(b)))
         return carrots
+
+    def _plan_batch(self, on_host, count, plan_poses, plan_offsets, robot_poses, slow_down, carrots, footprint_costs, problems):
+        """neo_mpc_plan_batch over NumPy arrays (`on_host`) or CUDA tensors."""
+        b = abi.NeoMpcPlanBatch()
+        b.count = count
+        (b.plan_poses, b.plan_offsets, b.robot_poses, b.footprint_costs, b.slow_down, b.carrots, b.problems) = self._addresses(
+            on_host, plan_poses, plan_offsets, robot_poses, footprint_costs, slow_down, carrots, problems)
+        return b
 
     def select_carrots_device(self, lp, plan_poses, plan_offsets, robot_poses, slow_down, carrots,
                               footprint_costs=None, problems=None, stream=None):
         """Device-resident variant: torch CUDA tensors; enqueues K4 on `stream`."""
-        import torch
-        b = abi.NeoMpcPlanBatch()
-        b.count = robot_poses.shape[0]
-        b.plan_poses = plan_poses.data_ptr()
-        b.plan_offsets = plan_offsets.data_ptr()
-        b.robot_poses = robot_poses.data_ptr()
-        b.footprint_costs = footprint_costs.data_ptr() if footprint_costs is not None else None
-        b.slow_down = slow_down.data_ptr()
-        b.carrots = carrots.data_ptr()
-        b.problems = problems.data_ptr() if problems is not None else None
-        if stream is None:
-            stream = torch.cuda.current_stream(robot_poses.device).cuda_stream
-        _lib.check(self._lib.neo_mpc_select_carrots_device(self._handle, C.byref(lp), C.byref(b), C.c_void_p(stream)))
+        b = self._plan_batch(False, robot_poses.shape[0], plan_poses, plan_offsets, robot_poses, slow_down, carrots,
+                             footprint_costs, problems)
+        self._call("neo_mpc_select_carrots", self._stream(False, robot_poses) if stream is None else stream, C.byref(lp),
+                   C.byref(b))
 
     # -- plan check (the fleet's plans against the live world map) -------------------------
-    @staticmethod
-    def _plan_check_batch(count, footprint_points, max_cost, unknown_blocks, outside_value, max_poses):
+    def _plan_check_batch(self, on_host, plan_poses, plan_offsets, results, robot_poses, footprint, max_cost, unknown_blocks,
+                          outside_value, max_poses):
+        """neo_mpc_plan_check_batch over NumPy arrays (`on_host`) or CUDA tensors."""
         b = abi.NeoMpcPlanCheckBatch()
-        b.count = count
-        b.footprint_points = footprint_points
+        b.count = plan_offsets.shape[0] - 1
+        b.footprint_points = footprint.shape[0] if footprint is not None else 0
         b.max_cost, b.unknown_blocks, b.outside_value, b.max_poses = int(max_cost), int(unknown_blocks), int(outside_value), int(max_poses)
+        b.plan_poses, b.plan_offsets, b.results, b.robot_poses, b.footprint = self._addresses(
+            on_host, plan_poses, plan_offsets, results, robot_poses, footprint)
         return b
 
     def check_plans(self, plan_poses, plan_offsets, robot_poses=None, footprint=None, max_cost=253, unknown_blocks=False,
@@ -770,20 +693,14 @@ class BatchSolver:
         plan_offsets = np.ascontiguousarray(plan_offsets, dtype=np.uint32)
         count = plan_offsets.shape[0] - 1
         results = np.zeros(count, dtype=abi.PLAN_CHECK_DTYPE)
-        points = 0
         if footprint is not None:
             footprint = np.ascontiguousarray(footprint, dtype=np.float64)
             assert footprint.ndim == 2 and footprint.shape[1] == 2
-            points = footprint.shape[0]
-        b = self._plan_check_batch(count, points, max_cost, unknown_blocks, outside_value, max_poses)
-        b.plan_poses = plan_poses.ctypes.data
-        b.plan_offsets = plan_offsets.ctypes.data
         if robot_poses is not None:
             robot_poses = np.ascontiguousarray(robot_poses, dtype=np.float64).reshape(-1, 3)
             assert robot_poses.shape[0] == count
-            b.robot_poses = robot_poses.ctypes.data
-        b.footprint = footprint.ctypes.data if footprint is not None else None
-        b.results = results.ctypes.data
+        b = self._plan_check_batch(True, plan_poses, plan_offsets, results, robot_poses, footprint, max_cost, unknown_blocks,
+                                   outside_value, max_poses)
         _lib.check(self._lib.neo_mpc_check_plans(self._handle, C.byref(b)))
         return results
 
@@ -792,17 +709,9 @@ class BatchSolver:
         """Device-resident variant: contiguous torch CUDA tensors (float64; `plan_offsets` [count + 1] as int32 or uint32
         bits; `results` the records as bytes, 24 a robot); enqueues K15 on `stream` (default: torch's current) and
         returns without waiting.  Capturable in a HIP graph behind one call of the same shape."""
-        import torch
-        b = self._plan_check_batch(plan_offsets.shape[0] - 1, footprint.shape[0] if footprint is not None else 0,
-                                   max_cost, unknown_blocks, outside_value, max_poses)
-        b.plan_poses = plan_poses.data_ptr()
-        b.plan_offsets = plan_offsets.data_ptr()
-        b.robot_poses = robot_poses.data_ptr() if robot_poses is not None else None
-        b.footprint = footprint.data_ptr() if footprint is not None else None
-        b.results = results.data_ptr()
-        if stream is None:
-            stream = torch.cuda.current_stream(results.device).cuda_stream
-        _lib.check(self._lib.neo_mpc_check_plans_device(self._handle, C.byref(b), C.c_void_p(stream)))
+        b = self._plan_check_batch(False, plan_poses, plan_offsets, results, robot_poses, footprint, max_cost, unknown_blocks,
+                                   outside_value, max_poses)
+        self._call("neo_mpc_check_plans", self._stream(False, results) if stream is None else stream, C.byref(b))
 
     # -- footprint gate (the step before the carrot) --------------------------------------
     def footprint_gate(self, footprint, poses=None, problems=None, map_indices=None, want_polygons=False):
@@ -815,33 +724,33 @@ class BatchSolver:
         takes -- and with `want_polygons` also the oriented polygons [count, points, 2] (`solve(footprints=...)`)."""
         footprint = np.ascontiguousarray(footprint, dtype=np.float64)
         assert footprint.ndim in (2, 3) and footprint.shape[-1] == 2
-        b = abi.NeoMpcFootprintBatch()
         if poses is not None:
             poses = np.ascontiguousarray(poses, dtype=np.float64).reshape(-1, 3)
             count = poses.shape[0]
-            b.poses = poses.ctypes.data
         else:
             assert problems is not None, "poses or problems"
             count = problems.shape[0]
         if problems is not None:
             assert problems.dtype == abi.PROBLEM_DTYPE and problems.shape == (count,) and problems.flags.c_contiguous
-            b.problems = problems.ctypes.data
         if map_indices is not None:
             map_indices = np.ascontiguousarray(map_indices, dtype=np.int32)
             assert map_indices.shape == (count,)
-            b.map_indices = map_indices.ctypes.data
         assert footprint.ndim == 2 or footprint.shape[0] == count
-        points = footprint.shape[-2]
         costs = np.zeros(count, dtype=np.float64)
-        polygons = np.zeros((count, points, 2), dtype=np.float64) if want_polygons else None
-        b.count = count
-        b.footprint = footprint.ctypes.data
-        b.footprint_points = points
-        b.per_robot_footprints = 1 if footprint.ndim == 3 else 0
-        b.footprint_costs = costs.ctypes.data
-        b.footprints_out = polygons.ctypes.data if want_polygons else None
+        polygons = np.zeros((count, footprint.shape[-2], 2), dtype=np.float64) if want_polygons else None
+        b = self._footprint_batch(True, footprint, costs, poses, problems, map_indices, polygons)
         _lib.check(self._lib.neo_mpc_footprint_gate(self._handle, C.byref(b)))
         return (costs, polygons) if want_polygons else costs
+
+    def _footprint_batch(self, on_host, footprint, footprint_costs, poses, problems, map_indices, footprints_out):
+        """neo_mpc_footprint_batch over NumPy arrays (`on_host`) or CUDA tensors."""
+        b = abi.NeoMpcFootprintBatch()
+        b.count = footprint_costs.shape[0]
+        b.footprint_points = footprint.shape[-2]
+        b.per_robot_footprints = 1 if len(footprint.shape) == 3 else 0
+        b.footprint, b.poses, b.map_indices, b.problems, b.footprint_costs, b.footprints_out = self._addresses(
+            on_host, footprint, poses, map_indices, problems, footprint_costs, footprints_out)
+        return b
 
     def footprint_gate_device(self, footprint, footprint_costs, poses=None, problems=None, map_indices=None,
                               footprints_out=None, stream=None):
@@ -849,20 +758,8 @@ class BatchSolver:
         records as bytes); enqueues K6 on `stream` (default: torch's current) and returns without waiting.
         `footprint_costs` [count] and the optional `footprints_out` [count, points, 2] are written; `footprint` is
         [points, 2] or [count, points, 2]."""
-        import torch
-        b = abi.NeoMpcFootprintBatch()
-        b.count = footprint_costs.shape[0]
-        b.footprint = footprint.data_ptr()
-        b.footprint_points = footprint.shape[-2]
-        b.per_robot_footprints = 1 if footprint.dim() == 3 else 0
-        b.poses = poses.data_ptr() if poses is not None else None
-        b.map_indices = map_indices.data_ptr() if map_indices is not None else None
-        b.problems = problems.data_ptr() if problems is not None else None
-        b.footprint_costs = footprint_costs.data_ptr()
-        b.footprints_out = footprints_out.data_ptr() if footprints_out is not None else None
-        if stream is None:
-            stream = torch.cuda.current_stream(footprint_costs.device).cuda_stream
-        _lib.check(self._lib.neo_mpc_footprint_gate_device(self._handle, C.byref(b), C.c_void_p(stream)))
+        b = self._footprint_batch(False, footprint, footprint_costs, poses, problems, map_indices, footprints_out)
+        self._call("neo_mpc_footprint_gate", self._stream(False, footprint_costs) if stream is None else stream, C.byref(b))
 
     # -- device-resident batches (torch tensors as plain device memory) ----------------
     def balance_dispatch(self, commands, stream=None):

@@ -10,7 +10,7 @@ import numpy as np
 import pytest
 
 from neo_mpc_planner2_amd import _lib, abi
-from tests.c_probe import kernel_resources, run_c_probe
+from tests.c_probe import check_layout, kernel_resources, probe_header
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HEADER = os.path.join(ROOT, "include", "neo_mpc.h")
@@ -36,44 +36,33 @@ def test_library_exports_every_declared_symbol():
     assert "#define NEO_MPC_ABI_VERSION 2" in header and "#define NEO_MPC_BEHAVIOUR_VERSION 6" in header
 
 
+def declared_structs():
+    text = re.sub(r"/\*.*?\*/", "", open(HEADER).read(), flags=re.S)
+    return sorted(set(re.findall(r"\bstruct\s+(neo_mpc_[a-z_]+)\s*\{", text)))
+
+
+@pytest.mark.parametrize("c_name", declared_structs())
+def test_record_layout_matches_the_header(tmp_path, c_name):
+    """Every struct the header declares with a body is in abi.RECORDS, and there every field of it sits where the header puts
+    it, in the ctypes mirror and in the NumPy one; the sizes are the header's, the mirrors' and the registry's literal.  One
+    probe a record: a field the header does not have fails its own record's case, by name."""
+    assert len(declared_structs()) >= 17 and sorted(abi.RECORDS) == declared_structs()
+    check_layout(probe_header(tmp_path, [c_name]), c_name, abi.RECORDS[c_name].size)
+
+
 def test_record_layouts_match_the_header(tmp_path):
-    got = run_c_probe(tmp_path, r'''
-#include <stdio.h>
-#include <stddef.h>
-#include "neo_mpc.h"
-#define P(t, f) printf(#t "." #f " %zu\n", offsetof(t, f))
-int main(void) {
-  printf("sizeof.params %zu\nsizeof.problem %zu\nsizeof.state %zu\nsizeof.command %zu\nsizeof.batch %zu\n",
-         sizeof(neo_mpc_params), sizeof(neo_mpc_problem), sizeof(neo_mpc_state), sizeof(neo_mpc_command),
-         sizeof(neo_mpc_batch));
-  P(neo_mpc_params, control_steps); P(neo_mpc_params, step_tolerance); P(neo_mpc_params, kink_radius); P(neo_mpc_params, stall_step); P(neo_mpc_params, method); P(neo_mpc_params, window_tolerance);
-  P(neo_mpc_problem, carrot_xy); P(neo_mpc_problem, goal_xyz); P(neo_mpc_problem, cur_vel);
-  P(neo_mpc_problem, control_interval); P(neo_mpc_problem, footprint_cost); P(neo_mpc_problem, map_index);
-  P(neo_mpc_problem, switch_opt); P(neo_mpc_problem, skip);
-  P(neo_mpc_state, old_goal); P(neo_mpc_state, waiting_time); P(neo_mpc_state, has_old_goal);
-  P(neo_mpc_state, collision_footprint); P(neo_mpc_state, has_prev_u0); P(neo_mpc_state, prev_u0);
-  P(neo_mpc_command, cost); P(neo_mpc_command, status); P(neo_mpc_command, flags);
-  P(neo_mpc_batch, footprints); P(neo_mpc_batch, footprint_points); P(neo_mpc_batch, velocities);
-  return 0;
-}''')
-    got = {k: int(v) for k, v in got.items()}
-    assert got["sizeof.params"] == C.sizeof(abi.NeoMpcParams)
-    assert got["sizeof.problem"] == abi.PROBLEM_DTYPE.itemsize == 256
-    assert got["sizeof.state"] == abi.STATE_DTYPE.itemsize == 128
-    assert got["sizeof.command"] == abi.COMMAND_DTYPE.itemsize == 48
-    assert got["sizeof.batch"] == C.sizeof(abi.NeoMpcBatch)
-    for f in ("control_steps", "step_tolerance", "kink_radius", "stall_step", "method", "window_tolerance"):
-        assert got["neo_mpc_params." + f] == getattr(abi.NeoMpcParams, f).offset
-    for f in ("carrot_xy", "goal_xyz", "cur_vel", "control_interval", "footprint_cost", "map_index", "switch_opt", "skip"):
-        assert got["neo_mpc_problem." + f] == abi.PROBLEM_DTYPE.fields[f][1]
-    for f in ("old_goal", "waiting_time", "has_old_goal", "collision_footprint", "has_prev_u0", "prev_u0"):
-        assert got["neo_mpc_state." + f] == abi.STATE_DTYPE.fields[f][1]
+    got = probe_header(tmp_path, ["neo_mpc_params", "neo_mpc_problem", "neo_mpc_state", "neo_mpc_command", "neo_mpc_batch",
+                                  "neo_mpc_carrot", "neo_mpc_lookahead_params", "neo_mpc_plan_batch"])
+    check_layout(got, "neo_mpc_params", 232, struct=abi.NeoMpcParams)
+    check_layout(got, "neo_mpc_problem", 256, dtype=abi.PROBLEM_DTYPE)
+    check_layout(got, "neo_mpc_state", 128, dtype=abi.STATE_DTYPE)
+    check_layout(got, "neo_mpc_command", 48, dtype=abi.COMMAND_DTYPE)
+    check_layout(got, "neo_mpc_batch", 80, struct=abi.NeoMpcBatch)
+    check_layout(got, "neo_mpc_carrot", 80, dtype=abi.CARROT_DTYPE)
+    check_layout(got, "neo_mpc_lookahead_params", 32, struct=abi.NeoMpcLookaheadParams)
+    check_layout(got, "neo_mpc_plan_batch", 64, struct=abi.NeoMpcPlanBatch)
     # (round 5: the build's one hint lives where ABI 1 had reserved bytes -- the last 28 of the record, same size)
     assert got["neo_mpc_state.has_prev_u0"] == 100 and got["neo_mpc_state.prev_u0"] == 104
-    for f in ("cost", "status", "flags"):
-        assert got["neo_mpc_command." + f] == abi.COMMAND_DTYPE.fields[f][1]
-    for f in ("footprints", "footprint_points", "velocities"):
-        assert got["neo_mpc_batch." + f] == getattr(abi.NeoMpcBatch, f).offset
 
 
 def test_default_params_are_the_reference_nodes_declared_defaults():

@@ -10,7 +10,6 @@ cannot move a cell."""
 import ctypes as C
 import functools
 import math
-import re
 
 import numpy as np
 import pytest
@@ -19,7 +18,7 @@ from neo_mpc_planner2_amd import _lib, abi, synthetic
 from tests import fleet_stamp_reference as ref
 from tests import footprint_gate_reference as gate_ref
 from tests import rolling_window_reference as roll_ref
-from tests.c_probe import HEADER, run_c_probe
+from tests.c_probe import check_entry_points, check_layout, probe_header
 from tests.fleet_kit import RECT, Side, capture_fleet, gpu, replay_against_direct, standing_fleet
 
 ENTRY_POINTS = ("neo_mpc_stamp_fleet", "neo_mpc_stamp_fleet_device", "neo_mpc_inflation_costs")
@@ -90,24 +89,10 @@ def test_the_fast_transcription_equals_the_definition():
 
 # ------------------------------------------------------------------------------------------ 2: record and entry points
 def test_stamp_batch_layout_and_entry_points(tmp_path):
-    fields = [f for f, _ in abi.NeoMpcStampBatch._fields_]
-    got = run_c_probe(tmp_path, '#include <stdio.h>\n#include <stddef.h>\n#include "neo_mpc.h"\n'
-                      '#define P(f) printf(#f " %zu\\n", offsetof(neo_mpc_stamp_batch, f))\n'
-                      'int main(void) {\n  printf("sizeof %zu\\n", sizeof(neo_mpc_stamp_batch));\n'
-                      '  printf("cells %d\\n", NEO_MPC_MAX_INFLATION_CELLS);\n'
-                      + "".join("  P(%s);\n" % f for f in fields) +
-                      '  void* volatile f[3] = {' + ", ".join("(void*)%s" % n for n in ENTRY_POINTS) + '};\n'
-                      '  return f[0] == 0 || f[1] == 0 || f[2] == 0;\n}\n')
-    got = {k: int(v) for k, v in got.items()}
-    assert got["sizeof"] == C.sizeof(abi.NeoMpcStampBatch) == 80
-    assert got["cells"] == abi.MAX_INFLATION_CELLS == 64
-    for f in fields:
-        assert got[f] == getattr(abi.NeoMpcStampBatch, f).offset, f
-    text = re.sub(r"/\*.*?\*/", "", open(HEADER).read(), flags=re.S)
-    for name in ENTRY_POINTS:
-        assert re.search(r"\bint %s\s*\(" % name, text), name
-        assert name in _lib.EXPORTS and hasattr(_lib.load(), name)
-    assert "#define NEO_MPC_ABI_VERSION 2" in text and "#define NEO_MPC_BEHAVIOUR_VERSION 6" in text
+    got = probe_header(tmp_path, ["neo_mpc_stamp_batch"], ["MAX_INFLATION_CELLS"], ENTRY_POINTS)
+    check_layout(got, "neo_mpc_stamp_batch", 80, struct=abi.NeoMpcStampBatch)
+    assert got["MAX_INFLATION_CELLS"] == abi.MAX_INFLATION_CELLS == 64 and len(ENTRY_POINTS) == 3
+    check_entry_points(ENTRY_POINTS)
 
 
 # ------------------------------------------------------------------------------------------ 3: the cost table

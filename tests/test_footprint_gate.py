@@ -11,14 +11,13 @@ condition on the inputs (fixed seeds), not a tolerance; no robot is dropped."""
 import ctypes as C
 import functools
 import math
-import re
 
 import numpy as np
 import pytest
 
 from neo_mpc_planner2_amd import _lib, abi, synthetic
 from tests import footprint_gate_reference as ref
-from tests.c_probe import HEADER, run_c_probe
+from tests.c_probe import check_entry_points, check_layout, probe_header
 from tests.fleet_kit import RECT, gpu
 
 RES = synthetic.RESOLUTION
@@ -77,22 +76,10 @@ def test_closed_form_equals_the_iterative_walk_exhaustively():
 
 
 def test_footprint_batch_layout_and_entry_points(tmp_path):
-    fields = [f for f, _ in abi.NeoMpcFootprintBatch._fields_]
-    got = run_c_probe(tmp_path, '#include <stdio.h>\n#include <stddef.h>\n#include "neo_mpc.h"\n'
-                      '#define P(f) printf(#f " %zu\\n", offsetof(neo_mpc_footprint_batch, f))\n'
-                      'int main(void) {\n  printf("sizeof %zu\\n", sizeof(neo_mpc_footprint_batch));\n'
-                      + "".join("  P(%s);\n" % f for f in fields) +
-                      '  void* volatile f[2] = {(void*)neo_mpc_footprint_gate, (void*)neo_mpc_footprint_gate_device};\n'
-                      '  return f[0] == 0 || f[1] == 0;\n}\n')
-    got = {k: int(v) for k, v in got.items()}
-    assert got["sizeof"] == C.sizeof(abi.NeoMpcFootprintBatch) == 64
-    for f in fields:
-        assert got[f] == getattr(abi.NeoMpcFootprintBatch, f).offset, f
-    text = re.sub(r"/\*.*?\*/", "", open(HEADER).read(), flags=re.S)
-    for name in ("neo_mpc_footprint_gate", "neo_mpc_footprint_gate_device"):
-        assert re.search(r"\bint %s\s*\(" % name, text), name
-        assert name in _lib.EXPORTS and hasattr(_lib.load(), name)
-    assert "#define NEO_MPC_ABI_VERSION 2" in text and "#define NEO_MPC_BEHAVIOUR_VERSION 6" in text
+    entry_points = ("neo_mpc_footprint_gate", "neo_mpc_footprint_gate_device")
+    got = probe_header(tmp_path, ["neo_mpc_footprint_batch"], entry_points=entry_points)
+    check_layout(got, "neo_mpc_footprint_batch", 64, struct=abi.NeoMpcFootprintBatch)
+    check_entry_points(entry_points)
 
 
 # ------------------------------------------------------------------------------------------ shared GPU inputs

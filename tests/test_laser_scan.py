@@ -10,7 +10,6 @@ bit: the layer update is fed with the points the device produced."""
 import ctypes as C
 import functools
 import math
-import re
 
 import numpy as np
 import pytest
@@ -18,7 +17,7 @@ import pytest
 from neo_mpc_planner2_amd import _lib, abi
 from tests import laser_scan_reference as ref
 from tests import scan_layer_reference as scan_ref
-from tests.c_probe import HEADER, run_c_probe
+from tests.c_probe import check_entry_points, check_layout, probe_header
 from tests.fleet_kit import F32, RECT, Side, capture_fleet, gpu, inflation_for, replay_against_direct, same, scanner, standing_fleet, window_state
 
 ENTRY_POINTS = ("neo_mpc_laser_beam_table", "neo_mpc_project_laser", "neo_mpc_project_laser_device",
@@ -77,31 +76,12 @@ def test_beam_table_equals_the_transcription(beams):
 
 # ------------------------------------------------------------------------------------------ 3: records and entry points
 def test_laser_records_layout_and_entry_points(tmp_path):
-    records = (("neo_mpc_scanner", abi.NeoMpcScanner, abi.SCANNER_DTYPE, 64),
-               ("neo_mpc_laser_batch", abi.NeoMpcLaserBatch, abi.LASER_BATCH_DTYPE, 128))
-    body = ""
-    for name, struct, _, _ in records:
-        body += '  printf("sizeof_%s %%zu\\n", sizeof(%s));\n' % (name, name)
-        body += "".join('  printf("%s.%s %%zu\\n", offsetof(%s, %s));\n' % (name, f, name, f) for f, _ in struct._fields_)
-    got = run_c_probe(tmp_path, '#include <stdio.h>\n#include <stddef.h>\n#include "neo_mpc.h"\nint main(void) {\n' + body +
-                      '  printf("MAX_SCAN_SOURCES %u\\n", NEO_MPC_MAX_SCAN_SOURCES);\n'
-                      '  printf("LASER_INF_IS_VALID %u\\n", NEO_MPC_LASER_INF_IS_VALID);\n'
-                      '  void* volatile f[5] = {' + ", ".join("(void*)%s" % n for n in ENTRY_POINTS) + '};\n'
-                      '  return f[0] == 0 || f[1] == 0 || f[2] == 0 || f[3] == 0 || f[4] == 0;\n}\n')
-    got = {k: int(v) for k, v in got.items()}
-    for name, struct, dtype, size in records:
-        fields = [f for f, _ in struct._fields_]
-        assert got["sizeof_" + name] == C.sizeof(struct) == dtype.itemsize == size
-        assert list(dtype.names) == fields
-        for f in fields:
-            assert got["%s.%s" % (name, f)] == getattr(struct, f).offset == dtype.fields[f][1], (name, f)
+    got = probe_header(tmp_path, ["neo_mpc_scanner", "neo_mpc_laser_batch"], ["MAX_SCAN_SOURCES", "LASER_INF_IS_VALID"], ENTRY_POINTS)
+    check_layout(got, "neo_mpc_scanner", 64, struct=abi.NeoMpcScanner, dtype=abi.SCANNER_DTYPE)
+    check_layout(got, "neo_mpc_laser_batch", 128, struct=abi.NeoMpcLaserBatch, dtype=abi.LASER_BATCH_DTYPE)
     assert got["MAX_SCAN_SOURCES"] == abi.MAX_SCAN_SOURCES == 4 and got["LASER_INF_IS_VALID"] == abi.LASER_INF_IS_VALID == 1
-    text = re.sub(r"/\*.*?\*/", "", open(HEADER).read(), flags=re.S)
-    for name in ENTRY_POINTS:
-        assert re.search(r"\bint %s\s*\(" % name, text), name
-        assert name in _lib.EXPORTS and hasattr(_lib.load(), name)
-    assert "#define NEO_MPC_ABI_VERSION 2" in text and "#define NEO_MPC_BEHAVIOUR_VERSION 6" in text
-    assert _lib.load().neo_mpc_abi_version() == 2 and _lib.load().neo_mpc_behaviour_version() == 6
+    assert len(ENTRY_POINTS) == 5
+    check_entry_points(ENTRY_POINTS)
 
 
 # ------------------------------------------------------------------------------------------ 4: clear before mark, two scanners

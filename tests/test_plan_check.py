@@ -13,7 +13,6 @@ Point mode needs no such condition: the plan poses are kept clear of the edges b
 import ctypes as C
 import functools
 import math
-import re
 
 import numpy as np
 import pytest
@@ -22,7 +21,7 @@ from neo_mpc_planner2_amd import _lib, abi, synthetic
 from tests import footprint_gate_reference as fref
 from tests import plan_check_reference as ref
 from tests import world_scan_layer_reference as wref
-from tests.c_probe import HEADER, run_c_probe
+from tests.c_probe import check_entry_points, check_layout, probe_header
 from tests.fleet_kit import F32, RECT, capture, eager_on_side_stream, gpu, pairs_fleet
 
 R = ref.record
@@ -137,29 +136,13 @@ def test_transcription_on_hand_worked_maps():
 
 
 def test_plan_check_layout_and_entry_points(tmp_path):
-    batch = [f for f, _ in abi.NeoMpcPlanCheckBatch._fields_]
-    result = [f for f, _ in abi.NeoMpcPlanCheck._fields_]
-    got = run_c_probe(tmp_path, '#include <stdio.h>\n#include <stddef.h>\n#include "neo_mpc.h"\n'
-                      '#define B(f) printf("b_" #f " %zu\\n", offsetof(neo_mpc_plan_check_batch, f))\n'
-                      '#define Q(f) printf("r_" #f " %zu\\n", offsetof(neo_mpc_plan_check, f))\n'
-                      'int main(void) {\n  printf("sizeof_b %zu\\n", sizeof(neo_mpc_plan_check_batch));\n'
-                      '  printf("sizeof_r %zu\\n", sizeof(neo_mpc_plan_check));\n'
-                      + "".join("  B(%s);\n" % f for f in batch) + "".join("  Q(%s);\n" % f for f in result) +
-                      '  void* volatile f[2] = {(void*)neo_mpc_check_plans, (void*)neo_mpc_check_plans_device};\n'
-                      '  return f[0] == 0 || f[1] == 0;\n}\n')
-    got = {k: int(v) for k, v in got.items()}
-    assert got["sizeof_b"] == C.sizeof(abi.NeoMpcPlanCheckBatch) == 72
-    assert got["sizeof_r"] == C.sizeof(abi.NeoMpcPlanCheck) == abi.PLAN_CHECK_DTYPE.itemsize == 24
-    for f in batch:
-        assert got["b_" + f] == getattr(abi.NeoMpcPlanCheckBatch, f).offset, f
-    for f in result:
-        assert got["r_" + f] == getattr(abi.NeoMpcPlanCheck, f).offset == abi.PLAN_CHECK_DTYPE.fields[f][1], f
+    entry_points = ("neo_mpc_check_plans", "neo_mpc_check_plans_device")
+    got = probe_header(tmp_path, ["neo_mpc_plan_check_batch", "neo_mpc_plan_check"], entry_points=entry_points)
+    check_layout(got, "neo_mpc_plan_check_batch", 72, struct=abi.NeoMpcPlanCheckBatch)
+    check_layout(got, "neo_mpc_plan_check", 24, struct=abi.NeoMpcPlanCheck, dtype=abi.PLAN_CHECK_DTYPE)
+    result = abi.PLAN_CHECK_DTYPE.names
     assert len(result) == 6 and all(abi.PLAN_CHECK_DTYPE.fields[f][0].itemsize == 4 for f in result)
-    text = re.sub(r"/\*.*?\*/", "", open(HEADER).read(), flags=re.S)
-    for name in ("neo_mpc_check_plans", "neo_mpc_check_plans_device"):
-        assert re.search(r"\bint %s\s*\(" % name, text), name
-        assert name in _lib.EXPORTS and hasattr(_lib.load(), name)
-    assert "#define NEO_MPC_ABI_VERSION 2" in text and "#define NEO_MPC_BEHAVIOUR_VERSION 6" in text
+    check_entry_points(entry_points)
 
 
 @pytest.mark.gpu

@@ -6,14 +6,13 @@ identically on both sides, so every comparison with the transcription is exact e
 origins: no tolerance, no dropped case, no condition on the inputs."""
 import ctypes as C
 import functools
-import re
 
 import numpy as np
 import pytest
 
 from neo_mpc_planner2_amd import _lib, abi, synthetic
 from tests import rolling_window_reference as ref
-from tests.c_probe import HEADER, run_c_probe
+from tests.c_probe import check_entry_points, check_layout, probe_header
 from tests.fleet_kit import RECT, Side, capture_fleet, gpu, replay_against_direct
 
 WRES = synthetic.RESOLUTION
@@ -54,22 +53,10 @@ def test_transcription_on_a_hand_worked_map():
 
 # ------------------------------------------------------------------------------------------ 2: record and entry points
 def test_window_batch_layout_and_entry_points(tmp_path):
-    fields = [f for f, _ in abi.NeoMpcWindowBatch._fields_]
-    got = run_c_probe(tmp_path, '#include <stdio.h>\n#include <stddef.h>\n#include "neo_mpc.h"\n'
-                      '#define P(f) printf(#f " %zu\\n", offsetof(neo_mpc_window_batch, f))\n'
-                      'int main(void) {\n  printf("sizeof %zu\\n", sizeof(neo_mpc_window_batch));\n'
-                      + "".join("  P(%s);\n" % f for f in fields) +
-                      '  void* volatile f[5] = {' + ", ".join("(void*)%s" % n for n in ENTRY_POINTS) + '};\n'
-                      '  return f[0] == 0 || f[1] == 0 || f[2] == 0 || f[3] == 0 || f[4] == 0;\n}\n')
-    got = {k: int(v) for k, v in got.items()}
-    assert got["sizeof"] == C.sizeof(abi.NeoMpcWindowBatch) == 56
-    for f in fields:
-        assert got[f] == getattr(abi.NeoMpcWindowBatch, f).offset, f
-    text = re.sub(r"/\*.*?\*/", "", open(HEADER).read(), flags=re.S)
-    for name in ENTRY_POINTS:
-        assert re.search(r"\bint %s\s*\(" % name, text), name
-        assert name in _lib.EXPORTS and hasattr(_lib.load(), name)
-    assert "#define NEO_MPC_ABI_VERSION 2" in text and "#define NEO_MPC_BEHAVIOUR_VERSION 6" in text
+    got = probe_header(tmp_path, ["neo_mpc_window_batch"], entry_points=ENTRY_POINTS)
+    check_layout(got, "neo_mpc_window_batch", 56, struct=abi.NeoMpcWindowBatch)
+    assert len(ENTRY_POINTS) == 5
+    check_entry_points(ENTRY_POINTS)
 
 
 # ------------------------------------------------------------------------------------------ shared GPU inputs

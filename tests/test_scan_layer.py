@@ -8,17 +8,16 @@ transcription is exact equality of uint8 cells and float64 origins -- no toleran
 import collections
 import ctypes as C
 import functools
-import re
 
 import numpy as np
 import pytest
 
-from neo_mpc_planner2_amd import _lib, abi
+from neo_mpc_planner2_amd import abi
 from tests import fleet_stamp_reference as stamp_ref
 from tests import footprint_gate_reference as gate_ref
 from tests import rolling_window_reference as roll_ref
 from tests import scan_layer_reference as ref
-from tests.c_probe import HEADER, run_c_probe
+from tests.c_probe import check_entry_points, check_layout, probe_header
 from tests.fleet_kit import RECT, Side, capture_fleet, gpu, inflation_for, replay_against_direct, same, standing_fleet, window_state
 from tests.world_scan_cases import distance_64_case
 
@@ -78,26 +77,11 @@ def test_the_line_walk_on_a_hand_worked_map():
 
 # ------------------------------------------------------------------------------------------ 2: record and entry points
 def test_scan_batch_layout_and_entry_points(tmp_path):
-    fields = [f for f, _ in abi.NeoMpcScanBatch._fields_]
-    got = run_c_probe(tmp_path, '#include <stdio.h>\n#include <stddef.h>\n#include "neo_mpc.h"\n'
-                      '#define P(f) printf(#f " %zu\\n", offsetof(neo_mpc_scan_batch, f))\n'
-                      'int main(void) {\n  printf("sizeof %zu\\n", sizeof(neo_mpc_scan_batch));\n'
-                      '  printf("MAX_SCAN_POINTS %u\\n", NEO_MPC_MAX_SCAN_POINTS);\n'
-                      '  printf("SCAN_CLEAR %u\\n", NEO_MPC_SCAN_CLEAR);\n  printf("SCAN_MARK %u\\n", NEO_MPC_SCAN_MARK);\n'
-                      + "".join("  P(%s);\n" % f for f in fields) +
-                      '  void* volatile f[4] = {' + ", ".join("(void*)%s" % n for n in ENTRY_POINTS) + '};\n'
-                      '  return f[0] == 0 || f[1] == 0 || f[2] == 0 || f[3] == 0;\n}\n')
-    got = {k: int(v) for k, v in got.items()}
-    assert got["sizeof"] == C.sizeof(abi.NeoMpcScanBatch) == abi.SCAN_BATCH_DTYPE.itemsize == 104
+    got = probe_header(tmp_path, ["neo_mpc_scan_batch"], ["MAX_SCAN_POINTS", "SCAN_CLEAR", "SCAN_MARK"], ENTRY_POINTS)
+    check_layout(got, "neo_mpc_scan_batch", 104, struct=abi.NeoMpcScanBatch, dtype=abi.SCAN_BATCH_DTYPE)
     assert got["MAX_SCAN_POINTS"] == abi.MAX_SCAN_POINTS == 8192 and got["SCAN_CLEAR"] == abi.SCAN_CLEAR == 1 and got["SCAN_MARK"] == abi.SCAN_MARK == 2
-    assert list(abi.SCAN_BATCH_DTYPE.names) == fields
-    for f in fields:
-        assert got[f] == getattr(abi.NeoMpcScanBatch, f).offset == abi.SCAN_BATCH_DTYPE.fields[f][1], f
-    text = re.sub(r"/\*.*?\*/", "", open(HEADER).read(), flags=re.S)
-    for name in ENTRY_POINTS:
-        assert re.search(r"\bint %s\s*\(" % name, text), name
-        assert name in _lib.EXPORTS and hasattr(_lib.load(), name)
-    assert "#define NEO_MPC_ABI_VERSION 2" in text and "#define NEO_MPC_BEHAVIOUR_VERSION 6" in text
+    assert len(ENTRY_POINTS) == 4
+    check_entry_points(ENTRY_POINTS)
 
 
 # ------------------------------------------------------------------------------------------ the generator

@@ -12,18 +12,17 @@ import collections
 import ctypes as C
 import functools
 import math
-import re
 
 import numpy as np
 import pytest
 
-from neo_mpc_planner2_amd import _lib, abi
+from neo_mpc_planner2_amd import abi
 from tests import fleet_stamp_reference as stamp_ref
 from tests import rolling_window_reference as roll_ref
 from tests import scan_layer_reference as scan_ref
 from tests import world_inflation_reference as world_ref
 from tests import world_scan_layer_reference as ref
-from tests.c_probe import HEADER, run_c_probe
+from tests.c_probe import check_entry_points, check_layout, probe_header
 from tests.fleet_kit import (F32, RECT, Side, capture_fleet, gpu, inflation_for, pairs_fleet, rectangle, replay_against_direct,
                              rolled_pool, same, scanner, world_scan_callback, world_state)
 from tests.world_scan_cases import UPDATE_FLAGS, WORLDS, case, distance_64_case, expected, ranges_for
@@ -98,24 +97,10 @@ def test_the_two_forms_of_the_clearing_rule_agree_and_take_every_branch():
 
 # ------------------------------------------------------------------------------------------ 3: record and entry points
 def test_fleet_clear_layout_and_entry_points(tmp_path):
-    fields = [f for f, _ in abi.NeoMpcFleetClear._fields_]
-    got = run_c_probe(tmp_path, '#include <stdio.h>\n#include <stddef.h>\n#include "neo_mpc.h"\n'
-                      '#define P(f) printf(#f " %zu\\n", offsetof(neo_mpc_fleet_clear, f))\n'
-                      'int main(void) {\n  printf("sizeof %zu\\n", sizeof(neo_mpc_fleet_clear));\n'
-                      + "".join("  P(%s);\n" % f for f in fields) +
-                      '  void* volatile f[6] = {' + ", ".join("(void*)%s" % n for n in ENTRY_POINTS) + '};\n'
-                      '  return f[0] == 0 || f[1] == 0 || f[2] == 0 || f[3] == 0 || f[4] == 0 || f[5] == 0;\n}\n')
-    got = {k: int(v) for k, v in got.items()}
-    assert got["sizeof"] == C.sizeof(abi.NeoMpcFleetClear) == abi.FLEET_CLEAR_DTYPE.itemsize == 64
-    assert list(abi.FLEET_CLEAR_DTYPE.names) == fields
-    for f in fields:
-        assert got[f] == getattr(abi.NeoMpcFleetClear, f).offset == abi.FLEET_CLEAR_DTYPE.fields[f][1], f
-    text = re.sub(r"/\*.*?\*/", "", open(HEADER).read(), flags=re.S)
-    for name in ENTRY_POINTS:
-        assert re.search(r"\bint %s\s*\(" % name, text), name
-        assert name in _lib.EXPORTS and hasattr(_lib.load(), name)
-    assert "#define NEO_MPC_ABI_VERSION 2" in text and "#define NEO_MPC_BEHAVIOUR_VERSION 6" in text
-    assert _lib.load().neo_mpc_abi_version() == 2 and _lib.load().neo_mpc_behaviour_version() == 6
+    got = probe_header(tmp_path, ["neo_mpc_fleet_clear"], entry_points=ENTRY_POINTS)
+    check_layout(got, "neo_mpc_fleet_clear", 64, struct=abi.NeoMpcFleetClear, dtype=abi.FLEET_CLEAR_DTYPE)
+    assert len(ENTRY_POINTS) == 6
+    check_entry_points(ENTRY_POINTS)
 
 
 # ------------------------------------------------------------------------------------------ the generator has teeth
