@@ -1,6 +1,9 @@
 // dense_newton.h -- the dense projected-Newton direction of K1 (control_steps <= 8: a system of at most 24 x 24).
 //
-// In: hc = column `lane` of the smooth part's Hessian (finite differences of the adjoint gradient, k_solve), the reduced
+// NEO_DENSE_NEWTON_HESSIAN_PASS: the gradient pass of this direction -- every lane runs the rollout and the reverse sweep on
+// a copy of the iterate of its own, lane k < 3N with coordinate k perturbed: one pass yields the smooth part's gradient and
+// the 3N columns of its Hessian by forward differences.  dense_newton_direction: the system those columns feed.
+// In: hc = column `lane` of the smooth part's Hessian (finite differences of the adjoint gradient, above), the reduced
 // gradient gr and the face records the tangent-cone pass wrote (tangent_cone.h: projector P and block curvature C per
 // control block).  The system H_r = P (H + C) P + (I - P) is built column-wise then row-wise through LDS, eliminated with
 // the rows in registers (pivot row by v_readlane, float32: it only yields a search direction -- the arc search and the
@@ -10,11 +13,92 @@
 #pragma once
 #include "neo_mpc_device.h"
 #include "wave_ops.h"
+#include "fast_math.h"
+#include "solver_context.h"
 #include "tangent_cone.h"
 
 namespace neo_mpc {
 namespace {
 
+// ---- the gradient pass of the dense direction: the smooth part's gradient and its Hessian by forward differences.
+// Reads: the iterate u (LDS); dt, the tracking and terminal weights (p) and the carrot and yaw targets (c), in registers;
+// the loop's opaque lane index; n.
+// Leaves: the gradient of the smooth part in gs (LDS, written by lane 63); column `lane` of the Hessian in hc (registers,
+// float32, an array of kVars = 3 * kNwSteps; zero beyond the run-time size); the wave synchronised behind the write of gs.
+// Its own locals (hcol, pcs, psn, the rollout's state) end with it.
+// A MACRO, expanded in solve_search (k1_solve.h), not a function: as a __forceinline__ function, in six shapes of its
+// operands, as an ordinary inline function and with its arrays and barrier left in the caller, the pass changed the opcode
+// counts of every kernel with a dense branch (21 of the 36 K1 variants; docs/NOTEBOOK.md A.29) -- the inliner puts a
+// function's locals in front of the caller's, and the later passes go another way.  Expanded as text the kernels are
+// instruction for instruction what they were.  Its instructions count under the line that expands it (tools/).
+// (comments inside are block comments: a line comment would swallow the continuation)
+#define NEO_DENSE_NEWTON_HESSIAN_PASS(kSteps, kNwSteps, kTame, kVars, p, c, u, gs, hc, lane, n)                        \
+  {                                                                                                                    \
+  double hcol[kSteps ? kVars : 1];  /* control_steps specialisation: gradient of this lane's perturbed copy */         \
+  /* Every lane runs the rollout + adjoint sweep on its own copy of u: lane k < 3N perturbs */                         \
+  /* coordinate k by h, the other lanes leave u alone.  One pass therefore yields the gradient */                      \
+  /* (any unperturbed lane) and all 3N Hessian columns by forward differences -- the sweep */                          \
+  /* costs the same whether the lanes agree or not. */                                                                 \
+  const double hstep = 1e-6, inv_h = 1.0 / hstep;                                                                      \
+  /* forward: keep only sin/cos per step; the reverse pass rebuilds increments and residuals */                        \
+  /* while it unwinds x, y, theta (fewer live registers -> one more wave per SIMD) */                                  \
+  double pcs[kNwSteps], psn[kNwSteps];                                                                                 \
+  double x = 0.0, y = 0.0, th = 0.0;                                                                                   \
+  _Pragma("unroll")                                                                                                    \
+  for (int i = 0; i < kNwSteps; ++i) {                                                                                 \
+    if (kSteps || i < n) {                                                                                             \
+      const double vx = u[3 * i] + (lane == 3 * i ? hstep : 0.0);                                                      \
+      const double vy = u[3 * i + 1] + (lane == 3 * i + 1 ? hstep : 0.0);                                              \
+      const double w = u[3 * i + 2] + (lane == 3 * i + 2 ? hstep : 0.0);                                               \
+      th += w * p.dt;                                                                                                  \
+      sincos_heading<kTame>(th, &psn[i], &pcs[i]);                                                                     \
+      x += (vx * pcs[i] - vy * psn[i]) * p.dt;                                                                         \
+      y += (vx * psn[i] + vy * pcs[i]) * p.dt;                                                                         \
+    }                                                                                                                  \
+  }                                                                                                                    \
+  double SX = 0.0, SY = 0.0, ST = 0.0;                                                                                 \
+  _Pragma("unroll")                                                                                                    \
+  for (int k = kNwSteps - 1; k >= 0; --k) {                                                                            \
+    if (kSteps || k < n) {                                                                                             \
+      const double vx = u[3 * k] + (lane == 3 * k ? hstep : 0.0);                                                      \
+      const double vy = u[3 * k + 1] + (lane == 3 * k + 1 ? hstep : 0.0);                                              \
+      const double w = u[3 * k + 2] + (lane == 3 * k + 2 ? hstep : 0.0);                                               \
+      const double pdx = (vx * pcs[k] - vy * psn[k]) * p.dt, pdy = (vx * psn[k] + vy * pcs[k]) * p.dt;                 \
+      double prt = -2.0 * p.wo_n * (c.tyaw - th);                                                                      \
+      if (k == n - 1) prt += -2.0 * p.wterm_o * (c.fyaw - th);                                                         \
+      SX += -2.0 * p.wt_n * (c.cx - x); SY += -2.0 * p.wt_n * (c.cy - y);                                              \
+      ST += prt - pdy * SX + pdx * SY;                                                                                 \
+      /* gradient entries of this lane's copy; the unperturbed lane 63 supplies the gradient itself */                 \
+      /* and the base of the forward difference */                                                                     \
+      const double g0 = p.dt * (pcs[k] * SX + psn[k] * SY), g1 = p.dt * (-psn[k] * SX + pcs[k] * SY),                  \
+                   g2 = p.dt * ST;                                                                                     \
+      if (kSteps) {  /* (few variables: differencing after the sweep schedules better) */                              \
+        hcol[3 * k] = g0; hcol[3 * k + 1] = g1; hcol[3 * k + 2] = g2;                                                  \
+      } else {       /* (up to 24: difference at once, no second register array) */                                    \
+        const double b0 = lane_value(g0, 63), b1 = lane_value(g1, 63), b2 = lane_value(g2, 63);                        \
+        if (lane == 63) { gs[3 * k] = b0; gs[3 * k + 1] = b1; gs[3 * k + 2] = b2; }                                    \
+        hc[3 * k] = (float)((g0 - b0) * inv_h);                                                                        \
+        hc[3 * k + 1] = (float)((g1 - b1) * inv_h);                                                                    \
+        hc[3 * k + 2] = (float)((g2 - b2) * inv_h);                                                                    \
+      }                                                                                                                \
+      x -= pdx; y -= pdy; th -= w * p.dt;                                                                              \
+    } else {                                                                                                           \
+      hc[3 * k] = 0.0f; hc[3 * k + 1] = 0.0f; hc[3 * k + 2] = 0.0f;                                                    \
+    }                                                                                                                  \
+  }                                                                                                                    \
+  if (kSteps) {                                                                                                        \
+    _Pragma("unroll")                                                                                                  \
+    for (int j = 0; j < kVars; ++j) {                                                                                  \
+      const double base = lane_value(hcol[j], 63);                                                                     \
+      if (lane == 63) gs[j] = base;                                                                                    \
+      hc[j] = (float)((hcol[j] - base) * inv_h);                                                                       \
+    }                                                                                                                  \
+  }                                                                                                                    \
+  WAVE_SYNC();                                                                                                         \
+  }
+
+// ---- the dense system (header of this file).  Reads: hc (registers), gr and the face records (LDS).  Leaves: d (LDS)
+// and, returned, this lane's entry of it; hc is used up.
 template <int kSteps, int kNwSteps, bool kTame>
 __device__ __forceinline__ float dense_newton_direction(const SolveArgs& a, double* L, float (&hc)[3 * kNwSteps], bool corner_any,
                                                         int lane, int n, int nvr) {

@@ -1,5 +1,5 @@
-// k1_solve.h -- K1 of the batched MPC solver, gfx950 (CDNA4 / MI355X): k_solve, k_solve_routed, their phase functions
-// and the helper that launches them.  Part of libneo_mpc.so's device code; each of the two units that include it holds
+// k1_solve.h -- K1 of the batched MPC solver, gfx950 (CDNA4 / MI355X): k_solve, k_solve_routed, the outline of their
+// phases and the helper that launches them.  Part of libneo_mpc.so's device code; each of the two units that include it holds
 // the variants it launches: neo_mpc_kernels.hip the dense-Newton and L-BFGS ones, neo_mpc_riccati.hip the rest.
 //
 //   K1 k_solve        one 64-lane wavefront per instance.  Per iteration the wave
@@ -19,6 +19,14 @@
 //                     sqrt(eps); MI355X has full-rate vector f64); the Newton systems themselves
 //                     are float32 (they only yield a direction).
 // No MFMA: a 3*control_steps-variable problem has no dense contraction.
+//
+// Where what is:
+//   k1_variant.h   K1Variant<...>: a kernel's template parameters and every constant derived from them, once; fresh_args
+//                  and the other helpers by which a phase gets its operands afresh.
+//   dense_newton.h the dense direction: its gradient pass (NEO_DENSE_NEWTON_HESSIAN_PASS, expanded in solve_search) and its system.
+//   this file      solve_setup, solve_search, solve_finish, the search's LDS pointers (search_lds), what the kernels start
+//                  with (NEO_K1_PROLOGUE: solve_lds, solve_instance), the kernels, and the preamble the two dispatch
+//                  tables share (K1Launch).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <hip/hip_ext.h>
@@ -40,97 +48,12 @@
 #include "dense_newton.h"
 #include "lbfgs.h"
 #include "cell_scan.h"
+#include "k1_variant.h"
 #include "k1_timing.h"
 
 namespace neo_mpc {
 namespace {
 
-// (the stop rules and their constants: solver_rules.h, shared with the host side and with the CPU mirror)
-// largest control_steps the run-time-sized Newton kernel takes (a 24 x 24 system: rows in registers)
-constexpr int kNewtonMaxSteps = 8;
-
-// ---------------------------------------------------------------- K1: phases
-// K1 runs in phases -- set-up, search, cell scan, K2 -- and the search can be taken up again behind the scan.  Each phase
-// starts from a FRESH copy of the launch arguments (re-read from the kernarg segment through a pointer the compiler cannot
-// see through) and of the per-instance constants (re-read from the tolerance block of LDS, where the set-up leaves them): the
-// vector-register residents of the solver loop are then dead outside it.  Allocated as ONE live range across the scan they
-// came out spilled -- and reloaded from scratch inside the loop, +20 % on a C2 launch for code that runs once per solve.
-// kRouted: the stage-wise branch of the routed control_steps-3 kernel (k_solve_routed).  Its LDS carve-up is the stage-wise
-// one for three stages laid INSIDE the dense kernel's (records, tolerance block, term table, iterate and gradients sit at the
-// same offsets in both; the reach tile stays where the set-up staged it), control_steps is the constant 3 -- the run-time-sized
-// code below folds to three stages -- and the prox-only zone around the kink is the stage-wise direction's.
-constexpr int kRoutedSteps = 3;
-constexpr LdsLayout make_routed_stagewise_layout() {
-  LdsLayout l = make_lds_layout(kRoutedSteps, 0, true, true);
-  constexpr LdsLayout dense = make_lds_layout(kRoutedSteps, 4, false);
-  l.tile = dense.tile;
-  l.total_bytes = dense.total_bytes;
-  return l;
-}
-static_assert(make_lds_layout(kRoutedSteps, 0, true, true).tile <= make_lds_layout(kRoutedSteps, 4, false).tile,
-              "the stage-wise arrays of three stages fit in front of the dense kernel's reach tile");
-static_assert(make_lds_layout(kRoutedSteps, 0, true, true).gr == make_lds_layout(kRoutedSteps, 4, false).gr,
-              "records, iterate and gradients share their offsets");
-template <int kSteps, int kStaticTile, int kLayoutSteps, bool kRouted = false>
-__device__ __forceinline__ void fresh_args(SolveArgs& a) {
-  auto kp = (const __attribute__((address_space(4))) char*)__builtin_amdgcn_kernarg_segment_ptr();   // (k_solve's only argument: offset 0)
-  asm volatile("" : "+s"(kp));
-  a = *(const SolveArgs*)kp;
-  if (kRouted) {
-    constexpr LdsLayout kLayout = make_routed_stagewise_layout();
-    const int tile_w = a.lds.tile_w, tile_h = a.lds.tile_h, reach = a.lds.reach;
-    a.lds = kLayout;
-    a.lds.tile_w = tile_w; a.lds.tile_h = tile_h; a.lds.reach = reach;
-    a.p.n = kRoutedSteps;
-  } else if (kSteps || kStaticTile) {  // compile-time LDS offsets (lbfgs_memory is 4 in the specialisations' layout)
-    constexpr LdsLayout kStaticLayout = make_lds_layout(kLayoutSteps, kSteps ? 4 : 0, false);
-    const int tile_w = a.lds.tile_w, tile_h = a.lds.tile_h, reach = a.lds.reach;
-    a.lds = kStaticLayout;
-    a.lds.tile_w = tile_w; a.lds.tile_h = tile_h; a.lds.reach = reach;
-    if (kSteps) a.p.n = kSteps;
-  }
-}
-// The parameters the solver loop reads are detached from the wide scalar loads that bring the
-// kernel arguments in: a spilled s_load_dwordx16 tuple comes back whole (16 v_readlane) for every
-// use of one of its members; as values of their own they are reloaded pair by pair.
-__device__ __forceinline__ void own_loop_params(SolveArgs& a) {
-  auto own = [](double& v) { asm volatile("" : "+s"(v)); };
-  own(a.p.dt); own(a.p.wt_n); own(a.p.wo_n); own(a.p.wc_n); own(a.p.wterm_o); own(a.p.r);
-  own(a.p.lo[2]); own(a.p.hi[2]);
-  own(a.map.origin_x); own(a.map.origin_y); own(a.map.resolution); own(a.map.inv_resolution);
-}
-// the per-instance constants as the set-up left them in LDS (request record + tolerance block); wave-uniform: scalar
-// registers -- except, kVectorPose, the four the costmap lookup of every stage of every candidate needs (k_solve says why)
-template <bool kVectorPose>
-__device__ __forceinline__ void ctx_from_lds(const SolveArgs& a, const double* L, Ctx& c) {
-  const double* P = L + a.lds.prob;
-  const double* t = L + a.lds.tol;
-  c.cx = lane_value(P[P_CARROT_X], 0); c.cy = lane_value(P[P_CARROT_Y], 0);
-  c.tyaw = lane_value(t[T_TYAW], 0); c.fyaw = lane_value(t[T_FYAW], 0);
-  c.v0 = lane_value(P[P_VEL], 0); c.v1 = lane_value(P[P_VEL + 1], 0); c.v2 = lane_value(P[P_VEL + 2], 0);
-  c.c0 = t[T_C0]; c.s0 = t[T_S0]; c.X0 = P[P_CUR_X]; c.Y0 = P[P_CUR_Y];
-  if (kVectorPose) asm volatile("" : "+v"(c.c0), "+v"(c.s0), "+v"(c.X0), "+v"(c.Y0));
-  else { c.c0 = lane_value(c.c0, 0); c.s0 = lane_value(c.s0, 0); c.X0 = lane_value(c.X0, 0); c.Y0 = lane_value(c.Y0, 0); }
-  const int* ti = reinterpret_cast<const int*>(t + T_TILE);
-  c.tile_x0 = uniform_int(ti[0]); c.tile_y0 = uniform_int(ti[1]); c.tile_geom = uniform_int(ti[2]);
-  c.konst = 0.0; c.true_yaw = 0.0;   // (inside the search f excludes the constant terms; K2 reads both from the block)
-}
-
-// ---------------------------------------------------------------- K1: template parameters of the phase functions and the kernels
-// kSteps > 0: specialisation for control_steps == kSteps -- every lane keeps its candidate's controls and sin/cos in
-// registers, so the winner is stored without being recomputed and the next adjoint sweep needs no trigonometry.
-// kSteps == 0: any control_steps (LDS-only path).
-// kDir: search direction of lanes 32-63 -- 0 projected L-BFGS, 1 projected Newton with the dense system: control_steps ==
-// kSteps, or with kSteps == 0 any control_steps <= kNewtonMaxSteps (measured against L-BFGS on the 1000^2 map, 65 536
-// instances: +28 % at control_steps 1, +54 % at 2, +50 % at 4, +38 % at 5-7, +42 % at 8), 2 projected Newton solved stage by
-// stage (riccati.h; kSteps == 0 only, any control_steps).
-// kTame: instantiation for parameter sets (the README's among them) whose max_vel_trans disc lies inside the vx/vy box --
-// the box/disc corner cases of the projection and of the tangent cone drop out -- and whose heading cannot leave
-// [-pi/4, pi/4] within the horizon -- no range reduction in the rollout's sin/cos.
-// kStaticTile > 0: LDS is a static array sized for the compile-time layout plus a reach
-// tile of at most kStaticTile bytes -- every LDS address is then an instruction immediate instead of a
-// "dynamic LDS base + offset" value that lives in (and gets spilled from) a scalar register.
-// kRouted: the stage-wise branch of k_solve_routed (fresh_args).  kMinWavesPerSimd: the occupancy a variant is built for.
 // What the phases hand to one another in registers (everything else goes through LDS).
 struct SolveCarry {
   int flags;                 // NEO_MPC_FLAG_RESET (set-up -> K2)
@@ -143,14 +66,15 @@ struct SolveCarry {
 // ---- phase 0: set-up.  Records, reset, footprint, reach tile; the per-instance constants and the stop tolerances go to
 //      the tolerance block of LDS (layout: solver_context.h), where every later phase reads them; x0.
 //      Returns false when the instance makes no request this tick (nothing more to do).
-template <int kSteps, bool kTame, int kStaticTile, int kLayoutSteps>
+template <class V>
 __device__ __forceinline__ bool solve_setup(double* L, uint32_t b, int lane, SolveCarry& s) {
-  constexpr bool kCovered = kStaticTile > 0;   // the reach tile is there and covers every lookup (costmap.h cell_raw)
+  constexpr int kSteps = V::kSteps;
+  constexpr bool kTame = V::kTame;
   int flags;
   bool cold = true;
   {
     SolveArgs a;
-    fresh_args<kSteps, kStaticTile, kLayoutSteps>(a);
+    fresh_args<V>(a);
     const DevParams& p = a.p;
     const int n = kSteps ? kSteps : p.n, nv = 3 * n;
     load_records(a, L, b, lane);
@@ -219,7 +143,7 @@ __device__ __forceinline__ bool solve_setup(double* L, uint32_t b, int lane, Sol
     if (!cold && n > 1 && !(p.compat & kCompatNoUnshift) && p.max_it < kDumpGradient) {   // (not in the test hooks: they dump AT the given point)
       const double* A0 = L + a.lds.state + S_PREV_U0;
       double ts = 0.0;
-      const double fs = rollout_cost<kSteps, kTame, kCovered>(
+      const double fs = rollout_cost<kSteps, kTame, V::kCovered>(
           a, c, L,
           [&](int i, double& b0, double& b1, double& b2) {
             const double* src = lane == 1 ? (i == 0 ? A0 : u + 3 * (i - 1)) : u + 3 * i;
@@ -248,44 +172,42 @@ __device__ __forceinline__ bool solve_setup(double* L, uint32_t b, int lane, Sol
   return true;
 }
 
+// ---- the search's arrays in LDS (layout: solver_context.h)
+struct SearchLds {
+  double *u, *gs, *gt, *gr, *d, *u_prev, *gt_prev, *u_new, *ACS, *ASN;
+  int* AMODE;  // [4n]: mode, wfroz, near, near_prev
+};
+__device__ __forceinline__ SearchLds search_lds(const SolveArgs& a, double* L) {
+  SearchLds m;
+  m.u = L + a.lds.u;
+  m.gs = L + a.lds.gs;
+  m.gt = L + a.lds.gt;
+  m.gr = L + a.lds.gr;
+  m.d = L + a.lds.d;
+  m.u_prev = L + a.lds.u_prev;
+  m.gt_prev = L + a.lds.gt_prev;
+  m.u_new = L + a.lds.u_new;
+  m.ACS = L + a.lds.cs;
+  m.ASN = L + a.lds.sn;
+  m.AMODE = reinterpret_cast<int*>(L + a.lds.mode);
+  return m;
+}
+
 // ---- phases 1 and 2: the search, the cell scan behind it, and the search once more behind a scan that paid.
-// Template parameters: above.  Returns true when a test hook has dumped what it was asked for (the kernel ends there).
-template <int kMinWavesPerSimd, int kSteps, int kDir, bool kTame, int kStaticTile, int kLayoutSteps, bool kRouted = false>
+// The phases of an iteration are text here, between the NEO_PHASE marks: each was tried as a function of its own, and each
+// changed the kernels' code (docs/NOTEBOOK.md A.29 has the counts).  Returns true when a test hook has dumped what it was
+// asked for (the kernel ends there).
+// (tools/: the lines between the two K1-SEARCH-LOOP marks are what the static tables call "the loop", and they find the
+// routed kernel's two searches by the K1-ROUTED-*-SEARCH marks)
+template <class V>
 __device__ __forceinline__ bool solve_search(double* L, uint32_t b, SolveCarry& sc) {
-  constexpr bool kCovered = kStaticTile > 0;   // the reach tile is there and covers every lookup (costmap.h cell_raw)
-  constexpr bool kNewton = kDir == 1;    // dense system in registers
-  constexpr bool kRiccati = kDir == 2;   // stage-wise recursion
-  constexpr bool kSecond = kDir != 0;    // either: Newton stop rules, no quasi-Newton state
-  // the control_steps-3 stop rules of the dense direction -- the window rule on every run of three iterations, the blocked-run
-  // rule, closing-in behind two blocked iterations -- also end the stage-wise searches of the routed kernel: what ends a search
-  // depends on the horizon, not on how the direction was computed (solver_rules.h neo_rules_derive_routed)
-  constexpr bool kBlockedRule = kNewton || kRouted;
-  static_assert(!kRiccati || kSteps == 0 || kRouted, "the stage-wise direction: run-time-sized, or the routed kernel's control_steps-3 branch");
-  static_assert(!kRouted || (kRiccati && kSteps == kRoutedSteps), "the routed branch is the stage-wise one, three stages in registers");
-  // (kSteps > 0 with the stage-wise direction -- the routed branch: candidates in registers, unrolled rollouts, the winner
-  // stored without being recomputed like the dense specialisation; gradient and sweep run lane = stage on three lanes)
-  constexpr int kFew = (kRiccati && kSteps > 0) ? kSteps : 0;
-  // three stages: the sweep hands each lane its own stage's step in registers, riccati_finish writes d once and hands the
-  // step test its maximum (riccati.h SweepHandOff); the tame kernels, which never sweep twice with another active set, also
-  // know each stage's case as a scalar before the sweep starts
-  constexpr bool kHandOff = kFew > 0;
-  constexpr bool kScalarCase = kFew > 0 && kTame;
-  // ... and, sweeping once per iteration, keep the sweep's gains in registers from its backward to its forward half
-  constexpr bool kKeepGains = kFew > 0 && kTame;
-  // ... and lane = stage fetches what the tangent-cone pass reads of its block at the END of the adjoint pass (adjoint.h)
-  constexpr bool kStageCarry = kFew > 0 && kTame;
-  constexpr bool kAcceptFetch = kFew > 0 && kTame;
-  // Newton: control_steps == kSteps, or (kSteps == 0) any control_steps <= kNewtonMaxSteps -- the
-  // system's arrays are sized for the bound and every loop over them is guarded by the run-time size
-  constexpr int kNwSteps = !kNewton ? 1 : kSteps ? kSteps : kNewtonMaxSteps;
-  // the four constants the costmap lookup of every stage of every candidate needs (world position = X0 + Rot(psi0) (x, y))
-  // stay in VECTOR registers (every lane holds the same value).  The scalar file is over-subscribed -- a hundred
-  // scalars are spilled to vector lanes -- and each use of a spilled pair costs two v_readlane and a wait state: twelve
-  // lane reads per stage.  (Round 4: the three-address polynomial kernels freed nine vector registers.)
-  // (the general kernels have no vector register to spare at four waves per SIMD: scalar there, as before)
-  constexpr bool kVectorPose = kTame;
-  constexpr int kRegSteps = kSteps ? kSteps : 1;
-  constexpr int kPairs = kSteps ? 4 : NEO_MPC_MAX_LBFGS_MEMORY;  // specialisations: lbfgs_memory <= 4
+  // (the variant's constants under the names the text below has always used; what each means: K1Variant.  A bridge while
+  // the phases are text of this function: a phase that becomes a function takes V itself, and its names leave this list)
+  constexpr int kMinWavesPerSimd = V::kMinWavesPerSimd, kSteps = V::kSteps, kFew = V::kFew, kNwSteps = V::kNwSteps;
+  constexpr int kVars = V::kVars, kRegSteps = V::kRegSteps, kPairs = V::kPairs;
+  constexpr bool kTame = V::kTame, kRouted = V::kRouted, kCovered = V::kCovered, kNewton = V::kNewton, kRiccati = V::kRiccati;
+  constexpr bool kSecond = V::kSecond, kBlockedRule = V::kBlockedRule, kHandOff = V::kHandOff, kFewTame = V::kFewTame;
+  constexpr bool kVectorPose = V::kVectorPose;
   double f = sc.f;
   const bool cold = sc.cold;
   // ---- what the search carries from one iteration to the next -- and across the cell scan when it is taken up again
@@ -297,20 +219,12 @@ __device__ __forceinline__ bool solve_search(double* L, uint32_t b, SolveCarry& 
   bool scanned = false;   // the cell scan has had its turn (cell_scan.h)
   int nscans = 0;         // ... scans of its round so far: a scan that found a cheaper cell is followed by another from the new point
   bool scan_only = false; // this pass of the loop below only scans again
-  // (the lane index is not kept in a register across the loop -- the stage-wise kernels at four waves per SIMD parked it in
-  // scratch and reloaded it at the top of every iteration: it is re-derived from the hardware's lane mask count, seeded
-  // with an opaque zero so that the compiler cannot hoist it either)
-  auto lane_again = []() {
-    int zero;
-    asm volatile("v_mov_b32 %0, 0" : "=v"(zero));
-    return (int)__builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, (unsigned)zero));
-  };
   NEO_SEGMENT_DECL;
   NEO_SEGMENT(0);
   for (;;) {   // (the search; taken up again behind a cell scan that paid)
   // ---- phase 1: the search
   SolveArgs a;
-  fresh_args<kSteps, kStaticTile, kLayoutSteps, kRouted>(a);
+  fresh_args<V>(a);
   own_loop_params(a);
   select_map(a.map, L + a.lds.prob);
   const DevParams& p = a.p;
@@ -319,24 +233,10 @@ __device__ __forceinline__ bool solve_search(double* L, uint32_t b, SolveCarry& 
   bool have_trig = false;  // ACS/ASN already hold sin/cos of the rollout at u
   Ctx c;
   ctx_from_lds<kVectorPose>(a, L, c);
-  double* u = L + a.lds.u;
-  double* gs = L + a.lds.gs;
-  double* gt = L + a.lds.gt;
-  double* gr = L + a.lds.gr;
-  double* d = L + a.lds.d;
-  double* u_prev = L + a.lds.u_prev;
-  double* gt_prev = L + a.lds.gt_prev;
-  double* u_new = L + a.lds.u_new;
-  double* ACS = L + a.lds.cs;
-  double* ASN = L + a.lds.sn;
-  int* AMODE = reinterpret_cast<int*>(L + a.lds.mode);  // [4n]: mode, wfroz, near, near_prev
-  // Newton: one float32 record per control block (projector + block curvature), written by the
-  // tangent-cone pass; it lives in the cs..rt step arrays, which the Newton kernel does not use
-  static_assert(2 * 7 >= kNewtonRecord, "Newton records do not fit the step arrays");
-
+  const SearchLds m = search_lds(a, L);
   if (!scanned && nscans == 0) {
     const int lane = lane_again();
-    for (int i = lane; i < n; i += kLanes) { AMODE[4 * i + 2] = 0; AMODE[4 * i + 3] = 0; }
+    for (int i = lane; i < n; i += kLanes) { m.AMODE[4 * i + 2] = 0; m.AMODE[4 * i + 3] = 0; }
     // (routed stage-wise branch: this direction's prox-only zone around the kink -- the set-up wrote the dense direction's)
     if (kRouted && lane == 0) L[a.lds.tol + T_KINK] = p.kink_radius_stagewise;
     // Long horizons (Riccati direction): the curvature of a block falls with 1/N^2, so the proximal step starts
@@ -367,7 +267,7 @@ __device__ __forceinline__ bool solve_search(double* L, uint32_t b, SolveCarry& 
     int l0 = lane_again();
     my_scale = kRiccati ? 0.0 : lane_scale<kSecond>(l0);
   }
-  for (; it < p.max_it && !scan_only; ++it) {
+  for (; it < p.max_it && !scan_only; ++it) {   // K1-SEARCH-LOOP-BEGIN
     // The lane index is re-read opaquely every iteration: otherwise the compiler hoists two dozen
     // lane-derived constants (step multipliers, compare masks, LDS addresses) out of the loop and,
     // at 4 waves/SIMD, parks them in scratch -- recomputing them costs a few integer operations.
@@ -382,7 +282,6 @@ __device__ __forceinline__ bool solve_search(double* L, uint32_t b, SolveCarry& 
     NEO_PHASE_DECL;
     NEO_PHASE(0);
     // ---- adjoint gradient of the tracking + terminal cost
-    constexpr int kVars = 3 * kNwSteps;  // compile-time bound of the Newton system (= its size when kSteps > 0)
     const int nvr = kSteps ? kVars : nv;  // its size
     bool free_path = false;   // Riccati: every stage of the rollout at u sits in a free cell (raw cost 0)
     int nhops = 0;            // Riccati: hop candidates of this iteration (wave-uniform; the table is in the tolerance block)
@@ -390,76 +289,14 @@ __device__ __forceinline__ bool solve_search(double* L, uint32_t b, SolveCarry& 
     float newton_sol = 0.0f;  // Newton: entry `lane` of the direction
     float dm_reg = 0.0f;                // kHandOff: the step test's maximum over this lane's three entries of d (riccati_finish)
     int near_reg = 0;                   // ... and the near word of the lane's stage
-    StageCarry carry = {};              // kStageCarry: the cone pass' operands, fetched at the adjoint pass' end
-    if (kNewton) {
-      double hcol[kSteps ? kVars : 1];  // control_steps specialisation: gradient of this lane's perturbed copy
-      // Every lane runs the rollout + adjoint sweep on its own copy of u: lane k < 3N perturbs
-      // coordinate k by h, the other lanes leave u alone.  One pass therefore yields the gradient
-      // (any unperturbed lane) and all 3N Hessian columns by forward differences -- the sweep
-      // costs the same whether the lanes agree or not.
-      const double hstep = 1e-6, inv_h = 1.0 / hstep;
-      // forward: keep only sin/cos per step; the reverse pass rebuilds increments and residuals
-      // while it unwinds x, y, theta (fewer live registers -> one more wave per SIMD)
-      double pcs[kNwSteps], psn[kNwSteps];
-      double x = 0.0, y = 0.0, th = 0.0;
-    #pragma unroll
-      for (int i = 0; i < kNwSteps; ++i) {
-        if (kSteps || i < n) {
-          const double vx = u[3 * i] + (lane == 3 * i ? hstep : 0.0);
-          const double vy = u[3 * i + 1] + (lane == 3 * i + 1 ? hstep : 0.0);
-          const double w = u[3 * i + 2] + (lane == 3 * i + 2 ? hstep : 0.0);
-          th += w * p.dt;
-          sincos_heading<kTame>(th, &psn[i], &pcs[i]);
-          x += (vx * pcs[i] - vy * psn[i]) * p.dt;
-          y += (vx * psn[i] + vy * pcs[i]) * p.dt;
-        }
-      }
-      double SX = 0.0, SY = 0.0, ST = 0.0;
-    #pragma unroll
-      for (int k = kNwSteps - 1; k >= 0; --k) {
-        if (kSteps || k < n) {
-          const double vx = u[3 * k] + (lane == 3 * k ? hstep : 0.0);
-          const double vy = u[3 * k + 1] + (lane == 3 * k + 1 ? hstep : 0.0);
-          const double w = u[3 * k + 2] + (lane == 3 * k + 2 ? hstep : 0.0);
-          const double pdx = (vx * pcs[k] - vy * psn[k]) * p.dt, pdy = (vx * psn[k] + vy * pcs[k]) * p.dt;
-          double prt = -2.0 * p.wo_n * (c.tyaw - th);
-          if (k == n - 1) prt += -2.0 * p.wterm_o * (c.fyaw - th);
-          SX += -2.0 * p.wt_n * (c.cx - x); SY += -2.0 * p.wt_n * (c.cy - y);
-          ST += prt - pdy * SX + pdx * SY;
-          // gradient entries of this lane's copy; the unperturbed lane 63 supplies the gradient itself
-          // and the base of the forward difference
-          const double g0 = p.dt * (pcs[k] * SX + psn[k] * SY), g1 = p.dt * (-psn[k] * SX + pcs[k] * SY),
-                       g2 = p.dt * ST;
-          if (kSteps) {  // (few variables: differencing after the sweep schedules better)
-            hcol[3 * k] = g0; hcol[3 * k + 1] = g1; hcol[3 * k + 2] = g2;
-          } else {       // (up to 24: difference at once, no second register array)
-            const double b0 = lane_value(g0, 63), b1 = lane_value(g1, 63), b2 = lane_value(g2, 63);
-            if (lane == 63) { gs[3 * k] = b0; gs[3 * k + 1] = b1; gs[3 * k + 2] = b2; }
-            hc[3 * k] = (float)((g0 - b0) * inv_h);
-            hc[3 * k + 1] = (float)((g1 - b1) * inv_h);
-            hc[3 * k + 2] = (float)((g2 - b2) * inv_h);
-          }
-          x -= pdx; y -= pdy; th -= w * p.dt;
-        } else {
-          hc[3 * k] = 0.0f; hc[3 * k + 1] = 0.0f; hc[3 * k + 2] = 0.0f;
-        }
-      }
-      if (kSteps) {
-    #pragma unroll
-        for (int j = 0; j < kVars; ++j) {
-          const double base = lane_value(hcol[j], 63);
-          if (lane == 63) gs[j] = base;
-          hc[j] = (float)((hcol[j] - base) * inv_h);
-        }
-      }
-      WAVE_SYNC();
-    }
-    else if (!kSteps || kRiccati) adjoint_by_scans<kTame, kRiccati, kFew, kCovered>(a, c, L, exact_step, lane, n, free_path, nhops, kStageCarry ? &carry : nullptr);
+    StageCarry carry = {};              // kFewTame: the cone pass' operands, fetched at the adjoint pass' end
+    if (kNewton) { NEO_DENSE_NEWTON_HESSIAN_PASS(kSteps, kNwSteps, kTame, kVars, p, c, m.u, m.gs, hc, lane, n); }   // (dense_newton.h)
+    else if (!kSteps || kRiccati) adjoint_by_scans<kTame, kRiccati, kFew, kCovered>(a, c, L, exact_step, lane, n, free_path, nhops, kFewTame ? &carry : nullptr);
     else adjoint_short_sweep<kSteps, kTame>(a, c, L, have_trig, lane, n);
     NEO_PHASE(1);
     // ---- total gradient (control norm: minimal-norm subgradient at the kink), tangent-cone reduction at active bounds,
     //      face records of the second-order directions (tangent_cone.h)
-    const bool my_corner = tangent_cone_pass<kTame, kNewton, kRiccati>(a, c, L, TOL[T_KINK], lane, n, kStageCarry ? &carry : nullptr);
+    const bool my_corner = tangent_cone_pass<kTame, kNewton, kRiccati>(a, c, L, TOL[T_KINK], lane, n, kFewTame ? &carry : nullptr);
     WAVE_SYNC();
     // (in free space only -- no costmap term under the iterate's rollout: next to a cost step the Newton model is off either
     // way; the dense kernel knows that sum from the previous iteration's winner)
@@ -468,28 +305,28 @@ __device__ __forceinline__ bool solve_search(double* L, uint32_t b, SolveCarry& 
     if (p.max_it == kDumpGradient) {
       // test hook (neo_mpc_gradient_batch): hand back the total gradient this kernel variant works with at
       // the projected x0 -- adjoint gradient of the smooth part + gradient of the control norm -- and stop
-      for (int k = lane; k < nv; k += kLanes) a.solution[(size_t)b * nv + k] = gt[k];
+      for (int k = lane; k < nv; k += kLanes) a.solution[(size_t)b * nv + k] = m.gt[k];
       return true;
     }
     if (kSecond && it == 0 && cold) {
       // a cold start (x0 = 0, the reference's reset state py:359) is far from the minimiser and the
       // Newton step almost never wins there: steepest descent on the face for this one iteration
-      if (kRiccati) { for (int k = lane; k < nv; k += kLanes) d[k] = -gr[k]; }
-      else if (lane < nvr) d[lane] = -gr[lane];
-      if (kRiccati) for (int i = lane; i < n; i += kLanes) AMODE[4 * i + 3] = 0;
+      if (kRiccati) { for (int k = lane; k < nv; k += kLanes) m.d[k] = -m.gr[k]; }
+      else if (lane < nvr) m.d[lane] = -m.gr[lane];
+      if (kRiccati) for (int i = lane; i < n; i += kLanes) m.AMODE[4 * i + 3] = 0;
       WAVE_SYNC();
     } else if (kRiccati) {
       const int my_flags = riccati_prepare(a, c, L, n, lane, v_feasible, (float)TOL[T_MU]);
       // (the stages' cases as scalars: the sweep's switch does not wait for the record, its conversion and a lane read)
       int stage_flags[kFew ? kFew : 1] = {};
-      if (kScalarCase) {
+      if (kFewTame) {
         for (int i = 0; i < kFew; ++i) stage_flags[i] = __builtin_amdgcn_readlane(my_flags, i);
       }
       WAVE_SYNC();
       if (corner_any) riccati_keep_linear_terms(a, L, n, lane, true);   // (the sweep writes its gains over them)
       auto sweep = [&]() {
         SweepHandOff<float> ho = {};
-        riccati_sweep<float, (kMinWavesPerSimd < 4), kFew, kHandOff, kScalarCase, kKeepGains>(a, L, n, lane, &ho, stage_flags);
+        riccati_sweep<float, (kMinWavesPerSimd < 4), kFew, kHandOff, kFewTame, kFewTame>(a, L, n, lane, &ho, stage_flags);
         riccati_finish<kHandOff>(a, c, L, n, lane, &ho, &dm_reg);
         near_reg = ho.near;
       };
@@ -519,11 +356,11 @@ __device__ __forceinline__ bool solve_search(double* L, uint32_t b, SolveCarry& 
       } else if (kRiccati) {
         // (a non-finite direction must not read as "no step left": fmaxf drops NaN)
         for (int k = lane; k < nv; k += kLanes) {
-          const float v = (float)fabs(d[k]);
+          const float v = (float)fabs(m.d[k]);
           dm = (v == v) ? fmaxf(dm, v) : INFINITY;
-          anynear |= (AMODE[4 * (k / 3) + 2] == 1);
+          anynear |= (m.AMODE[4 * (k / 3) + 2] == 1);
         }
-      } else if (lane < nvr) { dm = fabsf(newton_sol); anynear = (AMODE[4 * (lane / 3) + 2] == 1); }   // (d[lane], still in a register)
+      } else if (lane < nvr) { dm = fabsf(newton_sol); anynear = (m.AMODE[4 * (lane / 3) + 2] == 1); }   // (d[lane], still in a register)
       // (three stages: nine values in lanes 0-8, each finite and non-negative or INFINITY -- one DPP row)
       if constexpr (kHandOff) dm = wave_max_f_few<kFew>(dm);
       else if constexpr (kFew > 0 && 3 * kFew <= 16) dm = wave_max_f_few<3 * kFew>(dm); else dm = wave_max_f(dm);
@@ -535,7 +372,7 @@ __device__ __forceinline__ bool solve_search(double* L, uint32_t b, SolveCarry& 
     NEO_PHASE(4);
     if (p.max_it > kDumpGradient && it == p.max_it - kDumpGradient - 1) {
       // test hook (neo_mpc_direction_batch): the search direction of lanes 32-63 in this iteration
-      for (int k = lane; k < nv; k += kLanes) a.solution[(size_t)b * nv + k] = d[k];
+      for (int k = lane; k < nv; k += kLanes) a.solution[(size_t)b * nv + k] = m.d[k];
       return true;
     }
     // ---- 64 candidates, one rollout per lane; lowest objective wins
@@ -567,14 +404,14 @@ __device__ __forceinline__ bool solve_search(double* L, uint32_t b, SolveCarry& 
     double fc = rollout_cost<kSteps, kTame, kCovered>(
         a, c, L,
         [&](int i, double& b0, double& b1, double& b2) {
-          candidate_block<kTame, kRiccati, (kFew > 0 && kTame)>(a, c, L, lane, step, pstep, i, b0, b1, b2, hop_stage, hop_x, hop_y);
+          candidate_block<kTame, kRiccati, kFewTame>(a, c, L, lane, step, pstep, i, b0, b1, b2, hop_stage, hop_x, hop_y);
           // (a scalar branch taken in the first iteration only -- the empty asm keeps the compiler from turning it into
           // six selects per block that every iteration pays)
           if (it == 0) {
             asm volatile("");
-            if (lane == 0) { b0 = u[3 * i]; b1 = u[3 * i + 1]; b2 = u[3 * i + 2]; }
+            if (lane == 0) { b0 = m.u[3 * i]; b1 = m.u[3 * i + 1]; b2 = m.u[3 * i + 2]; }
             // (the un-shifted previous solution, armed by the set-up on the costmap: block 0 from the state slot)
-            if (lane == kAltLane && alt_armed) { const double* src = i == 0 ? ALT0 : u + 3 * (i - 1); b0 = src[0]; b1 = src[1]; b2 = src[2]; }
+            if (lane == kAltLane && alt_armed) { const double* src = i == 0 ? ALT0 : m.u + 3 * (i - 1); b0 = src[0]; b1 = src[1]; b2 = src[2]; }
           }
           if (kSteps) { cand[3 * i] = b0; cand[3 * i + 1] = b1; cand[3 * i + 2] = b2; }
         },
@@ -599,8 +436,8 @@ __device__ __forceinline__ bool solve_search(double* L, uint32_t b, SolveCarry& 
       if (lane == best) {
 #pragma unroll
         for (int k = 0; k < 3 * kRegSteps; ++k) {
-          stepmax = fmaxf(stepmax, (float)fabs(cand[k] - u[k]));
-          u[k] = cand[k];
+          stepmax = fmaxf(stepmax, (float)fabs(cand[k] - m.u[k]));
+          m.u[k] = cand[k];
         }
       }
       stepmax = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, stepmax), best));
@@ -610,8 +447,8 @@ __device__ __forceinline__ bool solve_search(double* L, uint32_t b, SolveCarry& 
         if (lane == best) {
 #pragma unroll
           for (int i = 0; i < kRegSteps; ++i) {
-            u_new[3 * i] = cand[3 * i]; u_new[3 * i + 1] = cand[3 * i + 1]; u_new[3 * i + 2] = cand[3 * i + 2];
-            ASN[i] = cand_sn[i]; ACS[i] = cand_cs[i];
+            m.u_new[3 * i] = cand[3 * i]; m.u_new[3 * i + 1] = cand[3 * i + 1]; m.u_new[3 * i + 2] = cand[3 * i + 2];
+            m.ASN[i] = cand_sn[i]; m.ACS[i] = cand_cs[i];
           }
         }
       } else if (!kSteps && !took_trial) {
@@ -627,17 +464,17 @@ __device__ __forceinline__ bool solve_search(double* L, uint32_t b, SolveCarry& 
         for (int i = lane; i < n; i += kLanes) {
           double b0, b1, b2;
           candidate_block<kTame, kRiccati>(a, c, L, best, bstep, bpstep, i, b0, b1, b2, bhop, bhx, bhy);
-          if (alt_won) { const double* src = i == 0 ? ALT0 : u + 3 * (i - 1); b0 = src[0]; b1 = src[1]; b2 = src[2]; }
-          u_new[3 * i] = b0; u_new[3 * i + 1] = b1; u_new[3 * i + 2] = b2;
+          if (alt_won) { const double* src = i == 0 ? ALT0 : m.u + 3 * (i - 1); b0 = src[0]; b1 = src[1]; b2 = src[2]; }
+          m.u_new[3 * i] = b0; m.u_new[3 * i + 1] = b1; m.u_new[3 * i + 2] = b2;
         }
       }
       have_trig = true;
       WAVE_SYNC();
       for (int k = lane; k < nv; k += kLanes) {
-        const double nu = u_new[k], ou = u[k];
+        const double nu = m.u_new[k], ou = m.u[k];
         stepmax = fmaxf(stepmax, (float)fabs(nu - ou));
-        if (!kSecond) { u_prev[k] = ou; gt_prev[k] = gt[k]; }
-        u[k] = nu;
+        if (!kSecond) { m.u_prev[k] = ou; m.gt_prev[k] = m.gt[k]; }
+        m.u[k] = nu;
       }
       stepmax = wave_max_f(stepmax);
     }
@@ -653,7 +490,7 @@ __device__ __forceinline__ bool solve_search(double* L, uint32_t b, SolveCarry& 
     // kernel-argument pointer, one wait, and scalar operands, instead of an LDS round trip behind each of the rule book's
     // conditions; nothing of it is held across the loop)
     double tolk[NEO_TOL_COUNT] = {};
-    if (kAcceptFetch) {
+    if (kFewTame) {
       auto kp = (const __attribute__((address_space(4))) char*)__builtin_amdgcn_kernarg_segment_ptr();
       asm volatile("" : "+s"(kp));
       const DevParams& q = ((const SolveArgs*)kp)->p;
@@ -665,7 +502,7 @@ __device__ __forceinline__ bool solve_search(double* L, uint32_t b, SolveCarry& 
     // rules carry are four vector registers held across the Hessian pass, and the run-time-sized kernel at four waves per SIMD
     // parked two more registers in scratch with the rules called than with their text in place)
     const double gain = kNewton ? lane_value(f - fb, 0) : f - fb;
-    const bool ends = neo_rules_iteration_ends(kRiccati, kRouted, kBlockedRule, kAcceptFetch ? tolk : TOL, &run, it, best >= 32, lane_value(step, best), hop_won,
+    const bool ends = neo_rules_iteration_ends(kRiccati, kRouted, kBlockedRule, kFewTame ? tolk : TOL, &run, it, best >= 32, lane_value(step, best), hop_won,
                                                gain, fb, (double)stepmax, free_now, free_rollout);
     double* TOLW = L + tol_off;
     if (kFew) { if (lane == 0) { TOLW[T_GAIN2] = run.gain2; TOLW[T_GAIN1] = run.gain1; } }
@@ -690,7 +527,7 @@ __device__ __forceinline__ bool solve_search(double* L, uint32_t b, SolveCarry& 
     NEO_PHASE(6);
     NEO_PHASE_DUMP();
     if (ends) { status = NEO_MPC_STATUS_CONVERGED; ++it; break; }
-  }
+  }   // K1-SEARCH-LOOP-END
 
   // ---- phase 2, second-order directions: a search that has ENDED looks once at the costmap cells around every stage
   //      (cell_scan.h): cheaper cells up to three cells away, which no descent direction sees -- the term has no gradient --
@@ -706,7 +543,7 @@ __device__ __forceinline__ bool solve_search(double* L, uint32_t b, SolveCarry& 
   bool resume = false;
   {
     SolveArgs as;
-    fresh_args<kSteps, kStaticTile, kLayoutSteps, kRouted>(as);
+    fresh_args<V>(as);
     select_map(as.map, L + as.lds.prob);
     Ctx cs;
     ctx_from_lds<false>(as, L, cs);
@@ -743,15 +580,15 @@ __device__ __forceinline__ bool solve_search(double* L, uint32_t b, SolveCarry& 
 }
 
 // ---- phase 3: K2 (py:365-403) on the search's result
-template <int kSteps, int kStaticTile, int kLayoutSteps>
+template <class V>
 __device__ __forceinline__ void solve_finish(double* L, uint32_t b, int lane, const SolveCarry& sc) {
   const int flags = sc.flags, status = sc.status, it = sc.it, nfev = sc.nfev;
   double f = sc.f;
   SolveArgs a;
-  fresh_args<kSteps, kStaticTile, kLayoutSteps>(a);
+  fresh_args<V>(a);
   select_map(a.map, L + a.lds.prob);
   const DevParams& p = a.p;
-  const int n = kSteps ? kSteps : p.n, nv = 3 * n;
+  const int n = V::kSteps ? V::kSteps : p.n, nv = 3 * n;
   double* u = L + a.lds.u;
   Ctx c;
   ctx_from_lds<false>(a, L, c);
@@ -767,27 +604,46 @@ __device__ __forceinline__ void solve_finish(double* L, uint32_t b, int lane, co
 }
 
 // ---------------------------------------------------------------- K1: the kernels
+// What every K1 kernel starts with: its LDS -- the static array of the kStaticTile variants, else the launch's dynamic
+// LDS -- and the instance its workgroup solves.
+// (the static array belongs to solve_lds<V>, not to a kernel: k_solve<w, 3, 1, t, tile> and k_solve_routed<w, t, tile> build
+// the same V and name the same array.  They are in different units today; whether two kernels of ONE unit that share it get
+// an allocation each is the compiler's business -- check `make resource-usage` (LDS size) if that ever happens)
+template <class V>
+__device__ __forceinline__ double* solve_lds() {
+  extern __shared__ __align__(16) double Ldyn[];
+  __shared__ __align__(16) double Lstat[V::kStaticDoubles];
+  return V::kStaticTile ? Lstat : Ldyn;
+}
+// (balanced dispatch, neo_mpc_balance_dispatch_device: which instance this workgroup solves -- instances are independent,
+// every result is bit for bit what it is in launch order; only which of them share a SIMD changes)
+__device__ __forceinline__ uint32_t solve_instance(const SolveArgs& args) {
+  return args.order ? (uint32_t)__builtin_amdgcn_readfirstlane((int)args.order[blockIdx.x]) : blockIdx.x;
+}
+
+// The prologue of both kernels: declares L (the kernel's LDS), lane, and b (the instance this workgroup solves), and ends the
+// kernel where there is none -- a workgroup beyond the count, or an order the caller launched this solve ahead of, on
+// another stream (never out of range).
+// A MACRO: `return` has to be the kernel's own.  As a function that reports "none" (a bool, a sentinel) or that takes the
+// kernel's body as a callable and returns early itself, the compiler lays 18 to 36 of the 36 K1 kernels out differently
+// (docs/NOTEBOOK.md A.29); as text they are instruction for instruction what they were.
+#define NEO_K1_PROLOGUE(V, args)             \
+  double* const L = solve_lds<V>();          \
+  const int lane = threadIdx.x;              \
+  if (blockIdx.x >= (args).count) return;    \
+  const uint32_t b = solve_instance(args);   \
+  if (b >= (args).count) return
+
 // k_solve<waves per SIMD, control_steps specialisation, direction, tame, static tile>: one direction for every instance.
 template <int kMinWavesPerSimd, int kSteps, int kDir = 0, bool kTame = false, int kStaticTile = 0>
 __global__ __launch_bounds__(kLanes, kMinWavesPerSimd) void k_solve(const SolveArgs args) {
-  extern __shared__ __align__(16) double Ldyn[];
-  // (the run-time-sized Newton kernel carves LDS for its largest system and no L-BFGS pairs)
-  constexpr int kLayoutSteps = kSteps ? kSteps : kNewtonMaxSteps;
-  constexpr LdsLayout kStaticLayout = make_lds_layout(kLayoutSteps, kSteps ? 4 : 0, false);
-  constexpr int kStaticDoubles = kStaticTile ? (kStaticLayout.total_bytes + kStaticTile) / 8 : 2;
-  __shared__ __align__(16) double Lstat[kStaticDoubles];
-  double* const L = kStaticTile ? Lstat : Ldyn;
-  const int lane = threadIdx.x;
-  if (blockIdx.x >= args.count) return;
-  // (balanced dispatch, neo_mpc_balance_dispatch_device: which instance this workgroup solves -- instances are independent,
-  // every result is bit for bit what it is in launch order; only which of them share a SIMD changes)
-  const uint32_t b = args.order ? (uint32_t)__builtin_amdgcn_readfirstlane((int)args.order[blockIdx.x]) : blockIdx.x;
-  if (b >= args.count) return;   // (an order the caller launched this solve ahead of, on another stream: never out of range)
+  using V = K1Variant<kMinWavesPerSimd, kSteps, kDir, kTame, kStaticTile>;
+  NEO_K1_PROLOGUE(V, args);
   NEO_WAVE_START;
   SolveCarry sc;
-  if (!solve_setup<kSteps, kTame, kStaticTile, kLayoutSteps>(L, b, lane, sc)) return;
-  if (solve_search<kMinWavesPerSimd, kSteps, kDir, kTame, kStaticTile, kLayoutSteps>(L, b, sc)) return;
-  solve_finish<kSteps, kStaticTile, kLayoutSteps>(L, b, lane, sc);
+  if (!solve_setup<V>(L, b, lane, sc)) return;
+  if (solve_search<V>(L, b, sc)) return;
+  solve_finish<V>(L, b, lane, sc);
   NEO_WAVE_END_ARGS(args);
 }
 
@@ -798,33 +654,26 @@ __global__ __launch_bounds__(kLanes, kMinWavesPerSimd) void k_solve(const SolveA
 // (Riccati) search, whose wall model slides along walls -- every objective miss the random-parameter fuzz against the reference
 // found at control_steps 3 was a dense search hemmed in by lethal cells.  One launch, one wave per instance, one wave-uniform
 // branch behind the set-up; the two branches share LDS (the stage-wise carve-up for three stages lies inside the dense one,
-// fresh_args) and the register budget (128 at four waves per SIMD, no scratch).
+// K1Variant) and the register budget (128 at four waves per SIMD, no scratch).
 template <int kMinWavesPerSimd, bool kTame = false, int kStaticTile = 0>
 __global__ __launch_bounds__(kLanes, kMinWavesPerSimd) void k_solve_routed(const SolveArgs args) {
-  extern __shared__ __align__(16) double Ldyn[];
-  constexpr int kSteps = kRoutedSteps;
-  constexpr LdsLayout kStaticLayout = make_lds_layout(kSteps, 4, false);
-  constexpr int kStaticDoubles = kStaticTile ? (kStaticLayout.total_bytes + kStaticTile) / 8 : 2;
-  __shared__ __align__(16) double Lstat[kStaticDoubles];
-  double* const L = kStaticTile ? Lstat : Ldyn;
-  const int lane = threadIdx.x;
-  if (blockIdx.x >= args.count) return;
-  const uint32_t b = args.order ? (uint32_t)__builtin_amdgcn_readfirstlane((int)args.order[blockIdx.x]) : blockIdx.x;
-  if (b >= args.count) return;
+  using Dense = K1Variant<kMinWavesPerSimd, kRoutedSteps, 1, kTame, kStaticTile>;
+  using Stagewise = K1Variant<kMinWavesPerSimd, kRoutedSteps, 2, kTame, kStaticTile, true>;
+  NEO_K1_PROLOGUE(Dense, args);
   NEO_WAVE_START;
   SolveCarry sc;
-  if (!solve_setup<kSteps, kTame, kStaticTile, kSteps>(L, b, lane, sc)) return;
+  if (!solve_setup<Dense>(L, b, lane, sc)) return;
   // (the test hooks dump what the instance's own direction works with)
   if (__builtin_amdgcn_readfirstlane((int)sc.wall_in_reach)) {
     // (the stage-wise searches are the long ones -- 7.3 iterations against 5.1, up to 19 against 11, 1.5 x the instructions per
     // iteration -- and a launch of 4096 ends with the longest of them: they issue ahead of the dense waves they share a SIMD
     // with, which finish early either way.  Same box, three runs each: 23.0 -> 24.5 M solves/s; 262 144 instances: no change)
     __builtin_amdgcn_s_setprio(3);
-    if (solve_search<kMinWavesPerSimd, kSteps, 2, kTame, kStaticTile, kSteps, true>(L, b, sc)) return;
+    if (solve_search<Stagewise>(L, b, sc)) return;   // K1-ROUTED-STAGEWISE-SEARCH
   } else {
-    if (solve_search<kMinWavesPerSimd, kSteps, 1, kTame, kStaticTile, kSteps, false>(L, b, sc)) return;
+    if (solve_search<Dense>(L, b, sc)) return;   // K1-ROUTED-DENSE-SEARCH
   }
-  solve_finish<kSteps, kStaticTile, kSteps>(L, b, lane, sc);
+  solve_finish<Dense>(L, b, lane, sc);
   NEO_WAVE_END_ARGS(args);
 }
 
@@ -836,16 +685,29 @@ __global__ __launch_bounds__(kLanes, kMinWavesPerSimd) void k_solve_routed(const
 // of neo_mpc_create overrides (LaunchTuning), for A/B runs.
 int solve_variant(const LaunchTuning& t, int fallback) { return t.solve_waves ? t.solve_waves : fallback; }
 
-// One launch of a K1 kernel, one workgroup per instance; `lds_bytes`: its dynamic LDS (0 for the static-tile variants).
-// with events: hipExtLaunchKernel stamps them from the dispatch packet itself (no barrier packets in
-// front of and behind the kernel, which is what separate hipEventRecord calls put on the queue)
+// What the two dispatch tables (launch_solve, launch_solve_riccati) know before they pick a row, and the launch itself.
 using SolveKernel = void (*)(const SolveArgs);
-void launch_k1(SolveKernel kernel, size_t lds_bytes, const SolveArgs& a, void* stream, void* ev_start, void* ev_stop) {
-  const dim3 grid(a.count), block(kLanes);
-  hipEvent_t e0 = (hipEvent_t)ev_start, e1 = (hipEvent_t)ev_stop;
-  if (e0 || e1) hipExtLaunchKernelGGL(kernel, grid, block, lds_bytes, (hipStream_t)stream, e0, e1, 0, a);
-  else hipLaunchKernelGGL(kernel, grid, block, lds_bytes, (hipStream_t)stream, a);
-}
+struct K1Launch {
+  const SolveArgs& a;
+  void *stream, *ev_start, *ev_stop;
+  bool disc;         // the tame instantiations apply (K1Variant kTame)
+  size_t lds;        // the launch's dynamic LDS
+  // (the static-tile kernels count on the tile being there: no tile at all -- a reach of 60 cells and more -- is not "small")
+  bool small_tile;
+  K1Launch(const SolveArgs& a_, const LaunchTuning& tuning, void* stream_, void* ev_start_, void* ev_stop_)
+      : a(a_), stream(stream_), ev_start(ev_start_), ev_stop(ev_stop_),
+        disc(a_.p.tame != 0 && !tuning.no_tame), lds(a_.lds.total_bytes),
+        small_tile(a_.lds.tile_w * a_.lds.tile_h > 0 && a_.lds.tile_w * a_.lds.tile_h <= 1024 && !tuning.dynamic_lds) {}
+  // One launch of a K1 kernel, one workgroup per instance; `lds_bytes`: its dynamic LDS (0 for the static-tile variants).
+  // with events: hipExtLaunchKernel stamps them from the dispatch packet itself (no barrier packets in
+  // front of and behind the kernel, which is what separate hipEventRecord calls put on the queue)
+  void operator()(SolveKernel kernel, size_t lds_bytes) const {
+    const dim3 grid(a.count), block(kLanes);
+    hipEvent_t e0 = (hipEvent_t)ev_start, e1 = (hipEvent_t)ev_stop;
+    if (e0 || e1) hipExtLaunchKernelGGL(kernel, grid, block, lds_bytes, (hipStream_t)stream, e0, e1, 0, a);
+    else hipLaunchKernelGGL(kernel, grid, block, lds_bytes, (hipStream_t)stream, a);
+  }
+};
 // the variant of `kernel<waves per SIMD, ...>` built for w = 4, 3 or (anything else) 2 waves per SIMD
 #define NEO_K1_BY_WAVES(w, kernel, ...) \
   ((w) == 4 ? (SolveKernel)kernel<4, __VA_ARGS__> : (w) == 3 ? (SolveKernel)kernel<3, __VA_ARGS__> : (SolveKernel)kernel<2, __VA_ARGS__>)

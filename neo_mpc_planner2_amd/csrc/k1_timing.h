@@ -16,7 +16,7 @@
 #define NEO_SEGMENT_DUMP()                                                                                   \
   {                                                                                                          \
     SolveArgs ad;                                                                                            \
-    fresh_args<kSteps, kStaticTile, kLayoutSteps, kRouted>(ad);                                              \
+    fresh_args<V>(ad);                                                                                       \
     const int nvd = 3 * ad.p.n;                                                                              \
     if (ad.solution && lane_again() == 0 && nvd >= 9) {                                                      \
       ad.solution[(size_t)b * nvd + 4] = (double)seg_t0; ad.solution[(size_t)b * nvd + 5] = (double)seg_t1;  \

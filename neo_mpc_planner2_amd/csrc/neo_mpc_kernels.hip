@@ -217,11 +217,9 @@ void launch_solve_riccati(const SolveArgs& a, const LaunchTuning& tuning, void* 
 void launch_solve(const SolveArgs& a, const LaunchTuning& tuning, void* stream, void* ev_start, void* ev_stop) {
   if (a.count == 0) return;
   const bool generic = a.p.mem != 4;  // (the control_steps-3 L-BFGS specialisation carves LDS for four pairs)
-  const bool disc = a.p.tame != 0 && !tuning.no_tame;
-  const size_t lds = a.lds.total_bytes;
-  // (the static-tile kernels count on the tile being there: no tile at all -- a reach of 60 cells and more -- is not "small")
-  const bool small_tile = a.lds.tile_w * a.lds.tile_h > 0 && a.lds.tile_w * a.lds.tile_h <= 1024 && !tuning.dynamic_lds;
-  auto launch = [&](SolveKernel kernel, size_t lds_bytes) { launch_k1(kernel, lds_bytes, a, stream, ev_start, ev_stop); };
+  const K1Launch launch(a, tuning, stream, ev_start, ev_stop);   // (k1_solve.h: what both tables know before they pick a row)
+  const bool disc = launch.disc, small_tile = launch.small_tile;
+  const size_t lds = launch.lds;
   if (a.p.newton == 2) { launch_solve_riccati(a, tuning, stream, ev_start, ev_stop); return; }
   if (a.p.n == 3 && a.p.newton == 1) {  // projected Newton, dense 9 x 9 system (its layout does not depend on lbfgs_memory)
     // (the general variant at 4 waves/SIMD spills 7 VGPRs -- 32 bytes of scratch -- and is still the faster one: measured

@@ -12,10 +12,9 @@ namespace neo_mpc {
 
 void launch_solve_riccati(const SolveArgs& a, const LaunchTuning& tuning, void* stream, void* ev_start, void* ev_stop) {
   if (a.count == 0) return;
-  const bool disc = a.p.tame != 0 && !tuning.no_tame;
-  const size_t lds = a.lds.total_bytes;
-  const bool small_tile = a.lds.tile_w * a.lds.tile_h > 0 && a.lds.tile_w * a.lds.tile_h <= 1024 && !tuning.dynamic_lds;
-  auto launch = [&](SolveKernel kernel, size_t lds_bytes) { launch_k1(kernel, lds_bytes, a, stream, ev_start, ev_stop); };
+  const K1Launch launch(a, tuning, stream, ev_start, ev_stop);   // (k1_solve.h: what both tables know before they pick a row)
+  const bool disc = launch.disc, small_tile = launch.small_tile;
+  const size_t lds = launch.lds;
   if (a.p.routed) {   // control_steps 3, AUTO: direction by neighbourhood (k_solve_routed; the dense layout, 4 waves/SIMD like the dense kernels)
     const int w = solve_variant(tuning, 4);
     if (disc && w == 4 && small_tile) launch(k_solve_routed<4, true, 1024>, 0);   // (the static variant takes no dynamic LDS)

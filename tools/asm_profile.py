@@ -2,7 +2,9 @@
 """Static instruction count of one kernel per top-level source line (inlined code is attributed to
 the call site inside the kernel).  usage: asm_profile.py <kernel-mangled-substring> [lo hi]
 Compiles the kernel's translation unit with -gline-tables-only -S (device only) and parses the .loc chain; the lines are
-those of k1_solve.h, where K1 lives."""
+those of k1_solve.h, where K1 lives.  Only frames in k1_solve.h count as K1's own: code of the helpers in k1_variant.h
+(fresh_args, own_loop_params, ctx_from_lds, lane_again) is attributed to the line of k1_solve.h that calls them, like the
+code of every other header -- before they moved there it was listed under their own lines (`inner`)."""
 import collections, os, re, subprocess, sys
 root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 key = sys.argv[1]

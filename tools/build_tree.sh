@@ -1,6 +1,7 @@
 #!/bin/bash
 # build libneo_mpc.so from a (patched) copy of the working tree's sources: tools/_build/libneo_mpc_<name>.so
 # usage: bash tools/build_tree.sh <name> [sed expression on k1_solve.h ...]
+# (k1_solve.h: K1's phases, kernels and launch; the variant record and fresh_args are in k1_variant.h, which the expressions do not reach)
 set -e
 NAME=$1; shift
 ROOT=$(cd "$(dirname "$0")/.." && pwd)

@@ -24,13 +24,13 @@ subprocess.run(["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++
                ["-gline-tables-only", "-x", "hip", "--cuda-device-only", "-S", src, "-o", out],
                check=True, stderr=subprocess.DEVNULL)
 ksrc = open(os.path.join(csrc, "k1_solve.h")).read().split("\n")   # (K1's own file: the lines below are its lines)
-loop_lo = next(i + 1 for i, l in enumerate(ksrc) if "for (; it < p.max_it && !scan_only; ++it) {" in l)
+# (marker comments of k1_solve.h, not the text of its source lines)
+loop_lo = next(i + 1 for i, l in enumerate(ksrc) if "K1-SEARCH-LOOP-BEGIN" in l)
 branch = sys.argv[sys.argv.index("--branch") + 1] if "--branch" in sys.argv else None
 # (the two call sites of solve_search in k_solve_routed: direction 2 = stage-wise, 1 = dense)
-site = {"stagewise": next(i + 1 for i, l in enumerate(ksrc) if "solve_search<kMinWavesPerSimd, kSteps, 2, kTame" in l),
-        "dense": next(i + 1 for i, l in enumerate(ksrc) if "solve_search<kMinWavesPerSimd, kSteps, 1, kTame" in l)}
-# (the loop ends where the exit-hop block of the dense direction, or the epilogue, begins)
-loop_hi = next(i for i, l in enumerate(ksrc) if ("a search that has ENDED" in l or "NEO_SEGMENT(1);" in l or "phase 2, second-order directions" in l) and i + 1 > loop_lo)
+site = {"stagewise": next(i + 1 for i, l in enumerate(ksrc) if "K1-ROUTED-STAGEWISE-SEARCH" in l),
+        "dense": next(i + 1 for i, l in enumerate(ksrc) if "K1-ROUTED-DENSE-SEARCH" in l)}
+loop_hi = next(i + 1 for i, l in enumerate(ksrc) if "K1-SEARCH-LOOP-END" in l)
 text = open(out).read().split("\n")
 start = next(i for i, l in enumerate(text) if l.startswith("_Z") and key in l and ":" in l)
 end = next(i for i in range(start, len(text)) if ".amdhsa_kernel" in text[i])

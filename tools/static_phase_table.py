@@ -46,9 +46,9 @@ def main():
     flags = re.search(r"^RICCATI_FLAGS := (.*)$", mk, re.M).group(1).split()
     src = open(os.path.join(csrc, "k1_solve.h")).read().split("\n")
     marks = {int(re.search(r"NEO_PHASE\((\d)\)", l).group(1)): i + 1 for i, l in enumerate(src) if re.match(r"\s*NEO_PHASE\(\d\);", l)}
-    loop_top = next(i + 1 for i, l in enumerate(src) if "for (; it < p.max_it" in l)
+    loop_top = next(i + 1 for i, l in enumerate(src) if "K1-SEARCH-LOOP-BEGIN" in l)   # (marker comments of k1_solve.h)
     loop_end = next(i + 1 for i, l in enumerate(src) if re.match(r"\s*NEO_PHASE_DUMP\(\);", l))
-    site = next(i + 1 for i, l in enumerate(src) if re.search(r"solve_search<kMinWavesPerSimd, kSteps, 2, .*true>", l))
+    site = next(i + 1 for i, l in enumerate(src) if "K1-ROUTED-STAGEWISE-SEARCH" in l)
     with tempfile.TemporaryDirectory() as tmp:
         out = os.path.join(tmp, "unit.s")
         subprocess.run(["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-Wno-pass-failed"] + flags +
