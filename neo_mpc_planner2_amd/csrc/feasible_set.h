@@ -7,6 +7,7 @@
 
 #include "neo_mpc_device.h"
 #include "fast_math.h"
+#include "lane_scale_table.h"
 #include "solver_context.h"
 
 namespace neo_mpc {
@@ -50,13 +51,13 @@ __device__ __forceinline__ void project_block(const DevParams& p, double& b0, do
   b0 = bx; b1 = by;
 }
 
-// candidate step multipliers: lanes 0..31 scale the proximal-gradient step by 2^(-12 + l/2),
-// lanes 32..63 are step lengths along the L-BFGS direction
-#define NEO_QN_STEPS                                                                                  \
-  1.0, 0.84, 1.19, 0.71, 1.41, 0.59, 1.68, 0.5, 2.0, 0.42, 2.38, 0.35, 2.83, 0.25, 4.0, 0.177,         \
-  0.125, 0.088, 0.0625, 0.044, 0.03125, 0.0156, 0.0078, 0.0039, 0.00195, 0.00098, 4.9e-4, 2.4e-4,    \
-  1.2e-4, 6e-5, 3e-5, 1.5e-5
+// candidate step multipliers (NEO_QN_STEPS: lane_scale_table.h): lanes 0..31 scale the proximal-gradient step by
+// 2^(-12 + l/2), lanes 32..63 are step lengths along the L-BFGS direction
 __constant__ double kQnSteps[32] = {NEO_QN_STEPS};
+// ... and all 64 of them as lane_scale<kLongShots> below returns them, for the kernels that fetch theirs once per search
+// (the tame three-stage stage-wise kernels park them in LDS, k1_solve.h)
+template <bool kLongShots>
+__constant__ LaneScaleTable kLaneScales = make_lane_scale_table<kLongShots>();
 // Which Newton lanes (32-63, long shots included) step at least / less than a given length: bit `lane` of a 64-bit mask -- a
 // rule that asks "was the iteration won by a step of at least 0.8" tests one bit with scalar instructions instead of
 // comparing a float64 against a constant the compiler keeps in (and, at four waves per SIMD, spills from) a vector register

@@ -250,6 +250,9 @@ __device__ __forceinline__ bool solve_search(double* L, uint32_t b, SolveCarry& 
     if (kFew && lane == 0) { double* t = L + a.lds.tol; t[T_GAIN1] = INFINITY; t[T_GAIN2] = INFINITY; t[T_ALPHA] = alpha; }
     // (mu lives in the tolerance block of LDS: two scalar registers fewer across the loop)
     if (kRiccati && lane == 0) L[a.lds.tol + T_MU] = n > 8 ? (double)(n - 8) * 0.125 : 0.0;
+    // (three tame stages: every lane parks its step multiplier in LDS, once per search -- k1_variant.h kRoutedLaneScales;
+    // the candidates phase reads it back)
+    if (kFewTame) L[kRoutedLaneScales + lane] = kLaneScales<kSecond>.v[lane];
   }
   // Riccati: a block may be sent straight onto the kink u_i = v_cur only when v_cur is feasible
   bool v_feasible = false;
@@ -378,7 +381,10 @@ __device__ __forceinline__ bool solve_search(double* L, uint32_t b, SolveCarry& 
     // ---- 64 candidates, one rollout per lane; lowest objective wins
     // (run-time-sized Riccati kernel: the multiplier is re-read here -- one constant-memory load per iteration
     // against 2 x control_steps stages of work, and two registers fewer across the sweep)
-    const double lscale = kRiccati ? lane_scale<kSecond>(lane) : my_scale;
+    // (three tame stages, a wave alone on its SIMD at the launch's end: the constant-memory load was the loop's only
+    // vector-memory round trip, fully exposed, behind three lane-divergent arms.  The multiplier comes from LDS instead,
+    // where the search's entry parked it -- one read next to T_ALPHA's, through the same opaque offset, one wait for both)
+    const double lscale = kFewTame ? TOL[kRoutedLaneScales - V::kLayout.tol + lane] : kRiccati ? lane_scale<kSecond>(lane) : my_scale;
     const double alpha_now = kFew ? TOL[T_ALPHA] : alpha;
     const double pstep = alpha_now * lscale;
     const double step = lane < 32 ? pstep : lscale;

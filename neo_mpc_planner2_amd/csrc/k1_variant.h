@@ -34,6 +34,13 @@ static_assert(make_lds_layout(kRoutedSteps, 0, true, true).tile <= make_lds_layo
               "the stage-wise arrays of three stages fit in front of the dense kernel's reach tile");
 static_assert(make_lds_layout(kRoutedSteps, 0, true, true).gr == make_lds_layout(kRoutedSteps, 4, false).gr,
               "records, iterate and gradients share their offsets");
+// The tame routed stage-wise search keeps its 64 lane step multipliers (feasible_set.h kLaneScales) in LDS, one double per
+// lane, written once at the search's entry: behind the last stage-wise array and in front of the reach tile -- room the
+// dense carve-up leaves and no stage-wise phase, cell scan included, addresses (every other offset of the routed layout lies
+// below it).  The kernel's LDS size does not change.
+constexpr int kRoutedLaneScales = make_lds_layout(kRoutedSteps, 0, true, true).tile;
+static_assert(kRoutedLaneScales + kLanes <= make_lds_layout(kRoutedSteps, 4, false).tile,
+              "the lane multipliers fit between the stage-wise arrays and the reach tile");
 
 // ---------------------------------------------------------------- K1: template parameters of the phase functions and the kernels
 // kSteps > 0: specialisation for control_steps == kSteps -- every lane keeps its candidate's controls and sin/cos in
