@@ -53,6 +53,8 @@ extern "C" {
  * added two entry points and a constant and no record: still ABI 2, behaviour 6.
  * The plan check (neo_mpc_plan_check_batch, neo_mpc_plan_check, neo_mpc_check_plans[_device]) added two records and two
  * entry points in the same way: still ABI 2, behaviour 6.
+ * The read-back of the dispatch order (neo_mpc_get_dispatch_order, a test hook) added an entry point only: still ABI 2,
+ * behaviour 6.
  *
  * Behaviour history (iterates and iteration counts differ between versions, results stay inside the parity protocol of
  * DESIGN.md section 1; neo_mpc_behaviour_version() returns the number of the build that answers):
@@ -910,6 +912,14 @@ int neo_mpc_solve_batch_device(neo_mpc_handle* handle, const neo_mpc_batch* batc
  * d_previous_commands == NULL: back to launch order. */
 int neo_mpc_balance_dispatch_device(neo_mpc_handle* handle, const neo_mpc_command* d_previous_commands, size_t count,
                                     void* stream);
+/* Test hook: what the last neo_mpc_balance_dispatch_device left in the handle.  Host pointers; either array may be NULL.
+ * `*count_out`: the count the handle is armed for, 0 when it is disarmed (never armed, disarmed with NULL, or a failed
+ * call) -- then nothing else is written.  `order_out` receives `count` entries: workgroup w of the next solve of that
+ * count solves instance order_out[w].  `load_out` receives `count` entries, the exponential averages the order is sorted
+ * by, ONLY for a count the library sorts (a multiple of 1024 up to 4096): for a count that gets launch order the averages
+ * are never computed and `load_out` is left untouched.  Off the hot path: waits for the whole device (the order is built
+ * on the caller's stream), then copies. */
+int neo_mpc_get_dispatch_order(neo_mpc_handle* handle, uint32_t* order_out, float* load_out, size_t* count_out);
 /* Same; `start_event` / `stop_event` (hipEvent_t, either may be NULL) are stamped with the start and the
  * end of the solve kernel by the dispatch itself (hipExtLaunchKernel): a measurement harness gets K1's
  * duration without putting event-record packets between consecutive launches. */

@@ -32,6 +32,7 @@ PROTOTYPES = {
     "neo_mpc_behaviour_version": (C.c_int, None),
     "neo_mpc_effective_method": (C.c_int, [_H]),
     "neo_mpc_balance_dispatch_device": (C.c_int, [_H, _V, _SIZE, _V]),
+    "neo_mpc_get_dispatch_order": (C.c_int, [_H, _V, _V, _P(_SIZE)]),
     "neo_mpc_last_error": (C.c_char_p, None),
     "neo_mpc_last_error_code": None,
     "neo_mpc_default_params": (C.c_int, [_P(abi.NeoMpcParams)]),

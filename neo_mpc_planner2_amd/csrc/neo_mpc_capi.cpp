@@ -988,6 +988,23 @@ int neo_mpc_balance_dispatch_device(neo_mpc_handle* h, const neo_mpc_command* d_
   return NEO_MPC_OK;
 }
 
+// Test hook: the order and the averages K5 left in the handle.  K5 runs on the caller's stream, not through the fence:
+// there is no writer to wait on, so the whole device is waited for.
+int neo_mpc_get_dispatch_order(neo_mpc_handle* h, uint32_t* order_out, float* load_out, size_t* count_out) {
+  if (!h) return fail(NEO_MPC_ERR_INVALID_ARGUMENT, "null handle");
+  const size_t count = h->order_count;
+  if (count_out) *count_out = count;
+  if (count == 0 || (!order_out && !load_out)) return NEO_MPC_OK;
+  HIP_TRY(hipSetDevice(h->device));
+  HIP_TRY(hipDeviceSynchronize());
+  if (order_out) HIP_TRY(hipMemcpy(order_out, h->order_buf.ptr, count * sizeof(uint32_t), hipMemcpyDeviceToHost));
+  // (a count that gets launch order -- k_dispatch_order's first branch -- never has its averages written: that memory is
+  // nobody's to read)
+  if (load_out && count % kDispatchSimds == 0 && count <= 4 * kDispatchSimds)
+    HIP_TRY(hipMemcpy(load_out, h->load_buf.ptr, count * sizeof(float), hipMemcpyDeviceToHost));
+  return NEO_MPC_OK;
+}
+
 int neo_mpc_solve_batch_device(neo_mpc_handle* h, const neo_mpc_batch* batch, void* stream) {
   return neo_mpc_solve_batch_device_timed(h, batch, stream, nullptr, nullptr);
 }

@@ -775,6 +775,21 @@ class BatchSolver:
         _lib.check(self._lib.neo_mpc_balance_dispatch_device(self._handle, C.c_void_p(commands.data_ptr()), commands.shape[0],
                                                              C.c_void_p(stream)))
 
+    def dispatch_order(self):
+        """Test hook (neo_mpc_get_dispatch_order): what the last `balance_dispatch` left in the handle -> (order, load), or
+        None when no order is armed.  `order` uint32 [count]: workgroup w of the next device solve of that count solves
+        instance order[w].  `load` float32 [count]: the averages the order is sorted by -- None for a count that gets launch
+        order (not a multiple of 1024, or beyond 4096), which has none.  Synchronous; waits for the device."""
+        count = C.c_size_t()
+        _lib.check(self._lib.neo_mpc_get_dispatch_order(self._handle, None, None, C.byref(count)))
+        if count.value == 0:
+            return None
+        order = np.zeros(count.value, dtype=np.uint32)
+        load = np.zeros(count.value, dtype=np.float32) if count.value % 1024 == 0 and count.value <= 4096 else None
+        _lib.check(self._lib.neo_mpc_get_dispatch_order(self._handle, *self._addresses(True, order, load), C.byref(count)))
+        assert count.value == len(order)
+        return order, load
+
     def solve_device(self, problems, states, warm, commands, solution=None, path=None, footprints=None,
                      stream=None, velocities=None, events=None):
         """All arguments are CUDA uint8/float64 torch tensors holding the C records

@@ -28,6 +28,7 @@ class Recorder:
 
     def __init__(self):
         self.calls = []
+        self.armed = 0       # the count neo_mpc_get_dispatch_order answers with
 
     def __getattr__(self, name):
         if not name.startswith("neo_mpc_"):
@@ -37,7 +38,7 @@ class Recorder:
             self.calls.append((name, [self.seen(a) for a in args]))
             outs = [a._obj for a in args if isinstance(a, BY_REFERENCE) and not isinstance(a._obj, C.Structure)]
             answer = {"neo_mpc_get_world_map": tuple(WORLD.values()), "neo_mpc_kernel_info": KERNEL_INFO,
-                      "neo_mpc_solve_batch_begin": (TICKET,)}.get(name, ())
+                      "neo_mpc_solve_batch_begin": (TICKET,), "neo_mpc_get_dispatch_order": (self.armed,)}.get(name, ())
             if name == "neo_mpc_get_world_map":          # (asked for the size alone, for the whole geometry, or for the cells)
                 answer = answer[:len(outs)]
             assert len(outs) == len(answer), (name, len(outs))
@@ -132,6 +133,14 @@ def test_lifecycle_and_configuration():
     assert one_call(s, "neo_mpc_kernel_info") == ["out", "out", "out"]
     assert s.balance_dispatch(None) is None
     assert one_call(s, "neo_mpc_balance_dispatch_device") == [None, 0, None]
+    assert s.dispatch_order() is None                                        # disarmed: asked for the count alone
+    assert one_call(s, "neo_mpc_get_dispatch_order") == [None, None, "out"]
+    for s._lib.armed, sorted_count in ((2048, True), (1500, False), (5120, False)):
+        order, load = s.dispatch_order()
+        assert order.shape == (s._lib.armed,) and order.dtype == U32
+        assert (load.shape == order.shape and load.dtype == F32) if sorted_count else load is None
+        assert s._lib.take() == [("neo_mpc_get_dispatch_order", [HANDLE, None, None, "out"]),
+                                 ("neo_mpc_get_dispatch_order", [HANDLE, at(order), at(load) if sorted_count else None, "out"])]
     s._last_call, s._keep, s._in_flight = "x", "y", {1: "z"}
     s.close()
     assert one_call(s, "neo_mpc_destroy") == [] and s._handle is None
