@@ -39,6 +39,8 @@ extern "C" {
  * neo_mpc_get_costmap_pool) added a record and five entry points in the same way: still ABI 2, behaviour 6.
  * The fleet stamp (neo_mpc_stamp_batch, neo_mpc_stamp_fleet[_device], neo_mpc_inflation_costs) added a record and three
  * entry points in the same way: still ABI 2, behaviour 6.
+ * The grid planner (neo_mpc_replan_batch, neo_mpc_replan, neo_mpc_replan_plans[_device]) added two records and two entry
+ * points in the same way: still ABI 2, behaviour 6.
  * The world inflation (neo_mpc_inflate_world_map[_device], neo_mpc_get_world_map) added three entry points and no record:
  * still ABI 2, behaviour 6.
  * The scan obstacle layer (neo_mpc_scan_batch, neo_mpc_update_scan_layer[_device], neo_mpc_get_scan_layer,
@@ -774,8 +776,8 @@ typedef struct neo_mpc_fleet_clear {
  *   value             blocked: the value of pose first_blocked.  Not blocked: the largest value below 255 met over
  *                     [begin, end), 0 when there is none -- how tight a still-valid plan has become.
  * The call writes `results` and nothing else: neo_mpc_problem.skip stays neo_mpc_select_carrots' to set, and what to do about
- * a blocked plan is the caller's decision.
- * Out of scope: replanning; the rolling windows; one footprint per robot; the arc length to the blocked pose (the caller has
+ * a blocked plan is the caller's decision -- neo_mpc_replan_plans[_device] below takes these records as its mask.
+ * Out of scope: replanning (the grid planner below is a call of its own); the rolling windows; one footprint per robot; the arc length to the blocked pose (the caller has
  * the index); neo_mpc_select_carrots or this call inside a closed fleet loop that has no plans.
  * Pointers are host pointers for neo_mpc_check_plans and device pointers for neo_mpc_check_plans_device.  72 bytes. */
 typedef struct neo_mpc_plan_check {   /* 24 bytes */
@@ -800,6 +802,88 @@ typedef struct neo_mpc_plan_check_batch {
   uint32_t reserved;             /* MUST be zero */
   neo_mpc_plan_check* results;   /* [count] out */
 } neo_mpc_plan_check_batch;
+
+/* ---- detours for the fleet's blocked plans, searched on the live world map: a grid planner (K16) --------- */
+
+/* The consumer of the plan check's answer: for every robot whose plan the live map blocks, a path from where it stands to a
+ * goal the caller chose, searched on the same map, for the whole fleet in one launch (neo_mpc_replan_plans[_device]).
+ * nav2's planners (NavFn, Smac) cannot be built next to this library and hold float potentials; this is the library's own
+ * rule, in integers alone, and the text below is the contract (tests/grid_planner_reference.py is its executable form).
+ * The result is unique by construction -- a shortest-path cost and a walk with a fixed tie rule --, every loop of the kernel
+ * is bounded by the window, and a robot's search waits for no other robot's.
+ *
+ * Which map.  The plan check's exactly: the composition of the last world-scan update while one is current (`live`), else
+ * the handle's copy of the world map; WSX x WSY cells, resolution wres, origin (wox, woy).  The rolling windows and the
+ * other robots are not looked at.
+ *
+ * For robot i, starts[i] = (x, y) and goals[i] = (x, y), float64, in that map's frame:
+ *   cells             the plan check's point-mode rule gives the start cell s = (sx, sy) and the goal cell g = (gx, gy): off
+ *                     the map when X < wox, Y < woy or a coordinate is not finite; else mx = trunc((X - wox) / wres), my
+ *                     likewise, off the map unless mx < WSX and my < WSY.
+ *   search window     W x W cells, W = `window`: x0 = clamp((sx + gx) / 2 - W / 2, 0, max(WSX - W, 0)) in integer
+ *                     division, y0 likewise from sy, gy and WSY; its cells are [x0, x0 + W) x [y0, y0 + W) intersected with
+ *                     the map.  Everything outside the window is not traversable.
+ *   traversable       a cell with the raw value v: v == 255 ? unknown_cost > 0 : v < max_cost.  Its cost m is unknown_cost
+ *                     for 255, else v.  The start cell's own value is never looked at where moves leave it: the robot
+ *                     stands there (so s == g is a path of one cell whatever the cell holds).  As a cell another move
+ *                     enters or passes, the start cell counts by its value like any other.
+ *   moves             8-connected, direction k = 0 .. 7 for E, NE, N, NW, W, SW, S, SE (N: towards larger my).  A move
+ *                     a -> b needs b traversable; a diagonal move also needs both cells it passes between -- (bx, ay) and
+ *                     (ax, by) -- traversable: no corner is cut.
+ *   step(a -> b)      (k odd ? 14 : 10) * (neutral_cost + m(b)), uint32.  The worst path of a window stays below 1.2e8:
+ *                     nothing wraps.
+ *   potential         G(g) = 0, G(a) = min over the allowed moves a -> b of step(a -> b) + G(b): the cost of the cheapest
+ *                     path from a to the goal inside the window.
+ *   path              from s, at every cell the allowed move that minimises step + G, the lowest k on a tie, until g.  G
+ *                     falls strictly along it: at most W * W cells.
+ *   status            the first that applies:
+ *                       4  not asked: `checks` was given and checks[i].status != 1
+ *                       3  s or g is off the map, or outside the window
+ *                       2  the goal cell is not traversable (and is not the start cell)
+ *                       1  no path inside the window
+ *                       5  a path was found and is longer than max_path_cells
+ *                       0  a path was found
+ *   length, cost      the path's cells, both ends included, and G(s); both 0 unless status is 0 or 5.
+ *   window_x0, _y0    x0, y0; 0 for status 4, and for status 3 where s or g is off the map.
+ * Paths have the fixed stride max_path_cells a robot:
+ *   path_cells[i][j]  = (mx, my), int32, for j < min(length, max_path_cells).
+ *   path_poses[i][j]  = (x, y, yaw), float64, optional: x = wox + (mx + 0.5) * wres as one rounded multiply and one rounded
+ *                     add (no fused multiply-add), y likewise; yaw is entry k of the table below for the move that leaves
+ *                     cell j (whether or not cell j + 1 is written), the last pose of a path repeats the yaw of the pose
+ *                     before it, a path of one cell has yaw 0.  The table, k = 0 .. 7 (k * pi / 4, from k = 5 on
+ *                     (k - 8) * pi / 4, as float64):
+ *                       0.0, 0.7853981633974483, 1.5707963267948966, 2.356194490192345, 3.141592653589793,
+ *                       -2.356194490192345, -1.5707963267948966, -0.7853981633974483
+ * Entries beyond a path, and every entry of a robot with another status than 0 or 5, are not written (the host variant
+ * leaves the caller's values there).
+ * Out of scope: splicing the result into the ragged plan_poses / plan_offsets arrays (the stride is fixed, the caller
+ * compacts); a footprint-aware search (inflate with neo_mpc_inflate_world_map and choose max_cost); windows beyond 128
+ * cells; smoothing; other robots as obstacles; choosing the goal from the old plan; the call inside a closed fleet loop that
+ * has no plans.
+ * Pointers are host pointers for neo_mpc_replan_plans and device pointers for neo_mpc_replan_plans_device.  80 bytes. */
+typedef struct neo_mpc_replan {   /* 24 bytes */
+  int32_t status;                 /* 0 .. 5, see above */
+  uint32_t length;                /* cells of the path, both ends included */
+  uint32_t cost;                  /* G(s) */
+  int32_t window_x0, window_y0;   /* the search window's first cell */
+  uint32_t reserved;              /* written as 0 */
+} neo_mpc_replan;
+
+typedef struct neo_mpc_replan_batch {
+  size_t count;
+  const double* starts;              /* [count][2] */
+  const double* goals;               /* [count][2] */
+  const neo_mpc_plan_check* checks;  /* optional [count]: the plan check's records as a mask; NULL: every robot is asked */
+  uint32_t window;                   /* W: 4 .. 128 */
+  uint32_t max_cost;                 /* 1 .. 254 */
+  uint32_t unknown_cost;             /* 0 .. 252; 0: the value 255 is a wall */
+  uint32_t neutral_cost;             /* 1 .. 255 */
+  uint32_t max_path_cells;           /* >= 1: the stride of path_cells and path_poses */
+  uint32_t reserved;                 /* MUST be zero */
+  int32_t* path_cells;               /* [count][max_path_cells][2] out */
+  double* path_poses;                /* optional [count][max_path_cells][3] out */
+  neo_mpc_replan* results;           /* [count] out */
+} neo_mpc_replan_batch;
 
 typedef struct neo_mpc_handle neo_mpc_handle;
 
@@ -1238,6 +1322,20 @@ int neo_mpc_check_plans(neo_mpc_handle* handle, const neo_mpc_plan_check_batch* 
  * next one sees that update's map.  It allocates nothing, copies nothing and does not synchronise, so it can be captured in
  * a HIP graph with the rest of the tick. */
 int neo_mpc_check_plans_device(neo_mpc_handle* handle, const neo_mpc_plan_check_batch* batch, void* stream);
+
+/* The grid planner for `count` robots (neo_mpc_replan_batch above; K16).  Host pointers, synchronous: records and paths are in
+ * the caller's arrays when it returns.  Refusals look at the record's shape alone: NEO_MPC_ERR_NO_COSTMAP without a world
+ * map; NEO_MPC_ERR_INVALID_ARGUMENT for a null handle or record, a null starts / goals / path_cells / results with count > 0,
+ * window outside 4 .. 128, max_cost outside 1 .. 254, unknown_cost > 252, neutral_cost outside 1 .. 255, max_path_cells == 0,
+ * reserved != 0, a count beyond 2^31 - 1.  Coordinates are taken as they come: one that is not finite is off the map.
+ * count == 0 is NEO_MPC_OK and launches nothing. */
+int neo_mpc_replan_plans(neo_mpc_handle* handle, const neo_mpc_replan_batch* batch);
+/* Same with every pointer in device memory; enqueued on `stream`, returns without waiting; no value behind a pointer is
+ * looked at on the host.  It orders itself exactly like neo_mpc_check_plans_device, whose map it reads: behind the world
+ * map's writer, and a later rewrite of that map waits for its reads.  `checks` may be the `results` of a
+ * neo_mpc_check_plans_device call enqueued on the same stream before it: check and replan chain on the device.  It allocates
+ * nothing, copies nothing and does not synchronise, so it can be captured in a HIP graph with the rest of the tick. */
+int neo_mpc_replan_plans_device(neo_mpc_handle* handle, const neo_mpc_replan_batch* batch, void* stream);
 
 /* ---- multi-GPU fleets: the one exchange step ------------------------------------------------
  * Instances of one tick shard embarrassingly over the GPUs of a node (one handle per GPU, costmap and parameters

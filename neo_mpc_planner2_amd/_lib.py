@@ -81,6 +81,7 @@ PROTOTYPES = {
     "neo_mpc_set_world_scan_decay": (C.c_int, [_H, _U32]),
     "neo_mpc_get_world_scan_ages": (C.c_int, [_H, _V]),
     **_pair("neo_mpc_check_plans", _P(abi.NeoMpcPlanCheckBatch)),
+    **_pair("neo_mpc_replan_plans", _P(abi.NeoMpcReplanBatch)),
     "neo_mpc_rccl_available": None, "neo_mpc_comm_init_all": None, "neo_mpc_comm_destroy": None,
     "neo_mpc_group_start": None, "neo_mpc_group_end": None,
     "neo_mpc_allgather_velocities": None, "neo_mpc_broadcast_costmap": None,

@@ -136,6 +136,18 @@ NeoMpcPlanCheck, PLAN_CHECK_DTYPE = _record(
         ("begin", "u4"), ("end", "u4"), ("first_blocked", "u4"), ("status", "i4"),
         ("value", "u4"), ("reserved", "u4")])
 
+NeoMpcReplanBatch, _ = _record(
+    "neo_mpc_replan_batch", 80,
+    "`neo_mpc_replan_batch` (include/neo_mpc.h): detours for the fleet's blocked plans, searched on the live world map (K16).", [
+        ("count", "size"), ("starts", "ptr"), ("goals", "ptr"), ("checks", "ptr"),
+        ("window", "u4"), ("max_cost", "u4"), ("unknown_cost", "u4"), ("neutral_cost", "u4"),
+        ("max_path_cells", "u4"), ("reserved", "u4"), ("path_cells", "ptr"), ("path_poses", "ptr"), ("results", "ptr")])
+
+#: `neo_mpc_replan` (24 bytes), and as a NumPy dtype
+NeoMpcReplan, REPLAN_DTYPE = _record(
+    "neo_mpc_replan", 24, "`neo_mpc_replan` (include/neo_mpc.h): one robot's result of the grid planner.", [
+        ("status", "i4"), ("length", "u4"), ("cost", "u4"), ("window_x0", "i4"), ("window_y0", "i4"), ("reserved", "u4")])
+
 NeoMpcWindowBatch, _ = _record(
     "neo_mpc_window_batch", 56,
     "`neo_mpc_window_batch` (include/neo_mpc.h): one roll of a fleet's costmap windows over the world map.", [

@@ -13,7 +13,7 @@
 // K4 carrots, K6 footprint gate, K7 rolling windows; a fleet's outlines (K8's and K12's one view, shape check and host
 // staging), K8 fleet stamp, K9 world inflation; the scan layers -- their checks, K10's and K12 / K13's updates, the staging of an
 // observation and the entry points from points, then K11: the projection, the staging of ranges and the entry points from
-// ranges --; the layers read back, reset, K13's and K14's settings; K15 plan check.  A new entry point checks with the shared checks, stages with upload()
+// ranges --; the layers read back, reset, K13's and K14's settings; K15 plan check; K16 grid planner.  A new entry point checks with the shared checks, stages with upload()
 // -- an observation, ranges or outlines with the routine there is --, and launches through fence.read() or between
 // fence.begin_write() and end_write(); a new kind of update is a switch of update_from_points() and from_ranges(), not a copy.
 #include <hip/hip_runtime.h>
@@ -2329,6 +2329,79 @@ int neo_mpc_check_plans(neo_mpc_handle* h, const neo_mpc_plan_check_batch* b) {
   if ((rc = plan_check(h, d, nullptr))) return finish_on_null_stream(rc);
   // (a blocking copy on the null stream, behind the kernel)
   HIP_TRY(hipMemcpy(b->results, h->plan_checks.ptr, n * sizeof(neo_mpc_plan_check), hipMemcpyDeviceToHost));
+  return NEO_MPC_OK;
+}
+
+// ---------------------------------------------------------------------------------------------- K16: the grid planner
+// What both entry points check: the record's shape, never a value behind a pointer.
+static int check_replan_batch(const neo_mpc_handle* h, const neo_mpc_replan_batch* b) {
+  if (!h || !b) return fail(NEO_MPC_ERR_INVALID_ARGUMENT, "null argument");
+  if (!h->world.has) return fail(NEO_MPC_ERR_NO_COSTMAP, "neo_mpc_set_world_map has not been called");
+  if (b->reserved != 0) return fail(NEO_MPC_ERR_INVALID_ARGUMENT, "neo_mpc_replan_batch.reserved must be zero (got %u)", b->reserved);
+  if (b->window < 4 || b->window > 128) return fail(NEO_MPC_ERR_INVALID_ARGUMENT, "window %u outside [4, 128]", b->window);
+  if (b->max_cost < 1 || b->max_cost > 254) return fail(NEO_MPC_ERR_INVALID_ARGUMENT, "max_cost %u outside [1, 254]", b->max_cost);
+  if (b->unknown_cost > 252) return fail(NEO_MPC_ERR_INVALID_ARGUMENT, "unknown_cost %u outside [0, 252]", b->unknown_cost);
+  if (b->neutral_cost < 1 || b->neutral_cost > 255)
+    return fail(NEO_MPC_ERR_INVALID_ARGUMENT, "neutral_cost %u outside [1, 255]", b->neutral_cost);
+  if (b->max_path_cells == 0) return fail(NEO_MPC_ERR_INVALID_ARGUMENT, "max_path_cells must be at least 1");
+  if (b->count > 0 && (!b->starts || !b->goals || !b->path_cells || !b->results))
+    return fail(NEO_MPC_ERR_INVALID_ARGUMENT, "starts/goals/path_cells/results must not be null");
+  return check_count(b->count);
+}
+
+// `d`: the record with device pointers.  Ordered exactly like plan_check(), whose map it reads.
+static int replan(neo_mpc_handle* h, const neo_mpc_replan_batch& d, void* stream) {
+  hipStream_t st = (hipStream_t)stream;
+  int rc;
+  if ((rc = h->fence.begin_write(st))) return rc;
+  if ((rc = h->world.wait_writer(st))) return rc;
+  const WorldMap& w = h->world;
+  ReplanArgs a;
+  std::memset(&a, 0, sizeof(a));
+  a.starts = d.starts; a.goals = d.goals; a.checks = d.checks;
+  a.path_cells = d.path_cells; a.path_poses = d.path_poses; a.results = d.results;
+  a.world = h->world_scan.live_valid ? h->world_scan.live.as<const uint8_t>() : w.buf.as<const uint8_t>();
+  a.wres = w.resolution; a.winv = 1.0 / w.resolution; a.wox = w.origin_x; a.woy = w.origin_y;
+  a.wsx = w.size_x; a.wsy = w.size_y;
+  a.count = (uint32_t)d.count; a.window = d.window;
+  a.max_cost = d.max_cost; a.unknown_cost = d.unknown_cost; a.neutral_cost = d.neutral_cost; a.max_path_cells = d.max_path_cells;
+  launch_replan(a, stream);
+  HIP_TRY(hipGetLastError());
+  return h->fence.end_write(st);
+}
+
+int neo_mpc_replan_plans_device(neo_mpc_handle* h, const neo_mpc_replan_batch* b, void* stream) {
+  int rc = check_replan_batch(h, b);
+  if (rc) return rc;
+  if (b->count == 0) return NEO_MPC_OK;
+  HIP_TRY(hipSetDevice(h->device));
+  return replan(h, *b, stream);
+}
+
+int neo_mpc_replan_plans(neo_mpc_handle* h, const neo_mpc_replan_batch* b) {
+  int rc = check_replan_batch(h, b);
+  if (rc) return rc;
+  if (b->count == 0) return NEO_MPC_OK;
+  HIP_TRY(hipSetDevice(h->device));
+  const size_t n = b->count, cells_bytes = n * b->max_path_cells * 8, poses_bytes = n * b->max_path_cells * 24;
+  // staged through the buffers of the other synchronous plan calls (K4's and K15's host variants: all of them on the null
+  // stream, each finished when it returns): starts and goals in `poses` and `verts`, the mask in `plan_checks`, the records in
+  // `carrots`, the paths in `plan_offsets` and `plan_poses` -- the handle holds nothing of K16's own
+  DeviceBuffer &results = h->carrots, &cells = h->plan_offsets, &poses = h->plan_poses;
+  if ((rc = results.reserve(n * sizeof(neo_mpc_replan)))) return rc;
+  neo_mpc_replan_batch d = *b;
+  d.results = results.as<neo_mpc_replan>();
+  if (!(d.starts = h->poses.upload(b->starts, n * 16))) return NEO_MPC_ERR_DEVICE;
+  if (!(d.goals = h->verts.upload(b->goals, n * 16))) return NEO_MPC_ERR_DEVICE;
+  if (b->checks && !(d.checks = h->plan_checks.upload(b->checks, n * sizeof(neo_mpc_plan_check)))) return NEO_MPC_ERR_DEVICE;
+  // the paths go up before they come back: what the kernel does not write keeps the caller's values
+  if (!(d.path_cells = cells.upload(b->path_cells, cells_bytes))) return NEO_MPC_ERR_DEVICE;
+  if (b->path_poses && !(d.path_poses = poses.upload(b->path_poses, poses_bytes))) return NEO_MPC_ERR_DEVICE;
+  if ((rc = replan(h, d, nullptr))) return finish_on_null_stream(rc);
+  // (blocking copies on the null stream, behind the kernel)
+  HIP_TRY(hipMemcpy(b->results, results.ptr, n * sizeof(neo_mpc_replan), hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(b->path_cells, cells.ptr, cells_bytes, hipMemcpyDeviceToHost));
+  if (b->path_poses) HIP_TRY(hipMemcpy(b->path_poses, poses.ptr, poses_bytes, hipMemcpyDeviceToHost));
   return NEO_MPC_OK;
 }
 

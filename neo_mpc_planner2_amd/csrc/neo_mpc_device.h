@@ -341,6 +341,22 @@ struct PlanCheckArgs {
   uint32_t max_cost, unknown_blocks, outside, max_poses;
 };
 
+// K16: the grid planner (neo_mpc_replan_batch, device pointers) on the map K15 reads
+struct ReplanArgs {
+  const double* starts;             // [count][2]
+  const double* goals;              // [count][2]
+  const neo_mpc_plan_check* checks; // optional [count]: K15's records as a mask
+  int32_t* path_cells;              // [count][max_path_cells][2]
+  double* path_poses;               // optional [count][max_path_cells][3]
+  neo_mpc_replan* results;          // [count]
+  const uint8_t* world;             // the world map or K12's composition, row-major wsx * wsy
+  double wres, winv, wox, woy;      // winv = 1 / wres (cell_of redoes the division where it matters)
+  int32_t wsx, wsy;
+  uint32_t count;
+  uint32_t window;                  // 4 .. 128
+  uint32_t max_cost, unknown_cost, neutral_cost, max_path_cells;
+};
+
 // A/B switches of the measurement tools: read from the environment ONCE, by neo_mpc_create (include/neo_mpc.h), kept in
 // the handle -- nothing on the solve path looks at the environment.
 struct LaunchTuning {
@@ -362,6 +378,7 @@ void launch_scan_layer(const ScanArgs& a, void* stream);         // K10: k_scan_
 void launch_laser_project(const LaserArgs& a, void* stream);     // K11: k_laser_project
 void launch_world_scan(const WorldScanArgs& a, void* stream);    // K12: k_world_scan_rays (clear, mark), [K14: k_world_scan_decay,] k_world_scan_footprints, [K13: k_world_scan_denoise,] k_world_scan_compose
 void launch_plan_check(const PlanCheckArgs& a, void* stream);    // K15: k_plan_check (point or footprint mode)
+void launch_replan(const ReplanArgs& a, void* stream);           // K16: k_replan (a window of up to 32, 64 or 128 cells)
 // K5: dispatch order of the next launch from the iteration counts of the previous one (neo_mpc_balance_dispatch_device)
 void launch_dispatch_order(const neo_mpc_command* commands, float* load, uint32_t* order, uint32_t count, bool fresh, void* stream);
 constexpr uint32_t kDispatchSimds = 1024;   // a 4096-instance launch is one residency round: workgroups w, w + 1024, w + 2048, w + 3072 share a SIMD

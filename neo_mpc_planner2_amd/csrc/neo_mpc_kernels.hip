@@ -26,6 +26,7 @@
 //   K14 k_world_scan_tick, k_world_scan_stamp_fill, k_world_scan_marks_stamped, k_world_scan_decay  world_scan_decay.h: that layer's old marks expire, counted in scan updates.
 //   K15 k_plan_check  plan_check.h: which of the fleet's global plans the live world map blocks, one wave per plan, HBM-streaming;
 //                     K4's closest-pose stream lives there too.
+//   K16 k_replan  grid_planner.h: detours for the blocked plans on that map, one workgroup per robot, the search in LDS.
 #include "k1_solve.h"
 #include "costmap_ingest.h"
 #include "footprint_gate.h"
@@ -38,6 +39,7 @@
 #include "world_scan_denoise.h"
 #include "world_scan_decay.h"
 #include "plan_check.h"
+#include "grid_planner.h"
 
 namespace neo_mpc {
 namespace {
@@ -402,6 +404,14 @@ void launch_plan_check(const PlanCheckArgs& a, void* stream) {
   if (a.count == 0) return;
   if (a.footprint_points != 0) hipLaunchKernelGGL(k_plan_check<true>, dim3(a.count), dim3(kLanes), 0, (hipStream_t)stream, a);
   else hipLaunchKernelGGL(k_plan_check<false>, dim3(a.count), dim3(kLanes), 0, (hipStream_t)stream, a);
+}
+// K16: one workgroup per robot; the kernel's static LDS follows the window (7.9 KB to 32, 30 KB to 64, 115 KB to 128 cells)
+void launch_replan(const ReplanArgs& a, void* stream) {
+  if (a.count == 0) return;
+  const dim3 grid(a.count), block(kReplanThreads);
+  if (a.window <= 32) hipLaunchKernelGGL(k_replan<32>, grid, block, 0, (hipStream_t)stream, a);
+  else if (a.window <= 64) hipLaunchKernelGGL(k_replan<64>, grid, block, 0, (hipStream_t)stream, a);
+  else hipLaunchKernelGGL(k_replan<128>, grid, block, 0, (hipStream_t)stream, a);
 }
 void launch_ingest(const IngestArgs& a, const LaunchTuning& tuning, void* stream) {
   hipLaunchKernelGGL(k_ingest, padded_map_grid(a.rows, a.pitch, kIngestUnroll, a.maps > 0 ? a.maps : 1), dim3(256), 0,

@@ -713,6 +713,57 @@ class BatchSolver:
                                    outside_value, max_poses)
         self._call("neo_mpc_check_plans", self._stream(False, results) if stream is None else stream, C.byref(b))
 
+    # -- grid planner (detours for the plans the live world map blocks) ---------------------
+    def _replan_batch(self, on_host, starts, goals, checks, path_cells, path_poses, results, window, max_cost, unknown_cost,
+                      neutral_cost):
+        """neo_mpc_replan_batch over NumPy arrays (`on_host`) or CUDA tensors; the stride is `path_cells`' second dimension."""
+        b = abi.NeoMpcReplanBatch()
+        count = b.count = starts.shape[0]
+        b.window, b.max_cost, b.unknown_cost, b.neutral_cost = int(window), int(max_cost), int(unknown_cost), int(neutral_cost)
+        stride = b.max_path_cells = path_cells.shape[1]
+        records = (count,) if on_host else None       # (a tensor holds records as bytes, flat or [count, 24])
+        _, b.starts = self._array(starts, on_host, np.float64, (count, 2), coerce=False)
+        _, b.goals = self._array(goals, on_host, np.float64, (count, 2), coerce=False)
+        _, b.path_cells = self._array(path_cells, on_host, np.int32, (count, stride, 2), coerce=False)
+        _, b.results = self._array(results, on_host, abi.REPLAN_DTYPE, records, coerce=False)
+        if checks is not None:
+            _, b.checks = self._array(checks, on_host, abi.PLAN_CHECK_DTYPE, records, coerce=False)
+        if path_poses is not None:
+            _, b.path_poses = self._array(path_poses, on_host, np.float64, (count, stride, 3), coerce=False)
+        return b
+
+    def replan_plans(self, starts, goals, window, checks=None, max_cost=253, unknown_cost=0, neutral_cost=50,
+                     max_path_cells=None, want_poses=False):
+        """A path from `starts[i]` to `goals[i]` ([count, 2], the world map's frame) for every robot, searched inside a window
+        of `window` x `window` cells of the world map the next roll would read (K16; the contract: include/neo_mpc.h,
+        neo_mpc_replan_batch).  `checks`: `check_plans`' records as a mask -- only robots with status 1 are searched.
+        `max_path_cells` (default window * window: every path fits) is the stride of the outputs.  Returns (records
+        abi.REPLAN_DTYPE [count], path_cells int32 [count, max_path_cells, 2][, path_poses float64 [count, max_path_cells, 3]
+        with `want_poses`]); entries beyond a path stay 0."""
+        starts = np.ascontiguousarray(starts, dtype=np.float64).reshape(-1, 2)
+        goals = np.ascontiguousarray(goals, dtype=np.float64).reshape(-1, 2)
+        count = starts.shape[0]
+        stride = int(window) * int(window) if max_path_cells is None else int(max_path_cells)
+        results = np.zeros(count, dtype=abi.REPLAN_DTYPE)
+        path_cells = np.zeros((count, stride, 2), dtype=np.int32)
+        path_poses = np.zeros((count, stride, 3), dtype=np.float64) if want_poses else None
+        if checks is not None:
+            checks = np.ascontiguousarray(checks, dtype=abi.PLAN_CHECK_DTYPE)
+        b = self._replan_batch(True, starts, goals, checks, path_cells, path_poses, results, window, max_cost, unknown_cost,
+                               neutral_cost)
+        self._call("neo_mpc_replan_plans", None, C.byref(b))
+        return (results, path_cells, path_poses) if want_poses else (results, path_cells)
+
+    def replan_plans_device(self, starts, goals, window, path_cells, results, checks=None, path_poses=None, max_cost=253,
+                            unknown_cost=0, neutral_cost=50, stream=None):
+        """Device-resident variant: contiguous torch CUDA tensors (`starts`, `goals` float64 [count, 2]; `path_cells` int32
+        [count, max_path_cells, 2]; `path_poses` float64 [count, max_path_cells, 3] or None; `results` and `checks` the
+        records as bytes, 24 a robot -- `checks` may be what `check_plans_device` wrote on the same stream); enqueues K16 on
+        `stream` (default: torch's current) and returns without waiting.  Capturable in a HIP graph."""
+        b = self._replan_batch(False, starts, goals, checks, path_cells, path_poses, results, window, max_cost, unknown_cost,
+                               neutral_cost)
+        self._call("neo_mpc_replan_plans", self._stream(False, results) if stream is None else stream, C.byref(b))
+
     # -- footprint gate (the step before the carrot) --------------------------------------
     def footprint_gate(self, footprint, poses=None, problems=None, map_indices=None, want_polygons=False):
         """`footprintCostAtPose` (NeoMpcPlanner.cpp:218-219; nav2's FootprintCollisionChecker on raw cell values) for a
